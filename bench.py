@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark: images/sec of one DMVAE tokenizer train step @256x256 (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 started plainly (no RANK in the env): this process checks that N devices exist and re-executes itself as N ranks, one per GPU, through
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (the reference's launcher: scripts/train_tokenizer.sh:20-38);
@@ -409,6 +409,32 @@ def _latest_profile(suffix: str) -> str:
     return best[1]
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, tr, loss: torch.Tensor) -> None:
+    """`--dump-outputs DIR`: what the last timed step handed back to its caller, as float32 .npy files, so that two builds can be compared output for output
+    (the inputs are the same on every run: weights from torch.manual_seed(42), images from a device generator seeded 42 + rank).  `loss` = the step's return
+    value; `log` = the eight values read_log() reads (L1, L2, LPIPS, rec_loss, vae_norm, KL, MMD, d_weight); `params`, `ema`, `grad` = the trainable
+    parameters after the optimiser step, their EMA and the step's gradient, in the flat buffer's order (optim.FlatParams).  When the three flat arrays would
+    exceed the 64 MB budget, each holds the same fixed sample of buffer positions: the sorted draws of torch.randint over the buffer under seed 0."""
+    import numpy as np
+    fp = tr.fp
+    n = fp.flat.numel()
+    k = min(n, (DUMP_BUDGET_BYTES - (1 << 20)) // (3 * 4))         # 1 MB left for loss, log and the .npy headers
+    idx = None
+    if k < n:
+        idx = torch.randint(0, n, (k,), generator=torch.Generator().manual_seed(0)).sort().values.to(fp.flat.device)
+    take = lambda t: (t if idx is None else t[idx]).float().cpu().numpy()
+    arrays = {"loss": loss.float().reshape(()).cpu().numpy(), "log": tr.log.float().cpu().numpy(),
+              "params": take(fp.flat), "ema": take(fp.ema), "grad": take(fp.grad)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(f'{k_}{list(a.shape)}' for k_, a in arrays.items())} to {out_dir} "
+          f"({'all' if idx is None else f'{k} sampled'} of {n} flat parameter positions)", file=sys.stderr, flush=True)
+
+
 def self_launch(n_gpus: int) -> int:
     """No RANK in the env and --gpus N > 1: become the launcher.  One rank per device over RCCL, rendezvous on 127.0.0.1, a free port; the
     ranks' stdout/stderr pass straight through (rank 0 prints the JSON line).  Returns the exit code of the job."""
@@ -442,6 +468,8 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the c3_dmd_cycle / c4_diffusion_step / gan_step keys (N = 1 only; ~1.5 min of model construction and steps)")
     ap.add_argument("--secondary", default="c3,c4,gan", help="which of the secondary stage keys to measure")
     ap.add_argument("--time-every", type=int, default=4, help="record the per-launch roofline events on every n-th timed step (1 = all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (rank 0; see dump_outputs)")
     ap.add_argument("--cpu-baseline-worker", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_worker:
@@ -449,6 +477,8 @@ def main():
         return
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if "RANK" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))
 
@@ -501,7 +531,7 @@ def main():
             win_ev[i] = torch.cuda.Event(enable_timing=True)
             win_ev[i].record()
         ops.KERNEL_TIMING = timing_all if i % max(1, args.time_every) == 0 else None
-        tr.step(images)
+        loss = tr.step(images)
     win_ev[args.steps] = torch.cuda.Event(enable_timing=True)
     win_ev[args.steps].record()
     ops.KERNEL_TIMING = timing_all
@@ -517,6 +547,8 @@ def main():
         torch.distributed.all_reduce(tdt, op=torch.distributed.ReduceOp.MAX)
     dt = tdt.item()
     log = tr.read_log()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss)
     if rank != 0:
         _emit("", rank0=False)      # leave the group together with rank 0 (it prints the line after everybody's native output is out)
         return

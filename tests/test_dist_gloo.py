@@ -16,6 +16,9 @@ def _free_port():
 
 
 def _worker(rank, world, port, q):
+    # CPU ranks on every node: init_distributed_mode selects no device and touches no kernel library in them (each rank still opens the GPU of a GPU node
+    # at its first backward, which is what bounds the world sizes below)
+    torch.cuda.is_available = lambda: False
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     from dmvae_amd import dist
     from dmvae_amd.optim import FlatParams
@@ -58,10 +61,11 @@ def _worker(rank, world, port, q):
     torch.distributed.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 3, 4])
 def test_flat_grad_sync_two_ranks_gloo(world):
-    """world 2, 4 and 8 (the node sizes the reference's launch scripts use: scripts/train_tokenizer.sh:20-38): averaging, bucket boundaries, every collective started
-    from a gradient hook."""
+    """world 2, 3 and 4: averaging (3: a divisor that is not a power of two), bucket boundaries, every collective started from a gradient hook.  At most four
+    ranks: on a GPU node every rank opens the device (PyTorch-ROCm's autograd engine asks HIP for the device count on a process's first backward), and the
+    ranks plus the test runner must stay within the six processes a shared GPU may have open at once -- the reference's 8-GPU node size does not fit."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
