@@ -32,6 +32,11 @@ class WtEntry(Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("N", c_int32), ("K", c_int32), ("start", c_uint), ("tiles_x", c_uint)]
 
 
+class OdeTerms(Structure):
+    """dmvae_ode_terms (include/dmvae_hip.h): up to 7 k pointers and their f32 weights, passed by value into the dopri5 kernels."""
+    _fields_ = [("k", c_void_p * 7), ("c", c_float * 7), ("nk", c_int32), ("k_bf16", c_int32)]
+
+
 ABI_VERSION = 8     # 8: dmvae_reparam_kl_*, dmvae_linear_bf16_sk*, the f32 transformer steps of csrc/parity_dit.hip; 7: dmvae_linear_wgrad_grouped_plan / _xcd, dmvae_conv_k4c1_*; 6: dmvae_dit_stack_* / dmvae_dit_boundary_bwd / batched rows Linears / batched weight transposes; 5: dmvae_groupnorm_*_short; include/dmvae_hip.h: dmvae_abi_version (3: struct dmvae_pack_entry, dmvae_pack_weights_batched, dmvae_linear_bf16*; 4: dmvae_norm_conv_out_bwd*)
 
 # name -> (restype, argtypes); every symbol include/dmvae_hip.h declares
@@ -95,6 +100,10 @@ SIGNATURES = {
     "dmvae_leaky_relu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p]),
     "dmvae_sde_euler_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t] + [c_float] * 6 + [c_void_p]),
     "dmvae_image_to_u8": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "dmvae_ode_rk_combine": (c_int, [c_void_p, POINTER(OdeTerms), c_void_p, c_size_t, c_int, c_void_p]),
+    "dmvae_ode_error_ratio_workspace": (c_size_t, [c_size_t]),
+    "dmvae_ode_error_ratio": (c_int, [c_void_p, c_void_p, POINTER(OdeTerms), c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dmvae_ode_dense_output": (c_int, [c_void_p] * 5 + [c_int, c_float, c_float, c_void_p, c_size_t, c_void_p]),
     "dmvae_batchnorm_running_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p]),
     "dmvae_diffaug_fwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "dmvae_diffaug_bwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),

@@ -5,6 +5,13 @@
 // Arithmetic follows the reference's f32 elementwise graph operation by operation (no contraction into FMAs, IEEE divide), so for the same
 // model output the state after a step is bit-identical to the PyTorch-CPU result; every coefficient depends on t only and arrives as a scalar
 // the host computed in f32 the way the reference does.
+//
+// The adaptive dopri5 ODE sampler (transport.py:356-407 -> torchdiffeq.odeint, integrators.py:79-118) adds three HBM passes per solver step: the
+// Runge-Kutta combine y0 + sum_j c_j k_j (stage inputs, y_mid), the error ratio (err, its tolerance-scaled mean square, partial sums per workgroup
+// summed in a fixed order in f64) and the quartic dense output.  Their coefficients and k pointers travel by value in struct dmvae_ode_terms.
+// Every kernel takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail.
+#include <initializer_list>
+
 #include "common.h"
 #include "dmvae_hip.h"
 
@@ -59,6 +66,193 @@ __global__ __launch_bounds__(256) void image_to_u8_kernel(const float* __restric
   }
 }
 
+
+// ---- dopri5 (torchdiffeq's RKAdaptiveStepsizeODESolver; integrators.py:79-118) -------------------------------------------------------------
+
+template <int W>
+__device__ __forceinline__ void load_w(const void* p, bool is_bf16, size_t e, float (&o)[W]) {
+  if constexpr (W == 4) {
+    if (is_bf16) {
+      const bf16x4 t = *reinterpret_cast<const bf16x4*>((const bf16*)p + e);
+#pragma unroll
+      for (int j = 0; j < 4; j++) o[j] = (float)t[j];
+    } else {
+      const float4 t = *reinterpret_cast<const float4*>((const float*)p + e);
+      o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+    }
+  } else {
+    o[0] = is_bf16 ? (float)((const bf16*)p)[e] : ((const float*)p)[e];
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void store_w(float* p, size_t e, const float (&v)[W]) {
+  if constexpr (W == 4) *reinterpret_cast<float4*>(p + e) = make_float4(v[0], v[1], v[2], v[3]);
+  else p[e] = v[0];
+}
+
+// s = sum_{j < nk} c_j k_j, j ascending, products and sums rounded to f32 one by one.  round_bf16: the autocast matmul of torchdiffeq's
+// k.matmul(coef * dt) -- c_j and k_j rounded to bf16 (their products are exact in f32), the f32 sum rounded to bf16 at the end.
+template <int W>
+__device__ __forceinline__ void rk_sum(const dmvae_ode_terms& T, int round_bf16, size_t e, float (&s)[W]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < DMVAE_ODE_MAX_TERMS; j++) {             // unrolled: constant indices into the by-value struct (no scratch copy)
+    if (j >= T.nk) break;
+    float kv[W];
+    load_w<W>(T.k[j], (T.k_bf16 >> j) & 1, e, kv);
+    const float c = round_bf16 ? (float)(bf16)T.c[j] : T.c[j];
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+      const float p = c * (round_bf16 ? (float)(bf16)kv[w] : kv[w]);
+      s[w] = j == 0 ? p : s[w] + p;
+    }
+  }
+  if (round_bf16) {
+#pragma unroll
+    for (int w = 0; w < W; w++) s[w] = (float)(bf16)s[w];
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void rk_combine_at(const float* __restrict__ y0, const dmvae_ode_terms& T, float* __restrict__ out, size_t e, int round_bf16) {
+#pragma clang fp contract(off)
+  float s[W];
+  rk_sum<W>(T, round_bf16, e, s);
+  if (y0) {
+    float a[W];
+    load_w<W>(y0, false, e, a);
+#pragma unroll
+    for (int w = 0; w < W; w++) s[w] = a[w] + s[w];
+  }
+  store_w<W>(out, e, s);
+}
+
+__global__ __launch_bounds__(256) void ode_rk_combine_kernel(const float* __restrict__ y0, dmvae_ode_terms T, float* __restrict__ out, size_t n, size_t nq,
+                                                             int round_bf16) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) rk_combine_at<4>(y0, T, out, 4 * i, round_bf16);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) rk_combine_at<1>(y0, T, out, e, round_bf16);
+}
+
+// err = rk_sum(c_err dt);  e = err / (atol + rtol * max(|y0|, |y1|))  (torch.max: a NaN operand gives NaN);  acc += e^2 in f64;  bad |= !isfinite(y1)
+template <int W>
+__device__ __forceinline__ void err_at(const float* __restrict__ y0, const float* __restrict__ y1, const dmvae_ode_terms& T, float* __restrict__ err_out,
+                                       size_t e, float atol, float rtol, int round_bf16, double& acc, int& bad) {
+#pragma clang fp contract(off)
+  float s[W], a[W], b[W];
+  rk_sum<W>(T, round_bf16, e, s);
+  load_w<W>(y0, false, e, a);
+  load_w<W>(y1, false, e, b);
+#pragma unroll
+  for (int w = 0; w < W; w++) {
+    const float fa = fabsf(a[w]), fb = fabsf(b[w]);
+    const float m = (fa > fb || fa != fa) ? fa : fb;
+    const float q = s[w] / (atol + rtol * m);
+    acc += (double)q * (double)q;
+    bad |= !isfinite(b[w]);
+  }
+  if (err_out) store_w<W>(err_out, e, s);
+}
+
+__device__ __forceinline__ void block_sum_256(double& v, int& f) {
+  __shared__ double sv[256];
+  __shared__ int sf[256];
+  sv[threadIdx.x] = v;
+  sf[threadIdx.x] = f;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {                       // fixed tree: the same bits on every run
+    if ((int)threadIdx.x < h) { sv[threadIdx.x] = sv[threadIdx.x] + sv[threadIdx.x + h]; sf[threadIdx.x] |= sf[threadIdx.x + h]; }
+    __syncthreads();
+  }
+  v = sv[0];
+  f = sf[0];
+}
+
+__global__ __launch_bounds__(256) void ode_err_partial_kernel(const float* __restrict__ y0, const float* __restrict__ y1, dmvae_ode_terms T,
+                                                              float* __restrict__ err_out, double* __restrict__ part, int* __restrict__ part_bad, size_t n,
+                                                              size_t nq, float atol, float rtol, int round_bf16) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  double acc = 0.0;
+  int bad = 0;
+  for (size_t i = tid; i < nq; i += stride) err_at<4>(y0, y1, T, err_out, 4 * i, atol, rtol, round_bf16, acc, bad);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) err_at<1>(y0, y1, T, err_out, e, atol, rtol, round_bf16, acc, bad);
+  block_sum_256(acc, bad);
+  if (threadIdx.x == 0) { part[blockIdx.x] = acc; part_bad[blockIdx.x] = bad; }
+}
+
+// one workgroup: result = {(float)(sum / n), any non-finite y1}; partials in a fixed order (strided per thread, then the fixed tree)
+__global__ __launch_bounds__(256) void ode_err_final_kernel(const double* __restrict__ part, const int* __restrict__ part_bad, int nparts, size_t n,
+                                                            void* __restrict__ result) {
+  double acc = 0.0;
+  int bad = 0;
+  for (int b = threadIdx.x; b < nparts; b += 256) { acc += part[b]; bad |= part_bad[b]; }
+  block_sum_256(acc, bad);
+  if (threadIdx.x == 0) {
+    reinterpret_cast<float*>(result)[0] = (float)(acc / (double)n);
+    reinterpret_cast<int*>(result)[1] = bad;
+  }
+}
+
+// torchdiffeq's _interp_fit (dopri5's y_mid given) + _interp_evaluate at x, in their operation order
+template <int W>
+__device__ __forceinline__ void dense_at(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ ym, const void* f0, const void* f1,
+                                         int f_bf16, float dt, float x, float* __restrict__ out, size_t e) {
+#pragma clang fp contract(off)
+  float Y0[W], Y1[W], YM[W], F0[W], F1[W], o[W];
+  load_w<W>(y0, false, e, Y0);
+  load_w<W>(y1, false, e, Y1);
+  load_w<W>(ym, false, e, YM);
+  load_w<W>(f0, f_bf16 & 1, e, F0);
+  load_w<W>(f1, (f_bf16 >> 1) & 1, e, F1);
+  const float x2 = x * x, x3 = x2 * x, x4 = x3 * x;
+#pragma unroll
+  for (int w = 0; w < W; w++) {
+    const float a = ((2.f * dt) * (F1[w] - F0[w]) - 8.f * (Y1[w] + Y0[w])) + 16.f * YM[w];
+    const float b = ((dt * (5.f * F0[w] - 3.f * F1[w]) + 18.f * Y0[w]) + 14.f * Y1[w]) - 32.f * YM[w];
+    const float c = ((dt * (F1[w] - 4.f * F0[w]) - 11.f * Y0[w]) - 5.f * Y1[w]) + 16.f * YM[w];
+    const float d = dt * F0[w];
+    float t = Y0[w] + x * d;
+    t = t + x2 * c;
+    t = t + x3 * b;
+    o[w] = t + x4 * a;
+  }
+  store_w<W>(out, e, o);
+}
+
+__global__ __launch_bounds__(256) void ode_dense_kernel(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ ym, const void* f0,
+                                                        const void* f1, int f_bf16, float dt, float x, float* __restrict__ out, size_t n, size_t nq) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) dense_at<4>(y0, y1, ym, f0, f1, f_bf16, dt, x, out, 4 * i);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) dense_at<1>(y0, y1, ym, f0, f1, f_bf16, dt, x, out, e);
+}
+
+constexpr int kErrMaxParts = 1024;
+
+inline int ode_grid(size_t n, size_t nq, int cap) {
+  const size_t work = nq + (n - 4 * nq);                    // quads, then the scalar tail
+  const size_t g = (work + 255) / 256;
+  return (int)(g < (size_t)cap ? (g > 0 ? g : 1) : (size_t)cap);
+}
+
+inline bool aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
+
+// quads only when every pointer is aligned for them: f32 arrays to 16 bytes, bf16 arrays to 8
+inline size_t ode_quads(size_t n, const dmvae_ode_terms* T, std::initializer_list<const void*> f32s) {
+  bool ok = true;
+  for (const void* p : f32s) ok = ok && aligned(p, 16);
+  if (T)
+    for (int j = 0; j < T->nk; j++) ok = ok && aligned(T->k[j], ((T->k_bf16 >> j) & 1) ? 8 : 16);
+  return ok ? n / 4 : 0;
+}
+
+inline bool terms_ok(const dmvae_ode_terms* T) {
+  if (!T || T->nk < 1 || T->nk > DMVAE_ODE_MAX_TERMS) return false;
+  for (int j = 0; j < T->nk; j++)
+    if (!T->k[j]) return false;
+  return true;
+}
+
 }  // namespace dmvae_sampler
 
 extern "C" int dmvae_sde_euler_step(const void* x, const void* v, int v_is_bf16, const void* w, void* x_out, void* mean_out, size_t n, float rar,
@@ -82,6 +276,49 @@ extern "C" int dmvae_image_to_u8(const void* y, void* out, size_t npix, int c, i
   DMVAE_CHECK_ARG(y && out && npix > 0 && c > 0 && c <= c_stride, "image_to_u8: bad argument");
   const int grid = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
   hipLaunchKernelGGL(image_to_u8_kernel, dim3(grid), dim3(256), 0, stream, (const float*)y, (uint8_t*)out, npix, c, c_stride, round_bf16);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_ode_rk_combine(const void* y0, const dmvae_ode_terms* terms, void* out, size_t n, int round_bf16, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(terms_ok(terms) && out && n > 0, "ode_rk_combine: bad argument (1 <= nk <= %d non-NULL k, out, n > 0)", DMVAE_ODE_MAX_TERMS);
+  const size_t nq = ode_quads(n, terms, {y0, out});
+  hipLaunchKernelGGL(ode_rk_combine_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)y0, *terms, (float*)out, n, nq, round_bf16);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t dmvae_ode_error_ratio_workspace(size_t n) {
+  (void)n;
+  return (size_t)dmvae_sampler::kErrMaxParts * (sizeof(double) + sizeof(int));
+}
+
+extern "C" int dmvae_ode_error_ratio(const void* y0, const void* y1, const dmvae_ode_terms* terms, float atol, float rtol, int round_bf16, void* err_out,
+                                     void* workspace, void* result, size_t n, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(y0 && y1 && terms_ok(terms) && workspace && result && n > 0 && aligned(workspace, 8) && aligned(result, 8),
+                  "ode_error_ratio: bad argument");
+  const size_t nq = ode_quads(n, terms, {y0, y1, err_out});
+  const int grid = ode_grid(n, nq, kErrMaxParts);
+  double* part = (double*)workspace;
+  int* part_bad = (int*)(part + kErrMaxParts);
+  hipLaunchKernelGGL(ode_err_partial_kernel, dim3(grid), dim3(256), 0, stream, (const float*)y0, (const float*)y1, *terms, (float*)err_out, part, part_bad,
+                     n, nq, atol, rtol, round_bf16);
+  DMVAE_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ode_err_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)part, (const int*)part_bad, grid, n, result);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_ode_dense_output(const void* y0, const void* y1, const void* y_mid, const void* f0, const void* f1, int f_bf16, float dt, float x,
+                                      void* out, size_t n, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(y0 && y1 && y_mid && f0 && f1 && out && n > 0, "ode_dense_output: bad argument");
+  bool ok = aligned(f0, (f_bf16 & 1) ? 8 : 16) && aligned(f1, (f_bf16 & 2) ? 8 : 16);
+  const size_t nq = ok ? ode_quads(n, nullptr, {y0, y1, y_mid, out}) : 0;
+  hipLaunchKernelGGL(ode_dense_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)y0, (const float*)y1, (const float*)y_mid, f0, f1,
+                     f_bf16, dt, x, (float*)out, n, nq);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -1594,6 +1594,85 @@ def sde_euler_step(x: torch.Tensor, v: torch.Tensor, w: Optional[torch.Tensor], 
     check(_lib.lib().dmvae_sde_euler_step(x.data_ptr(), v.data_ptr(), int(v.dtype == bf16), _ptr(w), out.data_ptr(), _ptr(mean), x.numel(), float(rar),
                                           float(var), float(diff), float(dt), float(sqrt_2diff), float(sqrt_dt), _stream()), "sde_euler_step")
     return out, mean
+
+
+def _ode_terms(ks: Sequence[torch.Tensor], cs: Sequence[float], like: torch.Tensor) -> "_lib.OdeTerms":
+    """k_j (bf16 or f32, contiguous, on like's device and of its shape) and their f32 weights -> struct dmvae_ode_terms."""
+    if not 1 <= len(ks) <= 7 or len(cs) != len(ks):
+        raise ValueError(f"ode terms: 1..7 tensors with one weight each, got {len(ks)} tensors and {len(cs)} weights")
+    terms = _lib.OdeTerms()
+    terms.nk, terms.k_bf16 = len(ks), 0
+    for j, (k, c) in enumerate(zip(ks, cs)):
+        _req(k, bf16 if k.dtype == bf16 else f32, f"k[{j}]")
+        _same(k, like, f"k[{j}]")
+        terms.k[j], terms.c[j] = k.data_ptr(), float(c)
+        terms.k_bf16 |= int(k.dtype == bf16) << j
+    return terms
+
+
+def _same(t: torch.Tensor, like: torch.Tensor, name: str) -> None:
+    if t.shape != like.shape or t.device != like.device:
+        raise ValueError(f"{name}: expected shape {tuple(like.shape)} on {like.device}, got {tuple(t.shape)} on {t.device}")
+
+
+def ode_rk_combine(y0: Optional[torch.Tensor], ks: Sequence[torch.Tensor], cs: Sequence[float], round_bf16: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = y0 + sum_j cs[j] * ks[j] (j ascending, f32; y0 None: the sum alone) -- dopri5's stage inputs and y_mid (integrators.py:79-118).  round_bf16:
+    the autocast form of torchdiffeq's k.matmul(coef * dt) -- weights and k rounded to bf16, the f32 sum rounded to bf16 before the f32 y0 is added.
+    y0 / out f32, ks bf16 or f32, all of one shape, contiguous, on one device."""
+    like = ks[0] if y0 is None else _req(y0, f32, "y0")
+    terms = _ode_terms(ks, cs, like)
+    if out is None:
+        out = torch.empty(like.shape, dtype=f32, device=like.device)
+    _same(_req(out, f32, "out"), like, "out")
+    check(_lib.lib().dmvae_ode_rk_combine(_ptr(y0), ctypes.byref(terms), out.data_ptr(), like.numel(), int(round_bf16), _stream()), "ode_rk_combine")
+    return out
+
+
+def ode_error_ratio_workspace(n: int, device) -> torch.Tensor:
+    return torch.empty(int(_lib.lib().dmvae_ode_error_ratio_workspace(int(n))), dtype=torch.uint8, device=device)
+
+
+def ode_error_ratio(y0: torch.Tensor, y1: torch.Tensor, ks: Sequence[torch.Tensor], cs: Sequence[float], atol: float, rtol: float, round_bf16: bool = False,
+                    result: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None, err_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dopri5's error test (integrators.py:79-118): err = sum_j cs[j] * ks[j] (ode_rk_combine's arithmetic), e = err / (atol + rtol * max(|y0|, |y1|)) ->
+    result [2] f32 on the device: result[0] = mean(e^2) (f64 partial sums in a fixed order), result.view(int32)[1] = 1 if y1 holds a non-finite value."""
+    _req(y0, f32, "y0")
+    _same(_req(y1, f32, "y1"), y0, "y1")
+    terms = _ode_terms(ks, cs, y0)
+    if err_out is not None:
+        _same(_req(err_out, f32, "err_out"), y0, "err_out")
+    if workspace is None:
+        workspace = ode_error_ratio_workspace(y0.numel(), y0.device)
+    _req(workspace, torch.uint8, "workspace")
+    if workspace.numel() < _lib.lib().dmvae_ode_error_ratio_workspace(y0.numel()) or workspace.device != y0.device:
+        raise ValueError("ode_error_ratio: workspace too small or on another device (ode_error_ratio_workspace)")
+    if result is None:
+        result = torch.empty(2, dtype=f32, device=y0.device)
+    _req(result, f32, "result")
+    if result.numel() != 2 or result.device != y0.device:
+        raise ValueError("ode_error_ratio: result must be a [2] f32 tensor on y0's device")
+    check(_lib.lib().dmvae_ode_error_ratio(y0.data_ptr(), y1.data_ptr(), ctypes.byref(terms), float(atol), float(rtol), int(round_bf16), _ptr(err_out),
+                                           workspace.data_ptr(), result.data_ptr(), y0.numel(), _stream()), "ode_error_ratio")
+    return result
+
+
+def ode_dense_output(y0: torch.Tensor, y1: torch.Tensor, y_mid: torch.Tensor, f0: torch.Tensor, f1: torch.Tensor, dt: float, x: float,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The quartic dense output of one accepted dopri5 step at x = (t - t0) / (t1 - t0) (torchdiffeq's _interp_fit + _interp_evaluate, integrators.py:79-118)
+    in their operation order.  y0, y1, y_mid, out f32; f0, f1 bf16 or f32; one shape; dt and x are used as f32."""
+    _req(y0, f32, "y0")
+    for name, t in (("y1", y1), ("y_mid", y_mid)):
+        _same(_req(t, f32, name), y0, name)
+    for name, t in (("f0", f0), ("f1", f1)):
+        _same(_req(t, bf16 if t.dtype == bf16 else f32, name), y0, name)
+    if out is None:
+        out = torch.empty_like(y0)
+    _same(_req(out, f32, "out"), y0, "out")
+    fb = int(f0.dtype == bf16) | (int(f1.dtype == bf16) << 1)
+    check(_lib.lib().dmvae_ode_dense_output(y0.data_ptr(), y1.data_ptr(), y_mid.data_ptr(), f0.data_ptr(), f1.data_ptr(), fb, float(dt), float(x),
+                                            out.data_ptr(), y0.numel(), _stream()), "ode_dense_output")
+    return out
 
 
 def image_to_u8(y: torch.Tensor, channels: int, round_bf16: bool = False) -> torch.Tensor:

@@ -5,11 +5,14 @@
 What runs where: a sampler step is one model forward (LightningDiT on the HIP kernels, models/lightningdit_fast.py) plus the state update;
 the Euler-Maruyama update -- velocity -> score, drift, mean, noise injection -- is ONE kernel pass over the state (`ops.sde_euler_step`, csrc/sampler.hip)
 with the reference's f32 arithmetic order, so for the same model output the trajectory is bit-identical to the PyTorch reference.  Heun and
-the fixed-grid ODE methods are composed from device tensor ops.  The per-step noise is drawn on the CPU generator and moved to the state's
+the fixed-grid ODE methods are composed from device tensor ops.  The reference's default ODE method, adaptive dopri5 (torchdiffeq's, restated below), runs
+on the device for a CUDA f32 state: the model forwards plus three kernels of csrc/sampler.hip per step (`ops.ode_rk_combine`, `ops.ode_error_ratio`,
+`ops.ode_dense_output`) and one 8-byte readback per attempted step for the step-size controller.  The per-step noise is drawn on the CPU generator and moved to the state's
 device exactly as the reference does (`th.randn(x.size()).to(x)`, integrators.py:28,38), so a seeded run consumes the same stream.
 
 Not built: the GVP / VP plans (path.py:138-191; never selected by the reference's scripts: `path_type` is "Linear" everywhere), the likelihood
-sampler (transport.py:409-458) and adaptive ODE solvers unless `torchdiffeq` (an unpinned third-party dependency, absent from this image) is importable."""
+sampler (transport.py:409-458), dopri5 on CPU or non-f32 states and the other adaptive ODE solvers unless `torchdiffeq` (an unpinned third-party
+dependency) is importable."""
 from __future__ import annotations
 
 import enum
@@ -20,7 +23,7 @@ import torch as th
 
 from . import ops
 
-FUSED_STATE_UPDATE = True      # False composes the Euler-Maruyama update from tensor ops (tests/test_gpu_sampler.py compares the two)
+FUSED_STATE_UPDATE = True      # False composes the Euler-Maruyama / dopri5 updates from tensor ops (tests/test_gpu_sampler.py, test_gpu_ode_dopri5.py compare)
 
 
 class ModelType(enum.Enum):
@@ -342,22 +345,234 @@ class sde:
 
 _FIXED_GRID = ("euler", "midpoint", "heun3", "rk4")
 
+# ---- dopri5: torchdiffeq 0.2.x's RKAdaptiveStepsizeODESolver with the Dormand-Prince-Shampine tableau (integrators.py:79-118 hands it the drift).
+# Unpinned (torchdiffeq is not a dependency); tests/dopri5_spec.py restates the method in float64 with exact fractions.  The tableau is written as
+# torchdiffeq writes it (float64 quotients, cast to the state's dtype).
+DOPRI5_ALPHA = (1 / 5, 3 / 10, 4 / 5, 8 / 9, 1., 1.)
+DOPRI5_BETA = ((1 / 5,),
+               (3 / 40, 9 / 40),
+               (44 / 45, -56 / 15, 32 / 9),
+               (19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729),
+               (9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656),
+               (35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84))
+DOPRI5_C_ERROR = (35 / 384 - 1951 / 21600, 0, 500 / 1113 - 22642 / 50085, 125 / 192 - 451 / 720, -2187 / 6784 - -12231 / 42400, 11 / 84 - 649 / 6300,
+                  -1. / 60.)
+DOPRI5_C_MID = (6025192743 / 30085553152 / 2, 0, 51252292925 / 65400821598 / 2, -2691868925 / 45128329728 / 2, 187940372067 / 1594534317056 / 2,
+                -1776094331 / 19743644256 / 2, 11237099 / 235043384 / 2)
+
+
+def dopri5_initial_h0(d0: float, d1: float) -> float:
+    """_select_initial_step's first guess from d0 = rms(y0 / scale), d1 = rms(f0 / scale)."""
+    return 1e-6 if d0 < 1e-5 or d1 < 1e-5 else 0.01 * d0 / d1
+
+
+def dopri5_initial_dt(h0: float, d1: float, d2: float, order: int = 4) -> float:
+    """_select_initial_step's result from h0, d1 and d2 = rms((f1 - f0) / scale) / h0; dopri5 passes order 5 - 1."""
+    if d1 <= 1e-15 and d2 <= 1e-15:
+        h1 = max(1e-6, h0 * 1e-3)
+    else:
+        h1 = (0.01 / max(d1, d2)) ** (1. / (order + 1))
+    return min(100 * h0, h1)
+
+
+def dopri5_next_dt(dt: float, ratio: float, safety=0.9, ifactor=10.0, dfactor=0.2, order=5) -> float:
+    """_optimal_step_size: the step after one with error ratio `ratio` (accepted or not).  A NaN ratio gives a NaN step, which the next step's
+    underflow check turns into an error (torch.max / torch.min propagate NaN; Python's min / max would not)."""
+    if ratio != ratio:
+        return float("nan")
+    if ratio == 0:
+        return dt * ifactor
+    if ratio < 1:
+        dfactor = 1.0
+    return dt * min(ifactor, max(safety / ratio ** (1. / order), dfactor))
+
+
+def dopri5_accept(ratio: float) -> bool:
+    return ratio <= 1
+
+
+def dopri5_stage_times(t0: float, dt: float):
+    """The six stage times of a step from t0 (float64): t0 + alpha_i dt in the state's dtype (f32), the last two at t1 = t0 + dt (float64, then f32)."""
+    t, h = np.float32(t0), np.float32(dt)
+    return [np.float32(t + np.float32(a) * h) for a in DOPRI5_ALPHA[:4]] + [np.float32(t0 + dt)] * 2
+
+
+def dopri5_weights(coef, dt: float):
+    """coef * dt in f32, as torchdiffeq's `beta_i * dt` / `dt * c_error` / `dt * mid` with the tableau cast to the state's dtype."""
+    return [float(np.float32(c) * np.float32(dt)) for c in coef]
+
+
+def dopri5_dense_x(t: float, t0: float, t1: float) -> float:
+    """_interp_evaluate's x, formed in float64 and cast to the state's dtype."""
+    return float(np.float32((t - t0) / (t1 - t0)))
+
+
+def dopri5_pending_outputs(ts, i: int, t1: float):
+    """Grid bookkeeping: the indices of the output times from i on that the step ending at t1 covers (torchdiffeq steps while t_i > t1)."""
+    j = i
+    while j < len(ts) and ts[j] <= t1:
+        j += 1
+    return range(i, j)
+
+
+def _rms(v):
+    return v.abs().pow(2).mean().sqrt()
+
+
+class _Dopri5:
+    """The solver on a CUDA f32 state.  fused: the combine / error-ratio / dense-output kernels of csrc/sampler.hip and one 8-byte readback per
+    attempted step; else the same algorithm composed from tensor ops (what the kernels are tested against).  round_bf16: the three weighted sums
+    in the bf16 form torchdiffeq's k.matmul takes under autocast(bf16)."""
+
+    def __init__(self, fn, y0, *, atol, rtol, fused, round_bf16):
+        self.fn, self.atol, self.rtol, self.fused, self.amp = fn, float(atol), float(rtol), fused, round_bf16
+        self.nfe = 0
+        self.k = [th.empty_like(y0) for _ in range(7)]      # f32, like torchdiffeq's k buffer: a bf16 model output is copied exactly
+        if fused:
+            self.ws = ops.ode_error_ratio_workspace(y0.numel(), y0.device)
+            self.res = th.empty(2, dtype=th.float32, device=y0.device)
+            self.host = th.empty(2, dtype=th.float32).pin_memory()
+
+    def f(self, t32, y, slot):
+        """k[slot] = drift(t, y); t goes to the model as th.full (== th.ones(B).to(x) * t without a blocking host copy)."""
+        tv = th.full((y.size(0),), float(t32), device=y.device, dtype=y.dtype)
+        r = self.fn(tv, y)
+        assert r.shape == y.shape, "Output shape from ODE solver must match input shape"
+        self.k[slot].copy_(r)
+        self.nfe += 1
+
+    def combine(self, y0, coef, dt, out):
+        """out = y0 + sum_j (coef_j dt) k_j; y0 None: the sum alone."""
+        cs = dopri5_weights(coef, dt)
+        ks = self.k[:len(cs)]
+        if self.fused:
+            return ops.ode_rk_combine(y0, ks, cs, round_bf16=self.amp, out=out)
+        s = None
+        for c, k in zip(cs, ks):
+            if self.amp:
+                c, k = float(th.tensor(c).to(th.bfloat16)), k.to(th.bfloat16).float()
+            s = c * k if s is None else s + c * k
+        if self.amp:
+            s = s.to(th.bfloat16).float()
+        out.copy_(s if y0 is None else y0 + s)
+        return out
+
+    def error_ratio(self, y0, y1, dt):
+        """-> (ratio, y1 holds a non-finite value) on the host: the one device -> host read of a step."""
+        cs = dopri5_weights(DOPRI5_C_ERROR, dt)
+        if self.fused:
+            ops.ode_error_ratio(y0, y1, self.k, cs, self.atol, self.rtol, round_bf16=self.amp, result=self.res, workspace=self.ws)
+            self.host.copy_(self.res, non_blocking=True)
+            ev = th.cuda.Event()
+            ev.record()
+            ev.synchronize()
+            return float(np.sqrt(np.float64(self.host[0].item()))), bool(self.host.view(th.int32)[1].item())
+        err = self.combine(None, DOPRI5_C_ERROR, dt, th.empty_like(y0))
+        tol = self.atol + self.rtol * th.max(y0.abs(), y1.abs())
+        mean_sq = (err / tol).double().pow(2).mean().float()         # the kernel's precision: f32 e, its squares summed in f64, the mean rounded to f32
+        return float(np.sqrt(np.float64(mean_sq.item()))), not bool(th.isfinite(y1).all())
+
+    def dense(self, y0, y1, ymid, dt, x, out):
+        f0, f1 = self.k[0], self.k[6]
+        if self.fused:
+            return ops.ode_dense_output(y0, y1, ymid, f0, f1, dt, x, out=out)
+        dt, x = float(np.float32(dt)), np.float32(x)          # Python floats holding f32 values: torch applies them in f32
+        a = 2 * dt * (f1 - f0) - 8 * (y1 + y0) + 16 * ymid
+        b = dt * (5 * f0 - 3 * f1) + 18 * y0 + 14 * y1 - 32 * ymid
+        c = dt * (f1 - 4 * f0) - 11 * y0 - 5 * y1 + 16 * ymid
+        d = dt * f0
+        total = y0 + float(x) * d
+        xp = x
+        for coef in (c, b, a):
+            xp = np.float32(xp * x)
+            total = total + float(xp) * coef
+        out.copy_(total)
+        return out
+
+    def initial_dt(self, t0, y0):
+        """_select_initial_step (order 5 - 1) with f0 = k[0] already evaluated; one more evaluation (k[1] holds it until the first stage)."""
+        scale = self.atol + y0.abs() * self.rtol
+        d0, d1 = (float(v) for v in th.stack([_rms(y0 / scale), _rms(self.k[0] / scale)]).tolist())
+        h0 = dopri5_initial_h0(d0, d1)
+        h32 = float(np.float32(h0))
+        self.f(np.float32(t0 + h32), y0 + h32 * self.k[0], 1)
+        d2 = float(_rms((self.k[1] - self.k[0]) / scale)) / h0
+        return dopri5_initial_dt(h0, d1, d2)
+
+    def solve(self, y0, ts, max_num_steps):
+        """-> [len(ts), *y0.shape]: out[0] = y0, then the dense output of the step covering each later grid time."""
+        out = th.empty((len(ts), *y0.shape), dtype=y0.dtype, device=y0.device)
+        out[0].copy_(y0)
+        self.n_accepted = self.n_rejected = 0
+        y, y1, ystage, ymid = y0.clone(), th.empty_like(y0), th.empty_like(y0), th.empty_like(y0)
+        finite = bool(th.isfinite(y).all())
+        t0 = ts[0]
+        self.f(np.float32(t0), y, 0)
+        dt = self.initial_dt(t0, y)
+        i, steps = 1, 0
+        while i < len(ts):
+            if steps >= max_num_steps:
+                raise RuntimeError(f"max_num_steps exceeded ({steps}>={max_num_steps})")
+            if not finite:
+                raise RuntimeError("non-finite values in state `y`")
+            if not t0 + dt > t0:
+                raise RuntimeError(f"underflow in dt {dt}")
+            steps += 1
+            times = dopri5_stage_times(t0, dt)
+            for s, beta in enumerate(DOPRI5_BETA):
+                yi = y1 if s == len(DOPRI5_BETA) - 1 else ystage       # the last stage's input is y1 (FSAL: its evaluation is the next f0)
+                self.combine(y, beta, dt, yi)
+                self.f(times[s], yi, s + 1)
+            ratio, y1_bad = self.error_ratio(y, y1, dt)
+            dt_next = dopri5_next_dt(dt, ratio)
+            if dopri5_accept(ratio):
+                self.n_accepted += 1
+                t1 = t0 + dt
+                todo = dopri5_pending_outputs(ts, i, t1)
+                if len(todo):
+                    self.combine(y, DOPRI5_C_MID, dt, ymid)
+                    for j in todo:
+                        self.dense(y, y1, ymid, np.float32(dt), dopri5_dense_x(ts[j], t0, t1), out[j])
+                    i, steps = todo.stop, 0
+                y, y1 = y1, y
+                self.k[0], self.k[6] = self.k[6], self.k[0]
+                t0, finite = t1, not y1_bad
+            else:
+                self.n_rejected += 1
+            dt = dt_next
+        return out
+
 
 class ode:
-    """integrators.py:79-118.  The reference hands the drift to `torchdiffeq.odeint`; that package is not in this image, so the fixed-grid methods
+    """integrators.py:79-118.  The reference hands the drift to `torchdiffeq.odeint`; that package is not a dependency, so the fixed-grid methods
     (torchdiffeq's fixed-grid set: explicit Euler, midpoint, Heun's third-order rule, the 3/8-rule RK4 -- one solver step per interval of the time grid; unpinned,
-    there is no torchdiffeq here to compare against) are
-    integrated here, and anything else ("dopri5", the reference's default) is delegated to torchdiffeq when it can be imported."""
+    there is no torchdiffeq here to compare against) and, for a CUDA f32 state, adaptive "dopri5" (the reference's default; `_Dopri5`) are
+    integrated here, and anything else is delegated to torchdiffeq when it can be imported.  After a dopri5 call `nfe`, `n_accepted` and
+    `n_rejected` hold its model evaluations and steps."""
 
-    def __init__(self, drift, *, t0, t1, sampler_type, num_steps, atol, rtol, time_dist_shift=1.0):
+    def __init__(self, drift, *, t0, t1, sampler_type, num_steps, atol, rtol, time_dist_shift=1.0, max_num_steps=2 ** 31 - 1):
         assert t0 < t1, "ODE sampler has to be in forward time"
         self.drift = drift
         t = th.linspace(t0, t1, num_steps)
         self.t = 1 - time_dist_shift * (1 - t) / (1 + (time_dist_shift - 1) * (1 - t))
         self.atol, self.rtol = atol, rtol
         self.sampler_type = sampler_type
+        self.max_num_steps = max_num_steps      # dopri5: attempted steps allowed per output interval (torchdiffeq's max_num_steps)
+        self.nfe = self.n_accepted = self.n_rejected = 0      # dopri5's counters of the last call
+
+    def _dopri5(self, x, model, **model_kwargs):
+        """dopri5 on a CUDA f32 state; the output is stacked [num_steps, ...] like odeint's."""
+        solver = _Dopri5(lambda t, y: self.drift(y, t, model, **model_kwargs), x, atol=self.atol, rtol=self.rtol, fused=FUSED_STATE_UPDATE,
+                         round_bf16=th.is_autocast_enabled())
+        try:
+            with th.no_grad():
+                return solver.solve(x.contiguous(), self.t.double().tolist(), self.max_num_steps)
+        finally:
+            self.nfe, self.n_accepted, self.n_rejected = solver.nfe, getattr(solver, "n_accepted", 0), getattr(solver, "n_rejected", 0)
 
     def sample(self, x, model, **model_kwargs):
+        if self.sampler_type == "dopri5" and not isinstance(x, tuple) and x.is_cuda and x.dtype == th.float32:
+            return self._dopri5(x, model, **model_kwargs)
         device = x[0].device if isinstance(x, tuple) else x.device
 
         def fn(t, x):

@@ -672,7 +672,7 @@ int dmvae_adamw_ema_step_shadow(void* params, const void* grads, void* exp_avg, 
                                 const void* norm_out3, size_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, int step, float ema_decay, dmvae_stream_t stream);
 
-/* ---- downstream consumers: SDE sampler state update and image -> uint8 (sample_50k.py:142-164) ---- */
+/* ---- downstream consumers: SDE sampler state update, image -> uint8 (sample_50k.py:142-164), the dopri5 ODE sampler ---- */
 
 /* One Euler-Maruyama step of diffusion/transport/integrators.py:27-35 on the whole state with the drift of transport.py:254-257 and
  * the velocity -> score conversion of path.py:74-89 folded in; every coefficient depends on t only (shared by the batch) and is
@@ -686,6 +686,38 @@ int dmvae_sde_euler_step(const void* x, const void* v, int v_is_bf16, const void
 /* out[npix][c] uint8 = (uint8) clamp(127.5 * y + 128, 0, 255) for y [npix][c_stride] f32 (NHWC decoder output, first c channels):
  * sample_50k.py:151 without the NCHW round trip.  round_bf16 != 0 rounds y to bf16 first (an autocast decoder's `.float()`). */
 int dmvae_image_to_u8(const void* y, void* out, size_t npix, int c, int c_stride, int round_bf16, dmvae_stream_t stream);
+
+/* The adaptive dopri5 ODE sampler: Sampler.sample_ode's default method (diffusion/transport/transport.py:356-407), which the reference hands to
+ * torchdiffeq.odeint (diffusion/transport/integrators.py:79-118; sample_50k.py:85-99, toy_example_2d/train_diffusion.py:308-312 run it under
+ * autocast(bf16)).  The host keeps the step-size controller (float64 scalars); these are the passes over the state.
+ * struct dmvae_ode_terms travels BY VALUE into the kernels (no device table): k[j] [n] bf16 (bit j of k_bf16 set) or f32, c[j] the f32 weight
+ * (tableau coefficient * dt, rounded to f32 by the host), j < nk <= DMVAE_ODE_MAX_TERMS. */
+#define DMVAE_ODE_MAX_TERMS 7
+typedef struct {
+  const void* k[DMVAE_ODE_MAX_TERMS];
+  float c[DMVAE_ODE_MAX_TERMS];
+  int32_t nk, k_bf16;
+} dmvae_ode_terms;
+/* out = y0 + S,  S = sum_{j < nk} c_j k_j (j ascending, each product and sum rounded to f32; no FMA); y0 = NULL: out = S.  The stage inputs and
+ * y_mid of torchdiffeq's _runge_kutta_step / _interp_fit (integrators.py:79-118).  round_bf16 != 0 is what torchdiffeq's k.matmul(coef * dt) does
+ * under autocast(bf16): c_j and k_j rounded to bf16, products summed in f32, S rounded to bf16 before it is added to the f32 y0.
+ * y0, out: [n] f32; any n (quads when every pointer is aligned for them, a scalar tail otherwise). */
+int dmvae_ode_rk_combine(const void* y0, const dmvae_ode_terms* terms, void* out, size_t n, int round_bf16, dmvae_stream_t stream);
+/* Bytes of the error ratio's workspace (per-workgroup partials) for a state of n elements. */
+size_t dmvae_ode_error_ratio_workspace(size_t n);
+/* The step's error test (integrators.py:79-118 -> torchdiffeq's _compute_error_ratio): err = S of dmvae_ode_rk_combine (c = c_err * dt, same
+ * round_bf16), e = err / (atol + rtol * max(|y0|, |y1|)), then result = {f32 mean(e^2), int32 "y1 holds a non-finite value"} (8 bytes, device).
+ * Two launches: per-workgroup f64 partial sums, then one workgroup sums them in a fixed order (the same bits on every run; no atomics).
+ * err_out ([n] f32) may be NULL.  y0, y1: [n] f32; any n. */
+int dmvae_ode_error_ratio(const void* y0, const void* y1, const dmvae_ode_terms* terms, float atol, float rtol, int round_bf16, void* err_out,
+                          void* workspace, void* result, size_t n, dmvae_stream_t stream);
+/* Dense output of the last accepted step at x = (t - t0) / (t1 - t0) (transport.py:356-407 returns the solution at the shifted grid; torchdiffeq's
+ * _interp_fit + _interp_evaluate, integrators.py:79-118), in their operation order:
+ *   a = 2dt(f1 - f0) - 8(y1 + y0) + 16 y_mid;  b = dt(5f0 - 3f1) + 18y0 + 14y1 - 32y_mid;  c = dt(f1 - 4f0) - 11y0 - 5y1 + 16y_mid;  d = dt f0
+ *   out = y0 + x d + x^2 c + x^3 b + x^4 a   (running powers of x)
+ * y0, y1, y_mid, out: [n] f32; f0 (bit 0 of f_bf16) and f1 (bit 1) bf16 or f32; any n. */
+int dmvae_ode_dense_output(const void* y0, const void* y1, const void* y_mid, const void* f0, const void* f1, int f_bf16, float dt, float x, void* out,
+                           size_t n, dmvae_stream_t stream);
 
 /* ---- fp32 parity mode (DMVAE_PARITY=1; csrc/parity.hip) ---------------------------------------------------------------------------
  * north_star: "match the reference PyTorch-CPU path within 1e-4 relative fp32".  In this mode activations are f32 NHWC and every
