@@ -104,6 +104,7 @@ SIGNATURES = {
     "dmvae_ode_error_ratio_workspace": (c_size_t, [c_size_t]),
     "dmvae_ode_error_ratio": (c_int, [c_void_p, c_void_p, POINTER(OdeTerms), c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dmvae_ode_dense_output": (c_int, [c_void_p] * 5 + [c_int, c_float, c_float, c_void_p, c_size_t, c_void_p]),
+    "dmvae_ode_hutchinson_pack": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
     "dmvae_batchnorm_running_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p]),
     "dmvae_diffaug_fwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "dmvae_diffaug_bwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
@@ -145,10 +146,12 @@ SIGNATURES = {
     "dmvae_qknorm_rope_bwd": (c_int, [c_void_p] * 12 + [c_size_t] + [c_int] * 5 + [c_float, c_int, c_void_p]),
     "dmvae_qknorm_rope_bwd_nblk": (c_int, [c_int] * 5),
     "dmvae_qknorm_rope_bwd_partial": (c_int, [c_void_p] * 10 + [c_size_t] + [c_int] * 5 + [c_float, c_void_p]),
+    "dmvae_qknorm_rope_bwd_dx": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_dit_stack_bps": (c_int, [c_int]),
     "dmvae_dit_stack_part_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dmvae_dit_stack_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dmvae_dit_boundary_bwd": (c_int, [c_void_p] * 4 + [c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dmvae_dit_boundary_bwd_dx": (c_int, [c_void_p] * 4 + [c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dmvae_dit_stack_finalize": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p] + [c_int] * 5 + [c_void_p]),
     "dmvae_colsum2_batched": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "dmvae_linear_rows_batched_bf16": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong] + [c_int] * 11 + [c_void_p]),

@@ -462,7 +462,9 @@ __global__ void rmsnorm_modulate_bwd_weight_kernel(const float* __restrict__ wpa
 }
 
 // Backward of qknorm_rope: dq', dk' [B*H][N][Dp] bf16 (w.r.t. the rotated, normalised q / k), dv [B*H][N][D] -> dqkv [B][N][3][H][D] bf16 and the
-// per-block partial sums of the two norm weights' gradients, part [gridDim.x][2][D].
+// per-block partial sums of the two norm weights' gradients, part [gridDim.x][2][D].  WGRAD = false: dqkv only (the input-gradient route: frozen norm
+// weights), no accumulators and nothing written to part.
+template <bool WGRAD>
 __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const bf16* __restrict__ dq, const bf16* __restrict__ dk, const bf16* __restrict__ dv,
                                                               const bf16* __restrict__ qkv, const float* __restrict__ qw, const float* __restrict__ kw,
                                                               const float* __restrict__ cosb, const float* __restrict__ sinb, bf16* __restrict__ dqkv,
@@ -501,7 +503,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const bf16* __rest
       const float rq = rsqrtf(wave_sum(q0 * q0 + q1 * q1) / (float)D + eps);
       const float rk = rsqrtf(wave_sum(k0 * k0 + k1 * k1) / (float)D + eps);
       const float nq0 = q0 * rq, nq1 = q1 * rq, nk0 = k0 * rk, nk1 = k1 * rk;
-      gq0 += dq0 * (float)(bf16)nq0; gq1 += dq1 * (float)(bf16)nq1; gk0 += dk0 * (float)(bf16)nk0; gk1 += dk1 * (float)(bf16)nk1;
+      if constexpr (WGRAD) { gq0 += dq0 * (float)(bf16)nq0; gq1 += dq1 * (float)(bf16)nq1; gk0 += dk0 * (float)(bf16)nk0; gk1 += dk1 * (float)(bf16)nk1; }
       const float eq0 = dq0 * wq0, eq1 = dq1 * wq1, ek0 = dk0 * wk0, ek1 = dk1 * wk1;       // d(normalised)
       const float mq = wave_sum(eq0 * nq0 + eq1 * nq1) / (float)D, mk = wave_sum(ek0 * nk0 + ek1 * nk1) / (float)D;
       if (live) {
@@ -513,6 +515,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const bf16* __rest
       }
     }
   }
+  if constexpr (!WGRAD) return;
   red[wave][0][lane] = gq0; red[wave][1][lane] = gq1; red[wave][2][lane] = gk0; red[wave][3][lane] = gk1;
   __syncthreads();
   if (threadIdx.x < 2 * D) {            // part[blk][0][d] = dq_weight, part[blk][1][d] = dk_weight
@@ -838,7 +841,8 @@ extern "C" int dmvae_rmsnorm_modulate_bwd(const void* da, const void* x, const v
 
 namespace dmvae_dit {
 // Backward with the same 16-lanes-per-row mapping (head dim % 8 == 0): per lane 8 channels of q and k, the two per-row reductions as 16-lane butterflies,
-// weight-gradient accumulators per lane over the rows it walks, combined over the block's 16 row groups in a fixed order.
+// weight-gradient accumulators per lane over the rows it walks, combined over the block's 16 row groups in a fixed order.  WGRAD = false: dqkv only.
+template <bool WGRAD>
 __global__ __launch_bounds__(256) void qknorm_rope16_bwd_kernel(const bf16* __restrict__ dq, const bf16* __restrict__ dk, const bf16* __restrict__ dv,
                                                                 const bf16* __restrict__ qkv, const float* __restrict__ qw, const float* __restrict__ kw,
                                                                 const float* __restrict__ cosb, const float* __restrict__ sinb, bf16* __restrict__ dqkv,
@@ -888,7 +892,7 @@ __global__ __launch_bounds__(256) void qknorm_rope16_bwd_kernel(const bf16* __re
 #pragma unroll
     for (int e = 0; e < 8; e++) {
       nq[e] = q[e] * rq; nk[e] = k[e] * rk;
-      gq[e] += eq[e] * (float)(bf16)nq[e]; gk[e] += ek[e] * (float)(bf16)nk[e];       // d(weight): the weight multiplies the bf16-rounded normalised value
+      if constexpr (WGRAD) { gq[e] += eq[e] * (float)(bf16)nq[e]; gk[e] += ek[e] * (float)(bf16)nk[e]; }   // d(weight): the weight multiplies the bf16-rounded normalised value
       eq[e] *= wq[e]; ek[e] *= wk[e];                                                 // d(normalised)
       mq += eq[e] * nq[e]; mk += ek[e] * nk[e];
     }
@@ -907,6 +911,7 @@ __global__ __launch_bounds__(256) void qknorm_rope16_bwd_kernel(const bf16* __re
       *reinterpret_cast<uint4*>(dbase + (size_t)(2 * H + h) * D) = dvv;
     }
   }
+  if constexpr (!WGRAD) return;
 #pragma unroll
   for (int e = 0; e < 8; e++) { red[grp][sub][e] = gq[e]; red[grp][sub][8 + e] = gk[e]; }
   __syncthreads();
@@ -933,24 +938,27 @@ extern "C" int dmvae_qknorm_rope_bwd_nblk(int batch, int seq, int heads, int hea
   return qk_bwd_nblk(batch, seq, heads, head_dim, head_dim_padded);
 }
 
+// part == NULL: the dx-only instantiations (no norm-weight partials; part_bytes is ignored)
 static int qk_bwd_launch(const void* dq, const void* dk, const void* dv, const void* qkv, const void* q_weight, const void* k_weight, const void* cos_table,
                          const void* sin_table, void* dqkv, void* part, size_t part_bytes, int batch, int seq, int heads, int head_dim, int head_dim_padded, float eps,
                          hipStream_t stream, int* nblk_out) {
-  DMVAE_CHECK_ARG(dq && dk && dv && qkv && q_weight && k_weight && cos_table && sin_table && dqkv && part && batch > 0 && seq > 0 && heads > 0,
+  DMVAE_CHECK_ARG(dq && dk && dv && qkv && q_weight && k_weight && cos_table && sin_table && dqkv && batch > 0 && seq > 0 && heads > 0,
                   "qknorm_rope_bwd: bad argument");
   DMVAE_CHECK_ARG(head_dim % 2 == 0 && head_dim >= 2 && head_dim_padded >= head_dim && head_dim_padded <= 128,
                   "qknorm_rope_bwd: head dim must be even, padded head dim <= 128 (got %d, %d)", head_dim, head_dim_padded);
   const int tokens = batch * seq;
   const int nblk = qk_bwd_nblk(batch, seq, heads, head_dim, head_dim_padded);
-  DMVAE_CHECK_ARG(part_bytes >= (size_t)nblk * 2 * head_dim * sizeof(float), "qknorm_rope_bwd: workspace too small");
+  DMVAE_CHECK_ARG(!part || part_bytes >= (size_t)nblk * 2 * head_dim * sizeof(float), "qknorm_rope_bwd: workspace too small");
+#define DMVAE_QK_BWD(K, WG)                                                                                                                               \
+  hipLaunchKernelGGL((K<WG>), dim3(nblk), dim3(256), 0, stream, (const bf16*)dq, (const bf16*)dk, (const bf16*)dv, (const bf16*)qkv, (const float*)q_weight, \
+                     (const float*)k_weight, (const float*)cos_table, (const float*)sin_table, (bf16*)dqkv, (float*)part, tokens, seq, heads, head_dim,       \
+                     head_dim_padded, eps)
   if (head_dim % 8 == 0 && head_dim_padded % 8 == 0 && 2 * head_dim <= 256) {
-    hipLaunchKernelGGL(qknorm_rope16_bwd_kernel, dim3(nblk), dim3(256), 0, stream, (const bf16*)dq, (const bf16*)dk, (const bf16*)dv, (const bf16*)qkv,
-                       (const float*)q_weight, (const float*)k_weight, (const float*)cos_table, (const float*)sin_table, (bf16*)dqkv, (float*)part,
-                       tokens, seq, heads, head_dim, head_dim_padded, eps);
-  } else
-  hipLaunchKernelGGL(qknorm_rope_bwd_kernel, dim3(nblk), dim3(256), 0, stream, (const bf16*)dq, (const bf16*)dk, (const bf16*)dv, (const bf16*)qkv,
-                     (const float*)q_weight, (const float*)k_weight, (const float*)cos_table, (const float*)sin_table, (bf16*)dqkv, (float*)part,
-                     tokens, seq, heads, head_dim, head_dim_padded, eps);
+    if (part) DMVAE_QK_BWD(qknorm_rope16_bwd_kernel, true);
+    else DMVAE_QK_BWD(qknorm_rope16_bwd_kernel, false);
+  } else if (part) DMVAE_QK_BWD(qknorm_rope_bwd_kernel, true);
+  else DMVAE_QK_BWD(qknorm_rope_bwd_kernel, false);
+#undef DMVAE_QK_BWD
   DMVAE_CHECK_LAUNCH();
   *nblk_out = nblk;
   return 0;
@@ -960,7 +968,7 @@ extern "C" int dmvae_qknorm_rope_bwd(const void* dq, const void* dk, const void*
                                      const void* cos_table, const void* sin_table, void* dqkv, void* dq_weight, void* dk_weight, void* workspace,
                                      size_t workspace_bytes, int batch, int seq, int heads, int head_dim, int head_dim_padded, float eps, int accumulate,
                                      hipStream_t stream) {
-  DMVAE_CHECK_ARG(dq_weight && dk_weight, "qknorm_rope_bwd: bad argument");
+  DMVAE_CHECK_ARG(dq_weight && dk_weight && workspace, "qknorm_rope_bwd: bad argument");
   int nblk = 0;
   const int rc = qk_bwd_launch(dq, dk, dv, qkv, q_weight, k_weight, cos_table, sin_table, dqkv, workspace, workspace_bytes, batch, seq, heads, head_dim, head_dim_padded, eps,
                                stream, &nblk);
@@ -976,6 +984,15 @@ extern "C" int dmvae_qknorm_rope_bwd(const void* dq, const void* dk, const void*
 extern "C" int dmvae_qknorm_rope_bwd_partial(const void* dq, const void* dk, const void* dv, const void* qkv, const void* q_weight, const void* k_weight,
                                              const void* cos_table, const void* sin_table, void* dqkv, void* part, size_t part_bytes, int batch, int seq, int heads,
                                              int head_dim, int head_dim_padded, float eps, hipStream_t stream) {
+  DMVAE_CHECK_ARG(part, "qknorm_rope_bwd_partial: null partial-sum buffer");
   int nblk = 0;
   return qk_bwd_launch(dq, dk, dv, qkv, q_weight, k_weight, cos_table, sin_table, dqkv, part, part_bytes, batch, seq, heads, head_dim, head_dim_padded, eps, stream, &nblk);
+}
+
+// dqkv only: the same first-stage kernels and grid as dmvae_qknorm_rope_bwd_partial (the same dqkv bits) with the norm-weight accumulators compiled out.
+extern "C" int dmvae_qknorm_rope_bwd_dx(const void* dq, const void* dk, const void* dv, const void* qkv, const void* q_weight, const void* k_weight,
+                                        const void* cos_table, const void* sin_table, void* dqkv, int batch, int seq, int heads, int head_dim, int head_dim_padded,
+                                        float eps, hipStream_t stream) {
+  int nblk = 0;
+  return qk_bwd_launch(dq, dk, dv, qkv, q_weight, k_weight, cos_table, sin_table, dqkv, nullptr, 0, batch, seq, heads, head_dim, head_dim_padded, eps, stream, &nblk);
 }

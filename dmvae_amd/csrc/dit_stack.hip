@@ -7,6 +7,7 @@
 //        GATE:  dy = bf16(gate[b] * dt) of the NEXT gated residual down the backward pass (its branch output y read here), with the partial sums of d gate.
 //        The per-block route ran these as two kernels (rmsnorm_modulate_bwd_apply_kernel + gated_residual_bwd_kernel, the second on 80 workgroups); fused, dt is
 //        read once and written once per boundary.
+//        PARTS = false is the dx-only form (dmvae_dit_boundary_bwd_dx) for a frozen model's input gradient.
 //   dit_bwd_finalize / dit_bwd_weight  ONE reduction of every boundary's partial sums at the end of the backward pass (57 boundaries for 28 blocks) into the
 //        bf16 adaLN-chunk gradients d mod [L][B][6C] and the 2 L norm-weight gradients, instead of two small launches per boundary.
 //   rows_wgrad_mfma_kernel             weight + bias gradient of L per-sample Linears (adaLN_modulation[1] of every block) in one launch on the matrix cores:
@@ -20,7 +21,9 @@ namespace dmvae_dit_stack {
 
 // grid (bps, B); thread t owns columns 4 t .. 4 t + 3 of every row of its block's row range (fully coalesced row accesses, no cross-lane work).
 // part: [B][bps][4][C]: d shift | d scale | d norm weight | d gate contributions of the block (slots of a disabled half are not written).
-template <bool APPLY, bool GATE>
+// PARTS = false (the input-gradient route: frozen weights, no adaLN gradient): dx_io and dy only -- no accumulators, nothing written to part, and the gate
+// half does not read y (y feeds only the d gate partials).
+template <bool APPLY, bool GATE, bool PARTS = true>
 __global__ __launch_bounds__(512) void rms_gate_bwd_kernel(const bf16* __restrict__ da, const float* __restrict__ x, const float* __restrict__ w,
                                                            const bf16* __restrict__ mod, const float2* __restrict__ rowstat, float* __restrict__ dx_io,
                                                            float* __restrict__ part, int N, int C, int stride, int scale_off, const bf16* __restrict__ y,
@@ -55,21 +58,23 @@ __global__ __launch_bounds__(512) void rms_gate_bwd_kernel(const bf16* __restric
         const float nh = v[e] * st.x, dv = (float)d[e];
         const float g = dv * gw[e] * gm[e];
         o[e] += st.x * (g - nh * st.y);
-        a0[e] += dv; a1[e] += dv * nh * gw[e]; a2[e] += dv * gm[e] * nh;
+        if constexpr (PARTS) { a0[e] += dv; a1[e] += dv * nh * gw[e]; a2[e] += dv * gm[e] * nh; }
       }
       *reinterpret_cast<f32x4*>(dx_io + off) = o;
     }
     if constexpr (GATE) {   // dit.hip::gated_residual_bwd_kernel's expressions
-      const bf16x4 yv = *reinterpret_cast<const bf16x4*>(y + off);
       bf16x4 q;
 #pragma unroll
-      for (int e = 0; e < 4; e++) {
-        q[e] = (bf16)(gg[e] * o[e]);
-        a3[e] += o[e] * (float)yv[e];
+      for (int e = 0; e < 4; e++) q[e] = (bf16)(gg[e] * o[e]);
+      if constexpr (PARTS) {
+        const bf16x4 yv = *reinterpret_cast<const bf16x4*>(y + off);
+#pragma unroll
+        for (int e = 0; e < 4; e++) a3[e] += o[e] * (float)yv[e];
       }
       *reinterpret_cast<bf16x4*>(dy + off) = q;
     }
   }
+  if constexpr (!PARTS) return;
   float* po = part + ((size_t)b * gridDim.x + blockIdx.x) * 4 * C;
   if constexpr (APPLY) {
     *reinterpret_cast<f32x4*>(po + c) = a0;
@@ -260,6 +265,36 @@ extern "C" int dmvae_dit_boundary_bwd(const void* da, const void* x, const void*
 #define DMVAE_BND(A, G)                                                                                                                                        \
   hipLaunchKernelGGL((rms_gate_bwd_kernel<A, G>), dim3(bps, batch), dim3(bt), 0, stream, (const bf16*)da, (const float*)x, (const float*)w, (const bf16*)mod, \
                      (const float2*)rowstat, (float*)dx_io, (float*)part_slot, seq, c, mod_stride, scale_off, (const bf16*)y, (const bf16*)gate_mod, gate_stride,  \
+                     gate_off, (bf16*)dy)
+  if (apply && gate) DMVAE_BND(true, true);
+  else if (apply) DMVAE_BND(true, false);
+  else DMVAE_BND(false, true);
+#undef DMVAE_BND
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+// dx_io / dy of dmvae_dit_boundary_bwd without the partial sums (the same grid and expressions: the same bits): the input-gradient route of a frozen model.
+extern "C" int dmvae_dit_boundary_bwd_dx(const void* da, const void* x, const void* w, const void* mod, int mod_stride, int scale_off, float eps, void* dx_io,
+                                         const void* gate_mod, int gate_stride, int gate_off, void* dy, void* rowstat, int batch, int seq, int c,
+                                         hipStream_t stream) {
+  const bool apply = da != nullptr, gate = gate_mod != nullptr;
+  DMVAE_CHECK_ARG((apply || gate) && dx_io && batch > 0 && seq > 0, "dit_boundary_bwd_dx: nothing to do or null buffers");
+  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= 2048, "dit_boundary_bwd_dx: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(!apply || (x && w && mod && rowstat && scale_off >= 0 && scale_off % 4 == 0 && mod_stride % 4 == 0 && scale_off + c <= mod_stride),
+                  "dit_boundary_bwd_dx: the norm half needs x, w, mod, rowstat and a scale offset that is a multiple of 4 inside the modulation row");
+  DMVAE_CHECK_ARG(!gate || (dy && gate_off >= 0 && gate_off % 4 == 0 && gate_stride % 4 == 0 && gate_off + c <= gate_stride),
+                  "dit_boundary_bwd_dx: the gate half needs dy and a gate offset that is a multiple of 4 inside the modulation row");
+  const int rows = batch * seq, bps = stack_bps(batch);
+  if (apply) {
+    hipLaunchKernelGGL(rowstat_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x, (const float*)w, (const bf16*)mod,
+                       (float2*)rowstat, rows, seq, c, mod_stride, scale_off, eps);
+    DMVAE_CHECK_LAUNCH();
+  }
+  const int bt = ((c / 4) + 63) / 64 * 64;
+#define DMVAE_BND(A, G)                                                                                                                                        \
+  hipLaunchKernelGGL((rms_gate_bwd_kernel<A, G, false>), dim3(bps, batch), dim3(bt), 0, stream, (const bf16*)da, (const float*)x, (const float*)w,             \
+                     (const bf16*)mod, (const float2*)rowstat, (float*)dx_io, nullptr, seq, c, mod_stride, scale_off, nullptr, (const bf16*)gate_mod, gate_stride, \
                      gate_off, (bf16*)dy)
   if (apply && gate) DMVAE_BND(true, true);
   else if (apply) DMVAE_BND(true, false);

@@ -9,6 +9,8 @@
 // The adaptive dopri5 ODE sampler (transport.py:356-407 -> torchdiffeq.odeint, integrators.py:79-118) adds three HBM passes per solver step: the
 // Runge-Kutta combine y0 + sum_j c_j k_j (stage inputs, y_mid), the error ratio (err, its tolerance-scaled mean square, partial sums per workgroup
 // summed in a fixed order in f64) and the quartic dense output.  Their coefficients and k pointers travel by value in struct dmvae_ode_terms.
+// The likelihood sampler adds one pass per model evaluation (dmvae_ode_hutchinson_pack): the negated velocity into the flat stage buffer and the
+// per-sample Hutchinson sum of the input-VJP against the Rademacher probe.
 // Every kernel takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail.
 #include <initializer_list>
 
@@ -227,6 +229,40 @@ __global__ __launch_bounds__(256) void ode_dense_kernel(const float* __restrict_
   for (size_t e = 4 * nq + tid; e < n; e += stride) dense_at<1>(y0, y1, ym, f0, f1, f_bf16, dt, x, out, e);
 }
 
+// The likelihood sampler's stage value (transport.py:402-459, Hutchinson's trace estimator): k_x = -v (exact in f32), k_logp[b] = sum_i g[b][i] * eps[b][i].
+// One workgroup per sample; eps is +-1, so every product is exact and the f64 sum -- per-thread strided partials, then a fixed tree -- is the same on every run.
+template <int W>
+__device__ __forceinline__ void pack_at(const void* v, int v_bf16, const float* __restrict__ g, const float* __restrict__ eps, float* __restrict__ kx, size_t e,
+                                        double& acc) {
+  float a[W], gv[W], ev[W], o[W];
+  load_w<W>(v, v_bf16, e, a);
+  load_w<W>(g, false, e, gv);
+  load_w<W>(eps, false, e, ev);
+#pragma unroll
+  for (int w = 0; w < W; w++) {
+    o[w] = -a[w];
+    acc += (double)gv[w] * (double)ev[w];
+  }
+  store_w<W>(kx, e, o);
+}
+
+__global__ __launch_bounds__(1024) void ode_hutchinson_pack_kernel(const void* v, int v_bf16, const float* __restrict__ g, const float* __restrict__ eps,
+                                                                   float* __restrict__ kx, float* __restrict__ klogp, size_t per, int quads) {
+  __shared__ double red[1024];
+  const size_t base = (size_t)blockIdx.x * per;
+  const size_t nq = quads ? per / 4 : 0;
+  double acc = 0.0;
+  for (size_t i = threadIdx.x; i < nq; i += 1024) pack_at<4>(v, v_bf16, g, eps, kx, base + 4 * i, acc);
+  for (size_t e = 4 * nq + threadIdx.x; e < per; e += 1024) pack_at<1>(v, v_bf16, g, eps, kx, base + e, acc);
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = 512; h > 0; h >>= 1) {                      // fixed tree
+    if ((int)threadIdx.x < h) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) klogp[blockIdx.x] = (float)red[0];
+}
+
 constexpr int kErrMaxParts = 1024;
 
 inline int ode_grid(size_t n, size_t nq, int cap) {
@@ -319,6 +355,17 @@ extern "C" int dmvae_ode_dense_output(const void* y0, const void* y1, const void
   const size_t nq = ok ? ode_quads(n, nullptr, {y0, y1, y_mid, out}) : 0;
   hipLaunchKernelGGL(ode_dense_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)y0, (const float*)y1, (const float*)y_mid, f0, f1,
                      f_bf16, dt, x, (float*)out, n, nq);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_ode_hutchinson_pack(const void* v, int v_is_bf16, const void* g, const void* eps, void* k_x, void* k_logp, int batch, size_t per_sample,
+                                         hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(v && g && eps && k_x && k_logp && batch > 0 && batch <= 65535 && per_sample > 0, "ode_hutchinson_pack: bad argument");
+  const bool quads = per_sample % 4 == 0 && aligned(v, v_is_bf16 ? 8 : 16) && aligned(g, 16) && aligned(eps, 16) && aligned(k_x, 16);
+  hipLaunchKernelGGL(ode_hutchinson_pack_kernel, dim3(batch), dim3(1024), 0, stream, v, v_is_bf16, (const float*)g, (const float*)eps, (float*)k_x, (float*)k_logp,
+                     per_sample, (int)quads);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -931,13 +931,16 @@ def linear_swiglu(a2: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]):
 WGRAD_GROUPED = True      # DitStackFn / VitBlockFn: the Linear weight gradients of a stack / block as ONE grouped launch (ops.linear_wgrad_grouped) instead of one split-K call each
 
 
-def _lin_grads(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: torch.Tensor, need_dx: bool = True, defer: Optional[list] = None):
+def _lin_grads(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: torch.Tensor, need_dx: bool = True, defer: Optional[list] = None, need_w: bool = True):
     """Gradients of y = x @ w^T + b for bf16 operands [rows, .]: dW and db from the split-K weight-gradient kernel (f32 results, bias
     gradient fused on the matrix pipe; the 1x1 case of the conv wgrad) when its shape constraints hold, else a library GEMM + column sum;
-    dx = dy @ w on the Linear GEMM kernel against the transposed bf16 copy of w (bf16 like the reference's autocast backward)."""
+    dx = dy @ w on the Linear GEMM kernel against the transposed bf16 copy of w (bf16 like the reference's autocast backward).
+    need_w False (frozen w and b): the dx-only form -- no weight-gradient work, (dx, None, None); x2 may then be None."""
     rows, cout = dy2.shape
-    cin = x2.shape[1]
-    if defer is not None and WGRAD_GROUPED and not parity.on() and ops.linear_wgrad_grouped_supported(rows, cout, cin):
+    cin = x2.shape[1] if x2 is not None else w.shape[1]
+    if not need_w:
+        dw = db = None
+    elif defer is not None and WGRAD_GROUPED and not parity.on() and ops.linear_wgrad_grouped_supported(rows, cout, cin):
         # the caller collects (dy, x, dW, db) and launches ALL of them together when its backward pass ends: the destinations are returned now, filled then
         dst_w, dst_b = _dst(w), _dst(b)
         dw = dst_w.view(cout, cin) if dst_w is not None else torch.empty(cout, cin, dtype=f32, device=dy2.device)
@@ -1020,10 +1023,12 @@ class LinearFn(torch.autograd.Function):
         rows = xb.numel() // k
         # the PARAMETER itself where it is 2-D: a view would shed what is tagged on it -- the optimiser's bf16 shadow (a view's transposed operand is cast and
         # transposed again on every call: 28 casts of a 6912 x 1152 weight per DiT step), the flat-buffer gradient destination, the cached operands
-        dx, dw, db = _lin_grads(_c(dy).to(bf16).view(rows, n), xb.view(rows, k), w if w.dim() == 2 else w.view(n, k), ctx.bias, need_dx=ctx.needs_input_grad[0])
+        need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]       # False for a frozen Linear (the input-gradient route): dx only
+        dx, dw, db = _lin_grads(_c(dy).to(bf16).view(rows, n), xb.view(rows, k), w if w.dim() == 2 else w.view(n, k), ctx.bias, need_dx=ctx.needs_input_grad[0],
+                                need_w=need_w)
         if ctx.bias is None:
             db = None
-        return (None if dx is None else dx.view(xb.shape).to(ctx.x_dtype)), dw.view(w.shape), db
+        return (None if dx is None else dx.view(xb.shape).to(ctx.x_dtype)), (None if dw is None else dw.view(w.shape)), db
 
 
 class SiluFn(torch.autograd.Function):
@@ -1348,6 +1353,8 @@ class DitStackFn(torch.autograd.Function):
         b, n, c = acts[0].shape
         d, rows = c // heads, b * n
         dt = dh_out if _take_owned(dh_out, ctx.out_ref) else _c(dh_out).float().clone()      # becomes d(h_mid), d(h) of every block in turn
+        if not any(ctx.needs_input_grad[1:]):
+            return (DitStackFn._input_grad(ctx, dt, acts, params, mod_all, cos, sin), *([None] * (5 + P * nl)))
         S = ops.DitStackBwd(nl, b, n, c, heads, dt.device)
         grads = [None] * (P * nl)
         fresh = lambda p: _dst(p) if _dst(p) is not None else torch.empty(p.shape, dtype=f32, device=dt.device)
@@ -1394,6 +1401,36 @@ class DitStackFn(torch.autograd.Function):
                 dsc = sum(ops.linear_rows(dmod[i], wts[i].view(c, -1), out_f32=True) for i in range(nl)).to(sc_dtype)
         return (_own(dt), dsc, None, None, None, None, *grads)
 
+    @staticmethod
+    def _input_grad(ctx, dt, acts, params, mod_all, cos, sin):
+        """d h_in alone (no parameter and no conditioning needs a gradient: a frozen model's input-VJP, Sampler.sample_ode_likelihood): the launches of the
+        full backward that produce dt, in the same order and on the same kernels -- the same bits --, with every weight-gradient, adaLN-gradient and norm-weight
+        computation left out: no grouped weight-gradient launch, no finalize, no partial sums (dmvae_dit_boundary_bwd_dx, dmvae_qknorm_rope_bwd_dx)."""
+        P = DIT_STACK_PARAMS_PER_BLOCK
+        nl, heads, eps, _ = ctx.cfg
+        b, n, c = acts[0].shape
+        d, rows = c // heads, b * n
+        S = ops.DitStackBwd(nl, b, n, c, heads, dt.device, dx_only=True)
+        do3 = S.boundary_dx(dt, gate_mod=mod_all[nl - 1], gate_off=5 * c, dy_like=acts[13 * (nl - 1) + 12])
+        for i in range(nl - 1, -1, -1):
+            h_in, a1, qkv, q, k, v, o, o2, h_mid, a2, x12, g, o3 = acts[13 * i:13 * i + 13]
+            n1w, qkvw, qkvb, qnw, knw, pw, pb, n2w, w12w, w12b, w3w, w3b, _aw, _ab = params[P * i:P * i + P]
+            mod = mod_all[i]
+            dg = _lin_grads(do3.view(rows, c), None, w3w, w3b, need_w=False)[0]
+            dx12 = ops.swiglu_bwd(dg.view_as(g), x12)
+            da2 = _lin_grads(dx12.view(rows, -1), None, w12w, w12b, need_w=False)[0]
+            do2 = S.boundary_dx(dt, da=da2.view(b, n, c), x=h_mid, w=n2w, mod=mod, scale_off=4 * c, eps=eps, gate_mod=mod, gate_off=2 * c, dy_like=o2)
+            do = _lin_grads(do2.view(rows, c), None, pw, pb, need_w=False)[0]
+            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=ctx.lses[i] if ctx.lses else None)
+            dqkv = S.qknorm_rope_bwd_dx(dq, dk, dv, qkv, qnw, knw, cos, sin, eps)
+            da1 = _lin_grads(dqkv.view(rows, 3 * c), None, qkvw, qkvb, need_w=False)[0]
+            if i > 0:
+                do3 = S.boundary_dx(dt, da=da1.view(b, n, c), x=h_in, w=n1w, mod=mod, scale_off=c, eps=eps, gate_mod=mod_all[i - 1], gate_off=5 * c,
+                                    dy_like=acts[13 * (i - 1) + 12])
+            else:
+                S.boundary_dx(dt, da=da1.view(b, n, c), x=h_in, w=n1w, mod=mod, scale_off=c, eps=eps)
+        return _own(dt)
+
 
 
 
@@ -1411,6 +1448,13 @@ class RmsnormModulateFn(torch.autograd.Function):
     def backward(ctx, da):
         h, w, mod = ctx.saved_tensors
         shift_off, scale_off, eps = ctx.cfg
+        b, n, c = h.shape
+        if not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) and c % 4 == 0 and c <= 2048 and not parity.on():
+            # frozen weight and modulation (the input-gradient route): dit_stack.hip's dx-only norm pass -- the same expressions as the kernel below, no sums
+            dt = torch.zeros(h.shape, dtype=f32, device=h.device)
+            S = ops.DitStackBwd(1, b, n, c, 1, h.device, dx_only=True)
+            S.boundary_dx(dt, da=_c(da).to(bf16), x=_c(h), w=w, mod=mod, scale_off=scale_off, eps=eps)
+            return _own(dt), None, None, None, None, None
         dt = torch.zeros_like(h)
         dmod = torch.zeros(mod.shape, dtype=f32, device=h.device)
         dw = ops.rmsnorm_modulate_bwd_(dt, _c(da).to(bf16), h, w, mod, dmod, shift_off, scale_off, eps, dw_out=_dst(w))

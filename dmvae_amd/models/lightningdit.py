@@ -295,6 +295,10 @@ class LightningDiT(nn.Module):
             if lightningdit_fast.supported(self, x):
                 if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
                     return lightningdit_fast.forward_train(self, x, t, y)        # autograd Functions over csrc/dit.hip
+                if torch.is_grad_enabled() and x.requires_grad:
+                    # frozen weights, gradient wanted for the input only (the likelihood sampler's input-VJP): the training route's Functions, whose backward
+                    # passes then skip every parameter-gradient computation (functional.DitStackFn._input_grad, LinearFn / RmsnormModulateFn dx-only)
+                    return lightningdit_fast.forward_train(self, x, t, y)
                 return lightningdit_fast.forward_inference(self, x, t, y)
             why = ("call outside autocast(bfloat16) or a configuration the DiT kernels do not cover (RoPE + RMSNorm + SwiGLU blocks, width <= 2048, "
                    "even head dim <= 128, tokens a multiple of 32)")

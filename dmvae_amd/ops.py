@@ -1538,17 +1538,21 @@ class DitStackBwd:
     """Scratch of one whole-stack backward pass (functional.DitStackFn.backward): the boundary slots' partial sums, the deferred norm-weight partials of the QK-norm,
     the row statistics -- see include/dmvae_hip.h (dmvae_dit_boundary_bwd, dmvae_dit_stack_finalize, dmvae_colsum2_batched)."""
 
-    def __init__(self, layers: int, batch: int, seq: int, c: int, heads: int, device):
+    def __init__(self, layers: int, batch: int, seq: int, c: int, heads: int, device, dx_only: bool = False):
+        """dx_only: the scratch of `boundary_dx` / `qknorm_rope_bwd_dx` alone (the row statistics): no partial-sum arrays."""
         L = _lib.lib()
         self.layers, self.batch, self.seq, self.c, self.heads = layers, batch, seq, c, heads
         self.d = c // heads
         self.dp = (self.d + 31) // 32 * 32
         self.bps = L.dmvae_dit_stack_bps(batch)
         self.slot_elems = batch * self.bps * 4 * c
-        self.part = workspace(L.dmvae_dit_stack_part_bytes(layers, batch, c), device, "dit_stack_part").view(torch.float32)
         self.ws_bytes = L.dmvae_dit_stack_workspace(layers, batch, seq, c)
         self.ws = workspace(self.ws_bytes, device, "dit_stack_ws")
         self.rowstat_ptr = self.ws.data_ptr() + 2 * layers * batch * c * 4
+        if dx_only:
+            self.part = self.qk_part = None
+            return
+        self.part = workspace(L.dmvae_dit_stack_part_bytes(layers, batch, c), device, "dit_stack_part").view(torch.float32)
         self.nblk = L.dmvae_qknorm_rope_bwd_nblk(batch, seq, heads, self.d, self.dp)
         self.qk_part = workspace(layers * self.nblk * 2 * self.d * 4, device, "dit_stack_qk").view(torch.float32)
 
@@ -1567,6 +1571,24 @@ class DitStackBwd:
         check(_lib.lib().dmvae_qknorm_rope_bwd_partial(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), qkv.data_ptr(), qw.data_ptr(), kw.data_ptr(), cos.data_ptr(),
                                                        sin.data_ptr(), dqkv.data_ptr(), self.qk_part.data_ptr() + layer * nbytes, nbytes, self.batch, self.seq,
                                                        self.heads, self.d, dq.shape[-1], float(eps), _stream()), "qknorm_rope_bwd_partial")
+        return dqkv
+
+    def boundary_dx(self, dt: torch.Tensor, da=None, x=None, w=None, mod=None, scale_off: int = 0, eps: float = 1e-6, gate_mod=None, gate_off: int = 0,
+                    dy_like=None):
+        """`boundary` without the partial sums (dmvae_dit_boundary_bwd_dx: the same dt / dy bits): norm half when `da` is given, gate half (-> dy, shaped
+        like `dy_like`) when `gate_mod` is given.  The input-gradient route of a frozen model."""
+        dy = torch.empty(dy_like.shape, dtype=bf16, device=dt.device) if gate_mod is not None else None
+        check(_lib.lib().dmvae_dit_boundary_bwd_dx(_ptr(da), _ptr(x), _ptr(w), _ptr(mod), mod.shape[-1] if mod is not None else 0, int(scale_off), float(eps),
+                                                   dt.data_ptr(), _ptr(gate_mod), gate_mod.shape[-1] if gate_mod is not None else 0, int(gate_off), _ptr(dy),
+                                                   self.rowstat_ptr, self.batch, self.seq, self.c, _stream()), "dit_boundary_bwd_dx")
+        return dy
+
+    def qknorm_rope_bwd_dx(self, dq, dk, dv, qkv, qw, kw, cos, sin, eps: float) -> torch.Tensor:
+        """`qknorm_rope_bwd` without the norm-weight partials (dmvae_qknorm_rope_bwd_dx: the same dqkv bits)."""
+        dqkv = torch.empty_like(qkv)
+        check(_lib.lib().dmvae_qknorm_rope_bwd_dx(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), qkv.data_ptr(), qw.data_ptr(), kw.data_ptr(), cos.data_ptr(),
+                                                  sin.data_ptr(), dqkv.data_ptr(), self.batch, self.seq, self.heads, self.d, dq.shape[-1], float(eps), _stream()),
+              "qknorm_rope_bwd_dx")
         return dqkv
 
     def finalize(self, dmod: torch.Tensor, norm_dws, qn_dws, kn_dws) -> None:
@@ -1672,6 +1694,27 @@ def ode_dense_output(y0: torch.Tensor, y1: torch.Tensor, y_mid: torch.Tensor, f0
     fb = int(f0.dtype == bf16) | (int(f1.dtype == bf16) << 1)
     check(_lib.lib().dmvae_ode_dense_output(y0.data_ptr(), y1.data_ptr(), y_mid.data_ptr(), f0.data_ptr(), f1.data_ptr(), fb, float(dt), float(x),
                                             out.data_ptr(), y0.numel(), _stream()), "ode_dense_output")
+    return out
+
+
+def ode_hutchinson_pack(v: torch.Tensor, g: torch.Tensor, eps: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The likelihood sampler's stage value (transport.py:402-459) in one launch: v [B, ...] (bf16 or f32: the model's drift), g (f32: its input-VJP against
+    eps) and eps (f32, +-1) of v's shape -> out [B * per + B] f32 with out[:B * per] = -v and out[B * per + b] = sum_i g[b, i] * eps[b, i] (f64 partials in a
+    fixed order: the same bits on every run).  All contiguous on one CUDA device."""
+    _req(v, bf16 if v.dtype == bf16 else f32, "v")
+    for name, t in (("g", g), ("eps", eps)):
+        _same(_req(t, f32, name), v, name)
+    if v.dim() < 1 or v.numel() == 0:
+        raise ValueError("ode_hutchinson_pack: v must be a non-empty [B, ...] tensor")
+    b = v.shape[0]
+    n = v.numel() + b
+    if out is None:
+        out = torch.empty(n, dtype=f32, device=v.device)
+    _req(out, f32, "out")
+    if out.numel() != n or out.device != v.device:
+        raise ValueError(f"ode_hutchinson_pack: out must hold {n} f32 elements on {v.device}")
+    check(_lib.lib().dmvae_ode_hutchinson_pack(v.data_ptr(), int(v.dtype == bf16), g.data_ptr(), eps.data_ptr(), out.data_ptr(), out.data_ptr() + 4 * v.numel(),
+                                               b, v.numel() // b, _stream()), "ode_hutchinson_pack")
     return out
 
 

@@ -7,12 +7,13 @@ the Euler-Maruyama update -- velocity -> score, drift, mean, noise injection -- 
 with the reference's f32 arithmetic order, so for the same model output the trajectory is bit-identical to the PyTorch reference.  Heun and
 the fixed-grid ODE methods are composed from device tensor ops.  The reference's default ODE method, adaptive dopri5 (torchdiffeq's, restated below), runs
 on the device for a CUDA f32 state: the model forwards plus three kernels of csrc/sampler.hip per step (`ops.ode_rk_combine`, `ops.ode_error_ratio`,
-`ops.ode_dense_output`) and one 8-byte readback per attempted step for the step-size controller.  The per-step noise is drawn on the CPU generator and moved to the state's
+`ops.ode_dense_output`) and one 8-byte readback per attempted step for the step-size controller.  The likelihood sampler (`Sampler.sample_ode_likelihood`)
+integrates the tuple state (x, logp) as one flat f32 buffer with torchdiffeq's mixed norm; each evaluation is one model forward, its input-VJP and one
+kernel (`ops.ode_hutchinson_pack`) that writes the stage value.  The per-step noise is drawn on the CPU generator and moved to the state's
 device exactly as the reference does (`th.randn(x.size()).to(x)`, integrators.py:28,38), so a seeded run consumes the same stream.
 
-Not built: the GVP / VP plans (path.py:138-191; never selected by the reference's scripts: `path_type` is "Linear" everywhere), the likelihood
-sampler (transport.py:409-458), dopri5 on CPU or non-f32 states and the other adaptive ODE solvers unless `torchdiffeq` (an unpinned third-party
-dependency) is importable."""
+Not built: the GVP / VP plans (path.py:138-191; never selected by the reference's scripts: `path_type` is "Linear" everywhere), dopri5 and tuple states
+on CPU or non-f32 states and the other adaptive ODE solvers unless `torchdiffeq` (an unpinned third-party dependency) is importable."""
 from __future__ import annotations
 
 import enum
@@ -422,24 +423,40 @@ def _rms(v):
 class _Dopri5:
     """The solver on a CUDA f32 state.  fused: the combine / error-ratio / dense-output kernels of csrc/sampler.hip and one 8-byte readback per
     attempted step; else the same algorithm composed from tensor ops (what the kernels are tested against).  round_bf16: the three weighted sums
-    in the bf16 form torchdiffeq's k.matmul takes under autocast(bf16)."""
+    in the bf16 form torchdiffeq's k.matmul takes under autocast(bf16).
+    A tuple state (the likelihood sampler's (x, logp)) is ONE flat f32 buffer, as torchdiffeq's _TupleFunc holds it: `parts` are its [start, stop) ranges,
+    `batch` the samples the model's t vector needs, and `fn_into(t, y, out)` writes the drift of the flat state into the flat stage slot.  Norms are then
+    torchdiffeq's _mixed_norm -- the max over the parts of each part's RMS -- in the initial step and in the error ratio (one error-ratio launch pair per part,
+    8 bytes read back per part and attempted step); the combine and dense-output kernels run on the whole buffer."""
 
-    def __init__(self, fn, y0, *, atol, rtol, fused, round_bf16):
+    def __init__(self, fn, y0, *, atol, rtol, fused, round_bf16, parts=None, batch=None, fn_into=None):
         self.fn, self.atol, self.rtol, self.fused, self.amp = fn, float(atol), float(rtol), fused, round_bf16
+        self.parts, self.fn_into = parts, fn_into
+        self.batch = y0.size(0) if batch is None else batch
         self.nfe = 0
         self.k = [th.empty_like(y0) for _ in range(7)]      # f32, like torchdiffeq's k buffer: a bf16 model output is copied exactly
         if fused:
+            np_ = 1 if parts is None else len(parts)
             self.ws = ops.ode_error_ratio_workspace(y0.numel(), y0.device)
-            self.res = th.empty(2, dtype=th.float32, device=y0.device)
-            self.host = th.empty(2, dtype=th.float32).pin_memory()
+            self.res = th.empty(np_, 2, dtype=th.float32, device=y0.device)
+            self.host = th.empty(2 * np_, dtype=th.float32).pin_memory()
 
     def f(self, t32, y, slot):
         """k[slot] = drift(t, y); t goes to the model as th.full (== th.ones(B).to(x) * t without a blocking host copy)."""
-        tv = th.full((y.size(0),), float(t32), device=y.device, dtype=y.dtype)
-        r = self.fn(tv, y)
-        assert r.shape == y.shape, "Output shape from ODE solver must match input shape"
-        self.k[slot].copy_(r)
+        tv = th.full((self.batch,), float(t32), device=y.device, dtype=y.dtype)
+        if self.fn_into is not None:
+            self.fn_into(tv, y, self.k[slot])
+        else:
+            r = self.fn(tv, y)
+            assert r.shape == y.shape, "Output shape from ODE solver must match input shape"
+            self.k[slot].copy_(r)
         self.nfe += 1
+
+    def norm(self, v):
+        """torchdiffeq's norm: the RMS of a tensor state, _mixed_norm (max over the parts of their RMS) of a tuple state; a 0-d device tensor."""
+        if self.parts is None:
+            return _rms(v)
+        return th.stack([_rms(v[a:b]) for a, b in self.parts]).max()
 
     def combine(self, y0, coef, dt, out):
         """out = y0 + sum_j (coef_j dt) k_j; y0 None: the sum alone."""
@@ -460,17 +477,27 @@ class _Dopri5:
     def error_ratio(self, y0, y1, dt):
         """-> (ratio, y1 holds a non-finite value) on the host: the one device -> host read of a step."""
         cs = dopri5_weights(DOPRI5_C_ERROR, dt)
+        parts = [(0, y0.numel())] if self.parts is None else self.parts
         if self.fused:
-            ops.ode_error_ratio(y0, y1, self.k, cs, self.atol, self.rtol, round_bf16=self.amp, result=self.res, workspace=self.ws)
-            self.host.copy_(self.res, non_blocking=True)
+            for p, (a, b) in enumerate(parts):
+                sl = (lambda t: t) if self.parts is None else (lambda t, a=a, b=b: t[a:b])
+                ops.ode_error_ratio(sl(y0), sl(y1), [sl(k) for k in self.k], cs, self.atol, self.rtol, round_bf16=self.amp, result=self.res[p], workspace=self.ws)
+            self.host.copy_(self.res.view(-1), non_blocking=True)
             ev = th.cuda.Event()
             ev.record()
             ev.synchronize()
-            return float(np.sqrt(np.float64(self.host[0].item()))), bool(self.host.view(th.int32)[1].item())
+            flags = self.host.view(th.int32)
+            return (max(float(np.sqrt(np.float64(self.host[2 * p].item()))) for p in range(len(parts))),
+                    any(bool(flags[2 * p + 1].item()) for p in range(len(parts))))
         err = self.combine(None, DOPRI5_C_ERROR, dt, th.empty_like(y0))
         tol = self.atol + self.rtol * th.max(y0.abs(), y1.abs())
-        mean_sq = (err / tol).double().pow(2).mean().float()         # the kernel's precision: f32 e, its squares summed in f64, the mean rounded to f32
-        return float(np.sqrt(np.float64(mean_sq.item()))), not bool(th.isfinite(y1).all())
+        e = err / tol
+        ratios = []
+        for a, b in parts:
+            ep = e if self.parts is None else e[a:b]
+            mean_sq = ep.double().pow(2).mean().float()         # the kernel's precision: f32 e, its squares summed in f64, the mean rounded to f32
+            ratios.append(float(np.sqrt(np.float64(mean_sq.item()))))
+        return max(ratios), not bool(th.isfinite(y1).all())
 
     def dense(self, y0, y1, ymid, dt, x, out):
         f0, f1 = self.k[0], self.k[6]
@@ -492,11 +519,11 @@ class _Dopri5:
     def initial_dt(self, t0, y0):
         """_select_initial_step (order 5 - 1) with f0 = k[0] already evaluated; one more evaluation (k[1] holds it until the first stage)."""
         scale = self.atol + y0.abs() * self.rtol
-        d0, d1 = (float(v) for v in th.stack([_rms(y0 / scale), _rms(self.k[0] / scale)]).tolist())
+        d0, d1 = (float(v) for v in th.stack([self.norm(y0 / scale), self.norm(self.k[0] / scale)]).tolist())
         h0 = dopri5_initial_h0(d0, d1)
         h32 = float(np.float32(h0))
         self.f(np.float32(t0 + h32), y0 + h32 * self.k[0], 1)
-        d2 = float(_rms((self.k[1] - self.k[0]) / scale)) / h0
+        d2 = float(self.norm((self.k[1] - self.k[0]) / scale)) / h0
         return dopri5_initial_dt(h0, d1, d2)
 
     def solve(self, y0, ts, max_num_steps):
@@ -570,9 +597,48 @@ class ode:
         finally:
             self.nfe, self.n_accepted, self.n_rejected = solver.nfe, getattr(solver, "n_accepted", 0), getattr(solver, "n_rejected", 0)
 
+    def _flat(self, x, model, **model_kwargs):
+        """A tuple state as one flat f32 buffer (torchdiffeq's _TupleFunc: the flattened parts concatenated) -> (buffer, its [start, stop) parts, unflatten
+        of a stacked [T, n] result into the tuple, fn_into(t, y, out) writing the drift of the flat state y into the flat slot out).  A drift with a `packed`
+        form (Sampler.sample_ode_likelihood's: one kernel for the whole slot) uses it when FUSED_STATE_UPDATE is set."""
+        shapes = [p.shape for p in x]
+        bounds, a = [], 0
+        for p in x:
+            bounds.append((a, a + p.numel()))
+            a += p.numel()
+        y0 = th.cat([p.reshape(-1) for p in x])
+        views = lambda y: tuple(y[a:b].view(sh) for (a, b), sh in zip(bounds, shapes))
+        packed = getattr(self.drift, "packed", None)
+        if FUSED_STATE_UPDATE and packed is not None:
+            def fn_into(t, y, out):
+                packed(views(y), t, model, out=out, **model_kwargs)
+        else:
+            def fn_into(t, y, out):
+                r = self.drift(views(y), t, model, **model_kwargs)
+                for (a, b), sh, r_ in zip(bounds, shapes, r):
+                    assert r_.shape == sh, "Output shape from ODE solver must match input shape"
+                    out[a:b].copy_(r_.reshape(-1))
+        unflat = lambda ys: tuple(ys[:, a:b].reshape(ys.shape[0], *sh) for (a, b), sh in zip(bounds, shapes))
+        return y0, bounds, unflat, fn_into
+
+    def _dopri5_tuple(self, x, model, **model_kwargs):
+        """dopri5 on a tuple of CUDA f32 tensors (the likelihood sampler's (x, logp)) held as one flat buffer; the output is the tuple of the parts'
+        [num_steps, ...] trajectories."""
+        y0, bounds, unflat, fn_into = self._flat(x, model, **model_kwargs)
+        solver = _Dopri5(None, y0, atol=self.atol, rtol=self.rtol, fused=FUSED_STATE_UPDATE, round_bf16=th.is_autocast_enabled(), parts=bounds,
+                         batch=x[0].size(0), fn_into=fn_into)
+        try:
+            with th.no_grad():
+                return unflat(solver.solve(y0, self.t.double().tolist(), self.max_num_steps))
+        finally:
+            self.nfe, self.n_accepted, self.n_rejected = solver.nfe, getattr(solver, "n_accepted", 0), getattr(solver, "n_rejected", 0)
+
     def sample(self, x, model, **model_kwargs):
         if self.sampler_type == "dopri5" and not isinstance(x, tuple) and x.is_cuda and x.dtype == th.float32:
             return self._dopri5(x, model, **model_kwargs)
+        on_device = isinstance(x, tuple) and all(p.is_cuda and p.dtype == th.float32 for p in x)
+        if on_device and self.sampler_type == "dopri5":
+            return self._dopri5_tuple(x, model, **model_kwargs)
         device = x[0].device if isinstance(x, tuple) else x.device
 
         def fn(t, x):
@@ -588,8 +654,17 @@ class ode:
                                           f"{_FIXED_GRID}") from e
             k = len(x) if isinstance(x, tuple) else 1
             return odeint(fn, x, t, method=self.sampler_type, atol=[self.atol] * k, rtol=[self.rtol] * k)
+        unflat = None
         if isinstance(x, tuple):
-            raise NotImplementedError("tuple states (the likelihood sampler) are not built")
+            if not on_device:
+                raise NotImplementedError("tuple states (the likelihood sampler) are built for CUDA f32 tensors only")
+            batch = x[0].size(0)
+            x, _, unflat, fn_into = self._flat(x, model, **model_kwargs)      # elementwise methods: they run on the flat buffer as they stand
+
+            def fn(t, y):
+                out = th.empty_like(y)
+                fn_into(th.ones(batch).to(device) * t, y, out)
+                return out
         out = [x]
         with th.no_grad():
             for i in range(t.numel() - 1):
@@ -609,11 +684,11 @@ class ode:
                     k4 = fn(t0 + dt, x + dt * (k1 - k2 + k3))
                     x = x + dt * (k1 + 3 * (k2 + k3) + k4) * 0.125
                 out.append(x)
-        return th.stack(out)
+        return th.stack(out) if unflat is None else unflat(th.stack(out))
 
 
 class Sampler:
-    """transport.py:223-407 (`sample_sde`, `sample_ode`)."""
+    """transport.py:223-459 (`sample_sde`, `sample_ode`, `sample_ode_likelihood`)."""
 
     def __init__(self, transport: Transport):
         self.transport = transport
@@ -683,3 +758,51 @@ class Sampler:
                                                last_step_size=0.0)
         return ode(drift=drift, t0=t0, t1=t1, sampler_type=sampling_method, num_steps=num_steps, atol=atol, rtol=rtol,
                    time_dist_shift=self.transport.time_dist_shift).sample
+
+    def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3):
+        """transport.py:402-459 -> `_sample_fn(x, model, **model_kwargs)` returning (logp [B], z): the probability-flow ODE from the data (model time 1) to the
+        prior (model time 0) on the state (x, delta_logp), with the divergence of the drift estimated by Hutchinson's trick -- d logp / dt = eps^T J eps, one
+        Rademacher probe eps per evaluation, the VJP g = J^T eps from autograd -- and logp = prior_logp(z) - delta_logp at the last grid time.
+        The reference evaluates the model twice per drift call (once inside autograd.grad, once more for the drift itself); here the drift is the output of
+        the forward whose graph gives the VJP (the same values: the second call repeats the first).  On a CUDA f32 state the (x, logp) tuple is one flat
+        buffer (`ode._dopri5_tuple`) and each evaluation's stage value comes from one kernel (`ops.ode_hutchinson_pack`).  After a call `_sample_fn.ode` holds
+        the solver's `nfe`, `n_accepted` and `n_rejected`."""
+        drift_fn = self.drift
+
+        def _vjp(x, t, model, **kw):
+            """-> (v, g, eps): the drift at (x, 1 - t), the gradient of sum(v * eps) with respect to x, the probe -- eps drawn by the reference's own call,
+            so a seeded run consumes the device generator as the reference does."""
+            eps = th.randint(2, x.size(), dtype=th.float, device=x.device) * 2 - 1
+            t = th.ones_like(t) * (1 - t)
+            with th.enable_grad():
+                x = x.detach().requires_grad_(True)
+                v = drift_fn(x, t, model, **kw)
+                grad = th.autograd.grad(th.sum(v * eps), x)[0]
+            return v.detach(), grad, eps
+
+        def _likelihood_drift(x, t, model, **kw):
+            x, _ = x
+            v, grad, eps = _vjp(x, t, model, **kw)
+            return (-v, th.sum(grad * eps, dim=tuple(range(1, len(x.size())))))
+
+        def _packed(x, t, model, out, **kw):
+            """The same stage value written into the flat slot `out` ([n_x + B] f32) by one kernel: out[:n_x] = -v, out[n_x + b] = sum_i g * eps."""
+            x, _ = x
+            v, grad, eps = _vjp(x, t, model, **kw)
+            ops.ode_hutchinson_pack(v.contiguous(), grad.float().contiguous(), eps, out=out)
+
+        _likelihood_drift.packed = _packed
+        t0, t1 = self.transport.check_interval(self.transport.train_eps, self.transport.sample_eps, sde=False, eval=True, reverse=False,
+                                               last_step_size=0.0)
+        _ode = ode(drift=_likelihood_drift, t0=t0, t1=t1, sampler_type=sampling_method, num_steps=num_steps, atol=atol, rtol=rtol)
+
+        def _sample_fn(x, model, **model_kwargs):
+            init_logp = th.zeros(x.size(0)).to(x)
+            drift, delta_logp = _ode.sample((x, init_logp), model, **model_kwargs)
+            drift, delta_logp = drift[-1], delta_logp[-1]
+            prior_logp = self.transport.prior_logp(drift)
+            logp = prior_logp - delta_logp
+            return logp, drift
+
+        _sample_fn.ode = _ode
+        return _sample_fn

@@ -519,6 +519,11 @@ int dmvae_qknorm_rope_bwd_nblk(int batch, int seq, int heads, int head_dim, int 
 int dmvae_qknorm_rope_bwd_partial(const void* dq, const void* dk, const void* dv, const void* qkv, const void* q_weight, const void* k_weight,
                                   const void* cos_table, const void* sin_table, void* dqkv, void* part, size_t part_bytes, int batch, int seq, int heads,
                                   int head_dim, int head_dim_padded, float eps, dmvae_stream_t stream);
+/* dqkv of dmvae_qknorm_rope_bwd_partial alone (same kernels, grid and bits) with the norm-weight partial sums compiled out: the input-gradient route of a
+ * frozen LightningDiT (functional.DitStackFn with no parameter needing a gradient). */
+int dmvae_qknorm_rope_bwd_dx(const void* dq, const void* dk, const void* dv, const void* qkv, const void* q_weight, const void* k_weight,
+                             const void* cos_table, const void* sin_table, void* dqkv, int batch, int seq, int heads, int head_dim, int head_dim_padded,
+                             float eps, dmvae_stream_t stream);
 
 /* Whole-stack backward of LightningDiT's blocks (diffusion/lightningdit/lightningdit.py:236-250 x depth; the student's flow-matching step, train_dmd.py:565-575,
  * train_diffusion.py:290-297) -- csrc/dit_stack.hip, driven by dmvae_amd/functional.py::DitStackFn.
@@ -538,6 +543,10 @@ size_t dmvae_dit_stack_workspace(int layers, int batch, int seq, int c);
 int dmvae_dit_boundary_bwd(const void* da, const void* x, const void* w, const void* mod, int mod_stride, int scale_off, float eps, void* dx_io, const void* y,
                            const void* gate_mod, int gate_stride, int gate_off, void* dy, void* part_slot, void* rowstat, int batch, int seq, int c,
                            dmvae_stream_t stream);
+/* dx_io / dy of dmvae_dit_boundary_bwd alone (same grid and expressions: the same bits) without the partial sums: no part slot, and the gate half takes no y
+ * (gate_mod != NULL selects it).  The input-gradient route of a frozen LightningDiT. */
+int dmvae_dit_boundary_bwd_dx(const void* da, const void* x, const void* w, const void* mod, int mod_stride, int scale_off, float eps, void* dx_io,
+                              const void* gate_mod, int gate_stride, int gate_off, void* dy, void* rowstat, int batch, int seq, int c, dmvae_stream_t stream);
 int dmvae_dit_stack_finalize(const void* part, void* dmod, void* workspace, size_t workspace_bytes, const void* dw_table, int layers, int batch, int seq, int c,
                              int accumulate, dmvae_stream_t stream);
 /* part [layers][nblk][2][d] f32 -> o0_table[l][d], o1_table[l][d] (device arrays of `layers` pointers to f32 [d]): the second stage of
@@ -718,6 +727,12 @@ int dmvae_ode_error_ratio(const void* y0, const void* y1, const dmvae_ode_terms*
  * y0, y1, y_mid, out: [n] f32; f0 (bit 0 of f_bf16) and f1 (bit 1) bf16 or f32; any n. */
 int dmvae_ode_dense_output(const void* y0, const void* y1, const void* y_mid, const void* f0, const void* f1, int f_bf16, float dt, float x, void* out,
                            size_t n, dmvae_stream_t stream);
+/* The likelihood sampler's stage value (Sampler.sample_ode_likelihood, diffusion/transport/transport.py:402-459): for `batch` samples of per_sample
+ * elements, k_x = -v (v bf16 when v_is_bf16, else f32; exact in f32) and k_logp[b] = sum_i g[b][i] * eps[b][i] (g the input-VJP, eps the +-1 Rademacher
+ * probe, both f32): one workgroup per sample, f64 partials summed in a fixed order, rounded to f32 once (the same bits on every run).  k_x [batch *
+ * per_sample] and k_logp [batch] f32 -- in the sampler, the two parts of one flat stage buffer.  Any per_sample. */
+int dmvae_ode_hutchinson_pack(const void* v, int v_is_bf16, const void* g, const void* eps, void* k_x, void* k_logp, int batch, size_t per_sample,
+                              dmvae_stream_t stream);
 
 /* ---- fp32 parity mode (DMVAE_PARITY=1; csrc/parity.hip) ---------------------------------------------------------------------------
  * north_star: "match the reference PyTorch-CPU path within 1e-4 relative fp32".  In this mode activations are f32 NHWC and every
