@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark: images/sec of one DMVAE tokenizer train step @256x256 (BASELINE.json metric) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 started plainly (no RANK in the env): this process checks that N devices exist and re-executes itself as N ranks, one per GPU, through
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (the reference's launcher: scripts/train_tokenizer.sh:20-38);
@@ -12,8 +12,13 @@ Step = VAE forward (frozen ViT-L/16 encoder, bottleneck MLP, conv decoder) + L1 
 gradient all-reduce + clip + AdamW + EMA, bf16 compute, local batch 32 (train_tokenizer.py, config C2 of SURVEY.md 8),
 synthetic images, random-init weights of the reference architecture (no network for data / checkpoints).
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (implicit-GEMM conv forward/dgrad, csrc/conv_pp.hip, MFMA-bound),
-timed with HIP events on its launch stream inside the timed region; `cpu_baseline` is the CPU oracle
-(oracle/ref_cpu.py, "port") running the same whole step in fp32 at batch 2 on the host cores -- all usable physical cores and 8 threads (rank 0, N=1 only).
+timed with HIP events on its launch stream inside the timed region.
+
+A plain run does only what that line's headline needs: set up, warm up, time the K steps, dump (--dump-outputs), print.  `--full` (N = 1 only) adds,
+after the headline and in this order, the measurements that take runs of their own: `kl_mmd` (the KL + MMD op at three shapes), `comm_n1` (the step again in
+a fresh process with a one-rank RCCL group), `c3_dmd_cycle` / `c4_diffusion_step` / `gan_step` (the recipe's other stages) and `cpu_baseline` (the CPU
+oracle, oracle/ref_cpu.py, "port", running the same whole step in fp32 at batch 2 on the host cores -- all usable physical cores and 8 threads); about a
+minute more.  `--no-secondary` / `--no-cpu-baseline` leave parts of that out.
 """
 import argparse
 import json
@@ -197,7 +202,7 @@ def cpu_baseline_worker(threads: int, batch: int) -> None:
 def cpu_baseline(batch=2, timeout_s=150.0):
     """the CPU oracle ("port") running the SAME step (fp32, no autocast, batch 2, full step including clip + AdamW + EMA) on this
     box's host cores, once on all usable physical cores and once on 8 threads; each in its own process (fresh thread pools) under a timeout so that
-    the default bench run stays within minutes.  `value` is the faster of the runs that finished."""
+    a --full run stays within minutes.  `value` is the faster of the runs that finished."""
     import subprocess
     logical, usable, physical = host_cores()
     runs = []
@@ -464,9 +469,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=LOCAL_BATCH)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the c3_dmd_cycle / c4_diffusion_step / gan_step keys (N = 1 only; ~1.5 min of model construction and steps)")
-    ap.add_argument("--secondary", default="c3,c4,gan", help="which of the secondary stage keys to measure")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure kl_mmd, comm_n1, the c3 / c4 / gan stages and cpu_baseline (N = 1 only; about a minute more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline key")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the comm_n1 and c3_dmd_cycle / c4_diffusion_step / gan_step keys")
+    ap.add_argument("--secondary", default="c3,c4,gan", help="with --full: which of the secondary stage keys to measure")
     ap.add_argument("--time-every", type=int, default=4, help="record the per-launch roofline events on every n-th timed step (1 = all)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (rank 0; see dump_outputs)")
@@ -640,21 +647,21 @@ def main():
         # gradient hooks DURING backward, and the time the compute stream then still spent waiting for them (the un-overlapped remainder)
         out["comm"] = dict(tr.sync.comm_stats(), backend=str(torch.distributed.get_backend()) if dist.initialized() else None,
                            bucket_bytes=64 << 20, dynamic_tile_claiming=os.environ.get("DMVAE_PP_DYNAMIC", "0") not in ("", "0"))      # dist.init_distributed_mode sets it when it switches DYN on
-    if world == 1:
+    if world == 1 and args.full:
         out["kl_mmd"] = kl_mmd_roofline(dev)
-    del tr, images
-    if world == 1 and not args.no_secondary and os.environ.get("DMVAE_FORCE_DIST", "0") == "0":
+        del tr, images
+        if not args.no_secondary and os.environ.get("DMVAE_FORCE_DIST", "0") == "0":
+            torch.cuda.empty_cache()
+            out["comm_n1"] = comm_n1_overhead(out["ms_per_step"])
         torch.cuda.empty_cache()
-        out["comm_n1"] = comm_n1_overhead(out["ms_per_step"])
-    torch.cuda.empty_cache()
-    if world == 1 and not args.no_secondary:
-        try:
-            out.update(secondary_stages(dev, tuple(x for x in args.secondary.split(",") if x)))
-        except Exception as e:      # noqa: BLE001 -- the headline line must still come out; the failure is reported in it
-            out["secondary_error"] = f"{type(e).__name__}: {e}"[:400]
-    if world == 1 and not args.no_cpu_baseline:
-        torch.cuda.empty_cache()
-        out["cpu_baseline"] = cpu_baseline()
+        if not args.no_secondary:
+            try:
+                out.update(secondary_stages(dev, tuple(x for x in args.secondary.split(",") if x)))
+            except Exception as e:      # noqa: BLE001 -- the headline line must still come out; the failure is reported in it
+                out["secondary_error"] = f"{type(e).__name__}: {e}"[:400]
+        if not args.no_cpu_baseline:
+            torch.cuda.empty_cache()
+            out["cpu_baseline"] = cpu_baseline()
     _emit(json.dumps(out), rank0=True)
 
 
@@ -685,7 +692,7 @@ def comm_n1_overhead(headline_ms: float) -> dict:
                NCCL_DEBUG="INFO", NCCL_DEBUG_SUBSYS="INIT,COLL,TUNING")
     res = {"what": "C2 step with a one-rank RCCL group + dynamic tile claiming, fresh process, 10 steps after 3", "headline_ms": round(headline_ms, 3)}
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-secondary"], env=env,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", "10", "--warmup", "3"], env=env,
                            capture_output=True, text=True, timeout=240)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode != 0 or not lines:

@@ -1,5 +1,5 @@
 # Round-5 evidence job, one box: the full GPU suite, rocprofv3 kernel trace + stats of the bench command (C2 headline), per-stage traces of the DMD cycle / the
-# latent-diffusion step / the adversarial step cut into steps and families, the default bench (all keys), smoke().   usage: bash tools/probes/job_r5_end.sh [tag]
+# latent-diffusion step / the adversarial step cut into steps and families, the --full bench (all keys), smoke().   usage: bash tools/probes/job_r5_end.sh [tag]
 set -x
 R=$GRAFT_REPO_ROOT; TAG=${1:-r5_end}; OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 cd $R
@@ -14,7 +14,7 @@ for st in dmd diffusion gan; do
   python $R/tools/stage_trace_summary.py $T 45 > $OUT/${st}_trace_summary.txt 2>&1; rm -f $T
 done
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1
+timeout 900 python bench.py --steps 20 --warmup 5 --full > $OUT/bench.log 2>&1
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?" >> $OUT/smoke.log
 timeout 600 python tools/bench_dmd_step.py > $OUT/dmd_step.txt 2>&1
 timeout 600 python tools/bench_dit.py > $OUT/dit_fwd.txt 2>&1

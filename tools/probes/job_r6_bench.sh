@@ -1,2 +1,2 @@
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/r6_bench
-timeout 900 python bench.py 2>gpurun_out/r6_bench/bench.err | tee gpurun_out/r6_bench/bench_line.json | cut -c1-400
+cd "$(dirname "$0")/../.."; OUT=${1:?usage: bash tools/probes/job_r6_bench.sh <output dir>}; mkdir -p "$OUT"
+timeout 900 python bench.py --full 2>$OUT/bench.err | tee $OUT/bench_line.json | cut -c1-400
