@@ -37,7 +37,7 @@ class OdeTerms(Structure):
     _fields_ = [("k", c_void_p * 7), ("c", c_float * 7), ("nk", c_int32), ("k_bf16", c_int32)]
 
 
-ABI_VERSION = 8     # 8: dmvae_reparam_kl_*, dmvae_linear_bf16_sk*, the f32 transformer steps of csrc/parity_dit.hip; 7: dmvae_linear_wgrad_grouped_plan / _xcd, dmvae_conv_k4c1_*; 6: dmvae_dit_stack_* / dmvae_dit_boundary_bwd / batched rows Linears / batched weight transposes; 5: dmvae_groupnorm_*_short; include/dmvae_hip.h: dmvae_abi_version (3: struct dmvae_pack_entry, dmvae_pack_weights_batched, dmvae_linear_bf16*; 4: dmvae_norm_conv_out_bwd*)
+ABI_VERSION = 9     # 9: nine retired entry points removed (the two-kernel split-K, the NULL-lse attention aliases, ...); 8: dmvae_reparam_kl_*, dmvae_linear_bf16_sk*, the f32 transformer steps of csrc/parity_dit.hip; 7: dmvae_linear_wgrad_grouped_plan / _xcd, dmvae_conv_k4c1_*; 6: dmvae_dit_stack_* / dmvae_dit_boundary_bwd / batched rows Linears / batched weight transposes; 5: dmvae_groupnorm_*_short; include/dmvae_hip.h: dmvae_abi_version (3: struct dmvae_pack_entry, dmvae_pack_weights_batched, dmvae_linear_bf16*; 4: dmvae_norm_conv_out_bwd*)
 
 # name -> (restype, argtypes); every symbol include/dmvae_hip.h declares
 SIGNATURES = {
@@ -67,12 +67,8 @@ SIGNATURES = {
     "dmvae_linear_rows_bf16": (c_int, [c_void_p] * 4 + [c_int] * 10 + [c_void_p]),
     "dmvae_linear_rows_wgrad": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
     "dmvae_linear_bf16": (c_int, [c_void_p] * 4 + [c_int] * 10 + [c_void_p]),
-    "dmvae_linear_bf16_splitk_supported": (c_int, [c_int] * 4),
-    "dmvae_linear_bf16_splitk": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p]),
-    "dmvae_splitk_sum_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "dmvae_linear_bf16_swiglu_pre": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
     "dmvae_linear_bf16_sk_supported": (c_int, [c_int] * 5),
-    "dmvae_linear_bf16_sk_counter_bytes": (c_size_t, []),
     "dmvae_linear_bf16_sk_workspace": (c_size_t, [c_int] * 5),
     "dmvae_linear_bf16_sk": (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 11 + [c_void_p]),
     "dmvae_linear_bf16_batched_supported": (c_int, [c_int] * 4),
@@ -108,7 +104,6 @@ SIGNATURES = {
     "dmvae_batchnorm_running_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p]),
     "dmvae_diffaug_fwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "dmvae_diffaug_bwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
-    "dmvae_im2col_nhwc": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "dmvae_im2col_nhwc_taps": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
     "dmvae_im2col_nhwc_sub": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
     "dmvae_col2im_nhwc": (c_int, [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
@@ -120,11 +115,7 @@ SIGNATURES = {
     "dmvae_scale_residual_layernorm": (c_int, [c_void_p] * 6 + [c_int, c_int, c_float, c_void_p]),
     "dmvae_scale_residual_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "dmvae_softmax_rows_bf16": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_void_p]),
-    "dmvae_attention_qkv_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "dmvae_attention_heads_bf16": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_attention_qknorm_rope_bf16": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float, c_float, c_void_p]),
-    "dmvae_attention_bwd_qkv_bf16": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p]),
-    "dmvae_attention_bwd_heads_bf16": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_attention_qkv_lse_bf16": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_float, c_void_p]),
     "dmvae_attention_heads_lse_bf16": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_attention_bwd_qkv_lse_bf16": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_float, c_void_p]),

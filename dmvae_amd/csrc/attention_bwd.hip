@@ -942,15 +942,10 @@ static int launch(const Args& a, int batch, hipStream_t stream) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_lse_kernel<DP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
       attr2_done = true;
     }
-    static const int xcd = [] { const char* e = getenv("DMVAE_ATTN_XCD"); return !(e && e[0] == '0') ? 1 : 0; }();
-    static const int three = [] { const char* e = getenv("DMVAE_ATTN_3BUF"); return !(e && e[0] == '0') ? 1 : 0; }();
     Args b_ = a;
-    b_.xcd = xcd;
-    // measured (profiles/r5_attention_3buf_ab.txt): 5 % faster at 256 and 512 (batch, head) blocks, 4 % slower at 1 024 -- with four rounds per CU the kernel is in
-    // its bandwidth-bound regime and the larger load burst at the head of every block costs more than the hidden latency returns
-    static const int tight = [] { const char* e = getenv("DMVAE_ATTN_BWD_TIGHT"); return !(e && e[0] == '0') ? 1 : 0; }();
+    b_.xcd = 1;
     if constexpr (DP == 96) {
-      if (tight && a.D == 72 && a.S <= 256 && batch * a.H >= 512) {     // two or more items per CU: two out-of-phase 4-wave workgroups per CU on the 144-B layout
+      if (a.D == 72 && a.S <= 256 && batch * a.H >= 512) {     // two or more items per CU: two out-of-phase 4-wave workgroups per CU on the 144-B layout
         constexpr int ldst = 2 * 256 * 144 + 2 * 256 * (int)sizeof(float);
         static bool attrt_done = false;
         if (!attrt_done) {
@@ -962,7 +957,9 @@ static int launch(const Args& a, int batch, hipStream_t stream) {
         return 0;
       }
     }
-    if (three && a.S <= ROWS3 && batch * a.H <= 512) {
+    // the three-buffer form up to 512 (batch, head) blocks, measured (profiles/r5_attention_3buf_ab.txt): 5 % faster at 256 and 512 blocks, 4 % slower at 1 024 --
+    // with four rounds per CU the kernel is in its bandwidth-bound regime and the larger load burst at the head of every block costs more than the hidden latency returns
+    if (a.S <= ROWS3 && batch * a.H <= 512) {
       constexpr int lds3 = 3 * BUF3 + 2 * ROWS3 * (int)sizeof(float);
       static bool attr3_done = false;
       if (!attr3_done) {
@@ -983,12 +980,6 @@ static int launch(const Args& a, int batch, hipStream_t stream) {
 }  // namespace dmvae_attn_bwd
 
 extern "C" int dmvae_attention_bwd_qkv_lse_bf16(const void* qkv, const void* out, const void* dout, const void* lse, void* dqkv, int batch, int seq, int heads,
-                                                int head_dim, float scale, hipStream_t stream);
-extern "C" int dmvae_attention_bwd_qkv_bf16(const void* qkv, const void* out, const void* dout, void* dqkv, int batch, int seq, int heads, int head_dim,
-                                            float scale, hipStream_t stream) {
-  return dmvae_attention_bwd_qkv_lse_bf16(qkv, out, dout, nullptr, dqkv, batch, seq, heads, head_dim, scale, stream);
-}
-extern "C" int dmvae_attention_bwd_qkv_lse_bf16(const void* qkv, const void* out, const void* dout, const void* lse, void* dqkv, int batch, int seq, int heads,
                                                 int head_dim, float scale, hipStream_t stream) {
   using namespace dmvae_attn_bwd;
   DMVAE_CHECK_ARG(qkv && out && dout && dqkv && batch > 0 && heads > 0 && seq > 0, "attention_bwd_qkv_bf16: bad argument");
@@ -1004,12 +995,6 @@ extern "C" int dmvae_attention_bwd_qkv_lse_bf16(const void* qkv, const void* out
   return launch<64>(a, batch, stream);
 }
 
-extern "C" int dmvae_attention_bwd_heads_lse_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq, void* dk,
-                                                  void* dv, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale, hipStream_t stream);
-extern "C" int dmvae_attention_bwd_heads_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, void* dq, void* dk, void* dv,
-                                              int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale, hipStream_t stream) {
-  return dmvae_attention_bwd_heads_lse_bf16(q, k, v, out, dout, nullptr, dq, dk, dv, batch, seq, heads, head_dim, head_dim_padded, scale, stream);
-}
 extern "C" int dmvae_attention_bwd_heads_lse_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq, void* dk,
                                                   void* dv, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale, hipStream_t stream) {
   using namespace dmvae_attn_bwd;

@@ -737,9 +737,6 @@ extern "C" int dmvae_im2col_nhwc_sub(const void* x, void* col, int n, int h, int
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
-extern "C" int dmvae_im2col_nhwc(const void* x, void* col, int n, int h, int w, int c, int ks, int stride, int pad, hipStream_t stream) {
-  return dmvae_im2col_nhwc_taps(x, col, n, h, w, c, ks, stride, pad, ks * ks, stream);
-}
 extern "C" int dmvae_col2im_nhwc(const void* dcol, void* dx, int n, int h, int w, int c, int ks, int stride, int pad, int in_f32,
                                  hipStream_t stream) {
   int ho, wo;

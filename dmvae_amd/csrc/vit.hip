@@ -193,7 +193,7 @@ struct AttnArgs {
   float scale;
   int BH;          // batch * heads: blocks past it are the single-query blocks (eight (batch, head) pairs each)
   int xcd;         // 1: block -> (batch, head) through xcd_remap, so that the blocks resident on one XCD are CONSECUTIVE heads of the same samples and the 128-B lines
-                   // their head slices share (a 72-channel head is 144 B of a packed qkv row) are fetched into that XCD's L2 once (DMVAE_ATTN_XCD=0: plain order)
+                   // their head slices share (a 72-channel head is 144 B of a packed qkv row) are fetched into that XCD's L2 once (0: plain order)
   // NR variant: per-head RMSNorm (bf16 result) * weight and the 2-D rotary embedding are applied to q and k on their way in
   const float *qw, *kw, *cosb, *sinb;   // [D], [D], [S][D], [S][D]
   float eps;
@@ -472,16 +472,14 @@ static int launch_attention(const AttnArgs& a, int batch, hipStream_t stream) {
   }
   AttnArgs b_ = a;
   b_.BH = batch * a.H;
-  static const int xcd = [] { const char* e = getenv("DMVAE_ATTN_XCD"); return !(e && e[0] == '0') ? 1 : 0; }();
-  b_.xcd = xcd;
-  if constexpr (DP == 96 && !NR) {   // two or more (batch, head) items per CU: the persistent form that loads the next item's K / V under the current one's sweeps (DMVAE_ATTN_PIPE=0: off)
-    static const int pipe = [] { const char* e = getenv("DMVAE_ATTN_PIPE"); return !(e && e[0] == '0') ? 1 : 0; }();
+  b_.xcd = 1;
+  if constexpr (DP == 96 && !NR) {   // two or more (batch, head) items per CU: the persistent form that loads the next item's K / V under the current one's sweeps
     static const int cus = [] {
       int dev = 0, n = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
       return n & ~7;
     }();
-    if (pipe && b_.BH >= 2 * cus) {
+    if (b_.BH >= 2 * cus) {
       static bool attr_pipe = false;
       if (!attr_pipe) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DP, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -499,11 +497,6 @@ static int launch_attention(const AttnArgs& a, int batch, hipStream_t stream) {
 
 }  // namespace dmvae_vit
 
-extern "C" int dmvae_attention_qkv_lse_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, hipStream_t stream);
-extern "C" int dmvae_attention_qkv_bf16(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, float scale,
-                                        hipStream_t stream) {
-  return dmvae_attention_qkv_lse_bf16(qkv, out, nullptr, batch, seq, heads, head_dim, scale, stream);
-}
 extern "C" int dmvae_attention_qkv_lse_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, hipStream_t stream) {
   using namespace dmvae_vit;
   DMVAE_CHECK_ARG(qkv && out && batch > 0 && heads > 0 && seq > 0, "attention_qkv_bf16: bad argument");
@@ -518,12 +511,6 @@ extern "C" int dmvae_attention_qkv_lse_bf16(const void* qkv, void* out, void* ls
 }
 
 // Same kernel on head-major operands (q, k: [B*H][S][Dp], v: [B*H][S][D]; LightningDiT after QK-norm + RoPE, head dim 64 or 72 -> Dp 64 / 96).
-extern "C" int dmvae_attention_heads_lse_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
-                                              int head_dim_padded, float scale, hipStream_t stream);
-extern "C" int dmvae_attention_heads_bf16(const void* q, const void* k, const void* v, void* out, int batch, int seq, int heads, int head_dim,
-                                          int head_dim_padded, float scale, hipStream_t stream) {
-  return dmvae_attention_heads_lse_bf16(q, k, v, out, nullptr, batch, seq, heads, head_dim, head_dim_padded, scale, stream);
-}
 extern "C" int dmvae_attention_heads_lse_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
                                               int head_dim_padded, float scale, hipStream_t stream) {
   using namespace dmvae_vit;

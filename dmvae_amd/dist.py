@@ -192,7 +192,7 @@ class FlatGradSync:
         self._handles = []
         # the mean over ranks: RCCL / NCCL average INSIDE the collective (ncclAvg) -- no `div_` launch per bucket on the compute stream (42 per student step of the
         # DMD stage); gloo has no AVG: divide, then SUM (the CPU tests' transport)
-        self.avg_in_collective = bool(self.enabled and tdist.get_backend() == "nccl" and os.environ.get("DMVAE_DIST_AVG", "1") != "0")
+        self.avg_in_collective = bool(self.enabled and tdist.get_backend() == "nccl")
         self.hook_launches = 0      # buckets whose all-reduce was started from a gradient hook, i.e. DURING backward, in the last step
         self._in_wait = False
         self.time_wait = False      # bench.py: bracket wait() with events on the compute stream -- what of the collectives backward did NOT cover

@@ -461,8 +461,8 @@ _TAIL_WEIGHT_ONLY = [False]
 
 
 class tail_weight_only:
-    """Context: the decoder tail's backward node (NormConvOutFn) returns only conv_out's weight gradient (see its backward).  DMVAE_TAIL_WEIGHT_ONLY=0 disables it."""
-    ON = os.environ.get("DMVAE_TAIL_WEIGHT_ONLY", "1") != "0"
+    """Context: the decoder tail's backward node (NormConvOutFn) returns only conv_out's weight gradient (see its backward)."""
+    ON = True
 
     def __enter__(self):
         self.prev = _TAIL_WEIGHT_ONLY[0]
@@ -474,7 +474,6 @@ class tail_weight_only:
         return False
 
 
-K4_L1_LEAN = os.environ.get("DMVAE_K4_L1_LEAN", "1") != "0"      # first PatchGAN layer's weight gradient without the sliced copy of x / the padded copy of dY (0: with them, for A/B)
 K4_COUT1 = os.environ.get("DMVAE_K4_COUT1", "1") != "0"      # the one-output-channel 4x4 conv (PatchGAN logits) on csrc/conv_c1.hip's vector-unit kernels
 K4_WGRAD_THIN_CIN = True      # the <= 8-input-channel 4x4 conv's weight gradient on the im2col form of an 8-channel copy (ConvK4Fn.backward)
 K4_WGRAD_AS_GEMM = (1,)      # strides of the 4x4 convs whose weight gradient runs on the im2col form (ConvK4Fn.backward); () = never (tests compare the routes)
@@ -557,8 +556,8 @@ class ConvK4Fn(torch.autograd.Function):
             # one 128-channel group -- against the output gradient zero-padded to one group it is the large kernel's 1x1 case, bound by reading ~0.5 GB.
             # (the 8-channel im2col straight from the 32-channel tensor, and dY as it is when it has 64 channels -- the kernel masks the rows past Cout: the sliced
             # copy of x, the zero-padded copy of dY and half of dY's read were 0.33 ms per step)
-            col = ops.im2col(x, 4, stride, 1, c_take=8) if K4_L1_LEAN else ops.im2col(x[..., :8].contiguous(), 4, stride, 1)
-            cg = cpad if cpad in ((64, 128) if K4_L1_LEAN else (128,)) else 128
+            col = ops.im2col(x, 4, stride, 1, c_take=8)
+            cg = cpad if cpad in (64, 128) else 128
             dyg = dy if cpad == cg else torch.nn.functional.pad(dy, (0, cg - cpad))
             g2, dbp = ops.conv2d_nhwc_wgrad(dyg.view(1, 1, m, cg), col.view(1, 1, m, 128), 1, need_bias=b is not None)
             dwv = g2.view(cg, 16, 8)[:cout, :, :cin].permute(0, 2, 1).reshape(cout, cin, 4, 4)
@@ -842,29 +841,22 @@ def _bf_km(w: torch.Tensor) -> torch.Tensor:
     return packed(w, kmajor=True, frozen=True)._dmvae_kmajor.view(cin // 32, cout, 32)
 
 
-SPLITK = int(os.environ.get("DMVAE_SPLITK", "3"))                # DitStackFn: parts of the reduction for its few-tile deep-K GEMMs (0: off; tests compare)
-SPLITK_MIN_K = int(os.environ.get("DMVAE_SPLITK_MINK", "3072"))
-SPLITK_FUSED = os.environ.get("DMVAE_SPLITK_FUSED", "1") != "0"  # the parts summed inside the GEMM by the last one to arrive (ops.linear_sk, round 6) instead of slabs + a sum pass (ops.linear_splitk)
+SPLITK = 3                # DitStackFn: parts of the reduction for its few-tile deep-K GEMMs, summed inside the GEMM by the last one to arrive (ops.linear_sk)
+SPLITK_MIN_K = 3072
 _SPLITK_ACTIVE = [0]      # > 0 only inside DitStackFn's forward / backward: the inference route keeps one accumulation order for every batch size
 
 
 def _use_splitk(m: int, n: int, k: int) -> int:
     """Parts to cut this GEMM's reduction into: LightningDiT-XL/1 at batch 16 -- M = 4096 rows x N = 1152 columns are 80 tiles of 256 x 256 (160 of 256 x 128: 60 % of the
-    chip for the whole reduction); with K >= 3072 three parts make 240 work units of a third of the length (w3: 47 -> ~41 us incl. the slab sum, the input gradient of
-    w12: 88 -> ~70)."""
+    chip for the whole reduction); with K >= 3072 three parts make 240 work units of a third of the length (student-only step 34.7 -> 33.0-33.6 ms,
+    profiles/r6_splitk_fused_ab.txt)."""
     s_ = _SPLITK_ACTIVE[0]
     if s_ < 2 or parity.on() or not (2048 <= m <= 6144) or k < SPLITK_MIN_K:
         return 0
     tiles = ((m + 255) // 256) * ((n + 255) // 256)
     if tiles > 100:
         return 0
-    if SPLITK_FUSED:
-        return s_ if ops.linear_sk_supported(m, n, k, s_) else 0
-    return s_ if ops.linear_splitk_supported(m, n, k, s_) else 0
-
-
-def _splitk_linear(x2: torch.Tensor, w: torch.Tensor, bias, parts: int) -> torch.Tensor:
-    return ops.linear_sk(x2, w, bias, splits=parts) if SPLITK_FUSED else ops.linear_splitk(x2, w, bias, parts)
+    return s_ if ops.linear_sk_supported(m, n, k, s_) else 0
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, act: int = ops.ACT_NONE) -> torch.Tensor:
@@ -885,7 +877,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, a
         return ops.linear_rows(x.view(m, k), (w if w.dtype == bf16 else _bf(w)).view(n, k), bb, act).view(*x.shape[:-1], n)
     sk = _use_splitk(m, n, k) if act == ops.ACT_NONE else 0
     if sk:
-        return _splitk_linear(x.view(m, k), (w if w.dtype == bf16 else _bf(w)).view(n, k), bb, sk).view(*x.shape[:-1], n)
+        return ops.linear_sk(x.view(m, k), (w if w.dtype == bf16 else _bf(w)).view(n, k), bb, splits=sk).view(*x.shape[:-1], n)
     if ops.linear_supported(m, n, k) and (act != ops.ACT_SWIGLU or n % 16 == 0):
         # frozen weights -- an nn.Parameter that is not trainable AND not owned by one of this build's optimisers (a student DiT switched to requires_grad
         # False for the DMD loss's evaluations still changes every few steps: it keeps the row-major shadow its optimiser maintains) -- : the K-tile-major
@@ -911,24 +903,18 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, a
     return y.reshape(*x.shape[:-1], y.shape[-1])
 
 
-SWIGLU_IN_W12 = os.environ.get("DMVAE_SWIGLU_IN_W12", "1") != "0"      # the training route's w12 Linear writes silu(x1) * x2 AND the pre-activation in one launch (0: Linear, then the swiglu pass; tests compare)
-
-
 def linear_swiglu(a2: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]):
     """SwiGLUFFN's first half on the training route (swiglu_ffn.py:31-36): -> (x12 = bf16(a2 @ w12^T + b), g = silu(x1) * x2), both kept for the backward.  One launch of
     the Linear GEMM with the gated epilogue that also stores the pre-activation (ops.linear_swiglu_pre) where the large-tile kernel takes the shape -- the bits of
     the Linear followed by the swiglu pass, which is the fallback."""
     k, n = a2.shape[-1], w.shape[0]
     m = a2.numel() // k
-    if SWIGLU_IN_W12 and not parity.on() and a2.dtype == bf16 and n % 16 == 0 and ops.linear_supported(m, n, k) and not _use_splitk(m, n, k):
+    if not parity.on() and a2.dtype == bf16 and n % 16 == 0 and ops.linear_supported(m, n, k) and not _use_splitk(m, n, k):
         bb = None if b is None else (b if b.dtype == bf16 else _bf(b))
         g, x12 = ops.linear_swiglu_pre(_c(a2), (w if w.dtype == bf16 else _bf(w)).view(n, k), bb)
         return x12, g
     x12 = linear(a2, w, b)
     return x12, ops.swiglu(x12)
-
-
-WGRAD_GROUPED = True      # DitStackFn / VitBlockFn: the Linear weight gradients of a stack / block as ONE grouped launch (ops.linear_wgrad_grouped) instead of one split-K call each
 
 
 def _lin_grads(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: torch.Tensor, need_dx: bool = True, defer: Optional[list] = None, need_w: bool = True):
@@ -940,7 +926,7 @@ def _lin_grads(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: torch.Te
     cin = x2.shape[1] if x2 is not None else w.shape[1]
     if not need_w:
         dw = db = None
-    elif defer is not None and WGRAD_GROUPED and not parity.on() and ops.linear_wgrad_grouped_supported(rows, cout, cin):
+    elif defer is not None and not parity.on() and ops.linear_wgrad_grouped_supported(rows, cout, cin):
         # the caller collects (dy, x, dW, db) and launches ALL of them together when its backward pass ends: the destinations are returned now, filled then
         dst_w, dst_b = _dst(w), _dst(b)
         dw = dst_w.view(cout, cin) if dst_w is not None else torch.empty(cout, cin, dtype=f32, device=dy2.device)
@@ -983,7 +969,7 @@ def _lin_grads(dy2: torch.Tensor, x2: torch.Tensor, w: torch.Tensor, b: torch.Te
     if ops.linear_supported(rows, cin, cout) and not parity.on():
         sk = _use_splitk(rows, cin, cout)
         if sk:
-            return _splitk_linear(_c(dy2), _bf_t(w), None, sk), dw, db
+            return ops.linear_sk(_c(dy2), _bf_t(w), None, splits=sk), dw, db
         return ops.linear_bf16(_c(dy2), _bf_t(w)), dw, db                 # dX = dY . W as an NT GEMM against the transposed copy
     if cout % 32 == 0 and cin % 4 == 0:
         return ops.gemm_nt(_c(dy2), packed(w, True).view(cin, cout)), dw, db
@@ -1046,16 +1032,9 @@ class SiluFn(torch.autograd.Function):
         return ops.silu_bwd(x, _c(dy).to(bf16))
 
 
-ATTN_BWD_LSE = True        # the forward attention kernels also write the row statistics and the backward takes the eight-wave form built on them (False: recomputed; tests compare)
-QK_UNPADDED = os.environ.get("DMVAE_QK_UNPADDED", "1") != "0"      # DitStackFn: q / k (and dq / dk) rows of D = 72 channels instead of 96 zero-padded ones between QK-norm + RoPE and the attention kernels (0: padded, for A/B)
-ATTN_BWD_FUSED = True      # False: the GEMM-composed attention backward (probabilities through HBM; the first implementation) -- tests compare the two
 THIN_CIN_BWD_AS_GEMM = True      # ConvFn.backward of a 3x3 conv from 32 / 64 channels: weight and input gradient as GEMMs on the im2col form
 NORM_CONV_OUT_FUSED_FWD = True      # NormConvOutFn.forward: ops.norm_conv_out_fwd where the shape allows
 NORM_CONV_OUT_FUSED_BWD = True      # NormConvOutFn.backward: ops.norm_conv_out_bwd where the shape allows (tests compare it with the stored-operand route)
-
-
-def _fused_attn_bwd() -> bool:
-    return ATTN_BWD_FUSED
 
 
 def _attention_bwd(qkv: torch.Tensor, do: torch.Tensor, heads: int, scale: float) -> torch.Tensor:
@@ -1100,7 +1079,7 @@ class VitBlockFn(torch.autograd.Function):
         hn1 = ops.layernorm_bf16(t, n1w, n1b, eps)
         qkv = linear(hn1, qkvw, qkvb)
         lse = None
-        if ATTN_BWD_LSE and hd == 64 and s <= 288 and any(ctx.needs_input_grad):
+        if hd == 64 and s <= 288 and any(ctx.needs_input_grad):
             o, lse = ops.attention_qkv(qkv, heads, hd ** -0.5, need_lse=True)      # + the row statistics the backward kernel rebuilds P from
         else:
             o = ops.attention_qkv(qkv, heads, hd ** -0.5)
@@ -1136,7 +1115,7 @@ class VitBlockFn(torch.autograd.Function):
         # attention branch
         do2, dls1 = ops.layerscale_bwd(dt, o2, ls1, dg_out=_dst(ls1))
         do, dpw, dpb = _lin_grads(do2.view(rows, c), o.view(rows, c), pw, pb, defer=pend)
-        if c // heads == 64 and s <= 288 and _fused_attn_bwd():
+        if c // heads == 64 and s <= 288:
             dqkv = ops.attention_bwd_qkv(qkv, o, do.view(b, s, c), heads, (c // heads) ** -0.5, lse=ctx.lse)      # one kernel, nothing S x S in HBM
         else:
             dqkv = _attention_bwd(qkv, do.view(b, s, c), heads, (c // heads) ** -0.5)
@@ -1181,7 +1160,7 @@ class DitBlockFn(torch.autograd.Function):
         a1 = ops.rmsnorm_modulate(h, n1w, mod, 0, c, eps)
         qkv = linear(a1, qkvw, qkvb)
         q, k, v = ops.qknorm_rope(qkv, qnw, knw, cos, sin, heads, eps)
-        fused = ops.attention_heads_supported(n, d) and _fused_attn_bwd()
+        fused = ops.attention_heads_supported(n, d)
         if fused:       # the inference kernel; its backward recomputes the probabilities in registers (csrc/attention_bwd.hip)
             p = None
             o = ops.attention_heads(q, k, v, b, d ** -0.5)
@@ -1290,7 +1269,7 @@ DIT_STACK_PARAMS_PER_BLOCK = 14
 def dit_stack_supported(b: int, n: int, c: int, heads: int) -> bool:
     """Shapes `DitStackFn` takes (else the per-block `DitBlockFn` route): the fused attention kernels' token / head-dim range, at most 64 samples per call (the
     per-sample Linears' row limit), outside the fp32 parity mode."""
-    return bool(ops.attention_heads_supported(n, c // heads) and _fused_attn_bwd() and b <= 64 and c % 32 == 0 and not parity.on())
+    return bool(ops.attention_heads_supported(n, c // heads) and b <= 64 and c % 32 == 0 and not parity.on())
 
 
 class DitStackFn(torch.autograd.Function):
@@ -1324,12 +1303,9 @@ class DitStackFn(torch.autograd.Function):
             else:
                 h_in, a1 = ops.gated_residual_out(h_mid, o3, mod_all[i - 1], 5 * c, n1w, mod, 0, c, eps)
             qkv = linear(a1, qkvw, qkvb)
-            q, k, v = ops.qknorm_rope(qkv, qnw, knw, cos, sin, heads, eps, padded=not QK_UNPADDED)
-            if ATTN_BWD_LSE:
-                o, lse = ops.attention_heads(q, k, v, b, d ** -0.5, need_lse=True)
-                lses.append(lse)
-            else:
-                o = ops.attention_heads(q, k, v, b, d ** -0.5)
+            q, k, v = ops.qknorm_rope(qkv, qnw, knw, cos, sin, heads, eps, padded=False)      # q / k rows of the D real channels (72 at XL), not zero-padded to 96
+            o, lse = ops.attention_heads(q, k, v, b, d ** -0.5, need_lse=True)
+            lses.append(lse)
             o2 = linear(o, pw, pb)
             h_mid, a2 = ops.gated_residual_out(h_in, o2, mod, 2 * c, n2w, mod, 3 * c, 4 * c, eps)
             x12, g = linear_swiglu(a2, w12w, w12b)
@@ -1371,7 +1347,7 @@ class DitStackFn(torch.autograd.Function):
             da2, G[P * i + 8], G[P * i + 9] = _lin_grads(dx12.view(rows, -1), a2.view(rows, c), w12w, w12b, defer=pend)
             do2 = S.boundary(2 * i + 1, dt, da=da2.view(b, n, c), x=h_mid, w=n2w, mod=mod, scale_off=4 * c, eps=eps, y=o2, gate_mod=mod, gate_off=2 * c)
             do, G[P * i + 5], G[P * i + 6] = _lin_grads(do2.view(rows, c), o.view(rows, c), pw, pb, defer=pend)
-            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=ctx.lses[i] if ctx.lses else None)
+            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=ctx.lses[i])
             dqkv = S.qknorm_rope_bwd(i, dq, dk, dv, qkv, qnw, knw, cos, sin, eps)
             da1, G[P * i + 1], G[P * i + 2] = _lin_grads(dqkv.view(rows, 3 * c), a1.view(rows, c), qkvw, qkvb, defer=pend)
             if i > 0:
@@ -1421,7 +1397,7 @@ class DitStackFn(torch.autograd.Function):
             da2 = _lin_grads(dx12.view(rows, -1), None, w12w, w12b, need_w=False)[0]
             do2 = S.boundary_dx(dt, da=da2.view(b, n, c), x=h_mid, w=n2w, mod=mod, scale_off=4 * c, eps=eps, gate_mod=mod, gate_off=2 * c, dy_like=o2)
             do = _lin_grads(do2.view(rows, c), None, pw, pb, need_w=False)[0]
-            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=ctx.lses[i] if ctx.lses else None)
+            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=ctx.lses[i])
             dqkv = S.qknorm_rope_bwd_dx(dq, dk, dv, qkv, qnw, knw, cos, sin, eps)
             da1 = _lin_grads(dqkv.view(rows, 3 * c), None, qkvw, qkvb, need_w=False)[0]
             if i > 0:

@@ -35,7 +35,9 @@ const char* dmvae_last_error(void);
  * 5: dmvae_groupnorm_apply_short / _bwd_short / _short_supported / _bwd_short_workspace, dmvae_lpips_diff_pool.
  * 6: the whole-stack LightningDiT backward (dmvae_dit_boundary_bwd, dmvae_dit_stack_*, dmvae_colsum2_batched, dmvae_qknorm_rope_bwd_partial / _nblk), the batched
  *    per-sample Linears (dmvae_linear_rows_batched_bf16, dmvae_linear_rows_wgrad_batched), dmvae_linear_weight_t_kmajor_batched / dmvae_wt_entry_bytes, the grouped
- *    Linear weight gradients (dmvae_linear_wgrad_grouped*). */
+ *    Linear weight gradients (dmvae_linear_wgrad_grouped*).
+ * 9: nine retired entry points removed: the two-kernel split-K (its GEMM, predicate and sum pass; dmvae_linear_bf16_sk replaces it), the SK counter-size query,
+ *    the im2col form without taps_pad and the four attention entries without row statistics (their _lse forms take lse = NULL). */
 int dmvae_abi_version(void);
 
 /* ---- convolution / GEMM (MFMA-bound) -------------------------------------------------------- */
@@ -263,14 +265,6 @@ int dmvae_linear_bf16_plan(int M, int N, int K, int* tile_cols, int* tile_rows);
 int dmvae_linear_bf16_batched_supported(int batch, int M, int N, int K);
 int dmvae_linear_bf16_batched(const void* x, const void* w, void* y, int batch, int M, int N, int K, int lda, int ldw, int ldy, long long sx, long long sw,
                               long long sy, int out_f32, dmvae_stream_t stream);
-/* Split-K form of dmvae_linear_bf16 for few-tile, deep-K problems (LightningDiT at batch 16: M = 4096 x N = 1152 is 18 tiles of 256 x 256; K = 3072 ... 6144):
- * the reduction cut into `splits` equal parts computed as independent work units into f32 slabs [splits][M][N] (no bias, no activation), then
- * dmvae_splitk_sum_bf16: y bf16 [M][N] = bf16(slab_0 + slab_1 + ... + bias) in that order (bias f32, or bf16 when bias_bf16; may be NULL).
- * K % (32 splits) == 0, K / splits >= 384, N % 8 == 0; w row-major [N][ldw] (w_layout 0) or K-tile-major (1).  Deterministic.  Reference: LightningDiTBlock's Linears, diffusion/lightningdit/lightningdit.py:173-252, swiglu_ffn.py:15-36. */
-int dmvae_linear_bf16_splitk_supported(int M, int N, int K, int splits);
-int dmvae_linear_bf16_splitk(const void* x, const void* w, void* slabs, int splits, int M, int N, int K, int lda, int ldw, int w_layout, dmvae_stream_t stream);
-int dmvae_splitk_sum_bf16(const void* slabs, int splits, const void* bias, int bias_bf16, void* y, int M, int N, dmvae_stream_t stream);
-
 /* SwiGLU FFN's first half in one launch: x12 [M][ldx12] = bf16(x w^T + bias) over the N = 2 H columns [x1 | x2] AND g [M][ldg] = silu(x1) * x2 (H columns): the
  * bits of dmvae_linear_bf16 (act 0) followed by dmvae_swiglu_bf16, without the second pass over the 2 H-wide tensor; x12 is what SwiGLU's backward reads.
  * N % 16 == 0.  Reference: swiglu_ffn.py:31-36 (w12, chunk, silu(x1) * x2). */
@@ -283,11 +277,10 @@ int dmvae_linear_bf16_swiglu_pre(const void* x, const void* w, const void* bias,
  * (tile, K step) space, the cut depends on M; splits 2 .. 8: that many uniform parts per tile -- the cut depends on N and K only, so a row's bits do not depend
  * on the number of rows in the call (train_dmd.py:212-217 evaluated as one 2B call = two B calls).  Run-to-run identical either way (fixed summation order).
  * tile 0: 256 x 256 output tiles; tile 1: 256 columns x 128 rows (a third of the partial bytes per cut; what the few-tile shapes take).
- * act / bias / w_layout as dmvae_linear_bf16.  workspace >= dmvae_linear_bf16_sk_workspace(M, N, K, splits, tile) bytes whose FIRST dmvae_linear_bf16_sk_counter_bytes()
- * bytes are zero on entry (arrival counters; the kernel leaves them zero: zero the buffer once).  Reference: nn.Linear under autocast,
+ * act / bias / w_layout as dmvae_linear_bf16.  workspace >= dmvae_linear_bf16_sk_workspace(M, N, K, splits, tile) bytes whose FIRST 64 KiB
+ * are zero on entry (arrival counters; the kernel leaves them zero: zero the buffer once).  Reference: nn.Linear under autocast,
  * diffusion/lightningdit/lightningdit.py:66-75,236-250, swiglu_ffn.py:15-36, train_dmd.py:563-575 (their backward: dX = dY W). */
 int dmvae_linear_bf16_sk_supported(int M, int N, int K, int splits, int tile);
-size_t dmvae_linear_bf16_sk_counter_bytes(void);
 size_t dmvae_linear_bf16_sk_workspace(int M, int N, int K, int splits, int tile);
 int dmvae_linear_bf16_sk(const void* x, const void* w, const void* bias, void* y, void* workspace, size_t workspace_bytes, int splits, int tile,
                          int M, int N, int K, int lda, int ldw, int ldy, int act, int bias_bf16, int w_layout, dmvae_stream_t stream);
@@ -359,10 +352,9 @@ int dmvae_sumpool2x2_nhwc(const void* dy, void* dx, int n, int h, int w, int c, 
  * col[n,oy,ox,(ky*ks+kx)*c + ci] = x[n, oy*stride-pad+ky, ox*stride-pad+kx, ci] (zero outside), ho = (h+2*pad-ks)/stride+1;
  * col2im is its adjoint (f32 accumulation over the overlapping taps, gather form: deterministic; dcol bf16, or f32 when
  * in_f32 -- the GEMM's f32 result summed without an intermediate rounding, as a direct dgrad conv would).  bf16 x/col/dx, c%8==0.
- * The weight operand [cout][ks*ks][c] comes from dmvae_pack_conv_weight (ks up to 7). */
-int dmvae_im2col_nhwc(const void* x, void* col, int n, int h, int w, int c, int ks, int stride, int pad, dmvae_stream_t stream);
-/* The same with the tap count padded to taps_pad >= ks * ks: col is [n, ho, wo, taps_pad * c], taps past the last one are columns of zeros -- a 3x3 conv over 32
- * channels becomes a 384-column operand (12 x 32), which the 1x1 weight-gradient kernel's 128-column tiles take (the decoder's conv_in, flux_ae.py:196). */
+ * The weight operand [cout][ks*ks][c] comes from dmvae_pack_conv_weight (ks up to 7).
+ * im2col's tap count is padded to taps_pad >= ks * ks (ks * ks: none): col is [n, ho, wo, taps_pad * c], taps past the last one are columns of zeros -- a 3x3 conv
+ * over 32 channels becomes a 384-column operand (12 x 32), which the 1x1 weight-gradient kernel's 128-column tiles take (the decoder's conv_in, flux_ae.py:196). */
 int dmvae_im2col_nhwc_taps(const void* x, void* col, int n, int h, int w, int c, int ks, int stride, int pad, int taps_pad, dmvae_stream_t stream);
 /* The same from the first c of c_src channels of every source pixel (c_src % 8 == 0, c_src >= c): the 8-channel im2col of the first PatchGAN layer's 32-channel
  * padded input (models/patchgan.py:125) without a sliced copy in between. */
@@ -415,18 +407,15 @@ int dmvae_scale_residual_layernorm(void* x, const void* r, const void* ls_gamma,
 int dmvae_scale_residual_f32(void* x, const void* y, const void* gamma, size_t rows, int c, dmvae_stream_t stream);
 /* p[rows][cols] (bf16) = softmax(scale * s[rows][cols]) with bf16 scores, f32 inside; cols <= 512 (encoder attention, S = 257).  Reference: models/dino_layers/attention.py:56-69 (unfused path). */
 int dmvae_softmax_rows_bf16(const void* s, void* p, size_t rows, int cols, float scale, dmvae_stream_t stream);
-/* out[b][s][h*64+d] = softmax_k(scale * q.k) v for qkv [b][s][3][h][64] bf16 (the qkv Linear's output layout): the encoder's
- * multi-head self-attention (timm Attention; dino_layers/attention.py:56-69) fused in one kernel.  head_dim 64, seq <= 288. */
-int dmvae_attention_qkv_bf16(const void* qkv, void* out, int batch, int seq, int heads, int head_dim, float scale,
-                             dmvae_stream_t stream);
-/* The same fused kernel on head-major operands: q, k [batch*heads][seq][head_dim_padded] (channels >= head_dim zero), v
+/* _qkv: out[b][s][h*64+d] = softmax_k(scale * q.k) v for qkv [b][s][3][h][64] bf16 (the qkv Linear's output layout): the encoder's
+ * multi-head self-attention (timm Attention; dino_layers/attention.py:56-69) fused in one kernel.  head_dim 64, seq <= 288.
+ * _heads: the same fused kernel on head-major operands: q, k [batch*heads][seq][head_dim_padded] (channels >= head_dim zero), v
  * [batch*heads][seq][head_dim] bf16 -- what dmvae_qknorm_rope_bf16 produces -> out [batch][seq][heads*head_dim].  LightningDiT's
  * attention after QK-norm + RoPE (models/lightningdit.py:64-98, F.scaled_dot_product_attention); head_dim % 8 == 0, seq <= 288; head_dim_padded = the channels
- * a q / k row holds: 64 or 96, or head_dim itself (<= 96; rows without padding: the kernel does not touch the chunks past head_dim and computes the same bits). */
-int dmvae_attention_heads_bf16(const void* q, const void* k, const void* v, void* out, int batch, int seq, int heads, int head_dim,
-                               int head_dim_padded, float scale, dmvae_stream_t stream);
-/* The two kernels above with the row statistics written out: lse f32 [batch * heads][seq] = scale * max_k(q.k) + log(sum_k exp(scale (q.k - max))) per query -- what
- * dmvae_attention_bwd_*_lse_bf16 rebuild the probabilities from (lse may be NULL: the plain calls).  Reference: models/dino_layers/attention.py:56-69; diffusion/lightningdit/lightningdit.py:76-88 (F.scaled_dot_product_attention). */
+ * a q / k row holds: 64 or 96, or head_dim itself (<= 96; rows without padding: the kernel does not touch the chunks past head_dim and computes the same bits).
+ * Both write the row statistics: lse f32 [batch * heads][seq] = scale * max_k(q.k) + log(sum_k exp(scale (q.k - max))) per query -- what
+ * dmvae_attention_bwd_*_lse_bf16 rebuild the probabilities from (lse may be NULL: the kernel form without them).  Reference: models/dino_layers/attention.py:56-69;
+ * diffusion/lightningdit/lightningdit.py:76-88 (F.scaled_dot_product_attention). */
 int dmvae_attention_qkv_lse_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, dmvae_stream_t stream);
 int dmvae_attention_heads_lse_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
                                    int head_dim_padded, float scale, dmvae_stream_t stream);
@@ -441,13 +430,10 @@ int dmvae_attention_qknorm_rope_bf16(const void* qkv, const void* q_weight, cons
  * S x S probabilities are recomputed in registers and never reach HBM.  out = the forward result [batch][seq][heads*head_dim], dout = its gradient (bf16).
  * _qkv: qkv [batch][seq][3][heads][64] -> dqkv in the same layout (every element of rows < seq written).  head_dim 64, seq <= 288.
  * _heads: q, k [batch*heads][seq][head_dim_padded], v [batch*heads][seq][head_dim] -> dq, dk, dv in the same layouts (padded channels of dq / dk
- *         come out as the zeros the padded operands imply).  head_dim % 8 == 0, head_dim_padded 64, 96 or head_dim (rows without padding), seq <= 288. */
-int dmvae_attention_bwd_qkv_bf16(const void* qkv, const void* out, const void* dout, void* dqkv, int batch, int seq, int heads, int head_dim,
-                                 float scale, dmvae_stream_t stream);
-int dmvae_attention_bwd_heads_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, void* dq, void* dk, void* dv,
-                                   int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale, dmvae_stream_t stream);
-/* The same with the forward's row statistics handed in (lse from dmvae_attention_*_lse_bf16; NULL = the calls above): the probabilities are rebuilt as
- * exp(scale q.k - lse) without a max / sum pass, which frees the registers for two waves per SIMD (eight-wave workgroups).  Reference: Autograd of models/dino_layers/attention.py:56-69 and diffusion/lightningdit/lightningdit.py:76-88 (train_dmd.py:565-575). */
+ *         come out as the zeros the padded operands imply).  head_dim % 8 == 0, head_dim_padded 64, 96 or head_dim (rows without padding), seq <= 288.
+ * lse: the forward's row statistics (dmvae_attention_*_lse_bf16): the probabilities are rebuilt as exp(scale q.k - lse) without a max / sum pass, which frees the
+ * registers for two waves per SIMD (eight-wave workgroups); NULL: the four-wave form that recomputes them.  Reference: Autograd of models/dino_layers/attention.py:56-69
+ * and diffusion/lightningdit/lightningdit.py:76-88 (train_dmd.py:565-575). */
 int dmvae_attention_bwd_qkv_lse_bf16(const void* qkv, const void* out, const void* dout, const void* lse, void* dqkv, int batch, int seq, int heads, int head_dim,
                                      float scale, dmvae_stream_t stream);
 int dmvae_attention_bwd_heads_lse_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq, void* dk,

@@ -102,7 +102,7 @@ def test_qknorm_rope_kernel(heads, d):
 
 @pytest.mark.parametrize("b,heads,d,n", [(2, 16, 72, 256), (3, 2, 64, 64), (1, 4, 72, 288), (2, 3, 64, 37), (1, 2, 40, 96)])
 def test_fused_attention_heads_kernel(b, heads, d, n):
-    """dmvae_attention_heads_bf16 against softmax(scale q k^T) v in f64 on the same bf16 operands (P rounded to bf16 before the second product, as
+    """dmvae_attention_heads_lse_bf16 (lse = NULL) against softmax(scale q k^T) v in f64 on the same bf16 operands (P rounded to bf16 before the second product, as
     the kernel and the autocast graph's flash kernel do), including ragged key counts and the zero-padded head dim."""
     from dmvae_amd import ops
     g = torch.Generator().manual_seed(b * 1000 + d + n)
@@ -131,7 +131,7 @@ def test_fused_attention_heads_kernel(b, heads, d, n):
 
 @pytest.mark.parametrize("b,heads,d,n", [(2, 16, 72, 256), (3, 2, 64, 64), (1, 4, 72, 288), (2, 3, 64, 37), (1, 2, 40, 96)])
 def test_attention_with_qknorm_rope_inside_equals_the_two_kernels(b, heads, d, n):
-    """dmvae_attention_qknorm_rope_bf16 == dmvae_qknorm_rope_bf16 followed by dmvae_attention_heads_bf16 (same arithmetic; only the order of the
+    """dmvae_attention_qknorm_rope_bf16 == dmvae_qknorm_rope_bf16 followed by dmvae_attention_heads_lse_bf16 (same arithmetic; only the order of the
     f32 additions in the row's sum of squares differs)."""
     from dmvae_amd import ops
     g = torch.Generator().manual_seed(b * 100 + d + n)

@@ -1,6 +1,6 @@
 """Attention kernels at the shapes of the DMD / diffusion stages: LightningDiT-XL/1 heads (16 x 72 channels, 256 tokens, q / k padded to 96) at B = 16 / 64 and
 ViT-L/16's packed qkv (16 x 64, 257 tokens) at B = 16 / 32: forward (+ row statistics) and the backward on those statistics, us per call and the algorithmic
-bytes (every operand once, every result once) over that time.  DMVAE_ATTN_XCD=0 runs the plain block order for an A/B."""
+bytes (every operand once, every result once) over that time."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,7 +22,6 @@ def timed(fn, n=50):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-print(f"DMVAE_ATTN_XCD={os.environ.get('DMVAE_ATTN_XCD', '1 (default)')}")
 for B in (16, 32, 64):
     H, N, D, DP = 16, 256, 72, 96
     q = torch.zeros(B * H, N, DP, device="cuda", dtype=BF); k = torch.zeros_like(q)

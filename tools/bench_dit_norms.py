@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """HBM-bound passes of the LightningDiT block (csrc/dit.hip, dit_stack.hip) at the DMD stage's and the diffusion trainer's shapes: microseconds per call and achieved
 TB/s on the algorithmic bytes (every tensor once).  Cold inputs: the calls rotate over enough buffers to defeat the 256-MB Infinity Cache.
-    python tools/bench_dit_norms.py            DMVAE_RM8=0 python tools/bench_dit_norms.py   (the four-channel norm kernels)"""
+    python tools/bench_dit_norms.py"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

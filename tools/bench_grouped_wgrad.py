@@ -1,11 +1,12 @@
 """The grouped Linear weight-gradient launch at LightningDiT-XL/1's backward shapes (4 x 28 problems; B = 16 / 64 -> M = 4096 / 16384 token rows) and at a ViT-L block's
-(4 problems, M = 4112): ms per launch and TFLOP/s.  DMVAE_WGRAD_GROUPED_XCD=0 runs the first placement (every problem spread over all XCDs) for an A/B."""
+(4 problems, M = 4112): ms per launch and TFLOP/s.  --unplaced runs the first placement (every problem spread over all XCDs, ops.WGRAD_GROUPED_XCD = False) for an A/B."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from dmvae_amd import ops
 BF = torch.bfloat16
-print("DMVAE_WGRAD_GROUPED_XCD =", os.environ.get("DMVAE_WGRAD_GROUPED_XCD", "1 (default)"))
+ops.WGRAD_GROUPED_XCD = "--unplaced" not in sys.argv
+print("ops.WGRAD_GROUPED_XCD =", ops.WGRAD_GROUPED_XCD)
 for name, m, layers, shapes in (("DiT-XL/1 B=16", 4096, 28, [(3456, 1152), (1152, 1152), (6144, 1152), (1152, 3072)]), ("DiT-XL/1 B=64", 16384, 28, [(3456, 1152), (1152, 1152), (6144, 1152), (1152, 3072)]),
                                 ("ViT-L block B=16", 4112, 1, [(3072, 1024), (1024, 1024), (4096, 1024), (1024, 4096)])):
     xs = {c: torch.randn(m, c, device="cuda").to(BF) for c in {s[0] for s in shapes} | {s[1] for s in shapes}}

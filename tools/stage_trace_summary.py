@@ -8,7 +8,7 @@ import re
 import sys
 
 FAMILIES = [
-    ("GEMM fwd/dgrad (gemm_pp + split-K sum)", r"gemm_pp_kernel|splitk_sum"),
+    ("GEMM fwd/dgrad (gemm_pp)", r"gemm_pp_kernel"),
     ("GEMM wgrad (wgrad_pp + reduce)", r"wgrad_pp_kernel|wgrad_pp_grouped|wgrad_grouped_bias|rows_wgrad_mfma|linear_rows_wgrad|wgrad_reduce|wgrad_kernel|wgrad_small|wgrad_thin|colsum_kernel|colsum_partial|colsum_final"),
     ("rows Linear (adaLN / embedders)", r"linear_rows"),
     ("conv fwd/dgrad (conv_pp etc.)", r"conv_pp_kernel|conv_fwd|conv_thin|conv_in3|conv_to_image|convout"),
