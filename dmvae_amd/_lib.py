@@ -101,6 +101,7 @@ SIGNATURES = {
     "dmvae_ode_error_ratio": (c_int, [c_void_p, c_void_p, POINTER(OdeTerms), c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dmvae_ode_dense_output": (c_int, [c_void_p] * 5 + [c_int, c_float, c_float, c_void_p, c_size_t, c_void_p]),
     "dmvae_ode_hutchinson_pack": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
+    "dmvae_cfg_combine": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_size_t, c_int, c_float, c_void_p, c_float, c_void_p]),
     "dmvae_batchnorm_running_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p]),
     "dmvae_diffaug_fwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "dmvae_diffaug_bwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),

@@ -11,6 +11,8 @@
 // summed in a fixed order in f64) and the quartic dense output.  Their coefficients and k pointers travel by value in struct dmvae_ode_terms.
 // The likelihood sampler adds one pass per model evaluation (dmvae_ode_hutchinson_pack): the negated velocity into the flat stage buffer and the
 // per-sample Hutchinson sum of the input-VJP against the Rademacher probe.
+// Classifier-free guidance (lightningdit.py:423-447) adds one pass per guided model evaluation (dmvae_cfg_combine): the model's output for the batch
+// [cond | uncond] becomes what forward_with_cfg returns, with the reference's rounding sites and the interval gate read from t on the device.
 // Every kernel takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail.
 #include <initializer_list>
 
@@ -263,6 +265,67 @@ __global__ __launch_bounds__(1024) void ode_hutchinson_pack_kernel(const void* v
   if (threadIdx.x == 0) klogp[blockIdx.x] = (float)red[0];
 }
 
+// ---- classifier-free guidance (LightningDiT.forward_with_cfg, lightningdit.py:423-447) -----------------------------------------------------------
+
+// The reference's three ATen ops on one element: d = cond - uncond, m = scale * d, g = uncond + m.  Each computes in f32; a bf16 tensor rounds (RNE) after
+// every op, an f32 tensor keeps the three f32 roundings (no FMA).  gate: t[0] < cfg_interval_start -> the conditional value itself.
+template <typename T>
+__device__ __forceinline__ float cfg_one(float c, float u, float scale, bool gate) {
+#pragma clang fp contract(off)
+  if (gate) return c;
+  if constexpr (sizeof(T) == 2) {
+    const float d = (float)(bf16)(c - u);
+    const float m = (float)(bf16)(scale * d);
+    return (float)(bf16)(u + m);
+  } else {
+    const float d = c - u;
+    const float m = scale * d;
+    return u + m;
+  }
+}
+
+// src / dst [2][half] with half = n * channels * hw elements ([2n, C, H, W] contiguous): element e of the first half is the conditional sample's, e + half the
+// unconditional one's.  Channels below k: both halves receive the guided value; the others are copied.  nq quads (hw % 4 == 0: a quad never straddles a channel).
+template <typename T>
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const T* __restrict__ src, T* __restrict__ dst, size_t half, size_t nq, size_t hw, int channels, int k,
+                                                          float scale, const float* __restrict__ t, float interval_start) {
+  const bool gate = t != nullptr && t[0] < interval_start;
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) {
+    const size_t e = 4 * i;
+    float c[4], u[4];
+    if constexpr (sizeof(T) == 2) {
+      const bf16x4 a = *reinterpret_cast<const bf16x4*>(src + e), b = *reinterpret_cast<const bf16x4*>(src + half + e);
+#pragma unroll
+      for (int j = 0; j < 4; j++) { c[j] = (float)a[j]; u[j] = (float)b[j]; }
+    } else {
+      const float4 a = *reinterpret_cast<const float4*>(src + e), b = *reinterpret_cast<const float4*>(src + half + e);
+      c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w;
+      u[0] = b.x; u[1] = b.y; u[2] = b.z; u[3] = b.w;
+    }
+    if ((int)((e / hw) % (size_t)channels) < k) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) c[j] = u[j] = cfg_one<T>(c[j], u[j], scale, gate);
+    }
+    if constexpr (sizeof(T) == 2) {
+      bf16x4 a, b;
+#pragma unroll
+      for (int j = 0; j < 4; j++) { a[j] = (bf16)c[j]; b[j] = (bf16)u[j]; }      // exact: every value is a bf16 already
+      *reinterpret_cast<bf16x4*>(dst + e) = a;
+      *reinterpret_cast<bf16x4*>(dst + half + e) = b;
+    } else {
+      *reinterpret_cast<float4*>(dst + e) = make_float4(c[0], c[1], c[2], c[3]);
+      *reinterpret_cast<float4*>(dst + half + e) = make_float4(u[0], u[1], u[2], u[3]);
+    }
+  }
+  for (size_t e = 4 * nq + tid; e < half; e += stride) {
+    float c = (float)src[e], u = (float)src[half + e];
+    if ((int)((e / hw) % (size_t)channels) < k) c = u = cfg_one<T>(c, u, scale, gate);
+    dst[e] = (T)c;
+    dst[half + e] = (T)u;
+  }
+}
+
 constexpr int kErrMaxParts = 1024;
 
 inline int ode_grid(size_t n, size_t nq, int cap) {
@@ -366,6 +429,28 @@ extern "C" int dmvae_ode_hutchinson_pack(const void* v, int v_is_bf16, const voi
   const bool quads = per_sample % 4 == 0 && aligned(v, v_is_bf16 ? 8 : 16) && aligned(g, 16) && aligned(eps, 16) && aligned(k_x, 16);
   hipLaunchKernelGGL(ode_hutchinson_pack_kernel, dim3(batch), dim3(1024), 0, stream, v, v_is_bf16, (const float*)g, (const float*)eps, (float*)k_x, (float*)k_logp,
                      per_sample, (int)quads);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_cfg_combine(const void* out2n, int is_bf16, void* dst, int n, int channels, size_t hw, int k, float scale, const void* t_or_null,
+                                 float interval_start, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(out2n && dst, "cfg_combine: out2n and dst must not be NULL");
+  DMVAE_CHECK_ARG(dst != out2n, "cfg_combine: dst must not alias out2n");
+  DMVAE_CHECK_ARG(n > 0 && channels > 0 && hw > 0 && k >= 0, "cfg_combine: bad argument (n > 0, channels > 0, hw > 0, k >= 0; got n %d, channels %d, hw %zu, k %d)", n,
+                  channels, hw, k);
+  if (k > channels) k = channels;
+  const size_t half = (size_t)n * (size_t)channels * hw;
+  const size_t al = is_bf16 ? 8 : 16;                       // hw % 4 == 0 keeps a quad inside one channel and the second half as aligned as the first
+  const size_t nq = (hw % 4 == 0 && aligned(out2n, al) && aligned(dst, al)) ? half / 4 : 0;
+  const int grid = ode_grid(half, nq, 2048);
+  if (is_bf16)
+    hipLaunchKernelGGL(cfg_combine_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)out2n, (bf16*)dst, half, nq, hw, channels, k, scale,
+                       (const float*)t_or_null, interval_start);
+  else
+    hipLaunchKernelGGL(cfg_combine_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)out2n, (float*)dst, half, nq, hw, channels, k, scale,
+                       (const float*)t_or_null, interval_start);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence
 import torch
 import torch.distributed as tdist
 
-__all__ = ["init_distributed_mode", "initialized", "get_rank", "get_world_size", "get_local_rank", "barrier", "allreduce",
+__all__ = ["init_distributed_mode", "initialized", "get_rank", "get_world_size", "get_local_rank", "barrier", "allreduce", "all_gather_into",
            "is_master", "FlatGradSync", "broadcast_tensors", "broadcast_module_state", "require_initialized"]
 
 _initialized = False
@@ -88,6 +88,16 @@ def allreduce(t: torch.Tensor, async_op: bool = False, op=None):
     if _initialized:
         return tdist.all_reduce(t, op=op or tdist.ReduceOp.SUM, async_op=async_op)
     return None
+
+
+def all_gather_into(out: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """Every rank's `t` into `out` ([world * t.shape[0], ...], rank-major: tdist.all_gather_into_tensor, train_diffusion.py:355-356); a plain copy when no
+    process group is initialised."""
+    if _initialized:
+        tdist.all_gather_into_tensor(out, t.contiguous())
+    else:
+        out.copy_(t)
+    return out
 
 
 def require_initialized(what: str) -> None:

@@ -319,8 +319,34 @@ class LightningDiT(nn.Module):
             x, _ = x.chunk(2, dim=1)
         return x
 
+    def _takes_inference_route(self, x) -> bool:
+        """True where `forward` would hand this call to `lightningdit_fast.forward_inference` (the same tests in the same order)."""
+        if not x.is_cuda:
+            return False
+        from .. import parity
+        from . import lightningdit_fast
+        if parity.on():
+            from . import lightningdit_parity
+            if lightningdit_parity.structurally_supported(self):
+                return False
+        if lightningdit_fast.tokens1_supported(self, x) or not lightningdit_fast.supported(self, x):
+            return False
+        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+
     def forward_with_cfg(self, x, t, y, cfg_scale, cfg_interval=None, cfg_interval_start=None, standard_cfg=False):
-        """lightningdit.py:423-448: both halves of the batch share the latent; guidance on the first 3 (or all in_channels) channels."""
+        """lightningdit.py:423-448: both halves of the batch share the latent; guidance on the first 3 (or all in_channels) channels.  On the HIP inference route
+        the guidance arithmetic is one kernel behind the 2n-sample forward (`lightningdit_fast.forward_inference_cfg`: the composition's bits, and the
+        cfg_interval gate compared on the device instead of on the host); everywhere else the composition below."""
+        if self._takes_inference_route(x):
+            from . import lightningdit_fast
+            gate = cfg_interval is True
+            return lightningdit_fast.forward_inference_cfg(self, x, t, y, cfg_scale, self.in_channels if standard_cfg else 3, t if gate else None,
+                                                           cfg_interval_start if gate else 0.0)
+        return self.forward_with_cfg_composed(x, t, y, cfg_scale, cfg_interval, cfg_interval_start, standard_cfg)
+
+    def forward_with_cfg_composed(self, x, t, y, cfg_scale, cfg_interval=None, cfg_interval_start=None, standard_cfg=False):
+        """The reference's tensor-op composition over `forward` (CPU, parity mode, a gradient wanted, shapes the kernels do not cover; what tools/bench_cfg.py
+        measures the kernel route against).  With cfg_interval the test of t[0] reads the device: a host synchronisation per call."""
         half = x[: len(x) // 2]
         out = self.forward(torch.cat([half, half], dim=0), t, y)
         k = self.in_channels if standard_cfg else 3

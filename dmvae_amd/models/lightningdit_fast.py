@@ -7,6 +7,7 @@ alike: the staged head dim pads to 96; composed batched QK^T GEMM / f32 softmax 
 gated residual -- every token-level Linear on this build's GEMM kernel (`functional.linear`: csrc/gemm_pp.hip).
 The per-sample pieces (timestep / label embedding, adaLN Linear: one row per sample) stay stock PyTorch under autocast."""
 import os
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -132,6 +133,19 @@ def forward_inference(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) 
     return out
 
 
+@torch.no_grad()
+def forward_inference_cfg(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor, cfg_scale: float, k: int, t_gate: Optional[torch.Tensor] = None,
+                          interval_start: float = 0.0) -> torch.Tensor:
+    """`LightningDiT.forward_with_cfg` (lightningdit.py:423-447) on the kernels: x [2n,C,H,W] whose first half is the latent of both halves, y [2n] = labels | null
+    labels -> `forward_inference` at 2n, then ONE launch (`ops.cfg_combine`, csrc/sampler.hip) in place of the slices, sub, mul, add and two cats: the first k
+    channels of both halves become uncond + cfg_scale * (cond - uncond), with the reference's bf16 rounding after each op (the same bits as the composition).
+    `t_gate` (the model's t) switches the cfg_interval gate on: t_gate[0] < interval_start -> the conditional output, compared on the device -- no host read of
+    t, so a guided sampler step can be captured in a graph."""
+    half = x[: len(x) // 2]
+    out = forward_inference(model, torch.cat([half, half], dim=0), t, y)
+    return ops.cfg_combine(out.contiguous(), k, cfg_scale, t_gate, interval_start)
+
+
 class GraphedInference:
     """`forward_inference` of a FROZEN model captured once in a hipGraph and replayed: `f(x, t, y)` copies the arguments into the graph's static inputs,
     replays ~330 kernel launches with one host call and returns the graph's static output buffer (overwritten by the next call -- consume it first).
@@ -149,24 +163,59 @@ class GraphedInference:
         side.wait_stream(cur)
         with torch.cuda.stream(side), torch.no_grad():                      # warm-up off the capture: lazy kernel attributes, GEMM heuristics, weight caches
             for _ in range(warmup):
-                forward_inference(model, self.x, self.t, self.y)
+                self._run()
         cur.wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         # thread-local capture mode: in the default (global) mode every OTHER thread's event query is illegal while the capture lasts -- RCCL's watchdog thread
         # polls its work events all the time (sample_50k.py runs under torchrun) and aborts the process with "operation not permitted when stream is capturing"
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"), torch.no_grad():
-            self.out = forward_inference(model, self.x, self.t, self.y)
+            self.out = self._run()
+
+    def _run(self) -> torch.Tensor:
+        return forward_inference(self.model, self.x, self.t, self.y)
 
     def matches(self, x, t, y) -> bool:
         return x.shape == self.x.shape and x.dtype == self.x.dtype and t.shape == self.t.shape and y.shape == self.y.shape and x.device == self.x.device
 
     def __call__(self, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        assert self.matches(x, t, y), "GraphedInference: shapes differ from the captured ones"
+        assert GraphedInference.matches(self, x, t, y), "GraphedInference: shapes differ from the captured ones"
         self.x.copy_(x)
         self.t.copy_(t)
         self.y.copy_(y)
         self.graph.replay()
         return self.out
+
+
+class GraphedInferenceCfg(GraphedInference):
+    """The guided form: `forward_inference_cfg` captured at the [2n] shape -- the 2n-sample forward and the guidance kernel in one replay per model evaluation.
+    Arguments after (x, t, y) are `LightningDiT.forward_with_cfg`'s; the guidance scale, the number of guided channels and the interval start are fixed at capture.
+    `t` stays a static device input and the interval gate is evaluated by the kernel, so it follows the replayed t.  Called like `model.forward_with_cfg` (the
+    sampler passes cfg_scale / standard_cfg / cfg_interval* as keywords): keywords that differ from the captured ones are an error, not ignored.  Same capture
+    discipline, same lifetime of the returned buffer and the same rule about changed weights as `GraphedInference`."""
+
+    def __init__(self, model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor, cfg_scale: float, cfg_interval=None, cfg_interval_start=None,
+                 standard_cfg: bool = False, warmup: int = 2):
+        if x.shape[0] % 2:
+            raise ValueError("GraphedInferenceCfg: the batch is [cond | uncond], an even number of samples")
+        self.cfg_scale, self.k = float(cfg_scale), int(model.in_channels if standard_cfg else 3)
+        self.interval_start = float(cfg_interval_start) if cfg_interval is True else None
+        super().__init__(model, x, t, y, warmup)
+
+    def _run(self) -> torch.Tensor:
+        gate = self.interval_start is not None
+        return forward_inference_cfg(self.model, self.x, self.t, self.y, self.cfg_scale, self.k, self.t if gate else None, self.interval_start if gate else 0.0)
+
+    def matches(self, x, t, y, cfg_scale, k, interval_start=None) -> bool:
+        """Shapes as `GraphedInference.matches`, and the captured guidance: `cfg_scale`, `k` (guided channels), `interval_start` (None: gate off)."""
+        return (super().matches(x, t, y) and float(cfg_scale) == self.cfg_scale and int(k) == self.k
+                and (None if interval_start is None else float(interval_start)) == self.interval_start)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor, cfg_scale=None, cfg_interval=None, cfg_interval_start=None, standard_cfg=None) -> torch.Tensor:
+        cfg_scale = self.cfg_scale if cfg_scale is None else cfg_scale
+        k = self.k if standard_cfg is None else (self.model.in_channels if standard_cfg else 3)
+        start = self.interval_start if cfg_interval is None else (cfg_interval_start if cfg_interval is True else None)
+        assert self.matches(x, t, y, cfg_scale, k, start), "GraphedInferenceCfg: shapes or guidance settings differ from the captured ones"
+        return GraphedInference.__call__(self, x, t, y)
 
 
 STACK_SEGMENTS = 1        # autograd nodes the block stack is cut into in a single process

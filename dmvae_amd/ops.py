@@ -1692,6 +1692,33 @@ def ode_hutchinson_pack(v: torch.Tensor, g: torch.Tensor, eps: torch.Tensor, out
     return out
 
 
+def cfg_combine(out2n: torch.Tensor, k: int, scale: float, t: Optional[torch.Tensor] = None, interval_start: float = 0.0,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Classifier-free guidance on a model output in one launch (LightningDiT.forward_with_cfg, lightningdit.py:423-447): out2n [2n, C, H, W] (bf16 or f32,
+    contiguous) is the model's output for [cond | uncond]; channels below k (clamped to C) become uncond + scale * (cond - uncond) in both halves -- rounded
+    where the reference's three ops round, bit-identical to PyTorch on the CPU --, the others keep each half's value.  `t` (any floating dtype, at least one
+    element, on out2n's device) switches the interval gate on: where t[0] < interval_start the guided channels are cond; the comparison runs on the device.
+    `out` (optional) must not be out2n."""
+    _req(out2n, bf16 if out2n.dtype == bf16 else f32, "out2n")
+    if out2n.dim() != 4 or out2n.shape[0] < 2 or out2n.shape[0] % 2 or out2n.numel() == 0:
+        raise ValueError(f"cfg_combine: out2n must be a non-empty [2n, C, H, W] tensor, got {tuple(out2n.shape)}")
+    if int(k) < 0:
+        raise ValueError(f"cfg_combine: k must be >= 0, got {k}")
+    if t is not None:
+        if not t.is_cuda or t.device != out2n.device or not t.is_floating_point() or t.numel() < 1:
+            raise ValueError(f"cfg_combine: t must be a non-empty floating-point tensor on {out2n.device}")
+        t = t.reshape(-1)[:1].to(f32).contiguous()           # device-side conversion: no host read
+    if out is None:
+        out = torch.empty_like(out2n)
+    _same(_req(out, out2n.dtype, "out"), out2n, "out")
+    if out.data_ptr() == out2n.data_ptr():
+        raise ValueError("cfg_combine: out must not alias out2n")
+    n2, c, h, w = out2n.shape
+    check(_lib.lib().dmvae_cfg_combine(out2n.data_ptr(), int(out2n.dtype == bf16), out.data_ptr(), n2 // 2, c, h * w, int(k), float(scale), _ptr(t),
+                                       float(interval_start), _stream()), "cfg_combine")
+    return out
+
+
 def image_to_u8(y: torch.Tensor, channels: int, round_bf16: bool = False) -> torch.Tensor:
     """y [N,H,W,Cs] f32 (NHWC, first `channels` used) -> [N,H,W,channels] uint8 = clamp(127.5 y + 128, 0, 255) truncated (sample_50k.py:151)."""
     y = _req(y, f32, "y")

@@ -48,6 +48,21 @@ def tokens_to_dit_input(tokens: torch.Tensor, latent_mean: float, latent_scale: 
     return x.reshape(b, h, h, c).permute(0, 3, 1, 2).contiguous()
 
 
+def cfg_inputs(z: torch.Tensor, y: torch.Tensor, null_label: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """train_diffusion.py:250-253: the guided sampler's state and labels -- [z | z] and [y | null], the null label being the embedding table's extra row
+    (lightningdit.py:149-150; index num_classes)."""
+    return torch.cat([z, z], dim=0), torch.cat([y, torch.full_like(y, null_label)], dim=0)
+
+
+def guided_sample(sample_fn, model_fn_for, z: torch.Tensor, y: torch.Tensor, null_label: int, **model_kwargs) -> torch.Tensor:
+    """The guided run of train_diffusion.py:250-255,340-344: the sampler integrates the doubled state [2n] as the reference does (dopri5's error norm and the
+    SDE's noise draws cover both halves, and the first half's trajectory depends on that) and the null half of the last state is dropped.
+    `model_fn_for(zz, yy)` returns the `forward_with_cfg` to call at the doubled shape (the bound method, or its graph); `model_kwargs`: cfg_scale,
+    standard_cfg, cfg_interval, cfg_interval_start."""
+    zz, yy = cfg_inputs(z, y, null_label)
+    return sample_fn(zz, model_fn_for(zz, yy), y=yy, **model_kwargs)[-1].chunk(2, dim=0)[0]
+
+
 class _PngWriter:
     """Encodes and writes PNGs on a host thread (PIL), bounded queue."""
 
@@ -83,14 +98,24 @@ class _PngWriter:
 
 
 class SamplePipeline:
-    """`model`: LightningDiT (eval); `vae`: dmvae_amd.models.vae.VAE (eval).  Keyword names follow sample_50k.Args."""
+    """`model`: LightningDiT (eval); `vae`: dmvae_amd.models.vae.VAE (eval).  Keyword names follow sample_50k.Args.
+
+    `guidance=None` (default) is the reference's script: its `using_cfg` (sample_50k.py:120) is never used, so `cfg_scale` is accepted and ignored.
+    `guidance="cfg"` with `cfg_scale > 1` samples with classifier-free guidance the way train_diffusion.py:250-255,340-344 does -- state [z | z], labels
+    [y | null], `model.forward_with_cfg` (one hipGraph replay per evaluation with `use_graph`), the conditional half kept; `standard_cfg` and
+    `cfg_interval_start` (None: no interval gate) are `forward_with_cfg`'s.  `guidance="cfg"` with `cfg_scale == 1` is the unguided path."""
 
     def __init__(self, model, vae, *, mode="SDE", sampling_method="Euler", num_sampling_steps=250, diffusion_form="sigma", diffusion_norm=1.0,
                  last_step="Mean", last_step_size=0.04, atol=1e-6, rtol=1e-3, reverse=False, cfg_scale=1.0, latent_mean=0.0, latent_scale=1.0,
-                 path_type="Linear", prediction="velocity", loss_weight=None, train_eps=0.0, sample_eps=0.0, time_dist_shift=1.0, use_graph=True):
+                 path_type="Linear", prediction="velocity", loss_weight=None, train_eps=0.0, sample_eps=0.0, time_dist_shift=1.0, use_graph=True,
+                 guidance=None, standard_cfg=True, cfg_interval_start=None):
         assert cfg_scale >= 1.0, "In almost all cases, cfg_scale be >= 1.0"
+        if guidance not in (None, "cfg"):
+            raise ValueError(f"guidance: None or 'cfg', got {guidance!r}")
         self.model, self.vae = model, vae
         self.latent_mean, self.latent_scale, self.cfg_scale = latent_mean, latent_scale, cfg_scale
+        self.guided = guidance == "cfg" and cfg_scale > 1.0
+        self.standard_cfg, self.cfg_interval_start = bool(standard_cfg), cfg_interval_start
         self.use_graph, self._graphed = use_graph, None      # the frozen DiT forward as one hipGraph replay per sampler step (models/lightningdit_fast.GraphedInference)
         transport = create_transport(path_type, prediction, loss_weight, train_eps, sample_eps, time_dist_shift=time_dist_shift)
         sampler = Sampler(transport)
@@ -100,20 +125,36 @@ class SamplePipeline:
             self.sample_fn = sampler.sample_sde(sampling_method=sampling_method, diffusion_form=diffusion_form, diffusion_norm=diffusion_norm,
                                                 last_step=last_step, last_step_size=last_step_size, num_steps=num_sampling_steps)
 
+    def _cfg_kwargs(self) -> dict:
+        """`forward_with_cfg`'s keywords for this pipeline's guidance settings."""
+        kw = dict(cfg_scale=self.cfg_scale, standard_cfg=self.standard_cfg)
+        if self.cfg_interval_start is not None:
+            kw.update(cfg_interval=True, cfg_interval_start=self.cfg_interval_start)
+        return kw
+
     @torch.no_grad()
     def latents(self, z: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """noise [n, C, h, w] + labels [n] -> latent tokens [n, h*w, C] (sample_50k.py:138-148), under autocast(bf16) like the script."""
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            samples = self.sample_fn(z, self._model_fn(z, y), y=y)[-1]        # the script never enables guidance (cfg_scale stays 1.0, :79)
+            if self.guided:
+                samples = guided_sample(self.sample_fn, self._model_fn, z, y, self.model.y_embedder.num_classes, **self._cfg_kwargs())
+            else:
+                samples = self.sample_fn(z, self._model_fn(z, y), y=y)[-1]        # the script never enables guidance (cfg_scale stays 1.0, :79)
         return dit_output_to_tokens(samples.float(), self.latent_mean, self.latent_scale)
 
     def _model_fn(self, z, y):
-        """`model.forward`, or its hipGraph replay when the model takes the HIP inference route at this shape (called under autocast)."""
+        """`model.forward` (guided: `model.forward_with_cfg`), or its hipGraph replay when the model takes the HIP inference route at this shape (called under
+        autocast with the state and labels the sampler will pass: doubled when guided)."""
         from .models import lightningdit_fast as fast
         if not (self.use_graph and z.is_cuda and hasattr(self.model, "blocks") and fast.supported(self.model, z)):
-            return self.model.forward
+            return self.model.forward_with_cfg if self.guided else self.model.forward
         t = torch.zeros(z.shape[0], device=z.device, dtype=z.dtype)
-        if self._graphed is None or not self._graphed.matches(z, t, y):
+        if self.guided:
+            k = self.model.in_channels if self.standard_cfg else 3
+            g = self._graphed
+            if not (isinstance(g, fast.GraphedInferenceCfg) and g.matches(z, t, y, self.cfg_scale, k, self.cfg_interval_start)):
+                self._graphed = fast.GraphedInferenceCfg(self.model, z, t, y, **self._cfg_kwargs())
+        elif self._graphed is None or not self._graphed.matches(z, t, y):
             self._graphed = fast.GraphedInference(self.model, z, t, y)
         return self._graphed
 

@@ -655,6 +655,71 @@ class DiffusionTrainer:
         self.train_steps += 1
         return loss.detach()
 
+    def _ema_twin(self):
+        """The EMA model of train_diffusion.py:192-193,231-233 as a module: a copy of the model (built once; eval, no gradients) whose trainable parameters are
+        overwritten with the current averages of `fp.ema` before each use.  The in-place copy bumps each parameter's version, so the cached bf16 operands of the
+        kernels (functional._bf) are converted again -- into NEW tensors, which is why a graph of the twin is captured per `sample` call, after the refresh."""
+        import copy
+        self.opt.wait()
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        if getattr(self, "_twin", None) is None:
+            twin = copy.deepcopy(self.model)
+            for p in twin.parameters():                       # the copy owns plain tensors: nothing of the flat buffers' bookkeeping
+                for a in [a for a in vars(p) if a.startswith("_dmvae")]:
+                    delattr(p, a)
+            self._twin = twin.eval().requires_grad_(False)
+        tp = dict(self._twin.named_parameters())
+        with torch.no_grad():
+            for p, e in zip(self.fp.params, self.fp.ema_state()):
+                tp[names[id(p)]].copy_(e)
+            for n, p in self.model.named_parameters():
+                if not p.requires_grad:                       # pos_embed: fixed; ema_state_dict carries the model's
+                    tp[n].copy_(p)
+        return self._twin
+
+    @torch.no_grad()
+    def sample(self, labels: torch.Tensor, noise: Optional[torch.Tensor] = None, *, cfg_scale: float = 4.0, sampling_method: str = "dopri5", num_steps: int = 50,
+               atol: float = 1e-6, rtol: float = 1e-3, decode: bool = True) -> torch.Tensor:
+        """The EMA samples of train_diffusion.py:242-258,335-359: the ODE sampler on the EMA weights under autocast(bf16), with classifier-free guidance when
+        `cfg_scale > 1` (`forward_with_cfg`, standard_cfg=True, state and labels doubled, null half dropped), tokens / latent_scale + latent_mean,
+        `vae.decode(...).float()`, gathered over the ranks when a process group is initialised.  `decode=False` returns the latent tokens [n, h*w, C].
+        `noise` [n, C, h, w]: drawn from a generator of the call's own when not given, so the global generators -- and with them the draws of the following
+        `step()` -- are untouched.  The training model, its mode and the optimiser state are left as they were."""
+        from .models import lightningdit_fast as fast
+        from .sample import dit_output_to_tokens, guided_sample
+        from .transport import Sampler
+        ema = self._ema_twin()                                # waits for an overlapped optimiser step first
+        dev = self.fp.flat.device
+        labels = labels.to(dev)
+        n = labels.shape[0]
+        if noise is None:
+            size = int(round(ema.x_embedder.num_patches ** 0.5)) * ema.patch_size
+            gen = torch.Generator(device=dev).manual_seed(self.train_steps)
+            noise = torch.randn(n, ema.in_channels, size, size, device=dev, generator=gen)
+        noise = noise.to(dev)
+        sample_fn = Sampler(self.transport).sample_ode(sampling_method=sampling_method, num_steps=num_steps, atol=atol, rtol=rtol)
+        use_cfg = cfg_scale > 1.0
+        kw = dict(cfg_scale=cfg_scale, standard_cfg=True) if use_cfg else {}
+
+        def model_fn_for(z, y):
+            if z.is_cuda and fast.supported(ema, z) and not parity.on():      # one replay per evaluation; captured per call (see _ema_twin)
+                t = torch.zeros(z.shape[0], device=z.device, dtype=z.dtype)
+                return fast.GraphedInferenceCfg(ema, z, t, y, **kw) if use_cfg else fast.GraphedInference(ema, z, t, y)
+            return ema.forward_with_cfg if use_cfg else ema.forward
+
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            if use_cfg:
+                samples = guided_sample(sample_fn, model_fn_for, noise, labels, ema.y_embedder.num_classes, **kw)
+            else:
+                samples = sample_fn(noise, model_fn_for(noise, labels), y=labels)[-1]
+            dist.barrier()
+            tok = dit_output_to_tokens(samples, self.latent_mean, self.latent_scale)
+            if not decode:
+                return tok.float()
+            images = self.vae.decode(tok).float()
+        out = torch.zeros((n * dist.get_world_size(),) + tuple(images.shape[1:]), device=dev)
+        return dist.all_gather_into(out, images)
+
     def ema_state_dict(self):
         """The `ema` entry of the reference's checkpoint (:316-323): the model's state_dict with the trainable parameters replaced by their averages."""
         self.opt.wait()

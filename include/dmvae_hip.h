@@ -719,6 +719,15 @@ int dmvae_ode_dense_output(const void* y0, const void* y1, const void* y_mid, co
  * per_sample] and k_logp [batch] f32 -- in the sampler, the two parts of one flat stage buffer.  Any per_sample. */
 int dmvae_ode_hutchinson_pack(const void* v, int v_is_bf16, const void* g, const void* eps, void* k_x, void* k_logp, int batch, size_t per_sample,
                               dmvae_stream_t stream);
+/* Classifier-free guidance on a model output (LightningDiT.forward_with_cfg, diffusion/lightningdit/lightningdit.py:423-447), one launch: out2n [2n, channels, hw]
+ * is the model's output for the batch [cond | uncond] (bf16 when is_bf16, else f32); dst, of the same shape and type and never out2n itself, receives
+ *   channel c <  k: g = uncond + scale * (cond - uncond) in BOTH halves     (k = in_channels for standard_cfg, 3 otherwise; clamped to channels)
+ *   channel c >= k: each half's own value
+ * t_or_null != NULL: the interval gate, read on the device -- when ((const float*)t_or_null)[0] < interval_start the guided channels are cond instead.
+ * Rounding is the reference's: a bf16 output rounds (to nearest even) after each of the three ops -- d = bf16(cond - uncond), m = bf16(scale * d) with scale in
+ * f32, g = bf16(uncond + m) --; an f32 output keeps the three f32 operations apart (no FMA): bit-identical to the PyTorch-CPU result in either type. */
+int dmvae_cfg_combine(const void* out2n, int is_bf16, void* dst, int n, int channels, size_t hw, int k, float scale, const void* t_or_null,
+                      float interval_start, dmvae_stream_t stream);
 
 /* ---- fp32 parity mode (DMVAE_PARITY=1; csrc/parity.hip) ---------------------------------------------------------------------------
  * north_star: "match the reference PyTorch-CPU path within 1e-4 relative fp32".  In this mode activations are f32 NHWC and every
