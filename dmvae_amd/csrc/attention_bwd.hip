@@ -40,13 +40,6 @@ struct Args {
   int xcd;                       // 1: block -> (batch, head) through xcd_remap (vit.hip::AttnArgs::xcd)
 };
 
-__device__ __forceinline__ s16x4 tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  bf16x2 t = {(bf16)a, (bf16)b};
-  return *reinterpret_cast<unsigned*>(&t);
-}
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * PITCH + (((chunk & ~3) | ((chunk & 3) ^ ((row >> 2) & 3))) << 4); }
 // LDS operand layouts of the lse kernels' two block functions.  Wide: the 192-B rows above (both head widths).  Tight (72-channel heads, S <= 256 only): 144-B rows
 // holding the 72 real channels, no swizzle -- row reads: sixteen rows 36 banks apart land on sixteen distinct 4-bank slots (9 is odd), conflict-free as they are;
@@ -85,8 +78,8 @@ __device__ __forceinline__ float dot8(const uint4& a, const uint4& b) {
 __device__ __forceinline__ void to_afrag(const f32x16& c, bf16x8 out[2]) {
 #pragma unroll
   for (int half = 0; half < 2; half++) {
-    const unsigned p0 = pack2(c[half * 8 + 0], c[half * 8 + 1]), p1 = pack2(c[half * 8 + 2], c[half * 8 + 3]);
-    const unsigned p2 = pack2(c[half * 8 + 4], c[half * 8 + 5]), p3 = pack2(c[half * 8 + 6], c[half * 8 + 7]);
+    const unsigned p0 = dmvae_pack_bf16x2(c[half * 8 + 0], c[half * 8 + 1]), p1 = dmvae_pack_bf16x2(c[half * 8 + 2], c[half * 8 + 3]);
+    const unsigned p2 = dmvae_pack_bf16x2(c[half * 8 + 4], c[half * 8 + 5]), p3 = dmvae_pack_bf16x2(c[half * 8 + 6], c[half * 8 + 7]);
     // lanes < 32 hold rows {0-3, 8-11} of the half, lanes >= 32 rows {4-7, 12-15}: the fragment wants {0-7} / {8-15}
     const auto s0 = __builtin_amdgcn_permlane32_swap(p0, p2, false, false);
     const auto s1 = __builtin_amdgcn_permlane32_swap(p1, p3, false, false);
@@ -226,8 +219,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(Args a) {
 #pragma unroll
         for (int db = 0; db < DB; db++) {
           union { bf16x8 v; s16x4 hlf[2]; } kf;
-          kf.hlf[0] = tr_read(base + toff0[db]);
-          kf.hlf[1] = tr_read(base + toff1[db]);
+          kf.hlf[0] = tr_read_ordered(base + toff0[db]);
+          kf.hlf[1] = tr_read_ordered(base + toff1[db]);
           dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[half], kf.v, dq[db], 0, 0, 0);
         }
       }
@@ -298,10 +291,10 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(Args a) {
 #pragma unroll
         for (int db = 0; db < DB; db++) {
           union { bf16x8 v; s16x4 hlf[2]; } df, qf2;
-          df.hlf[0] = tr_read(buf1 + rbase + toff0[db]);
-          df.hlf[1] = tr_read(buf1 + rbase + toff1[db]);
-          qf2.hlf[0] = tr_read(buf0 + rbase + toff0[db]);
-          qf2.hlf[1] = tr_read(buf0 + rbase + toff1[db]);
+          df.hlf[0] = tr_read_ordered(buf1 + rbase + toff0[db]);
+          df.hlf[1] = tr_read_ordered(buf1 + rbase + toff1[db]);
+          qf2.hlf[0] = tr_read_ordered(buf0 + rbase + toff0[db]);
+          qf2.hlf[1] = tr_read_ordered(buf0 + rbase + toff1[db]);
           dv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[half], df.v, dv[db], 0, 0, 0);
           dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsf[half], qf2.v, dk[db], 0, 0, 0);
         }
@@ -355,8 +348,8 @@ __device__ __forceinline__ void lse_dq_block(const char* buf0, const char* buf1,
       const char* base = buf0 + (kb * 2 + half) * 16 * L::PITCH_;
 #pragma unroll
       for (int db = 0; db < DB; db++) {
-        ktr[half][db].hlf[0] = tr_read(base + toff0[db]);
-        ktr[half][db].hlf[1] = tr_read(base + toff1[db]);
+        ktr[half][db].hlf[0] = tr_read_ordered(base + toff0[db]);
+        ktr[half][db].hlf[1] = tr_read_ordered(base + toff1[db]);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -430,10 +423,10 @@ __device__ __forceinline__ void lse_dkdv_block(const char* bufq, const char* buf
 #pragma unroll
     for (int db = 0; db < DB; db++) {
       const int rbase = (qb * 2) * 16 * L::PITCH_;
-      dft[0][db].hlf[0] = tr_read(bufd + rbase + toff0[db]);
-      dft[0][db].hlf[1] = tr_read(bufd + rbase + toff1[db]);
-      qft[0][db].hlf[0] = tr_read(bufq + rbase + toff0[db]);
-      qft[0][db].hlf[1] = tr_read(bufq + rbase + toff1[db]);
+      dft[0][db].hlf[0] = tr_read_ordered(bufd + rbase + toff0[db]);
+      dft[0][db].hlf[1] = tr_read_ordered(bufd + rbase + toff1[db]);
+      qft[0][db].hlf[0] = tr_read_ordered(bufq + rbase + toff0[db]);
+      qft[0][db].hlf[1] = tr_read_ordered(bufq + rbase + toff1[db]);
     }
     __builtin_amdgcn_sched_barrier(0);
     bf16x8 pf[2], dsf[2];
@@ -442,10 +435,10 @@ __device__ __forceinline__ void lse_dkdv_block(const char* bufq, const char* buf
 #pragma unroll
     for (int db = 0; db < DB; db++) {
       const int rbase = (qb * 2 + 1) * 16 * L::PITCH_;
-      dft[1][db].hlf[0] = tr_read(bufd + rbase + toff0[db]);
-      dft[1][db].hlf[1] = tr_read(bufd + rbase + toff1[db]);
-      qft[1][db].hlf[0] = tr_read(bufq + rbase + toff0[db]);
-      qft[1][db].hlf[1] = tr_read(bufq + rbase + toff1[db]);
+      dft[1][db].hlf[0] = tr_read_ordered(bufd + rbase + toff0[db]);
+      dft[1][db].hlf[1] = tr_read_ordered(bufd + rbase + toff1[db]);
+      qft[1][db].hlf[0] = tr_read_ordered(bufq + rbase + toff0[db]);
+      qft[1][db].hlf[1] = tr_read_ordered(bufq + rbase + toff1[db]);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -931,27 +924,15 @@ __global__ __launch_bounds__(512) void attention_bwd_lse3_kernel(Args a) {
 template <int DP>
 static int launch(const Args& a, int batch, hipStream_t stream) {
   constexpr int lds = 2 * BUF + 2 * KEYS * (int)sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_kernel<DP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, attention_bwd_kernel<DP>);
   if (a.lse) {
-    static bool attr2_done = false;
-    if (!attr2_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_lse_kernel<DP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      attr2_done = true;
-    }
+    DMVAE_LDS_OPTIN(lds, attention_bwd_lse_kernel<DP>);
     Args b_ = a;
     b_.xcd = 1;
     if constexpr (DP == 96) {
       if (a.D == 72 && a.S <= 256 && batch * a.H >= 512) {     // two or more items per CU: two out-of-phase 4-wave workgroups per CU on the 144-B layout
         constexpr int ldst = 2 * 256 * 144 + 2 * 256 * (int)sizeof(float);
-        static bool attrt_done = false;
-        if (!attrt_done) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_lse_tight_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ldst);
-          attrt_done = true;
-        }
+        DMVAE_LDS_OPTIN(ldst, attention_bwd_lse_tight_kernel);
         hipLaunchKernelGGL(attention_bwd_lse_tight_kernel, dim3(batch * a.H), dim3(256), ldst, stream, b_);
         DMVAE_CHECK_LAUNCH();
         return 0;
@@ -961,11 +942,7 @@ static int launch(const Args& a, int batch, hipStream_t stream) {
     // with four rounds per CU the kernel is in its bandwidth-bound regime and the larger load burst at the head of every block costs more than the hidden latency returns
     if (a.S <= ROWS3 && batch * a.H <= 512) {
       constexpr int lds3 = 3 * BUF3 + 2 * ROWS3 * (int)sizeof(float);
-      static bool attr3_done = false;
-      if (!attr3_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_bwd_lse3_kernel<DP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds3);
-        attr3_done = true;
-      }
+      DMVAE_LDS_OPTIN(lds3, attention_bwd_lse3_kernel<DP>);
       hipLaunchKernelGGL((attention_bwd_lse3_kernel<DP>), dim3(batch * a.H), dim3(512), lds3, stream, b_);
     } else {
       hipLaunchKernelGGL((attention_bwd_lse_kernel<DP>), dim3(batch * a.H), dim3(512), lds, stream, b_);

@@ -23,6 +23,68 @@ void dmvae_set_error(const char* fmt, ...);
 #define DMVAE_CHECK_ARG(cond, ...) do { if (!(cond)) { dmvae_set_error(__VA_ARGS__); return -22; } } while (0)
 #define DMVAE_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { dmvae_set_error("%s:%d launch failed: %s", __FILE__, __LINE__, hipGetErrorString(e_)); return -5; } } while (0)
 
+// Grid of a grid-stride kernel: ceil(n / block) blocks, at least 1, at most `cap`.  No default cap: some kernels lay their partial sums out by grid size, so
+// every caller names the cap it was tuned and tested with.
+static inline int grid_for(size_t n, int block, int cap) {
+  size_t g = (n + block - 1) / block;
+  return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
+}
+
+// Opt-in to more than the default 64 KB of dynamic LDS, which a kernel needs set once on every device it is launched on (the attribute is kept per device, so
+// a process-wide "done" flag would leave a second device without it and its launches failing).  `seen` is the call site's static: bit d = set on device d
+// (devices past 63 share bit 63's "set it every time").  After the first call on a device this is one hipGetDevice and one relaxed load; no lock, no
+// allocation -- two threads racing through the first call both set the same value.  Returns 0, or -5 with the site in dmvae_last_error().  (api.hip)
+struct dmvae_lds_seen { unsigned long long devs; };
+int dmvae_lds_optin(dmvae_lds_seen* seen, const void* kernel, int bytes, const char* file, int line);
+// DMVAE_LDS_OPTIN(bytes, kernel<template, arguments>): in front of the launch, in a function that returns the C ABI's int
+#define DMVAE_LDS_OPTIN(bytes, ...) do { static dmvae_lds_seen seen_; if (dmvae_lds_optin(&seen_, reinterpret_cast<const void*>(__VA_ARGS__), (int)(bytes), __FILE__, __LINE__)) return -5; } while (0)
+
+// ---- primitives of the LDS-DMA pipelined kernels (conv_pp, gemm_pp, conv_wgrad_pp, wgrad_thin) ---------------------------------------------------------
+
+// Raw buffer descriptor over `bytes` bytes at p (stride 0: voffset + soffset is a byte offset, range-checked against `bytes`; a load past it returns zeros, an
+// LDS-DMA writes zeros, a store is dropped).  The last word is dword 3 of the gfx9 / CDNA descriptor: DATA_FORMAT (bits 18:15) = 4, BUF_DATA_FORMAT_32 (0 is
+// BUF_DATA_FORMAT_INVALID), and everything else zero: no swizzle, no add-tid; dst_sel and num_format are not used by the untyped accesses of these kernels.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t dmvae_buffer_rsrc(const void* p, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+// A voffset beyond any descriptor's num_records: loads return zeros, the LDS-DMA writes zeros, stores are dropped.
+constexpr unsigned SENT = 0x80000000u;
+
+// Chunk key of 64-B LDS rows, 4 rows per 256-B bank row.  Fragments are read for v_mfma_f32_16x16x32_bf16: lane l takes the 16-B chunk l >> 4 of row (l & 15), and
+// ds_read_b128 serves the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... in one pass each; with the chunk XOR-ed by (-(row >> 2)) & 3 the four lanes of
+// a group that share row % 4 land in four different 16-B slots of the bank row (derivation in DESIGN_HISTORY.md 3.1).
+__device__ __forceinline__ int swz64(int row) { return (0 - (row >> 2)) & 3; }
+
+// s_waitcnt vmcnt(N) through the builtin, not inline asm: the compiler's own wait-count pass then SEES the wait.  With the asm form it kept a VMEM event from
+// before the K loop pending on a fragment register for ever (the loop's own LDS-DMA instructions make its count imprecise) and put an s_waitcnt vmcnt(0) in
+// front of the second ds_read of every K tile.  Removing that drain changed nothing measurable in conv_pp (342 vs 340 us per launch in the step): by then the
+// pieces of the next tiles have landed anyway -- the loop is not waiting on the DMA queue.
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit field on gfx9");
+  __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));   // gfx9 encoding: vmcnt[3:0] | expcnt 7 | lgkmcnt 15 | vmcnt[5:4] << 14
+  asm volatile("" ::: "memory");
+}
+
+// The transpose read (ds_read_b64_tr_b16) in two forms.  Which one a kernel takes depends on who orders it behind the writes of the tile it reads:
+//
+// tr_read_uncounted<OFF>(lds byte address): inline asm, for kernels whose LDS is filled by LDS-DMA into a ring.  The compiler's wait-count pass orders every
+// LDS read it can see behind every earlier LDS-DMA (it cannot prove the ring slots disjoint) and put an s_waitcnt vmcnt(0) at the head of the K loop -- the
+// three-tile prefetch queue was drained once per K tile and the loop ran at the latency of the newest piece (tools/loop_waits.py shows the skeleton;
+// conv_wgrad_pp 128->128 @256^2: DESIGN_HISTORY.md 8.12).  The asm form carries no memory operand: the CALLER's counted wait_vmcnt + barrier protocol is what
+// orders the read behind the pieces it needs, and the caller's lgkmcnt(0) ahead of the barrier covers the result.
+template <int OFF>
+__device__ __forceinline__ s16x4 tr_read_uncounted(unsigned lds_addr) {
+  s16x4 r;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF));
+  return r;
+}
+// tr_read_ordered(pointer into LDS): the builtin, for kernels that fill LDS with ordinary ds_write / global loads + __syncthreads(): the compiler sees the
+// memory operand and places every wait itself.  Never inside an LDS-DMA ring (above).
+__device__ __forceinline__ s16x4 tr_read_ordered(const char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -32,6 +94,7 @@ __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 // v_rcp_f32 (1 ulp), not an IEEE division: `1.0f / y` compiles to v_div_scale x2 + v_rcp + four FMAs + v_div_fmas + v_div_fixup -- ten instructions per element in
 // kernels (GroupNorm backward: 23 of ~37 VALU instructions per element were the two divisions' sequences) whose results are rounded to bf16 anyway.
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }   // the f32 parity kernels' (parity.hip, parity_dit.hip): IEEE division, libm expf
 
 // Exact-form GELU 0.5 x (1 + erf(x / sqrt 2)) (nn.GELU() of timm's Mlp, reached through models/vae.py:47-53) with erf from Abramowitz & Stegun 7.1.26
 // (|error| <= 1.5e-7): E = (a1 t + ... + a5 t^5) exp(-z^2), t = 1 / (1 + p z), z = |x| / sqrt 2, and 1 + erf(x / sqrt 2) = E for x < 0, 2 - E for x >= 0 --

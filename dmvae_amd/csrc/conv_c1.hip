@@ -20,13 +20,13 @@ namespace dmvae_c1 {
 
 constexpr int W_IN = 31, W_OUT = 30;
 
-__device__ __forceinline__ void cvt8(const uint4& u, float (&f)[8]) {
+__device__ __forceinline__ void cvt8_raw(const uint4& u, float (&f)[8]) {
   const bf16x8 v = *reinterpret_cast<const bf16x8*>(&u);
 #pragma unroll
   for (int i = 0; i < 8; i++) f[i] = (float)v[i];
 }
 // the lane's eight channels of tap (ky, kx) from the parameter [1][C][4][4] f32, rounded to bf16 as the autocast conv's operand
-__device__ __forceinline__ void load_w(const float* __restrict__ w, int c0, float (&wr)[16][8]) {
+__device__ __forceinline__ void load_w_taps(const float* __restrict__ w, int c0, float (&wr)[16][8]) {
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     const f32x4* p = reinterpret_cast<const f32x4*>(w + (size_t)(c0 + i) * 16);
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void fwd_kernel(const bf16* __restrict__ x, co
 #pragma unroll
       for (int ix = 0; ix < W_IN; ix++) {
         float v[8];
-        cvt8(px[ix], v);
+        cvt8_raw(px[ix], v);
 #pragma unroll
         for (int kx = 0; kx < 4; kx++) {
           const int xo = ix - kx + 1;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void dgrad_kernel(const float* __restrict__ dy
   }
   for (int c0 = lane * 8; c0 < C; c0 += 512) {
     float wr[16][8];
-    load_w(w, c0, wr);
+    load_w_taps(w, c0, wr);
     bf16* row = dx + ((size_t)(n * H + iy) * W_IN) * C + c0;
     // Pixels unrolled (the broadcast's lane index is then an immediate): 3 800 instructions, 28 KB -- measured 23.7 us against 30.7 us as a loop with the index in a
     // scalar register.  (The forward kernel is the opposite case: with its four kernel rows unrolled as well it was 50 KB of straight-line code run once per wave
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const bf16* __restrict__ x, 
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           float v[8];
-          cvt8(cur[k], v);       // pixels past the row's end are zeros: they add nothing
+          cvt8_raw(cur[k], v);       // pixels past the row's end are zeros: they add nothing
 #pragma unroll
           for (int ky = 0; ky < 4; ky++)
 #pragma unroll

@@ -234,12 +234,7 @@ int launch(const ConvArgs& a_in, hipStream_t st, int batch = 1) {
   a.korder = 1;      // channel chunk outer, tap inner
   dim3 grid(((a.M + TPk - 1) / TPk) * a.ctiles, 1, batch);
   const int lds = 2 * (TMk + TPk) * Geo<BK>::ROWB;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_kernel<BK, F32, TMk, TPk>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, conv_fwd_kernel<BK, F32, TMk, TPk>);
   hipLaunchKernelGGL((conv_fwd_kernel<BK, F32, TMk, TPk>), grid, dim3(256), lds, st, a);
   DMVAE_CHECK_LAUNCH();
   return 0;

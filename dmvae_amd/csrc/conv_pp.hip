@@ -56,13 +56,7 @@ struct Args {
   unsigned long long* dbg;  // optional per-block s_memtime stamps (dmvae_debug_timing), null in production
 };
 
-constexpr unsigned SENT = 0x80000000u;  // voffset beyond any descriptor's num_records -> the DMA writes zeros
-
-// 64-B rows, 4 rows per 256-B bank row.  Fragments are read for v_mfma_f32_16x16x32_bf16: lane l takes the 16-B chunk l >> 4 of row (l & 15), and
-// ds_read_b128 serves the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... in one pass each; with the chunk XOR-ed by (-(row >> 2)) & 3 the four lanes of
-// a group that share row % 4 land in four different 16-B slots of the bank row (derivation in DESIGN_HISTORY.md 3.1).
-__device__ __forceinline__ int swz64(int row) { return (0 - (row >> 2)) & 3; }
-__device__ __forceinline__ int hswz(int row) { return (row >> 1) & 2; }   // HALO rows: the key that stays conflict-free under a shift of 0..2 rows
+__device__ __forceinline__ int hswz(int row) { return (row >> 1) & 2; }   // HALO rows: the key that stays conflict-free under a shift of 0..2 rows (swz64, common.h, is not)
 
 // q = m / d, r = m % d for 0 <= m < 2^24 (exact in f32) via one reciprocal and a +-1 fix-up.  The host declines shapes with 2^24 pixels or more: a plain
 // integer division as the other arm kept its reciprocal sequences alive (and spilled) across the whole kernel.
@@ -71,16 +65,6 @@ __device__ __forceinline__ void divmod_small(int m, int d, float inv_d, bool, in
   r = m - q * d;
   if (r < 0) { q--; r += d; }
   if (r >= d) { q++; r -= d; }
-}
-
-// s_waitcnt vmcnt(N) through the builtin, not inline asm: the compiler's own wait-count pass then SEES the wait.  With the asm form it kept a VMEM event from
-// before the K loop pending on a fragment register for ever (the loop's own LDS-DMA instructions make its count imprecise) and put an s_waitcnt vmcnt(0) in
-// front of the second ds_read of every K tile.  Removing that drain changed nothing measurable (342 vs 340 us per launch in the step): by then the pieces
-// of the next tiles have landed anyway -- the loop is not waiting on the DMA queue.
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));   // gfx9 encoding: vmcnt[3:0] | expcnt 7 | lgkmcnt 15 | vmcnt[5:4] << 14
-  asm volatile("" ::: "memory");
 }
 
 // GEN: the general gather geometry (4x4 taps, output stride 2, zero-insertion sources) -- a separate instantiation, because its per-tile setup and per-K-tile
@@ -162,9 +146,9 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(Args a) {
   const int sds = GEN && a.sd == 2 ? 1 : 0;
   const unsigned shift = GEN ? ((!UPS && a.ks != 1) ? (unsigned)(SR * a.Wi + SR) * a.Cin * 2u : 0u)
                              : ((!UPS && (SUB || a.ks == 3)) ? (unsigned)(a.Wi + 1) * a.Cin * 2u : 0u);  // makes every tap offset >= 0
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, wbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = dmvae_buffer_rsrc(a.w, wbytes);
   const __amdgpu_buffer_rsrc_t rB =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(a.x) - shift), 0, xbytes + shift, 0x00020000);
+      dmvae_buffer_rsrc(reinterpret_cast<const char*>(a.x) - shift, xbytes + shift);
 
   // Persistent blocks: one per CU, each walks tiles blockIdx.x, blockIdx.x + gridDim.x, ...  Re-dispatching a 512-thread
   // workgroup costs ~2 k cycles per XCD-serialised launch (tools/probes/time_conv_pp.py); gridDim.x is a multiple of 8, so a
@@ -548,8 +532,8 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(Args a) {
     const int cc = lane_o & 15, gq = lane_o >> 4;
     const int col = n0c + wm * (TM / WM) + CL * cc;
     const bool c_ok = col < a.Cout;        // Cout % 8 == 0: a lane's couts are all inside or all outside
-    const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, (unsigned)a.M * (unsigned)a.Cout * 2u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rBias = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)a.Cout * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rY = dmvae_buffer_rsrc(a.y, (unsigned)a.M * (unsigned)a.Cout * 2u);
+    const __amdgpu_buffer_rsrc_t rBias = dmvae_buffer_rsrc(a.bias, a.bias ? (unsigned)a.Cout * 4u : 0u);
     // bias first, while the memory queue is empty (behind the next tile's prefetch its first use would wait for those pieces to land)
     float bsv[CL];
     {
@@ -583,7 +567,7 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(Args a) {
     auto body = [&](auto RESc, auto ACTc) __attribute__((always_inline)) {
       constexpr bool RES = decltype(RESc)::value;
       constexpr int ACTC = decltype(ACTc)::value;   // < 0: a.act is read at run time (the activations that are not hot)
-      const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, RES ? (unsigned)a.M * (unsigned)a.Cout * 2u : 0u, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rR = dmvae_buffer_rsrc(a.res, RES ? (unsigned)a.M * (unsigned)a.Cout * 2u : 0u);
       // residual / gate operand: the four rows of pixel block j + 1 are fetched while block j is converted and stored
       typedef std::conditional_t<CL == 8, u32x4, u32x2> rvec;
       rvec rnx[RES ? 4 : 1];   // a rolling window of four rows: row r of block j + 1 is requested as soon as row r of block j has been consumed
@@ -715,8 +699,8 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(Args a) {
     asm volatile("" : "+v"(lane_o));
     const int cl = lane_o % LPR, rg = lane_o / LPR;
     const unsigned mout = SUB ? 4u * (unsigned)a.M : (unsigned)a.M;   // output pixels (the host keeps mout * Cout * ES below 2^31: SENT stays out of range)
-    const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, mout * (unsigned)a.Cout * ES, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rBias = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)a.Cout * 4u : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rY = dmvae_buffer_rsrc(a.y, mout * (unsigned)a.Cout * ES);
+    const __amdgpu_buffer_rsrc_t rBias = dmvae_buffer_rsrc(a.bias, a.bias ? (unsigned)a.Cout * 4u : 0u);
     // bias of every pass, loaded while the memory queue is empty: behind the next tile's prefetch (vmcnt counts in order) the first use below would wait
     // for those LDS-DMA pieces to land -- 2-3 k cycles per tile
     f32x4 bias_lo[NH], bias_hi[NH];
@@ -750,7 +734,7 @@ __global__ __launch_bounds__(512) void conv_pp_kernel(Args a) {
     auto body = [&](auto RESc, auto ACTc) __attribute__((always_inline)) {
       constexpr bool RES = decltype(RESc)::value;
       constexpr int ACTC = decltype(ACTc)::value;   // < 0: a.act is read at run time (the activations that are not hot)
-      const __amdgpu_buffer_rsrc_t rR = __builtin_amdgcn_make_buffer_rsrc((void*)a.res, 0, RES ? mout * (unsigned)a.Cout * 2u : 0u, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rR = dmvae_buffer_rsrc(a.res, RES ? mout * (unsigned)a.Cout * 2u : 0u);
 #pragma unroll
       for (int hh = 0; hh < NH; hh++) {
         if (n0c + wm * (TM / WM) + hh * CWH >= a.Cout) continue;  // this wave's couts of the pass are all padding (wave-uniform; e.g. Cout = 64 on the 128-row tile)
@@ -981,12 +965,7 @@ int launch(Args a, hipStream_t st) {
   constexpr int ring = NBUF * (TM + TP) * 64, epi = 2 * (TM + TP) * 64 + 8 * 32 * (cwh * 4 + 16);
   constexpr int group = 2 * TM * 64 + (TP + 16) * 64, epi_h = 8 * 32 * (cwh * 4 + 16);   // the kernel's GROUP / EPI_BYTES / DUMP_OFF
   constexpr int lds = HALO ? group + (group > epi_h ? group : epi_h) + 1024 : (ring > epi ? ring : epi);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_pp_kernel<TM, TP, WM, WP, NBUF, UPS, F32, KO, GEN, SUB, DYN, STATS, HALO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, conv_pp_kernel<TM, TP, WM, WP, NBUF, UPS, F32, KO, GEN, SUB, DYN, STATS, HALO>);
   hipLaunchKernelGGL((conv_pp_kernel<TM, TP, WM, WP, NBUF, UPS, F32, KO, GEN, SUB, DYN, STATS, HALO>), dim3(grid), dim3(512), lds, st, a);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -1059,8 +1038,7 @@ extern "C" int dmvae_set_dynamic(int on) {
 }
 
 extern "C" int dmvae_debug_occupy(int blocks, int lds_bytes, int microseconds, hipStream_t stream) {
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(occupy_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_done = true; }
+  DMVAE_LDS_OPTIN(160 * 1024, occupy_kernel);
   hipLaunchKernelGGL(occupy_kernel, dim3(blocks), dim3(64), lds_bytes, stream, (unsigned long long)microseconds * 100ull);  // wall_clock64: 100 MHz
   DMVAE_CHECK_LAUNCH();
   return 0;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(Args a) {
   auto key = [](int q) { return CPP == 16 ? (q & 15) : ((q >> 1) & 7); };
 
   // ---- stage the halo tile -------------------------------------------------------------------------------------------------------------------------
-  const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (unsigned)a.N * a.H * a.W * PIXB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rX = dmvae_buffer_rsrc(a.x, (unsigned)a.N * a.H * a.W * PIXB);
   const unsigned img = (unsigned)n * a.H * a.W * PIXB;
   constexpr int NJ = (NPX * CPP + 255) / 256;      // NORM: 16-B chunks per thread (13 at CIN = 128); thread <-> chunk tid % CPP of pixels tid / CPP + (256 / CPP) j
   if constexpr (NORM) {

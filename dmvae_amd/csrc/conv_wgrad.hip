@@ -35,9 +35,6 @@ struct WgradArgs {
 constexpr int BKP = 64;              // pixels per K step
 constexpr int TILEB = BKP * 256;     // bytes per operand tile ([64][128] bf16)
 
-__device__ __forceinline__ s16x4 tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
 
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -142,8 +139,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradArgs a) {
         const int row = kk * 16 + kq * 8 + h * 4 + rr;  // row & 3 == rr
 #pragma unroll
         for (int i = 0; i < 2; i++) {
-          df[i].h[h] = tr_read(dt + row * 256 + ((seg_d[i] ^ rr) << 6) + choff_d[i]);
-          af[i].h[h] = tr_read(at + row * 256 + ((seg_a[i] ^ rr) << 6) + choff_a[i]);
+          df[i].h[h] = tr_read_ordered(dt + row * 256 + ((seg_d[i] ^ rr) << 6) + choff_d[i]);
+          af[i].h[h] = tr_read_ordered(at + row * 256 + ((seg_a[i] ^ rr) << 6) + choff_a[i]);
         }
       }
 #pragma unroll
@@ -427,11 +424,7 @@ extern "C" int dmvae_conv2d_nhwc_wgrad(const void* dy, const void* a, void* dw, 
   } else {
     w.kchunk = (((w.M + splits - 1) / splits) + BKP - 1) / BKP * BKP;
     splits = (w.M + w.kchunk - 1) / w.kchunk;
-    static bool attr_done = false;
-    if (!attr_done) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILEB);
-      attr_done = true;
-    }
+    DMVAE_LDS_OPTIN(4 * TILEB, wgrad_kernel);
     w.ntiles = tiles;
     hipLaunchKernelGGL(wgrad_kernel, dim3(splits * tiles), dim3(256), 4 * TILEB, stream, w);
     DMVAE_CHECK_LAUNCH();
@@ -522,11 +515,7 @@ extern "C" int dmvae_gemm_tn_batched(const void* A, const void* B, void* C, void
   splits = (K + w.kchunk - 1) / w.kchunk;
   const size_t total = (size_t)M * N;
   w.dy_bs = a_bs; w.a_bs = b_bs; w.slab_bs = (long long)splits * total;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILEB);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(4 * TILEB, wgrad_kernel);
   w.ntiles = tiles;
   hipLaunchKernelGGL(wgrad_kernel, dim3(splits * tiles, 1, batch), dim3(256), 4 * TILEB, stream, w);
   DMVAE_CHECK_LAUNCH();

@@ -45,28 +45,10 @@ struct Args {
   int mtiles, ntiles, ngroups, gpt;  // gpt: 128-channel column groups per cin row (Cin / 128)
 };
 
-constexpr unsigned SENT = 0x80000000u;
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  // the builtin, not inline asm, so that the compiler's wait-count pass sees it (see conv_pp.hip: otherwise it drains the queue with vmcnt(0) every K tile)
-  __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-  asm volatile("" ::: "memory");
-}
 // Wave-uniform values that come out of an integer division sit in VGPRs (the division runs on the VALU); everything derived from them then
 // stays there and every LDS-DMA issue whose soffset depends on them becomes a readfirstlane waterfall loop -- four per K tile, plus a
 // compiler-inserted vmcnt(0) at the loop head because its wait-count model cannot count loads inside those loops.  Pin them to SGPRs.
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-// Transpose read as inline asm, not __builtin_amdgcn_ds_read_tr16_b64: the compiler's wait-count pass orders every LDS read it can see behind every earlier LDS-DMA
-// (it cannot prove the ring slots disjoint) and put an s_waitcnt vmcnt(0) at the head of the K loop -- the three-tile prefetch queue was drained once per K tile and
-// the loop ran at the latency of the newest piece (tools/loop_waits.py shows the skeleton; 128->128 @256^2: 815 -> see DESIGN_HISTORY.md 8.12).  The asm form carries no memory
-// operand; the loop's own counted vmcnt + barrier protocol is what orders the reads behind the pieces they need, and lgkmcnt(0) ahead of the barrier covers the results.
-template <int OFF>
-__device__ __forceinline__ s16x4 tr_read(unsigned lds_addr) {
-  s16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF));
-  return r;
-}
 
 // GA / GB: 128-channel sub-tiles of the dy / activation operand per block; waves WM x WN.
 // HALO (3x3 stride 1, GB = 3): the block's three column groups are the taps kx = 0, 1, 2 of ONE (ky, 128-channel slice), and the activation operand of a K tile is
@@ -119,9 +101,9 @@ __device__ __forceinline__ void wgrad_pp_body(const Args& a, const unsigned flat
   const unsigned dybytes = (unsigned)a.M * a.Cout * 2u;
   const unsigned abytes = (unsigned)a.N * a.Hi * a.Wi * a.Cin * 2u;
   const unsigned shift = (S2 || (!UPS && a.ks == 3)) ? (unsigned)(a.Wi + 1) * a.Cin * 2u : 0u;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, dybytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = dmvae_buffer_rsrc(a.dy, dybytes);
   const __amdgpu_buffer_rsrc_t rB =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const char*>(a.a) - shift), 0, abytes + shift, 0x00020000);
+      dmvae_buffer_rsrc(reinterpret_cast<const char*>(a.a) - shift, abytes + shift);
 
   // ---- per-lane DMA sources ----------------------------------------------------------------------------------------------
   // piece pb (0 .. 8*G-1): sub-tile pb / 8, pixel rows 4*(pb % 8) .. +3; lane -> row + lane/16, physical 16-B chunk lane%16
@@ -302,24 +284,24 @@ __device__ __forceinline__ void wgrad_pp_body(const Args& a, const unsigned flat
     const unsigned sb = (unsigned)(size_t)LPTR(smem) + (unsigned)slot_rd;
 #pragma unroll
     for (int j = 0; j < BN; j++) {
-      bfr[0][j].h[0] = tr_read<0>(sb + boff[j]);
-      bfr[0][j].h[1] = HALO ? tr_read<0>(sb + boff1[HALO ? j : 0]) : tr_read<1024>(sb + boff[j]);
+      bfr[0][j].h[0] = tr_read_uncounted<0>(sb + boff[j]);
+      bfr[0][j].h[1] = HALO ? tr_read_uncounted<0>(sb + boff1[HALO ? j : 0]) : tr_read_uncounted<1024>(sb + boff[j]);
     }
 #pragma unroll
     for (int i = 0; i < BM; i++) {
-      af[0][i].h[0] = tr_read<0>(sb + aoff[i]);
-      af[0][i].h[1] = tr_read<1024>(sb + aoff[i]);
+      af[0][i].h[0] = tr_read_uncounted<0>(sb + aoff[i]);
+      af[0][i].h[1] = tr_read_uncounted<1024>(sb + aoff[i]);
     }
     if constexpr (KH == 2) {  // second 32-pixel half: 32 halo rows / one dy sub-tile further on (the swizzle key repeats every 16 rows)
 #pragma unroll
       for (int j = 0; j < BN; j++) {
-        bfr[KH - 1][j].h[0] = tr_read<8192>(sb + boff[j]);
-        bfr[KH - 1][j].h[1] = tr_read<8192>(sb + boff1[HALO ? j : 0]);
+        bfr[KH - 1][j].h[0] = tr_read_uncounted<8192>(sb + boff[j]);
+        bfr[KH - 1][j].h[1] = tr_read_uncounted<8192>(sb + boff1[HALO ? j : 0]);
       }
 #pragma unroll
       for (int i = 0; i < BM; i++) {
-        af[KH - 1][i].h[0] = tr_read<SUB>(sb + aoff[i]);
-        af[KH - 1][i].h[1] = tr_read<SUB + 1024>(sb + aoff[i]);
+        af[KH - 1][i].h[0] = tr_read_uncounted<SUB>(sb + aoff[i]);
+        af[KH - 1][i].h[1] = tr_read_uncounted<SUB + 1024>(sb + aoff[i]);
       }
     }
     issue(slot_wr);
@@ -452,11 +434,7 @@ __global__ __launch_bounds__(256) void wgrad_grouped_bias_kernel(const GBias* __
 template <int GA, int GB, int WM, int WN, bool S2 = false, bool HALO = false, bool UPS = false, int KP = 32>
 int launch(const Args& a, int splits, hipStream_t st) {
   constexpr int lds = (HALO ? (KP == 64 ? 4 : WG_NBUF) : WG_NBUF) * (GA * KP + (HALO ? KP + 4 : GB * 32)) * 256;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pp_kernel<GA, GB, WM, WN, S2, HALO, UPS, KP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, wgrad_pp_kernel<GA, GB, WM, WN, S2, HALO, UPS, KP>);
   hipLaunchKernelGGL((wgrad_pp_kernel<GA, GB, WM, WN, S2, HALO, UPS, KP>), dim3((unsigned)(splits * a.mtiles * a.ntiles)), dim3(512), lds, st, a);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -631,12 +609,8 @@ extern "C" int dmvae_linear_wgrad_grouped_xcd(const void* table, const void* chu
   using namespace dmvae_wgrad_pp;
   DMVAE_CHECK_ARG(table && chunks && xoff && grid > 0, "linear_wgrad_grouped_xcd: empty plan");
   constexpr int lds = WG_NBUF * (2 * 32 + 2 * 32) * 256;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pp_grouped_xcd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pp_grouped_xcd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, wgrad_pp_grouped_xcd_kernel<false>);
+  DMVAE_LDS_OPTIN(lds, wgrad_pp_grouped_xcd_kernel<true>);
   GPlan plan;
   for (int i = 0; i < 9; i++) plan.xoff[i] = xoff[i];
   if (ragged) hipLaunchKernelGGL(wgrad_pp_grouped_xcd_kernel<true>, dim3(grid), dim3(512), lds, stream, (const GEntry*)table, (const GChunk*)chunks, plan);
@@ -653,12 +627,8 @@ extern "C" int dmvae_linear_wgrad_grouped(const void* table, int n, unsigned tot
   using namespace dmvae_wgrad_pp;
   DMVAE_CHECK_ARG(table && n > 0 && total_blocks > 0, "linear_wgrad_grouped: empty table");
   constexpr int lds = WG_NBUF * (2 * 32 + 2 * 32) * 256;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pp_grouped_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_pp_grouped_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, wgrad_pp_grouped_kernel<false>);
+  DMVAE_LDS_OPTIN(lds, wgrad_pp_grouped_kernel<true>);
   if (ragged) hipLaunchKernelGGL(wgrad_pp_grouped_kernel<true>, dim3(total_blocks), dim3(512), lds, stream, (const GEntry*)table, n);
   else hipLaunchKernelGGL(wgrad_pp_grouped_kernel<false>, dim3(total_blocks), dim3(512), lds, stream, (const GEntry*)table, n);
   DMVAE_CHECK_LAUNCH();

@@ -140,10 +140,6 @@ __global__ __launch_bounds__(256) void bwd_kernel(const float* __restrict__ dy, 
   }
 }
 
-static inline int grid_for(size_t n, int block = 256, int cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
-}
 
 static int make_geo(Geo& g, int b, int c, int h, int w, int flags, int delta_h, int delta_w, int cut_h, int cut_w) {
   if (b <= 0 || c <= 0 || c > MAXC || h <= 0 || w <= 0 || flags < 0 || flags > 7) return -1;
@@ -168,7 +164,7 @@ extern "C" int dmvae_diffaug_fwd(const void* x, const void* rand01, void* y, voi
     hipLaunchKernelGGL(reduce_final_kernel, dim3((b + 63) / 64), dim3(64), 0, stream, (const double*)part, (float*)workspace, b, 1.0 / ((double)c * h * w));
     DMVAE_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(fwd_kernel, dim3(grid_for((size_t)b * h * w)), dim3(256), 0, stream, (const float*)x, (const float*)rand01,
+  hipLaunchKernelGGL(fwd_kernel, dim3(grid_for((size_t)b * h * w, 256, 4096)), dim3(256), 0, stream, (const float*)x, (const float*)rand01,
                      (const float*)workspace, (float*)y, g);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -186,7 +182,7 @@ extern "C" int dmvae_diffaug_bwd(const void* dy, const void* rand01, void* dx, v
     hipLaunchKernelGGL(reduce_final_kernel, dim3((b + 63) / 64), dim3(64), 0, stream, (const double*)part, (float*)workspace, b, 1.0 / ((double)c * h * w));
     DMVAE_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(bwd_kernel, dim3(grid_for((size_t)b * h * w)), dim3(256), 0, stream, (const float*)dy, (const float*)rand01,
+  hipLaunchKernelGGL(bwd_kernel, dim3(grid_for((size_t)b * h * w, 256, 4096)), dim3(256), 0, stream, (const float*)dy, (const float*)rand01,
                      (const float*)workspace, (float*)dx, g);
   DMVAE_CHECK_LAUNCH();
   return 0;

@@ -546,10 +546,6 @@ __global__ __launch_bounds__(256) void colsum2_kernel(const float* __restrict__ 
   }
 }
 
-static inline int grid_for(size_t n, int block = 256, int cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
-}
 
 }  // namespace dmvae_dit
 using namespace dmvae_dit;
@@ -739,7 +735,7 @@ extern "C" int dmvae_qknorm_rope_bf16(const void* qkv, const void* q_weight, con
 extern "C" int dmvae_swiglu_bf16(const void* x12, void* out, size_t rows, int hidden, hipStream_t stream) {
   DMVAE_CHECK_ARG(x12 && out && hidden > 0 && hidden % 8 == 0, "swiglu_bf16: hidden width must be a multiple of 8 (got %d)", hidden);
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(swiglu_kernel, dim3(grid_for(rows * (size_t)(hidden / 8))), dim3(256), 0, stream, (const bf16*)x12, (bf16*)out, rows, hidden / 8);
+  hipLaunchKernelGGL(swiglu_kernel, dim3(grid_for(rows * (size_t)(hidden / 8), 256, 4096)), dim3(256), 0, stream, (const bf16*)x12, (bf16*)out, rows, hidden / 8);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -749,7 +745,7 @@ extern "C" int dmvae_gated_residual_f32(void* x, const void* y, const void* mod,
   DMVAE_CHECK_ARG(x && y && mod && rows_per_sample > 0 && c > 0 && c % 8 == 0 && gate_off >= 0 && gate_off % 8 == 0 && mod_stride % 8 == 0 &&
                       gate_off + c <= mod_stride, "gated_residual_f32: width / offsets must be multiples of 8 inside the modulation row");
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(gated_residual_kernel, dim3(grid_for(rows * (size_t)(c / 8))), dim3(256), 0, stream, (float*)x, (const bf16*)y, (const bf16*)mod, rows,
+  hipLaunchKernelGGL(gated_residual_kernel, dim3(grid_for(rows * (size_t)(c / 8), 256, 4096)), dim3(256), 0, stream, (float*)x, (const bf16*)y, (const bf16*)mod, rows,
                      c / 8, rows_per_sample, mod_stride, gate_off);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -775,7 +771,7 @@ extern "C" int dmvae_gated_residual_bwd(const void* dx, const void* y, const voi
 extern "C" int dmvae_swiglu_bwd(const void* dh, const void* x12, void* dx12, size_t rows, int hidden, hipStream_t stream) {
   DMVAE_CHECK_ARG(dh && x12 && dx12 && hidden > 0 && hidden % 8 == 0, "swiglu_bwd: hidden width must be a multiple of 8 (got %d)", hidden);
   if (rows == 0) return 0;
-  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(rows * (size_t)(hidden / 8))), dim3(256), 0, stream, (const bf16*)dh, (const bf16*)x12, (bf16*)dx12,
+  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(rows * (size_t)(hidden / 8), 256, 4096)), dim3(256), 0, stream, (const bf16*)dh, (const bf16*)x12, (bf16*)dx12,
                      rows, hidden / 8);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -806,25 +802,24 @@ extern "C" int dmvae_rmsnorm_modulate_bwd(const void* da, const void* x, const v
                        (const bf16*)mod, rowstat, (float*)dx_io, (float*)workspace, seq, c, mod_stride, scale_off);
     DMVAE_CHECK_LAUNCH();
   } else {
-  auto go = [&](auto sw) {
+  auto go = [&](auto sw) -> int {
     constexpr int SW = decltype(sw)::value;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rmsnorm_modulate_bwd_kernel<SW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_lds = lds;
-    }
+    DMVAE_LDS_OPTIN((size_t)2 * 3 * MAX_SWEEPS * 256 * sizeof(float), rmsnorm_modulate_bwd_kernel<SW>);   // the widest row's: `lds` varies with c
     hipLaunchKernelGGL(rmsnorm_modulate_bwd_kernel<SW>, dim3(bps, batch), dim3(256), lds, stream, (const bf16*)da, (const float*)x, (const float*)w,
                        (const bf16*)mod, (float*)dx_io, (float*)workspace, seq, c, mod_stride, scale_off, eps);
+    return 0;
   };
+  int rc = 0;
   switch ((c + 255) / 256) {
-    case 1: go(std::integral_constant<int, 1>{}); break;
-    case 2: go(std::integral_constant<int, 2>{}); break;
-    case 3: go(std::integral_constant<int, 3>{}); break;
-    case 4: go(std::integral_constant<int, 4>{}); break;
-    case 5: go(std::integral_constant<int, 5>{}); break;
-    case 6: go(std::integral_constant<int, 6>{}); break;
-    default: go(std::integral_constant<int, 8>{}); break;
+    case 1: rc = go(std::integral_constant<int, 1>{}); break;
+    case 2: rc = go(std::integral_constant<int, 2>{}); break;
+    case 3: rc = go(std::integral_constant<int, 3>{}); break;
+    case 4: rc = go(std::integral_constant<int, 4>{}); break;
+    case 5: rc = go(std::integral_constant<int, 5>{}); break;
+    case 6: rc = go(std::integral_constant<int, 6>{}); break;
+    default: rc = go(std::integral_constant<int, 8>{}); break;
   }
+  if (rc) return rc;
   DMVAE_CHECK_LAUNCH();
   }
   float* wpart = (float*)workspace + (size_t)batch * RM_BPS * 3 * c;

@@ -62,17 +62,6 @@ struct Args {
 // whole-cache maintenance.  A first version used __threadfence() on both sides (buffer_wbl2 / buffer_inv, i.e. one L2 write-back + invalidate per wave and part):
 // 1 900 cache-wide operations in a 30-us kernel serialised per XCD and made it 3-5 x slower than the unsplit form (profiles/r6_gemm_sk_first_fences.txt).
 constexpr int SK_COHERENT = 1 | 16;
-constexpr unsigned SENT = 0x80000000u;  // voffset beyond any descriptor's num_records: loads return zeros, stores are dropped
-
-__device__ __forceinline__ int swz64(int row) { return (0 - (row >> 2)) & 3; }   // conv_pp.hip: the 64-B-row chunk key that keeps ds_read_b128 fragments conflict-free
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {   // through the builtin: the compiler's wait-count pass has to SEE the wait (conv_pp.hip)
-  __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-  asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ float gelu_f(float x) { return dmvae_gelu_f(x); }   // common.h; vit_bwd.hip::gelu_fwd_kernel computes the same bits
 
 // TM: output columns (weight rows) per tile, TP: output rows (tokens) per tile, WM x WP: wave grid over (columns, rows).
 //
@@ -144,11 +133,11 @@ __global__ __launch_bounds__(WM * WP * 64) void gemm_pp_kernel(Args a) {
   const bool gated = a.act == 6;
   const float inv_ntn = a.inv_ntn;   // from the host: a kernel argument lives in an SGPR (computed here it sat in a VGPR and was spilled)
 
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.wbytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, BATCHED ? a.xbytes : (unsigned)a.M * (unsigned)a.lda * 2u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rBias = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? (unsigned)a.N * bsz : 0u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, BATCHED ? a.ybytes : (unsigned)a.M * (unsigned)a.ldy * (OUT_F32 ? 4u : 2u), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rY2 = __builtin_amdgcn_make_buffer_rsrc(a.y2, 0, a.y2 ? (unsigned)a.M * (unsigned)a.ldy2 * 2u : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = dmvae_buffer_rsrc(a.w, a.wbytes);
+  const __amdgpu_buffer_rsrc_t rB = dmvae_buffer_rsrc(a.x, BATCHED ? a.xbytes : (unsigned)a.M * (unsigned)a.lda * 2u);
+  const __amdgpu_buffer_rsrc_t rBias = dmvae_buffer_rsrc(a.bias, a.bias ? (unsigned)a.N * bsz : 0u);
+  const __amdgpu_buffer_rsrc_t rY = dmvae_buffer_rsrc(a.y, BATCHED ? a.ybytes : (unsigned)a.M * (unsigned)a.ldy * (OUT_F32 ? 4u : 2u));
+  const __amdgpu_buffer_rsrc_t rY2 = dmvae_buffer_rsrc(a.y2, a.y2 ? (unsigned)a.M * (unsigned)a.ldy2 * 2u : 0u);
 
   // per-lane DMA source offsets of a tile: weight rows in the permuted order, token rows as they are, the bias slice (wave 0; 16 B per lane)
   auto calc = [&](unsigned work, unsigned (&vA)[NPA], unsigned (&vB)[NPB], unsigned& vBias, int& m0, int& n0, int& b0) {
@@ -383,7 +372,7 @@ __global__ __launch_bounds__(WM * WP * 64) void gemm_pp_kernel(Args a) {
     // ---- SK: a PART of a tile -> its slab slot; the wave that arrives last at the tile's counter sums the parts (K order) and goes on to the epilogue ---------------
     bool sk_final = true;                          // this wave writes the tile's result (always, outside SK)
     unsigned sk_base = 0;                          // byte offset of this wave's region inside a slab slot
-    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc((void*)a.slabs, 0, SK ? a.slab_bytes : 0u, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rS = dmvae_buffer_rsrc(a.slabs, SK ? a.slab_bytes : 0u);
     constexpr unsigned SLOT_BYTES = (unsigned)TM * (unsigned)TP * 4u, WREG = (unsigned)CL * BT * 4u * 64u * 4u;   // one partial tile; one wave's CL x BT x 4 floats per lane
     if constexpr (SK) {
       if (uc.P > 1) {
@@ -512,7 +501,7 @@ __global__ __launch_bounds__(WM * WP * 64) void gemm_pp_kernel(Args a) {
 #pragma unroll
               for (int i = 0; i < CL; i++) {
                 const float x = (float)(bf16)v[i];
-                v[i] = ACT == 5 ? gelu_f(x) : x * sigmoidf_(x);
+                v[i] = ACT == 5 ? dmvae_gelu_f(x) : x * sigmoidf_(x);
               }
             }
             const int m = row0 + j * 16 + r;
@@ -615,11 +604,7 @@ int launch(Args a, hipStream_t st, int batch = 1) {
   constexpr int nbuf = fit > GEMM_MAXBUF ? GEMM_MAXBUF : fit;
   static_assert(nbuf >= 4, "LDS");
   constexpr int lds = nbuf * slot + 3 * 1024;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pp_kernel<TM, TP, WM, WP, F32, nbuf, BATCHED>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, gemm_pp_kernel<TM, TP, WM, WP, F32, nbuf, BATCHED>);
   hipLaunchKernelGGL((gemm_pp_kernel<TM, TP, WM, WP, F32, nbuf, BATCHED>), dim3(grid), dim3(WM * WP * 64), lds, st, a);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -645,11 +630,7 @@ static int launch_sk_t(Args a, int splits, hipStream_t st) {
   constexpr int fit = (160 * 1024 - 3 * 1024) / slot;
   constexpr int nbuf = fit > GEMM_MAXBUF ? GEMM_MAXBUF : fit;
   constexpr int lds = nbuf * slot + 3 * 1024;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_pp_kernel<TM, TP, WM, WP, false, nbuf, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, gemm_pp_kernel<TM, TP, WM, WP, false, nbuf, false, true>);
   hipLaunchKernelGGL((gemm_pp_kernel<TM, TP, WM, WP, false, nbuf, false, true>), dim3(grid), dim3(512), lds, st, a);
   DMVAE_CHECK_LAUNCH();
   return 0;

@@ -237,8 +237,7 @@ extern "C" int dmvae_linear_rows_wgrad(const void* dy, const void* x, void* dw, 
   DMVAE_CHECK_ARG(lddy >= N && ldx >= K && ldx % 8 == 0, "linear_rows_wgrad: leading dimensions lddy=%d ldx=%d", lddy, ldx);
   DMVAE_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)dw % 16 == 0, "linear_rows_wgrad: x and dw must be 16-byte aligned");
   const size_t lds = (size_t)M * 2048 + (size_t)M * 64;
-  static bool attr_done = false;
-  if (!attr_done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(linear_rows_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 2048 + 64 * 64); attr_done = true; }
+  DMVAE_LDS_OPTIN(64 * 2048 + 64 * 64, linear_rows_wgrad_kernel);
   hipLaunchKernelGGL(linear_rows_wgrad_kernel, dim3((N + 15) / 16, (K + 1023) / 1024), dim3(256), lds, stream, (const bf16*)dy, (const bf16*)x, (float*)dw, (float*)db, M, N, K, lddy, ldx,
                      accumulate);
   DMVAE_CHECK_LAUNCH();

@@ -988,12 +988,8 @@ extern "C" int dmvae_kl_mmd(const void* z, const void* y, void* kl, void* mmd, v
   const size_t lds_v = (size_t)(2 * MMD_ROWS * 34 + 8) * sizeof(float) > (size_t)(MMD_CCH * MMD_D + MMD_CCH + 8) * sizeof(float)
                            ? (size_t)(2 * MMD_ROWS * 34 + 8) * sizeof(float) : (size_t)(MMD_CCH * MMD_D + MMD_CCH + 8) * sizeof(float);
   const size_t lds_g = lds_v;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mmd_pair_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mmd_pair_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_v);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds_g, mmd_pair_kernel<true>);
+  DMVAE_LDS_OPTIN(lds_v, mmd_pair_kernel<false>);
   const int csplit = fused ? csplit_ws : 1;
   const dim3 grid((2 * tx + ty) * csplit, groups);
   float* klpart = fused ? mom : nullptr;
@@ -1003,12 +999,8 @@ extern "C" int dmvae_kl_mmd(const void* z, const void* y, void* kl, void* mmd, v
     const int cper = csplit > 1 ? ((nmax + csplit - 1) / csplit + 31) & ~31 : (nmax + 31) & ~31;
     const size_t lds = ((size_t)cper * (MMD_D + 1) + 8) * sizeof(float);
     const size_t lds_eff = lds < 8192 ? 8192 : lds;     // the moment blocks' reduction scratch
-    static bool attr2 = false;
-    if (!attr2) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mmd_pair_mfma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mmd_pair_mfma_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024);
-      attr2 = true;
-    }
+    DMVAE_LDS_OPTIN(140 * 1024, mmd_pair_mfma_kernel<true>);
+    DMVAE_LDS_OPTIN(140 * 1024, mmd_pair_mfma_kernel<false>);
     const int npair = (2 * tx + ty) * csplit;
     const dim3 grid2(npair + tx, groups);           // + one moment block per x tile
     if (dz)

@@ -169,10 +169,6 @@ __global__ __launch_bounds__(256) void pack_tiled_kernel(const PackEntry* __rest
   }
 }
 static inline size_t pack_lds_bytes(int Tm) { return (size_t)32 * (32 * Tm + 1) * sizeof(float); }
-static inline void pack_attr() {   // 16 taps need 65.7 KB of dynamic LDS: above the 64-KB default
-  static bool done = false;
-  if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(pack_tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pack_lds_bytes(PACK_TMAX)); done = true; }
-}
 
 // ---- sub-pixel form of Upsample's conv (flux_ae.py:103-107: conv3x3(nearest-x2(x))) -----------------------------------
 // Output pixel (2y + py, 2x + px) of the 3x3 conv over the nearest-x2 image only ever sees the 2x2 source pixels
@@ -593,10 +589,6 @@ __global__ __launch_bounds__(256) void linear_wt_kmajor_batched_kernel(const WtE
   }
 }
 
-static inline int grid_for(size_t n, int block = 256, int cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
-}
 
 }  // namespace dmvae_misc
 using namespace dmvae_misc;
@@ -617,7 +609,7 @@ extern "C" int dmvae_pack_conv_weight_v2(const void* w, void* out, void* out_kma
   // single-weight calls stay on the element-wise kernel: the tiled kernel (the one-launch table, dmvae_pack_weights_batched) measured 1.5 x slower here -- a
   // 512 x 512 weight is 256 tiles, one block per CU, each a serial load -> store; the element-wise kernel spreads the same weight over 9 x as many blocks
   {
-    hipLaunchKernelGGL(pack_weight_kernel, dim3(grid_for(total)), dim3(256), 0, stream, (const float*)w, (bf16*)out, (bf16*)out_kmajor, cout, cin, T, rows_pad,
+    hipLaunchKernelGGL(pack_weight_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, stream, (const float*)w, (bf16*)out, (bf16*)out_kmajor, cout, cin, T, rows_pad,
                        cols_pad, for_dgrad ? 1 : 0);
   }
   DMVAE_CHECK_LAUNCH();
@@ -629,7 +621,7 @@ extern "C" int dmvae_pack_weights_batched(const void* table, int n_entries, unsi
   DMVAE_CHECK_ARG(table && n_entries > 0 && total_tiles > 0 && total_tiles < (1ull << 31), "pack_weights_batched: empty or oversized table");
   DMVAE_CHECK_ARG(max_taps >= 1 && max_taps <= PACK_TMAX, "pack_weights_batched: max_taps (the largest ks * ks of the table; 9 for a sub-pixel entry) must be 1 .. 16");
   PackEntry none = {};
-  pack_attr();
+  DMVAE_LDS_OPTIN(pack_lds_bytes(PACK_TMAX), pack_tiled_kernel);   // 16 taps need 65.7 KB of dynamic LDS: above the 64-KB default
   hipLaunchKernelGGL(pack_tiled_kernel, dim3((unsigned)total_tiles), dim3(256), pack_lds_bytes(max_taps), stream, (const PackEntry*)table, n_entries, none);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -671,34 +663,34 @@ extern "C" int dmvae_linear_weight_t_kmajor_batched(const void* table, int n_ent
 
 extern "C" int dmvae_subpixel_weight(const void* w, void* wd, int cout, int cin, hipStream_t stream) {
   DMVAE_CHECK_ARG(w && wd && cout > 0 && cin > 0, "subpixel_weight: bad argument");
-  hipLaunchKernelGGL(subpixel_weight_kernel, dim3(grid_for((size_t)cin * cout * 16)), dim3(256), 0, stream, (const float*)w, (float*)wd, cout, cin);
+  hipLaunchKernelGGL(subpixel_weight_kernel, dim3(grid_for((size_t)cin * cout * 16, 256, 4096)), dim3(256), 0, stream, (const float*)w, (float*)wd, cout, cin);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int dmvae_subpixel_weight_fold(const void* dwd, void* dw, int cout, int cin, int accumulate, hipStream_t stream) {
   DMVAE_CHECK_ARG(dwd && dw && cout > 0 && cin > 0, "subpixel_weight_fold: bad argument");
-  hipLaunchKernelGGL(subpixel_fold_kernel, dim3(grid_for((size_t)cin * cout * 9)), dim3(256), 0, stream, (const float*)dwd, (float*)dw, cout, cin, accumulate);
+  hipLaunchKernelGGL(subpixel_fold_kernel, dim3(grid_for((size_t)cin * cout * 9, 256, 4096)), dim3(256), 0, stream, (const float*)dwd, (float*)dw, cout, cin, accumulate);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int dmvae_sumpool2x2_nhwc(const void* dy, void* dx, int n, int h, int w, int c, hipStream_t stream) {
   DMVAE_CHECK_ARG(dy && dx && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "sumpool2x2_nhwc: bad argument (c must be a multiple of 8)");
-  hipLaunchKernelGGL(sumpool2x2_kernel, dim3(grid_for((size_t)n * h * w * (c / 8))), dim3(256), 0, stream, (const bf16*)dy, (bf16*)dx, n, h, w, c);
+  hipLaunchKernelGGL(sumpool2x2_kernel, dim3(grid_for((size_t)n * h * w * (c / 8), 256, 4096)), dim3(256), 0, stream, (const bf16*)dy, (bf16*)dx, n, h, w, c);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int dmvae_maxpool2x2_nhwc(const void* x, void* y, int n, int h, int w, int c, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && y && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "maxpool2x2_nhwc: bad argument (c must be a multiple of 8)");
-  hipLaunchKernelGGL(maxpool2x2_kernel, dim3(grid_for((size_t)n * h * w * (c / 8))), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, n, h, w, c);
+  hipLaunchKernelGGL(maxpool2x2_kernel, dim3(grid_for((size_t)n * h * w * (c / 8), 256, 4096)), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, n, h, w, c);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int dmvae_maxpool2x2_relu_bwd_nhwc(const void* dpool, const void* x, const void* extra, void* dx, int n, int h, int w, int c,
                                               hipStream_t stream) {
   DMVAE_CHECK_ARG(x && dx && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "maxpool2x2_relu_bwd_nhwc: bad argument (c must be a multiple of 8)");
-  hipLaunchKernelGGL(maxpool2x2_relu_bwd_kernel, dim3(grid_for((size_t)n * h * w * (c / 8))), dim3(256), 0, stream, (const bf16*)dpool,
+  hipLaunchKernelGGL(maxpool2x2_relu_bwd_kernel, dim3(grid_for((size_t)n * h * w * (c / 8), 256, 4096)), dim3(256), 0, stream, (const bf16*)dpool,
                      (const bf16*)x, (const bf16*)extra, (bf16*)dx, n, h, w, c);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -706,14 +698,14 @@ extern "C" int dmvae_maxpool2x2_relu_bwd_nhwc(const void* dpool, const void* x, 
 extern "C" int dmvae_relu_bwd(const void* dy, const void* y, void* dx, size_t n, hipStream_t stream) {
   DMVAE_CHECK_ARG(dy && y && dx && n % 8 == 0, "relu_bwd: element count must be a multiple of 8");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)y, (bf16*)dx, n / 8, 0.f);
+  hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)y, (bf16*)dx, n / 8, 0.f);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int dmvae_leaky_relu_bwd(const void* dy, const void* y, void* dx, size_t n, float slope, hipStream_t stream) {
   DMVAE_CHECK_ARG(dy && y && dx && n % 8 == 0 && slope >= 0.f, "leaky_relu_bwd: element count must be a multiple of 8, slope >= 0");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)y, (bf16*)dx, n / 8, slope);
+  hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)y, (bf16*)dx, n / 8, slope);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -732,7 +724,7 @@ extern "C" int dmvae_im2col_nhwc_sub(const void* x, void* col, int n, int h, int
   DMVAE_CHECK_ARG(x && col && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0 && im2col_geom(h, w, ks, stride, pad, &ho, &wo),
                   "im2col_nhwc: bad argument (c must be a multiple of 8; ks 1..7, stride 1..4, pad < ks)");
   DMVAE_CHECK_ARG(taps_pad >= ks * ks && taps_pad <= 64, "im2col_nhwc: taps_pad %d below ks * ks = %d (or above 64)", taps_pad, ks * ks);
-  hipLaunchKernelGGL(im2col_kernel, dim3(grid_for((size_t)n * ho * wo * taps_pad * (c / 8))), dim3(256), 0, stream, (const bf16*)x, (bf16*)col, n, h, w, c,
+  hipLaunchKernelGGL(im2col_kernel, dim3(grid_for((size_t)n * ho * wo * taps_pad * (c / 8), 256, 4096)), dim3(256), 0, stream, (const bf16*)x, (bf16*)col, n, h, w, c,
                      c_src, ho, wo, ks, stride, pad, taps_pad);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -742,7 +734,7 @@ extern "C" int dmvae_col2im_nhwc(const void* dcol, void* dx, int n, int h, int w
   int ho, wo;
   DMVAE_CHECK_ARG(dcol && dx && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0 && im2col_geom(h, w, ks, stride, pad, &ho, &wo),
                   "col2im_nhwc: bad argument (c must be a multiple of 8; ks 1..7, stride 1..4, pad < ks)");
-  const dim3 grid(grid_for((size_t)n * h * w * (c / 8)));
+  const dim3 grid(grid_for((size_t)n * h * w * (c / 8), 256, 4096));
   if (in_f32)
     hipLaunchKernelGGL(col2im_kernel<float>, grid, dim3(256), 0, stream, (const float*)dcol, (bf16*)dx, n, h, w, c, ho, wo, ks, stride, pad);
   else
@@ -754,9 +746,9 @@ extern "C" int dmvae_col2im_nhwc(const void* dcol, void* dx, int n, int h, int w
 extern "C" int dmvae_nchw_f32_to_nhwc_bf16(const void* src, void* dst, int n, int c, int hw, int c_pad, hipStream_t stream) {
   DMVAE_CHECK_ARG(src && dst && n > 0 && c > 0 && hw > 0 && c_pad >= c, "nchw_f32_to_nhwc_bf16: bad argument");
   if (c_pad % 8 == 0)
-    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((size_t)n * hw * (c_pad / 8))), dim3(256), 0, stream, (const float*)src, (bf16*)dst, n, c, hw, c_pad);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((size_t)n * hw * (c_pad / 8), 256, 4096)), dim3(256), 0, stream, (const float*)src, (bf16*)dst, n, c, hw, c_pad);
   else
-    hipLaunchKernelGGL(nchw_to_nhwc_scalar_kernel, dim3(grid_for((size_t)n * hw)), dim3(256), 0, stream, (const float*)src, (bf16*)dst, n, c, hw, c_pad);
+    hipLaunchKernelGGL(nchw_to_nhwc_scalar_kernel, dim3(grid_for((size_t)n * hw, 256, 4096)), dim3(256), 0, stream, (const float*)src, (bf16*)dst, n, c, hw, c_pad);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -764,9 +756,9 @@ extern "C" int dmvae_nchw_f32_to_nhwc_bf16(const void* src, void* dst, int n, in
 extern "C" int dmvae_nhwc_to_nchw_f32(const void* src, void* dst, int n, int c, int hw, int c_pad, int src_f32, hipStream_t stream) {
   DMVAE_CHECK_ARG(src && dst && n > 0 && c > 0 && hw > 0 && c_pad >= c, "nhwc_to_nchw_f32: bad argument");
   if (src_f32)
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for((size_t)n * hw)), dim3(256), 0, stream, (const float*)src, (float*)dst, n, c, hw, c_pad);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, dim3(grid_for((size_t)n * hw, 256, 4096)), dim3(256), 0, stream, (const float*)src, (float*)dst, n, c, hw, c_pad);
   else
-    hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16>, dim3(grid_for((size_t)n * hw)), dim3(256), 0, stream, (const bf16*)src, (float*)dst, n, c, hw, c_pad);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16>, dim3(grid_for((size_t)n * hw, 256, 4096)), dim3(256), 0, stream, (const bf16*)src, (float*)dst, n, c, hw, c_pad);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -774,14 +766,14 @@ extern "C" int dmvae_nhwc_to_nchw_f32(const void* src, void* dst, int n, int c, 
 extern "C" int dmvae_silu_fwd(const void* x, void* y, size_t n, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && y && n % 8 == 0, "silu_fwd: element count must be a multiple of 8");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(silu_fwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, n / 8);
+  hipLaunchKernelGGL(silu_fwd_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, n / 8);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int dmvae_silu_bwd(const void* x, const void* dy, void* dx, size_t n, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && dy && dx && n % 8 == 0, "silu_bwd: element count must be a multiple of 8");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(silu_bwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, (const bf16*)x, (const bf16*)dy, (bf16*)dx, n / 8);
+  hipLaunchKernelGGL(silu_bwd_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, stream, (const bf16*)x, (const bf16*)dy, (bf16*)dx, n / 8);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

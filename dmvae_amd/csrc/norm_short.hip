@@ -39,7 +39,6 @@ struct Geom {
   int HW, G, cpg, ppc, nchunk;
 };
 
-__device__ __forceinline__ bf16x8 ldnt(const bf16* p) { return __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(p)); }
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -89,7 +88,7 @@ __global__ __launch_bounds__(NW * 64) void short_apply_kernel(const bf16* __rest
   if (q >= p1) return;
   bf16x8 xr[8];
 #pragma unroll
-  for (int r = 0; r < 8; r++) xr[r] = ldnt(xn + (size_t)(q + 2 * r) * CB);
+  for (int r = 0; r < 8; r++) xr[r] = dmvae_ldnt8(xn + (size_t)(q + 2 * r) * CB);
   for (; q < p1; q += 16 * NW) {
     // the raw tile (the conv's operand) and the normalised activation, both from the same registers
 #pragma unroll
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(NW * 64) void short_apply_kernel(const bf16* __rest
     {  // the next run's loads (unconditional: past the end the last run is read again -- a branch here would make the loop top wait for every store)
       const int qn = q + 16 * NW < p1 ? q + 16 * NW : q;
 #pragma unroll
-      for (int r = 0; r < 8; r++) xr[r] = ldnt(xn + (size_t)(qn + 2 * r) * CB);
+      for (int r = 0; r < 8; r++) xr[r] = dmvae_ldnt8(xn + (size_t)(qn + 2 * r) * CB);
     }
     wave_sync();
     bf16x8 bf[CB / 32];
@@ -189,20 +188,20 @@ __global__ __launch_bounds__(NW * 64) void short_bwd_apply_kernel(const bf16* __
   if (q < p1) {
     bf16x8 yr[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) yr[i] = ldnt(yn + (size_t)(q + 4 * i) * CS);
+    for (int i = 0; i < 4; i++) yr[i] = dmvae_ldnt8(yn + (size_t)(q + 4 * i) * CS);
     for (; q < p1; q += 16 * NW) {
 #pragma unroll
       for (int i = 0; i < 4; i++) *reinterpret_cast<bf16x8*>(tile + (4 * i + kg) * SROW + 16 * p) = yr[i];
       bf16x8 xr[8], dr[8];
 #pragma unroll
       for (int r = 0; r < 8; r++) {
-        xr[r] = ldnt(x + eb + (size_t)(q + 2 * r) * CB);
-        dr[r] = ldnt(da + eb + (size_t)(q + 2 * r) * CB);
+        xr[r] = dmvae_ldnt8(x + eb + (size_t)(q + 2 * r) * CB);
+        dr[r] = dmvae_ldnt8(da + eb + (size_t)(q + 2 * r) * CB);
       }
       {
         const int qn = q + 16 * NW < p1 ? q + 16 * NW : q;
 #pragma unroll
-        for (int i = 0; i < 4; i++) yr[i] = ldnt(yn + (size_t)(qn + 4 * i) * CS);
+        for (int i = 0; i < 4; i++) yr[i] = dmvae_ldnt8(yn + (size_t)(qn + 4 * i) * CS);
       }
       wave_sync();
       bf16x8 bf[CS / 32];
@@ -307,7 +306,7 @@ __global__ __launch_bounds__(512) void coop_apply_kernel(const bf16* __restrict_
   bf16* sn = xs + ((size_t)n * g.HW + (threadIdx.x >> 5)) * CS + 8 * (threadIdx.x & 31);      // store layout of the 16 x CS tile
   bf16x8 xn[2];
 #pragma unroll
-  for (int r = 0; r < 2; r++) xn[r] = ldnt(x + eb + (size_t)(p0 + 8 * r) * CB);
+  for (int r = 0; r < 2; r++) xn[r] = dmvae_ldnt8(x + eb + (size_t)(p0 + 8 * r) * CB);
   for (int q = p0; q < p1; q += 16) {
     bf16x8 xr[2];
 #pragma unroll
@@ -315,7 +314,7 @@ __global__ __launch_bounds__(512) void coop_apply_kernel(const bf16* __restrict_
     {  // the next run's loads, a whole run ahead (unconditional: past the end this run is read again)
       const int qn = q + 16 < p1 ? q + 16 : q;
 #pragma unroll
-      for (int r = 0; r < 2; r++) xn[r] = ldnt(x + eb + (size_t)(qn + 8 * r) * CB);
+      for (int r = 0; r < 2; r++) xn[r] = dmvae_ldnt8(x + eb + (size_t)(qn + 8 * r) * CB);
     }
 #pragma unroll
     for (int r = 0; r < 2; r++) {
@@ -399,9 +398,9 @@ __global__ __launch_bounds__(512) void coop_bwd_apply_kernel(const bf16* __restr
   const int p0 = blockIdx.x * g.ppc, p1 = min(p0 + g.ppc, g.HW);
   const size_t eb = ((size_t)n * g.HW + wv) * CB + 8 * l;
   const bf16* yn = dys + ((size_t)n * g.HW + (threadIdx.x >> 5)) * CS + 8 * (threadIdx.x & 31);      // load layout of the 16 x CS tile
-  bf16x8 yr = ldnt(yn + (size_t)p0 * CS), xn[2], dn[2];
+  bf16x8 yr = dmvae_ldnt8(yn + (size_t)p0 * CS), xn[2], dn[2];
 #pragma unroll
-  for (int r = 0; r < 2; r++) { xn[r] = ldnt(x + eb + (size_t)(p0 + 8 * r) * CB); dn[r] = ldnt(da + eb + (size_t)(p0 + 8 * r) * CB); }
+  for (int r = 0; r < 2; r++) { xn[r] = dmvae_ldnt8(x + eb + (size_t)(p0 + 8 * r) * CB); dn[r] = dmvae_ldnt8(da + eb + (size_t)(p0 + 8 * r) * CB); }
   for (int q = p0; q < p1; q += 16) {
     *reinterpret_cast<bf16x8*>(yT + (threadIdx.x >> 5) * SROW + 16 * (threadIdx.x & 31)) = yr;
     bf16x8 xr[2], dr[2];
@@ -409,9 +408,9 @@ __global__ __launch_bounds__(512) void coop_bwd_apply_kernel(const bf16* __restr
     for (int r = 0; r < 2; r++) { xr[r] = xn[r]; dr[r] = dn[r]; }
     {
       const int qn = q + 16 < p1 ? q + 16 : q;
-      yr = ldnt(yn + (size_t)qn * CS);
+      yr = dmvae_ldnt8(yn + (size_t)qn * CS);
 #pragma unroll
-      for (int r = 0; r < 2; r++) { xn[r] = ldnt(x + eb + (size_t)(qn + 8 * r) * CB); dn[r] = ldnt(da + eb + (size_t)(qn + 8 * r) * CB); }
+      for (int r = 0; r < 2; r++) { xn[r] = dmvae_ldnt8(x + eb + (size_t)(qn + 8 * r) * CB); dn[r] = dmvae_ldnt8(da + eb + (size_t)(qn + 8 * r) * CB); }
     }
     __syncthreads();      // the run's dy pixels are in yT (and every wave is done with oT of the run before)
     f32x4 acc[4];
@@ -508,10 +507,9 @@ extern "C" int dmvae_groupnorm_apply_short(const void* x, const void* stats, con
     DMVAE_CHECK_LAUNCH();
     return 0;
   }
-  static bool attr[2] = {false, false};
 #define DMVAE_NS_APPLY(A)                                                                                                                                   \
   do {                                                                                                                                                      \
-    if (!attr[A]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(short_apply_kernel<A>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); attr[A] = true; } \
+    DMVAE_LDS_OPTIN(LDS_BYTES, short_apply_kernel<A>);                                                                                                      \
     hipLaunchKernelGGL(short_apply_kernel<A>, grid, dim3(NW * 64), LDS_BYTES, stream, (const bf16*)x, (const float*)stats, (const float*)gamma, (const float*)beta, \
                        (const bf16*)w, (const float*)bias, (bf16*)a, (bf16*)xs, g);                                                                         \
   } while (0)
@@ -554,10 +552,9 @@ extern "C" int dmvae_groupnorm_bwd_short(const void* da, const void* x, const vo
     if (colsum) return dmvae_colsum_final(colpart, (float*)colsum, n * g.nchunk, c, colsum_accumulate, stream);
     return 0;
   }
-  static bool attr[2] = {false, false};
 #define DMVAE_NS_BWD(A)                                                                                                                                         \
   do {                                                                                                                                                          \
-    if (!attr[A]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(short_bwd_apply_kernel<A>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); attr[A] = true; } \
+    DMVAE_LDS_OPTIN(LDS_BYTES, short_bwd_apply_kernel<A>);                                                                                                      \
     hipLaunchKernelGGL(short_bwd_apply_kernel<A>, grid, dim3(NW * 64), LDS_BYTES, stream, (const bf16*)da, (const bf16*)x, (const bf16*)dys, (const bf16*)wt,    \
                        (const float*)stats, (const float*)S, (const float*)gamma, (const float*)beta, (bf16*)dx, g, colpart,                                    \
                        dgamma ? (const float*)AB : (const float*)nullptr, (float*)dgamma, (float*)dbeta, n, accumulate);                                        \

@@ -20,13 +20,9 @@
 
 namespace dmvae_parity {
 
-static inline int grid_for(size_t n, int block = 256, int cap = 8192) {
-  size_t g = (n + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
-}
 #define GSTRIDE(i, total) for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (total); i += (size_t)gridDim.x * blockDim.x)
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {      // 256 threads
+__device__ __forceinline__ double block_sum_d_tree(double v, double* sh) {      // 256 threads; pairwise tree through LDS (parity_dit.hip::block_sum_d_waves adds in another order)
   sh[threadIdx.x] = v;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
@@ -37,7 +33,6 @@ __device__ __forceinline__ double block_sum_d(double v, double* sh) {      // 25
   __syncthreads();
   return r;
 }
-__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ---- exact three-way bf16 split ------------------------------------------------------------------------------------------------------
 // x [rows][cols] f32 -> six bf16 parts; element (part q, row r, col c) goes to out[(r / rpb) * batch_stride + q * part_stride + (r % rpb) * row_stride + c]
@@ -69,8 +64,8 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     const double v = base[(i / cpg) * C + (i % cpg)];
     s += v; ss += v * v;
   }
-  s = block_sum_d(s, sh);
-  ss = block_sum_d(ss, sh);
+  s = block_sum_d_tree(s, sh);
+  ss = block_sum_d_tree(ss, sh);
   if (threadIdx.x == 0) {
     const double mean = s / (double)cnt;
     double var = ss / (double)cnt - mean * mean;
@@ -301,7 +296,7 @@ __global__ __launch_bounds__(256) void lpips_diff_kernel(const float* __restrict
     }
     if (lane == 0) acc += (double)v;
   }
-  acc = block_sum_d(acc, sh);
+  acc = block_sum_d_tree(acc, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 __global__ void sum_parts_kernel(const double* __restrict__ part, float* __restrict__ out, int n, double scale, int accumulate) {
@@ -338,7 +333,7 @@ extern "C" int dmvae_split3_bf16(const void* x, void* out, size_t rows, int cols
   DMVAE_CHECK_ARG(x && out, "split3_bf16: null pointer");
   DMVAE_CHECK_ARG(rows > 0 && cols > 0 && rows_per_batch > 0 && (pattern == 0 || pattern == 1), "split3_bf16: bad shape / pattern");
   const size_t total = rows * (size_t)cols;
-  hipLaunchKernelGGL(split3_kernel, dim3(grid_for(total)), dim3(256), 0, stream, (const float*)x, (bf16*)out, total, cols, rows_per_batch, batch_stride,
+  hipLaunchKernelGGL(split3_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, stream, (const float*)x, (bf16*)out, total, cols, rows_per_batch, batch_stride,
                      part_stride, row_stride, pattern);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -358,7 +353,7 @@ extern "C" int dmvae_groupnorm_apply_f32(const void* x, const void* stats, const
   DMVAE_CHECK_ARG(x && stats && gamma && beta && y, "groupnorm_apply_f32: null pointer");
   DMVAE_CHECK_ARG(gn_ok(n, hw, c, groups) && act >= 0 && act <= 2, "groupnorm_apply_f32: unsupported shape / act");
   const size_t total = (size_t)n * hw * c;
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(grid_for(total)), dim3(256), 0, stream, (const float*)x, (const float*)stats, (const float*)gamma,
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, stream, (const float*)x, (const float*)stats, (const float*)gamma,
                      (const float*)beta, (float*)y, total, hw, c, groups, act);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -376,7 +371,7 @@ extern "C" int dmvae_groupnorm_bwd_f32(const void* da, const void* x, const void
                      (const float*)gamma, (const float*)beta, AB, S, hw, c, groups, act);
   DMVAE_CHECK_LAUNCH();
   const size_t total = (size_t)n * hw * c;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total)), dim3(256), 0, stream, (const float*)da, (const float*)x, (const float*)dres,
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total, 256, 8192)), dim3(256), 0, stream, (const float*)da, (const float*)x, (const float*)dres,
                      (const float*)stats, S, (const float*)gamma, (const float*)beta, (float*)dx, total, hw, c, groups, act, inv_count);
   DMVAE_CHECK_LAUNCH();
   if (dgamma && dbeta) {
@@ -392,7 +387,7 @@ extern "C" int dmvae_eltwise_f32(int op, const void* a, const void* b, const voi
   DMVAE_CHECK_ARG(op >= 0 && op <= 7, "eltwise_f32: unknown op %d", op);
   DMVAE_CHECK_ARG(!(op == 2 || op == 3 || op == 5 || op == 6 || (op == 0 && act == 3)) || b, "eltwise_f32: op %d needs a second operand", op);
   DMVAE_CHECK_ARG(op != 6 || (g && cols > 0), "eltwise_f32: op 6 needs the per-column scale");
-  hipLaunchKernelGGL(eltwise_kernel, dim3(grid_for(n)), dim3(256), 0, stream, op, (const float*)a, (const float*)b, (const float*)g, (float*)out, n,
+  hipLaunchKernelGGL(eltwise_kernel, dim3(grid_for(n, 256, 8192)), dim3(256), 0, stream, op, (const float*)a, (const float*)b, (const float*)g, (float*)out, n,
                      cols > 0 ? cols : 1, act, param);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -417,7 +412,7 @@ extern "C" int dmvae_softmax_rows_bwd_f32(const void* dp, const void* p, void* d
 extern "C" int dmvae_pool2x2_f32(int op, const void* a, const void* x, const void* extra, void* out, int n, int h, int w, int c, hipStream_t stream) {
   DMVAE_CHECK_ARG(out && op >= 0 && op <= 2 && n > 0 && h > 0 && w > 0 && c > 0, "pool2x2_f32: bad arguments");
   DMVAE_CHECK_ARG(op == 2 ? x != nullptr : a != nullptr, "pool2x2_f32: null operand");
-  hipLaunchKernelGGL(pool2x2_kernel, dim3(grid_for((size_t)n * h * w * c)), dim3(256), 0, stream, op, (const float*)a, (const float*)x, (const float*)extra,
+  hipLaunchKernelGGL(pool2x2_kernel, dim3(grid_for((size_t)n * h * w * c, 256, 8192)), dim3(256), 0, stream, op, (const float*)a, (const float*)x, (const float*)extra,
                      (float*)out, n, h, w, c);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -425,7 +420,7 @@ extern "C" int dmvae_pool2x2_f32(int op, const void* a, const void* x, const voi
 
 extern "C" int dmvae_nchw_f32_to_nhwc_f32(const void* src, void* dst, int n, int c, int hw, int c_pad, hipStream_t stream) {
   DMVAE_CHECK_ARG(src && dst && n > 0 && c > 0 && hw > 0 && c_pad >= c, "nchw_f32_to_nhwc_f32: bad arguments");
-  hipLaunchKernelGGL(nchw_to_nhwc_f32_kernel, dim3(grid_for((size_t)n * hw * c_pad)), dim3(256), 0, stream, (const float*)src, (float*)dst, n, c, hw, c_pad);
+  hipLaunchKernelGGL(nchw_to_nhwc_f32_kernel, dim3(grid_for((size_t)n * hw * c_pad, 256, 8192)), dim3(256), 0, stream, (const float*)src, (float*)dst, n, c, hw, c_pad);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

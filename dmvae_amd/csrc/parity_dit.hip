@@ -15,14 +15,13 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {   // 256 threads; fixed order
+__device__ __forceinline__ double block_sum_d_waves(double v, double* sh) {   // 256 threads; fixed order: butterfly per wave, then the four waves (parity.hip::block_sum_d_tree adds in another)
   v = wave_sum_d(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
   return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
-__device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // y = x * rstd * w * (1 + scale[b]) + shift[b]; rstd[row] kept for the backward.  shift / scale: chunks of the adaLN output, [B][ldm] with the chunk's offset
 // already added to the pointer; either may be null.  w null: no weight (the LayerNorm-free case is not needed).
@@ -35,7 +34,7 @@ __global__ __launch_bounds__(256) void rms_mod_fwd_kernel(const float* __restric
   const float* xr = x + r * C;
   double s = 0.0;
   for (int c = threadIdx.x; c < C; c += 256) { const double v = xr[c]; s += v * v; }
-  s = block_sum_d(s, sh);
+  s = block_sum_d_waves(s, sh);
   const float rs = (float)(1.0 / sqrt(s / C + (double)eps));
   if (threadIdx.x == 0) rstd[r] = rs;
   for (int c = threadIdx.x; c < C; c += 256) {
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(256) void rms_mod_bwd_kernel(const float* __restric
     const float m1 = scale ? 1.0f + scale[(size_t)b * ldm + c] : 1.0f;
     dot += (double)(dr[c] * w[c] * m1) * (double)(xr[c] * rs);
   }
-  dot = block_sum_d(dot, sh) / C;
+  dot = block_sum_d_waves(dot, sh) / C;
   for (int c = threadIdx.x; c < C; c += 256) {
     const float m1 = scale ? 1.0f + scale[(size_t)b * ldm + c] : 1.0f;
     const float xh = xr[c] * rs, a = dr[c] * w[c] * m1;
@@ -82,8 +81,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
   const float* dr = dy + r * C;
   double s = 0.0, ss = 0.0;
   for (int c = threadIdx.x; c < C; c += 256) { const double v = xr[c]; s += v; ss += v * v; }
-  s = block_sum_d(s, sh);
-  ss = block_sum_d(ss, sh);
+  s = block_sum_d_waves(s, sh);
+  ss = block_sum_d_waves(ss, sh);
   const double mean = s / C;
   double var = ss / C - mean * mean;
   if (var < 0) var = 0;
@@ -93,8 +92,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
     const double a = (double)(dr[c] * gamma[c]), xh = (double)((xr[c] - mu) * rs);
     sa += a; sax += a * xh;
   }
-  sa = block_sum_d(sa, sh) / C;
-  sax = block_sum_d(sax, sh) / C;
+  sa = block_sum_d_waves(sa, sh) / C;
+  sax = block_sum_d_waves(sax, sh) / C;
   for (int c = threadIdx.x; c < C; c += 256) {
     const float xh = (xr[c] - mu) * rs, a = dr[c] * gamma[c];
     dx[r * C + c] = rs * (a - (float)sa - xh * (float)sax);
@@ -225,7 +224,6 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const float* __res
   }
 }
 
-static inline unsigned grid_for(size_t n) { const size_t g = (n + 255) / 256; return (unsigned)(g > 65535 ? 65535 : (g ? g : 1)); }
 
 }  // namespace dmvae_parity_dit
 using namespace dmvae_parity_dit;
@@ -258,7 +256,7 @@ extern "C" int dmvae_bcast_rows_f32(int op, const void* a, const void* b, const 
                                     hipStream_t stream) {
   DMVAE_CHECK_ARG(a && out && rows > 0 && c > 0 && op >= 0 && op <= 2 && rows_per_sample > 0, "bcast_rows_f32: bad arguments");
   DMVAE_CHECK_ARG((op == 1 || b) && (op == 2 || g), "bcast_rows_f32: op %d misses an operand", op);
-  hipLaunchKernelGGL(bcast_kernel, dim3(grid_for(rows * c)), dim3(256), 0, stream, op, (const float*)a, (const float*)b, (const float*)g, (float*)out, rows * c, c,
+  hipLaunchKernelGGL(bcast_kernel, dim3(grid_for(rows * c, 256, 65535)), dim3(256), 0, stream, op, (const float*)a, (const float*)b, (const float*)g, (float*)out, rows * c, c,
                      rows_per_sample, ld_mod);
   DMVAE_CHECK_LAUNCH();
   return 0;
@@ -272,13 +270,13 @@ extern "C" int dmvae_colsum_groups_f32(const void* x, void* out, int groups, int
 }
 extern "C" int dmvae_swiglu_fwd_f32(const void* x12, void* g, size_t rows, int hidden, hipStream_t stream) {
   DMVAE_CHECK_ARG(x12 && g && rows > 0 && hidden > 0, "swiglu_fwd_f32: bad arguments");
-  hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(grid_for(rows * hidden)), dim3(256), 0, stream, (const float*)x12, (float*)g, rows, hidden);
+  hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(grid_for(rows * hidden, 256, 65535)), dim3(256), 0, stream, (const float*)x12, (float*)g, rows, hidden);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int dmvae_swiglu_bwd_f32(const void* dg, const void* x12, void* dx12, size_t rows, int hidden, hipStream_t stream) {
   DMVAE_CHECK_ARG(dg && x12 && dx12 && rows > 0 && hidden > 0, "swiglu_bwd_f32: bad arguments");
-  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(rows * hidden)), dim3(256), 0, stream, (const float*)dg, (const float*)x12, (float*)dx12, rows, hidden);
+  hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(rows * hidden, 256, 65535)), dim3(256), 0, stream, (const float*)dg, (const float*)x12, (float*)dx12, rows, hidden);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

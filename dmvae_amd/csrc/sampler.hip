@@ -159,7 +159,7 @@ __device__ __forceinline__ void err_at(const float* __restrict__ y0, const float
   if (err_out) store_w<W>(err_out, e, s);
 }
 
-__device__ __forceinline__ void block_sum_256(double& v, int& f) {
+__device__ __forceinline__ void block_sum_flag_256(double& v, int& f) {   // f64 sum and OR of a flag over 256 threads, both in place
   __shared__ double sv[256];
   __shared__ int sf[256];
   sv[threadIdx.x] = v;
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void ode_err_partial_kernel(const float* __res
   int bad = 0;
   for (size_t i = tid; i < nq; i += stride) err_at<4>(y0, y1, T, err_out, 4 * i, atol, rtol, round_bf16, acc, bad);
   for (size_t e = 4 * nq + tid; e < n; e += stride) err_at<1>(y0, y1, T, err_out, e, atol, rtol, round_bf16, acc, bad);
-  block_sum_256(acc, bad);
+  block_sum_flag_256(acc, bad);
   if (threadIdx.x == 0) { part[blockIdx.x] = acc; part_bad[blockIdx.x] = bad; }
 }
 
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void ode_err_final_kernel(const double* __rest
   double acc = 0.0;
   int bad = 0;
   for (int b = threadIdx.x; b < nparts; b += 256) { acc += part[b]; bad |= part_bad[b]; }
-  block_sum_256(acc, bad);
+  block_sum_flag_256(acc, bad);
   if (threadIdx.x == 0) {
     reinterpret_cast<float*>(result)[0] = (float)(acc / (double)n);
     reinterpret_cast<int*>(result)[1] = bad;

@@ -167,18 +167,6 @@ namespace dmvae_vit {
 
 constexpr int ATT_D = 64, ATT_KB = 9, ATT_KEYS = ATT_KB * 32;  // keys padded to 288
 
-template <int N>
-__device__ __forceinline__ void attn_wait_vmcnt() {   // through the builtin: the compiler's wait-count pass has to see the wait (conv_pp.hip)
-  __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ s16x4 tr_read_v(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  bf16x2 t = {(bf16)a, (bf16)b};
-  return *reinterpret_cast<unsigned*>(&t);
-}
 
 // DP: head dim as staged (64, or 96 = 72 zero-padded by the producer for LightningDiT-XL); D: real head dim (V / output width).
 // q / k / v: per-(batch, head) base = ptr + b * bs + h * hs (elements), token rows `rs` elements apart.
@@ -257,8 +245,8 @@ __global__ __launch_bounds__(ATTN_THREADS) void attention_kernel(AttnArgs a) {
     const bf16* vp = a.v + b_ * a.v_bs + h_ * a.v_hs;
     if constexpr (PIPE) {
       typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)kp, 0, 0x7fffffff, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rV = __builtin_amdgcn_make_buffer_rsrc((void*)vp, 0, 0x7fffffff, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rK = dmvae_buffer_rsrc(kp, 0x7fffffff);
+      const __amdgpu_buffer_rsrc_t rV = dmvae_buffer_rsrc(vp, 0x7fffffff);
 #pragma unroll
       for (int it = 0; it < SWEEPS; it++) {
         const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rK, voK[it], 0, 0), y = __builtin_amdgcn_raw_buffer_load_b128(rV, voV[it], 0, 0);
@@ -345,8 +333,8 @@ __global__ __launch_bounds__(ATTN_THREADS) void attention_kernel(AttnArgs a) {
 #pragma unroll
         for (int kk = 0; kk < KSTEPS; kk++) asm volatile("" : "+v"(qf[kk]));
       };
-      if (pre) { load_kv(item_bh(next)); pre = false; attn_wait_vmcnt<2 * SWEEPS>(); pin_q(); }
-      else { attn_wait_vmcnt<0>(); pin_q(); }
+      if (pre) { load_kv(item_bh(next)); pre = false; wait_vmcnt<2 * SWEEPS>(); pin_q(); }
+      else { wait_vmcnt<0>(); pin_q(); }
     }
     if constexpr (NR) {  // this lane and lane ^ 32 hold the two halves of query q's row
       float ss = 0.f;
@@ -409,18 +397,18 @@ __global__ __launch_bounds__(ATTN_THREADS) void attention_kernel(AttnArgs a) {
       for (int half = 0; half < 2; half++)
 #pragma unroll
         for (int db = 0; db < DB; db++) {
-          vf[half][db].hlf[0] = tr_read_v(vs + (kb * 2 + half) * (16 * VROW) + voff[db]);
-          vf[half][db].hlf[1] = tr_read_v(vs + (kb * 2 + half) * (16 * VROW) + voff[db] + 4 * VROW);
+          vf[half][db].hlf[0] = tr_read_ordered(vs + (kb * 2 + half) * (16 * VROW) + voff[db]);
+          vf[half][db].hlf[1] = tr_read_ordered(vs + (kb * 2 + half) * (16 * VROW) + voff[db] + 4 * VROW);
         }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int r = 0; r < 16; r++) { st[r] = __builtin_amdgcn_exp2f(fmaf(st[r], ec, -emc)); sum += st[r]; }
 #pragma unroll
       for (int half = 0; half < 2; half++) {  // 16-key step: registers r = half*8 .. half*8+7 of this block
-        unsigned p0 = pack_bf16(st[half * 8 + 0], st[half * 8 + 1]);
-        unsigned p1 = pack_bf16(st[half * 8 + 2], st[half * 8 + 3]);
-        unsigned p2 = pack_bf16(st[half * 8 + 4], st[half * 8 + 5]);
-        unsigned p3 = pack_bf16(st[half * 8 + 6], st[half * 8 + 7]);
+        unsigned p0 = dmvae_pack_bf16x2(st[half * 8 + 0], st[half * 8 + 1]);
+        unsigned p1 = dmvae_pack_bf16x2(st[half * 8 + 2], st[half * 8 + 3]);
+        unsigned p2 = dmvae_pack_bf16x2(st[half * 8 + 4], st[half * 8 + 5]);
+        unsigned p3 = dmvae_pack_bf16x2(st[half * 8 + 6], st[half * 8 + 7]);
         // lanes < 32 hold keys {0-3, 8-11} of the step, lanes >= 32 {4-7, 12-15}: the A fragment wants {0-7} / {8-15}
         auto s0 = __builtin_amdgcn_permlane32_swap(p0, p2, false, false);
         auto s1 = __builtin_amdgcn_permlane32_swap(p1, p3, false, false);
@@ -446,8 +434,8 @@ __global__ __launch_bounds__(ATTN_THREADS) void attention_kernel(AttnArgs a) {
           const int d0 = db * 32 + 8 * r4 + 4 * kg;
           if (d0 < a.D) {      // D % 8 == 0: the four channels are inside together
             uint2 pk;
-            pk.x = pack_bf16(o[db][4 * r4 + 0] * inv, o[db][4 * r4 + 1] * inv);
-            pk.y = pack_bf16(o[db][4 * r4 + 2] * inv, o[db][4 * r4 + 3] * inv);
+            pk.x = dmvae_pack_bf16x2(o[db][4 * r4 + 0] * inv, o[db][4 * r4 + 1] * inv);
+            pk.y = dmvae_pack_bf16x2(o[db][4 * r4 + 2] * inv, o[db][4 * r4 + 3] * inv);
             *reinterpret_cast<uint2*>(orow + d0) = pk;
           }
         }
@@ -465,11 +453,7 @@ __global__ __launch_bounds__(ATTN_THREADS) void attention_kernel(AttnArgs a) {
 template <int DP, bool NR = false>
 static int launch_attention(const AttnArgs& a, int batch, hipStream_t stream) {
   constexpr int lds = ATT_KEYS * (DP == 64 ? 128 : 256) + ATT_KEYS * (DP == 64 ? 128 : 256);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DP, NR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, attention_kernel<DP, NR>);
   AttnArgs b_ = a;
   b_.BH = batch * a.H;
   b_.xcd = 1;
@@ -480,11 +464,7 @@ static int launch_attention(const AttnArgs& a, int batch, hipStream_t stream) {
       return n & ~7;
     }();
     if (b_.BH >= 2 * cus) {
-      static bool attr_pipe = false;
-      if (!attr_pipe) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<DP, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_pipe = true;
-      }
+      DMVAE_LDS_OPTIN(lds, attention_kernel<DP, false, true>);
       hipLaunchKernelGGL((attention_kernel<DP, false, true>), dim3(cus), dim3(ATTN_THREADS), lds, stream, b_);
       DMVAE_CHECK_LAUNCH();
       return 0;

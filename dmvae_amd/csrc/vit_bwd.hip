@@ -141,7 +141,6 @@ __global__ __launch_bounds__(256) void layerscale_bwd_kernel(const float* __rest
   }
 }
 
-__device__ __forceinline__ float gelu_f(float x) { return dmvae_gelu_f(x); }   // common.h: erf from A&S 7.1.26, the same bits as the GEMM epilogue's
 __device__ __forceinline__ float gelu_grad_f(float x) {
   return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
@@ -151,7 +150,7 @@ __global__ void gelu_fwd_kernel(const bf16* __restrict__ x, bf16* __restrict__ y
     const bf16x8 v = reinterpret_cast<const bf16x8*>(x)[i];
     bf16x8 o;
 #pragma unroll
-    for (int e = 0; e < 8; e++) o[e] = (bf16)gelu_f((float)v[e]);
+    for (int e = 0; e < 8; e++) o[e] = (bf16)dmvae_gelu_f((float)v[e]);
     reinterpret_cast<bf16x8*>(y)[i] = o;
   }
 }
@@ -165,10 +164,6 @@ __global__ void gelu_bwd_kernel(const bf16* __restrict__ dy, const bf16* __restr
   }
 }
 
-static inline int grid_for(size_t n, int block = 256, int cap = 4096) {
-  size_t g = (n + block - 1) / block;
-  return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
-}
 
 }  // namespace dmvae_vit_bwd
 using namespace dmvae_vit_bwd;
@@ -222,14 +217,14 @@ extern "C" int dmvae_layerscale_bwd(const void* dt, const void* y, const void* g
 extern "C" int dmvae_gelu_fwd(const void* x, void* y, size_t n, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && y && n % 8 == 0, "gelu_fwd: element count must be a multiple of 8");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, n / 8);
+  hipLaunchKernelGGL(gelu_fwd_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, n / 8);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 extern "C" int dmvae_gelu_bwd(const void* dy, const void* x, void* dx, size_t n, hipStream_t stream) {
   DMVAE_CHECK_ARG(dy && x && dx && n % 8 == 0, "gelu_bwd: element count must be a multiple of 8");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for(n / 8)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)x, (bf16*)dx, n / 8);
+  hipLaunchKernelGGL(gelu_bwd_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)x, (bf16*)dx, n / 8);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -22,7 +22,6 @@
 
 namespace dmvae_wgrad_thin {
 
-constexpr unsigned SENT = 0x80000000u;
 constexpr int CIN = 128, NCOL = 48, NBUF = 6, PF = 5;
 constexpr int SLOT_A = 32 * 256, SLOT_B = 3 * 1024, SLOT = SLOT_A + SLOT_B;
 
@@ -34,18 +33,7 @@ struct Args {
   int steps, spb;   // K steps in all (N * H * W / 32), per block
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  __builtin_amdgcn_s_waitcnt((N & 15) | 0x0F70 | ((N >> 4) << 14));
-  asm volatile("" ::: "memory");
-}
-// inline asm, not the builtin: no memory operand for the compiler's wait-count pass to order behind the LDS-DMA queue (see conv_wgrad_pp.hip)
-template <int OFF>
-__device__ __forceinline__ s16x4 tr_read(unsigned lds_addr) {
-  s16x4 r;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(lds_addr), "n"(OFF));
-  return r;
-}
+// ds_read_b128 as inline asm for the reason tr_read_uncounted (common.h) is: no memory operand for the compiler's wait-count pass to order behind the LDS-DMA queue
 __device__ __forceinline__ bf16x8 lds_read16(unsigned lds_addr) {
   bf16x8 r;
   asm volatile("ds_read_b128 %0, %1" : "=v"(r) : "v"(lds_addr));
@@ -95,8 +83,8 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(Args a) {
   const int nK = s1 - s0;
   const int xpr = a.W >> 5;  // K steps per image row
 
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)a.a, 0, (unsigned)a.N * a.H * a.W * 256u, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)a.sh, 0, 3u * (unsigned)a.N * 4u * (unsigned)(a.H + 2) * (unsigned)a.W * 2u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = dmvae_buffer_rsrc(a.a, (unsigned)a.N * a.H * a.W * 256u);
+  const __amdgpu_buffer_rsrc_t rB = dmvae_buffer_rsrc(a.sh, 3u * (unsigned)a.N * 4u * (unsigned)(a.H + 2) * (unsigned)a.W * 2u);
 
   // ---- per-lane DMA sources ------------------------------------------------------------------------------------------------------------
   // A: pieces pb = 2 wave, 2 wave + 1 of the [32 px][128 ch] tile: pixel rows 4 pb + lane / 16, physical 16-B chunk lane % 16 (swizzle of conv_wgrad_pp.hip)
@@ -172,8 +160,8 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(Args a) {
     bf16x8 bfr[3];
 #pragma unroll
     for (int i = 0; i < 2; i++) {
-      af[i].h[0] = tr_read<0>(sb + aoff[i]);
-      af[i].h[1] = tr_read<1024>(sb + aoff[i]);
+      af[i].h[0] = tr_read_uncounted<0>(sb + aoff[i]);
+      af[i].h[1] = tr_read_uncounted<1024>(sb + aoff[i]);
     }
 #pragma unroll
     for (int j = 0; j < 3; j++) bfr[j] = lds_read16(sb + boff[j]);
@@ -258,11 +246,7 @@ extern "C" int dmvae_conv_out_wgrad(const void* dy, const void* a, void* dw, voi
   const int blocks = wgrad_thin_blocks(g.steps);
   g.spb = (g.steps + blocks - 1) / blocks;
   constexpr int lds = NBUF * SLOT + 1024;   // + wave 3's scratch KiB
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_thin_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_done = true;
-  }
+  DMVAE_LDS_OPTIN(lds, wgrad_thin_kernel);
   hipLaunchKernelGGL(wgrad_thin_kernel, dim3((unsigned)blocks), dim3(256), lds, stream, g);
   DMVAE_CHECK_LAUNCH();
   hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3(36), dim3(1024), 0, stream, (const float*)slab, (float*)dw, blocks, cout, accumulate);
