@@ -102,6 +102,11 @@ SIGNATURES = {
     "dmvae_ode_dense_output": (c_int, [c_void_p] * 5 + [c_int, c_float, c_float, c_void_p, c_size_t, c_void_p]),
     "dmvae_ode_hutchinson_pack": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
     "dmvae_cfg_combine": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_size_t, c_int, c_float, c_void_p, c_float, c_void_p]),
+    "dmvae_sde_heun_perturb": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_float, c_void_p]),
+    "dmvae_sde_heun_predict": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t] + [c_float] * 4 + [c_void_p]),
+    "dmvae_sde_heun_correct": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t] + [c_float] * 4 + [c_void_p]),
+    "dmvae_sde_last_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int] + [c_float] * 5 + [c_void_p]),
+    "dmvae_autoguidance_combine": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_size_t, c_int, c_float, c_void_p, c_float, c_float, c_void_p]),
     "dmvae_batchnorm_running_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p]),
     "dmvae_diffaug_fwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),
     "dmvae_diffaug_bwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),

@@ -13,7 +13,10 @@
 // per-sample Hutchinson sum of the input-VJP against the Rademacher probe.
 // Classifier-free guidance (lightningdit.py:423-447) adds one pass per guided model evaluation (dmvae_cfg_combine): the model's output for the batch
 // [cond | uncond] becomes what forward_with_cfg returns, with the reference's rounding sites and the interval gate read from t on the device.
-// Every kernel takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail.
+// The Heun step of the SDE sampler (integrators.py:37-48) is three passes around its two model evaluations -- perturb, predict (K1 and the predictor state),
+// correct --, and the "Tweedie" / "Euler" last steps (transport.py:279-288) one pass with a mode argument; autoguidance (lightningdit.py:450-465) is one pass
+// over the two models' outputs (dmvae_autoguidance_combine), its interval gate read from t on the device like the guidance kernel's.
+// Every kernel but the Euler-Maruyama one takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail.
 #include <initializer_list>
 
 #include "common.h"
@@ -326,6 +329,154 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const T* __restrict__ 
   }
 }
 
+// ---- Heun step of the SDE sampler (integrators.py:37-48) and the "Tweedie" / "Euler" last steps (transport.py:279-288) ------------------------------------
+
+// xhat = x + sqrt(2 diffusion) * (w sqrt(dt))
+template <int W>
+__device__ __forceinline__ void heun_perturb_at(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ xhat, size_t e, float sq2d, float sqdt) {
+#pragma clang fp contract(off)
+  float a[W], b[W], o[W];
+  load_w<W>(x, false, e, a);
+  load_w<W>(w, false, e, b);
+#pragma unroll
+  for (int j = 0; j < W; j++) o[j] = a[j] + sq2d * (b[j] * sqdt);
+  store_w<W>(xhat, e, o);
+}
+
+__global__ __launch_bounds__(256) void sde_heun_perturb_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ xhat, size_t n, size_t nq,
+                                                               float sq2d, float sqdt) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) heun_perturb_at<4>(x, w, xhat, 4 * i, sq2d, sqdt);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_perturb_at<1>(x, w, xhat, e, sq2d, sqdt);
+}
+
+// sde_drift at (y, v): v + diff * ((rar * v - y) / var)   (transport.py:253-256 over get_score_from_velocity, path.py:74-89)
+__device__ __forceinline__ float sde_drift_one(float v, float y, float rar, float var, float diff) {
+#pragma clang fp contract(off)
+  const float score = (rar * v - y) / var;
+  return v + diff * score;
+}
+
+// K1 = sde_drift(xhat, v1);  xp = xhat + dt * K1
+template <int W>
+__device__ __forceinline__ void heun_predict_at(const float* __restrict__ xhat, const void* v, int v_bf16, float* __restrict__ k1, float* __restrict__ xp, size_t e,
+                                                float rar, float var, float diff, float dt) {
+#pragma clang fp contract(off)
+  float y[W], vv[W], k[W], o[W];
+  load_w<W>(xhat, false, e, y);
+  load_w<W>(v, v_bf16, e, vv);
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    k[j] = sde_drift_one(vv[j], y[j], rar, var, diff);
+    o[j] = y[j] + dt * k[j];
+  }
+  store_w<W>(k1, e, k);
+  store_w<W>(xp, e, o);
+}
+
+__global__ __launch_bounds__(256) void sde_heun_predict_kernel(const float* __restrict__ xhat, const void* v, int v_bf16, float* __restrict__ k1, float* __restrict__ xp,
+                                                               size_t n, size_t nq, float rar, float var, float diff, float dt) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) heun_predict_at<4>(xhat, v, v_bf16, k1, xp, 4 * i, rar, var, diff, dt);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_predict_at<1>(xhat, v, v_bf16, k1, xp, e, rar, var, diff, dt);
+}
+
+// K2 = sde_drift(xp, v2) with the coefficients at t + dt;  x = xhat + (0.5 dt) * (K1 + K2)
+template <int W>
+__device__ __forceinline__ void heun_correct_at(const float* __restrict__ xhat, const float* __restrict__ xp, const float* __restrict__ k1, const void* v, int v_bf16,
+                                                float* __restrict__ out, size_t e, float rar, float var, float diff, float hdt) {
+#pragma clang fp contract(off)
+  float y[W], p[W], k[W], vv[W], o[W];
+  load_w<W>(xhat, false, e, y);
+  load_w<W>(xp, false, e, p);
+  load_w<W>(k1, false, e, k);
+  load_w<W>(v, v_bf16, e, vv);
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    const float k2 = sde_drift_one(vv[j], p[j], rar, var, diff);
+    o[j] = y[j] + hdt * (k[j] + k2);
+  }
+  store_w<W>(out, e, o);
+}
+
+__global__ __launch_bounds__(256) void sde_heun_correct_kernel(const float* __restrict__ xhat, const float* __restrict__ xp, const float* __restrict__ k1, const void* v,
+                                                               int v_bf16, float* __restrict__ out, size_t n, size_t nq, float rar, float var, float diff, float hdt) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) heun_correct_at<4>(xhat, xp, k1, v, v_bf16, out, 4 * i, rar, var, diff, hdt);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_correct_at<1>(xhat, xp, k1, v, v_bf16, out, e, rar, var, diff, hdt);
+}
+
+// Tweedie: x / a + c * ((rar * v - x) / var).  Euler: x + (v * h), the product rounded to bf16 when v is bf16 (`bf16 tensor * python float` stays bf16).
+template <int W>
+__device__ __forceinline__ void last_step_at(const float* __restrict__ x, const void* v, int v_bf16, float* __restrict__ out, size_t e, int mode, float a, float c,
+                                             float rar, float var, float h) {
+#pragma clang fp contract(off)
+  float y[W], vv[W], o[W];
+  load_w<W>(x, false, e, y);
+  load_w<W>(v, v_bf16, e, vv);
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    if (mode == DMVAE_LAST_STEP_TWEEDIE) {
+      const float score = (rar * vv[j] - y[j]) / var;
+      o[j] = y[j] / a + c * score;
+    } else {
+      float p = vv[j] * h;
+      if (v_bf16) p = (float)(bf16)p;
+      o[j] = y[j] + p;
+    }
+  }
+  store_w<W>(out, e, o);
+}
+
+__global__ __launch_bounds__(256) void sde_last_step_kernel(const float* __restrict__ x, const void* v, int v_bf16, float* __restrict__ out, size_t n, size_t nq, int mode,
+                                                            float a, float c, float rar, float var, float h) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) last_step_at<4>(x, v, v_bf16, out, 4 * i, mode, a, c, rar, var, h);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) last_step_at<1>(x, v, v_bf16, out, e, mode, a, c, rar, var, h);
+}
+
+// ---- autoguidance (LightningDiT.forward_with_autoguidance, lightningdit.py:450-465) ------------------------------------------------------------------------
+
+// eps [n][c_eps][hw], ag [n][c_ag][hw] -> dst [2][n][k][hw]: the first k channels of every sample, g = ag + scale * (eps - ag) where lo <= t[0] <= hi (read on the
+// device), eps itself elsewhere; both halves of dst receive it.  Rounding as cfg_one: a bf16 tensor rounds after each of the three ops.
+template <typename T, int W>
+__device__ __forceinline__ void autoguidance_at(const T* __restrict__ eps, const T* __restrict__ ag, T* __restrict__ dst, size_t e, size_t half, size_t per, size_t per_eps,
+                                                size_t per_ag, float scale, bool inside) {
+  const size_t s = e / per, r = e - s * per;                 // sample, offset inside its first k channels (W == 4: per % 4 == 0, a quad stays in one sample)
+  float a[W], b[W];
+  load_w<W>(eps, sizeof(T) == 2, s * per_eps + r, a);
+  if (inside) {
+    load_w<W>(ag, sizeof(T) == 2, s * per_ag + r, b);
+#pragma unroll
+    for (int j = 0; j < W; j++) a[j] = cfg_one<T>(a[j], b[j], scale, false);
+  }
+  if constexpr (sizeof(T) == 2) {
+    if constexpr (W == 4) {
+      bf16x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; j++) o[j] = (bf16)a[j];          // exact: every value is a bf16 already
+      *reinterpret_cast<bf16x4*>(dst + e) = o;
+      *reinterpret_cast<bf16x4*>(dst + half + e) = o;
+    } else {
+      dst[e] = dst[half + e] = (bf16)a[0];
+    }
+  } else {
+    store_w<W>(dst, e, a);
+    store_w<W>(dst + half, e, a);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void autoguidance_combine_kernel(const T* __restrict__ eps, const T* __restrict__ ag, T* __restrict__ dst, size_t half, size_t nq,
+                                                                   size_t per, size_t per_eps, size_t per_ag, float scale, const float* __restrict__ t, float lo,
+                                                                   float hi) {
+  const float t0 = t[0];
+  const bool inside = t0 >= lo && t0 <= hi;
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) autoguidance_at<T, 4>(eps, ag, dst, 4 * i, half, per, per_eps, per_ag, scale, inside);
+  for (size_t e = 4 * nq + tid; e < half; e += stride) autoguidance_at<T, 1>(eps, ag, dst, e, half, per, per_eps, per_ag, scale, inside);
+}
+
 constexpr int kErrMaxParts = 1024;
 
 inline int ode_grid(size_t n, size_t nq, int cap) {
@@ -451,6 +602,72 @@ extern "C" int dmvae_cfg_combine(const void* out2n, int is_bf16, void* dst, int 
   else
     hipLaunchKernelGGL(cfg_combine_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)out2n, (float*)dst, half, nq, hw, channels, k, scale,
                        (const float*)t_or_null, interval_start);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_heun_perturb(const void* x, const void* w, void* xhat, size_t n, float sqrt_2diff, float sqrt_dt, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(x && w && xhat && n > 0, "sde_heun_perturb: bad argument (x, w, xhat non-NULL, n > 0)");
+  const size_t nq = ode_quads(n, nullptr, {x, w, xhat});
+  hipLaunchKernelGGL(sde_heun_perturb_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, (const float*)w, (float*)xhat, n, nq, sqrt_2diff,
+                     sqrt_dt);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_heun_predict(const void* xhat, const void* v1, int v_is_bf16, void* k1, void* xp, size_t n, float rar, float var, float diff, float dt,
+                                      hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(xhat && v1 && k1 && xp && n > 0, "sde_heun_predict: bad argument (xhat, v1, k1, xp non-NULL, n > 0)");
+  const size_t nq = aligned(v1, v_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, k1, xp}) : 0;
+  hipLaunchKernelGGL(sde_heun_predict_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, v1, v_is_bf16 != 0, (float*)k1, (float*)xp, n, nq,
+                     rar, var, diff, dt);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_heun_correct(const void* xhat, const void* xp, const void* k1, const void* v2, int v_is_bf16, void* x_out, size_t n, float rar2, float var2,
+                                      float diff2, float half_dt, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(xhat && xp && k1 && v2 && x_out && n > 0, "sde_heun_correct: bad argument (xhat, xp, k1, v2, x_out non-NULL, n > 0)");
+  const size_t nq = aligned(v2, v_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, xp, k1, x_out}) : 0;
+  hipLaunchKernelGGL(sde_heun_correct_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, (const float*)xp, (const float*)k1, v2,
+                     v_is_bf16 != 0, (float*)x_out, n, nq, rar2, var2, diff2, half_dt);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_last_step(const void* x, const void* v, int v_is_bf16, void* out, size_t n, int mode, float a, float c, float rar, float var, float h,
+                                   hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(x && v && out && n > 0, "sde_last_step: bad argument (x, v, out non-NULL, n > 0)");
+  DMVAE_CHECK_ARG(mode == DMVAE_LAST_STEP_TWEEDIE || mode == DMVAE_LAST_STEP_EULER, "sde_last_step: mode must be DMVAE_LAST_STEP_TWEEDIE or _EULER, got %d", mode);
+  const size_t nq = aligned(v, v_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, out}) : 0;
+  hipLaunchKernelGGL(sde_last_step_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, v, v_is_bf16 != 0, (float*)out, n, nq, mode, a, c, rar,
+                     var, h);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_autoguidance_combine(const void* eps, int c_eps, const void* ag, int c_ag, int is_bf16, void* dst, int n, size_t hw, int k, float scale,
+                                          const void* t, float lo, float hi, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(eps && ag && dst && t, "autoguidance_combine: eps, ag, dst and t must not be NULL");
+  DMVAE_CHECK_ARG(dst != eps && dst != ag, "autoguidance_combine: dst must not alias eps or ag");
+  DMVAE_CHECK_ARG(n > 0 && hw > 0 && k > 0 && k <= c_eps && k <= c_ag,
+                  "autoguidance_combine: bad argument (n > 0, hw > 0, 0 < k <= channels of eps and ag; got n %d, hw %zu, k %d, channels %d and %d)", n, hw, k, c_eps, c_ag);
+  const size_t per = (size_t)k * hw, per_eps = (size_t)c_eps * hw, per_ag = (size_t)c_ag * hw, half = (size_t)n * per;
+  const size_t al = is_bf16 ? 8 : 16;                       // quads: every sample's first k channels start on a quad and hold whole quads, in all three arrays
+  const bool quads = per % 4 == 0 && per_eps % 4 == 0 && per_ag % 4 == 0 && aligned(eps, al) && aligned(ag, al) && aligned(dst, al);
+  const size_t nq = quads ? half / 4 : 0;
+  const int grid = ode_grid(half, nq, 2048);
+  if (is_bf16)
+    hipLaunchKernelGGL(autoguidance_combine_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)eps, (const bf16*)ag, (bf16*)dst, half, nq, per, per_eps, per_ag,
+                       scale, (const float*)t, lo, hi);
+  else
+    hipLaunchKernelGGL(autoguidance_combine_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)eps, (const float*)ag, (float*)dst, half, nq, per, per_eps,
+                       per_ag, scale, (const float*)t, lo, hi);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

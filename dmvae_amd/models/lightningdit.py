@@ -357,6 +357,29 @@ class LightningDiT(nn.Module):
             half_eps = cond
         return torch.cat([torch.cat([half_eps, half_eps], dim=0), rest], dim=1)
 
+    def forward_with_autoguidance(self, x, t, y, cfg_scale, additional_model_forward, cfg_interval=(-1e4, -1e4)):
+        """lightningdit.py:450-465: this model and `additional_model_forward` (the guide: a smaller or less trained model's forward) on the first half of the
+        batch; inside the interval the first `in_channels` channels are ag + cfg_scale * (eps - ag); both halves of the result hold them.  On the HIP inference
+        route the arithmetic, the channel slices and the cat are one kernel behind the two forwards (`lightningdit_fast.forward_inference_autoguidance`: the
+        composition's bits, the interval compared on the device instead of on the host); everywhere else the composition below."""
+        if self._takes_inference_route(x[: len(x) // 2]):
+            from . import lightningdit_fast
+            return lightningdit_fast.forward_inference_autoguidance(self, x, t, y, cfg_scale, additional_model_forward, cfg_interval)
+        return self.forward_with_autoguidance_composed(x, t, y, cfg_scale, additional_model_forward, cfg_interval)
+
+    def forward_with_autoguidance_composed(self, x, t, y, cfg_scale, additional_model_forward, cfg_interval=(-1e4, -1e4)):
+        """The reference's tensor-op composition over `forward` (CPU, parity mode, a gradient wanted, shapes the kernels do not cover).  The test of t[0] reads
+        the device: a host synchronisation per call."""
+        half, t, y = x[: len(x) // 2], t[: len(t) // 2], y[: len(y) // 2]
+        return self._autoguidance_compose(self.forward(half, t, y), additional_model_forward(half, t, y), t, cfg_scale, cfg_interval)
+
+    def _autoguidance_compose(self, model_out, ag_model_out, t, cfg_scale, cfg_interval):
+        eps, ag_eps = model_out[:, :self.in_channels], ag_model_out[:, :self.in_channels]
+        t = t[0]
+        if t >= cfg_interval[0] and t <= cfg_interval[1]:
+            eps = ag_eps + cfg_scale * (eps - ag_eps)
+        return torch.cat([eps, eps], dim=0)
+
 
 def _cfg(depth, hidden_size, patch_size, num_heads):
     return lambda **kw: LightningDiT(depth=depth, hidden_size=hidden_size, patch_size=patch_size, num_heads=num_heads, **kw)

@@ -146,6 +146,20 @@ def forward_inference_cfg(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tens
     return ops.cfg_combine(out.contiguous(), k, cfg_scale, t_gate, interval_start)
 
 
+@torch.no_grad()
+def forward_inference_autoguidance(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor, cfg_scale: float, additional_model_forward,
+                                   cfg_interval=(-1e4, -1e4)) -> torch.Tensor:
+    """`LightningDiT.forward_with_autoguidance` (lightningdit.py:450-465) on the kernels: x [2n,C,H,W], t [2n], y [2n] whose first halves are used ->
+    `forward_inference` and `additional_model_forward` on the n samples, then ONE launch (`ops.autoguidance_combine`, csrc/sampler.hip) in place of the two channel
+    slices, sub, mul, add and the cat: [2n, in_channels, H, W] whose two halves hold ag + cfg_scale * (eps - ag) where cfg_interval[0] <= t[0] <= cfg_interval[1]
+    and eps elsewhere, with the reference's rounding after each op.  The interval is compared on the device -- no host read of t, so the call can be captured in a
+    graph.  The guide's output must be a CUDA tensor of this model's output type (bf16 under autocast): `ops.autoguidance_combine` refuses anything else."""
+    half, th_, yh = x[: len(x) // 2], t[: len(t) // 2], y[: len(y) // 2]
+    out = forward_inference(model, half, th_, yh)
+    ag = additional_model_forward(half, th_, yh)
+    return ops.autoguidance_combine(out.contiguous(), ag.contiguous(), model.in_channels, cfg_scale, th_, cfg_interval)
+
+
 class GraphedInference:
     """`forward_inference` of a FROZEN model captured once in a hipGraph and replayed: `f(x, t, y)` copies the arguments into the graph's static inputs,
     replays ~330 kernel launches with one host call and returns the graph's static output buffer (overwritten by the next call -- consume it first).
@@ -215,6 +229,37 @@ class GraphedInferenceCfg(GraphedInference):
         k = self.k if standard_cfg is None else (self.model.in_channels if standard_cfg else 3)
         start = self.interval_start if cfg_interval is None else (cfg_interval_start if cfg_interval is True else None)
         assert self.matches(x, t, y, cfg_scale, k, start), "GraphedInferenceCfg: shapes or guidance settings differ from the captured ones"
+        return GraphedInference.__call__(self, x, t, y)
+
+
+class GraphedInferenceAutoguidance(GraphedInference):
+    """Autoguidance as one replay per model evaluation: `forward_inference_autoguidance` captured at the [2n] shape -- this model's forward, the guide's
+    (`additional_model_forward`, which must itself run on capturable kernels: a frozen LightningDiT's `forward` on the inference route) and the combine kernel, one
+    after the other on the capturing stream (a single chain of nodes, no parallel branches).  The scale and the interval are fixed at capture; `t` stays a static
+    device input and the kernel evaluates the interval, so it follows the replayed t.  Called like `model.forward_with_autoguidance` (the sampler passes cfg_scale /
+    additional_model_forward / cfg_interval as keywords): keywords that differ from the captured ones are an error, not ignored.  Same capture discipline, same
+    lifetime of the returned buffer and the same rule about changed weights (of either model) as `GraphedInference`."""
+
+    def __init__(self, model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor, cfg_scale: float, additional_model_forward, cfg_interval=(-1e4, -1e4),
+                 warmup: int = 2):
+        if x.shape[0] % 2:
+            raise ValueError("GraphedInferenceAutoguidance: the batch is [z | z], an even number of samples")
+        self.cfg_scale, self.guide, self.interval = float(cfg_scale), additional_model_forward, (float(cfg_interval[0]), float(cfg_interval[1]))
+        super().__init__(model, x, t, y, warmup)
+
+    def _run(self) -> torch.Tensor:
+        return forward_inference_autoguidance(self.model, self.x, self.t, self.y, self.cfg_scale, self.guide, self.interval)
+
+    def matches(self, x, t, y, cfg_scale, additional_model_forward, cfg_interval) -> bool:
+        """Shapes as `GraphedInference.matches`, and the captured guidance: scale, guide and interval."""
+        return (super().matches(x, t, y) and float(cfg_scale) == self.cfg_scale and additional_model_forward == self.guide
+                and (float(cfg_interval[0]), float(cfg_interval[1])) == self.interval)
+
+    def __call__(self, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor, cfg_scale=None, additional_model_forward=None, cfg_interval=None) -> torch.Tensor:
+        cfg_scale = self.cfg_scale if cfg_scale is None else cfg_scale
+        guide = self.guide if additional_model_forward is None else additional_model_forward
+        interval = self.interval if cfg_interval is None else cfg_interval
+        assert self.matches(x, t, y, cfg_scale, guide, interval), "GraphedInferenceAutoguidance: shapes or guidance settings differ from the captured ones"
         return GraphedInference.__call__(self, x, t, y)
 
 

@@ -1719,6 +1719,88 @@ def cfg_combine(out2n: torch.Tensor, k: int, scale: float, t: Optional[torch.Ten
     return out
 
 
+def _req_v(v: torch.Tensor, like: torch.Tensor, name: str) -> torch.Tensor:
+    """A model output next to the f32 state `like`: bf16 or f32, contiguous, of its shape, on its device."""
+    _same(_req(v, bf16 if v.dtype == bf16 else f32, name), like, name)
+    return v
+
+
+def sde_heun_perturb(x: torch.Tensor, w: torch.Tensor, sqrt_2diff: float, sqrt_dt: float) -> torch.Tensor:
+    """The Heun step's noise injection (integrators.py:37-48): xhat = x + sqrt_2diff * (w * sqrt_dt).  x, w f32 of one shape; any number of elements."""
+    _same(_req(w, f32, "w"), _req(x, f32, "x"), "w")
+    xhat = torch.empty_like(x)
+    check(_lib.lib().dmvae_sde_heun_perturb(x.data_ptr(), w.data_ptr(), xhat.data_ptr(), x.numel(), float(sqrt_2diff), float(sqrt_dt), _stream()), "sde_heun_perturb")
+    return xhat
+
+
+def sde_heun_predict(xhat: torch.Tensor, v1: torch.Tensor, rar: float, var: float, diff: float, dt: float):
+    """The Heun step's predictor (integrators.py:37-48 with transport.py:253-256 / path.py:74-89 folded in) -> (k1, xp), both f32:
+    k1 = v1 + diff * ((rar * v1 - xhat) / var), xp = xhat + dt * k1.  xhat f32; v1 bf16 or f32, of xhat's shape."""
+    _req_v(v1, _req(xhat, f32, "xhat"), "v1")
+    k1, xp = torch.empty_like(xhat), torch.empty_like(xhat)
+    check(_lib.lib().dmvae_sde_heun_predict(xhat.data_ptr(), v1.data_ptr(), int(v1.dtype == bf16), k1.data_ptr(), xp.data_ptr(), xhat.numel(), float(rar), float(var),
+                                            float(diff), float(dt), _stream()), "sde_heun_predict")
+    return k1, xp
+
+
+def sde_heun_correct(xhat: torch.Tensor, xp: torch.Tensor, k1: torch.Tensor, v2: torch.Tensor, rar2: float, var2: float, diff2: float, half_dt: float) -> torch.Tensor:
+    """The Heun step's corrector (integrators.py:37-48): k2 = v2 + diff2 * ((rar2 * v2 - xp) / var2) with the coefficients at t + dt, then
+    xhat + half_dt * (k1 + k2).  xhat, xp, k1 f32; v2 bf16 or f32; one shape."""
+    _req(xhat, f32, "xhat")
+    for name, t in (("xp", xp), ("k1", k1)):
+        _same(_req(t, f32, name), xhat, name)
+    _req_v(v2, xhat, "v2")
+    out = torch.empty_like(xhat)
+    check(_lib.lib().dmvae_sde_heun_correct(xhat.data_ptr(), xp.data_ptr(), k1.data_ptr(), v2.data_ptr(), int(v2.dtype == bf16), out.data_ptr(), xhat.numel(),
+                                            float(rar2), float(var2), float(diff2), float(half_dt), _stream()), "sde_heun_correct")
+    return out
+
+
+LAST_STEP_TWEEDIE, LAST_STEP_EULER = 0, 1      # DMVAE_LAST_STEP_* of include/dmvae_hip.h
+
+
+def sde_last_step(x: torch.Tensor, v: torch.Tensor, mode: int, *, a: float = 1.0, c: float = 0.0, rar: float = 0.0, var: float = 1.0, h: float = 0.0) -> torch.Tensor:
+    """The sampler's "Tweedie" and "Euler" last steps (transport.py:279-288) in one launch.  LAST_STEP_TWEEDIE: x / a + c * ((rar * v - x) / var) with
+    a = alpha(t1), c = sigma(t1)^2 / a in f32.  LAST_STEP_EULER: x + (v * h), the product kept in bf16 for a bf16 v.  x f32; v bf16 or f32, of x's shape."""
+    if mode not in (LAST_STEP_TWEEDIE, LAST_STEP_EULER):
+        raise ValueError(f"sde_last_step: mode must be LAST_STEP_TWEEDIE or LAST_STEP_EULER, got {mode!r}")
+    _req_v(v, _req(x, f32, "x"), "v")
+    out = torch.empty_like(x)
+    check(_lib.lib().dmvae_sde_last_step(x.data_ptr(), v.data_ptr(), int(v.dtype == bf16), out.data_ptr(), x.numel(), int(mode), float(a), float(c), float(rar),
+                                         float(var), float(h), _stream()), "sde_last_step")
+    return out
+
+
+def autoguidance_combine(eps: torch.Tensor, ag: torch.Tensor, k: int, scale: float, t: torch.Tensor, interval=(-1e4, -1e4),
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Autoguidance on two model outputs in one launch (LightningDiT.forward_with_autoguidance, lightningdit.py:450-465): eps [n, C, H, W] is this model's
+    output, ag [n, C', H, W] the additional model's (both bf16 or both f32, contiguous) -> [2n, k, H, W] whose two halves both hold the first k channels of
+    ag + scale * (eps - ag) where interval[0] <= t[0] <= interval[1], of eps elsewhere -- rounded where the reference's three ops round, bit-identical to
+    PyTorch on the CPU.  `t` (any floating dtype, at least one element, on eps's device) is compared on the device: no host read."""
+    _req(eps, bf16 if eps.dtype == bf16 else f32, "eps")
+    _req(ag, eps.dtype, "ag")
+    if eps.dim() != 4 or eps.numel() == 0 or ag.dim() != 4 or ag.shape[0] != eps.shape[0] or ag.shape[2:] != eps.shape[2:] or ag.device != eps.device:
+        raise ValueError(f"autoguidance_combine: eps [n, C, H, W] and ag [n, C', H, W] on one device, got {tuple(eps.shape)} and {tuple(ag.shape)}")
+    if not 0 < int(k) <= min(eps.shape[1], ag.shape[1]):
+        raise ValueError(f"autoguidance_combine: 0 < k <= channels of eps and ag, got k {k} for {eps.shape[1]} and {ag.shape[1]} channels")
+    if not torch.is_tensor(t) or not t.is_cuda or t.device != eps.device or not t.is_floating_point() or t.numel() < 1:
+        raise ValueError(f"autoguidance_combine: t must be a non-empty floating-point tensor on {eps.device}")
+    t = t.reshape(-1)[:1].to(f32).contiguous()               # device-side conversion: no host read
+    n, _, h, w = eps.shape
+    shape = (2 * n, int(k), h, w)
+    if out is None:
+        out = torch.empty(shape, dtype=eps.dtype, device=eps.device)
+    _req(out, eps.dtype, "out")
+    if tuple(out.shape) != shape or out.device != eps.device:
+        raise ValueError(f"autoguidance_combine: out must be {shape} on {eps.device}, got {tuple(out.shape)} on {out.device}")
+    if out.data_ptr() in (eps.data_ptr(), ag.data_ptr()):
+        raise ValueError("autoguidance_combine: out must not alias eps or ag")
+    lo, hi = interval
+    check(_lib.lib().dmvae_autoguidance_combine(eps.data_ptr(), eps.shape[1], ag.data_ptr(), ag.shape[1], int(eps.dtype == bf16), out.data_ptr(), n, h * w, int(k),
+                                                float(scale), t.data_ptr(), float(lo), float(hi), _stream()), "autoguidance_combine")
+    return out
+
+
 def image_to_u8(y: torch.Tensor, channels: int, round_bf16: bool = False) -> torch.Tensor:
     """y [N,H,W,Cs] f32 (NHWC, first `channels` used) -> [N,H,W,channels] uint8 = clamp(127.5 y + 128, 0, 255) truncated (sample_50k.py:151)."""
     y = _req(y, f32, "y")

@@ -103,18 +103,28 @@ class SamplePipeline:
     `guidance=None` (default) is the reference's script: its `using_cfg` (sample_50k.py:120) is never used, so `cfg_scale` is accepted and ignored.
     `guidance="cfg"` with `cfg_scale > 1` samples with classifier-free guidance the way train_diffusion.py:250-255,340-344 does -- state [z | z], labels
     [y | null], `model.forward_with_cfg` (one hipGraph replay per evaluation with `use_graph`), the conditional half kept; `standard_cfg` and
-    `cfg_interval_start` (None: no interval gate) are `forward_with_cfg`'s.  `guidance="cfg"` with `cfg_scale == 1` is the unguided path."""
+    `cfg_interval_start` (None: no interval gate) are `forward_with_cfg`'s.  `guidance="cfg"` with `cfg_scale == 1` is the unguided path.
+    `guidance="autoguidance"` samples through `model.forward_with_autoguidance` (lightningdit.py:450-465) -- state [z | z], labels [y | y], the first half kept --
+    with `guide_model` (a module, or its forward) as the additional model, `cfg_scale` and `cfg_interval=(lo, hi)`, the model times inside which the guide is used;
+    one hipGraph replay per evaluation with `use_graph` (both forwards and the combine: `lightningdit_fast.GraphedInferenceAutoguidance`)."""
 
     def __init__(self, model, vae, *, mode="SDE", sampling_method="Euler", num_sampling_steps=250, diffusion_form="sigma", diffusion_norm=1.0,
                  last_step="Mean", last_step_size=0.04, atol=1e-6, rtol=1e-3, reverse=False, cfg_scale=1.0, latent_mean=0.0, latent_scale=1.0,
                  path_type="Linear", prediction="velocity", loss_weight=None, train_eps=0.0, sample_eps=0.0, time_dist_shift=1.0, use_graph=True,
-                 guidance=None, standard_cfg=True, cfg_interval_start=None):
+                 guidance=None, standard_cfg=True, cfg_interval_start=None, guide_model=None, cfg_interval=(-1e4, -1e4)):
         assert cfg_scale >= 1.0, "In almost all cases, cfg_scale be >= 1.0"
-        if guidance not in (None, "cfg"):
-            raise ValueError(f"guidance: None or 'cfg', got {guidance!r}")
+        if guidance not in (None, "cfg", "autoguidance"):
+            raise ValueError(f"guidance: None, 'cfg' or 'autoguidance', got {guidance!r}")
+        if guidance == "autoguidance" and guide_model is None:
+            raise ValueError("guidance='autoguidance' needs guide_model: the additional model of forward_with_autoguidance")
+        if guidance == "autoguidance" and len(tuple(cfg_interval)) != 2:
+            raise ValueError(f"cfg_interval: (lo, hi) for guidance='autoguidance', got {cfg_interval!r}")
         self.model, self.vae = model, vae
         self.latent_mean, self.latent_scale, self.cfg_scale = latent_mean, latent_scale, cfg_scale
         self.guided = guidance == "cfg" and cfg_scale > 1.0
+        self.autoguided = guidance == "autoguidance"
+        self.guide_fn = getattr(guide_model, "forward", guide_model) if self.autoguided else None
+        self.cfg_interval = tuple(float(v) for v in cfg_interval) if self.autoguided else None
         self.standard_cfg, self.cfg_interval_start = bool(standard_cfg), cfg_interval_start
         self.use_graph, self._graphed = use_graph, None      # the frozen DiT forward as one hipGraph replay per sampler step (models/lightningdit_fast.GraphedInference)
         transport = create_transport(path_type, prediction, loss_weight, train_eps, sample_eps, time_dist_shift=time_dist_shift)
@@ -132,24 +142,37 @@ class SamplePipeline:
             kw.update(cfg_interval=True, cfg_interval_start=self.cfg_interval_start)
         return kw
 
+    def _autoguidance_kwargs(self) -> dict:
+        """`forward_with_autoguidance`'s keywords for this pipeline's guidance settings."""
+        return dict(cfg_scale=self.cfg_scale, additional_model_forward=self.guide_fn, cfg_interval=self.cfg_interval)
+
     @torch.no_grad()
     def latents(self, z: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """noise [n, C, h, w] + labels [n] -> latent tokens [n, h*w, C] (sample_50k.py:138-148), under autocast(bf16) like the script."""
         with torch.autocast("cuda", dtype=torch.bfloat16):
-            if self.guided:
+            if self.autoguided:
+                zz, yy = torch.cat([z, z], dim=0), torch.cat([y, y], dim=0)
+                samples = self.sample_fn(zz, self._model_fn(zz, yy), y=yy, **self._autoguidance_kwargs())[-1].chunk(2, dim=0)[0]
+            elif self.guided:
                 samples = guided_sample(self.sample_fn, self._model_fn, z, y, self.model.y_embedder.num_classes, **self._cfg_kwargs())
             else:
                 samples = self.sample_fn(z, self._model_fn(z, y), y=y)[-1]        # the script never enables guidance (cfg_scale stays 1.0, :79)
         return dit_output_to_tokens(samples.float(), self.latent_mean, self.latent_scale)
 
     def _model_fn(self, z, y):
-        """`model.forward` (guided: `model.forward_with_cfg`), or its hipGraph replay when the model takes the HIP inference route at this shape (called under
+        """`model.forward` (guided: `model.forward_with_cfg` / `model.forward_with_autoguidance`), or its hipGraph replay when the model takes the HIP inference route at this shape (called under
         autocast with the state and labels the sampler will pass: doubled when guided)."""
         from .models import lightningdit_fast as fast
         if not (self.use_graph and z.is_cuda and hasattr(self.model, "blocks") and fast.supported(self.model, z)):
+            if self.autoguided:
+                return self.model.forward_with_autoguidance
             return self.model.forward_with_cfg if self.guided else self.model.forward
         t = torch.zeros(z.shape[0], device=z.device, dtype=z.dtype)
-        if self.guided:
+        if self.autoguided:
+            g = self._graphed
+            if not (isinstance(g, fast.GraphedInferenceAutoguidance) and g.matches(z, t, y, **self._autoguidance_kwargs())):
+                self._graphed = fast.GraphedInferenceAutoguidance(self.model, z, t, y, **self._autoguidance_kwargs())
+        elif self.guided:
             k = self.model.in_channels if self.standard_cfg else 3
             g = self._graphed
             if not (isinstance(g, fast.GraphedInferenceCfg) and g.matches(z, t, y, self.cfg_scale, k, self.cfg_interval_start)):

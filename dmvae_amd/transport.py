@@ -4,8 +4,10 @@
 
 What runs where: a sampler step is one model forward (LightningDiT on the HIP kernels, models/lightningdit_fast.py) plus the state update;
 the Euler-Maruyama update -- velocity -> score, drift, mean, noise injection -- is ONE kernel pass over the state (`ops.sde_euler_step`, csrc/sampler.hip)
-with the reference's f32 arithmetic order, so for the same model output the trajectory is bit-identical to the PyTorch reference.  Heun and
-the fixed-grid ODE methods are composed from device tensor ops.  The reference's default ODE method, adaptive dopri5 (torchdiffeq's, restated below), runs
+with the reference's f32 arithmetic order, so for the same model output the trajectory is bit-identical to the PyTorch reference.  The Heun step is three
+such passes around its two evaluations (`ops.sde_heun_perturb`, `sde_heun_predict`, `sde_heun_correct`) and the "Tweedie" / "Euler" last steps one
+(`ops.sde_last_step`), on the same terms.  The fixed-grid ODE methods are composed from device tensor ops; every time vector of a CUDA state is filled on the
+device (`_time_vector`), so no model evaluation waits for a host-to-device copy.  The reference's default ODE method, adaptive dopri5 (torchdiffeq's, restated below), runs
 on the device for a CUDA f32 state: the model forwards plus three kernels of csrc/sampler.hip per step (`ops.ode_rk_combine`, `ops.ode_error_ratio`,
 `ops.ode_dense_output`) and one 8-byte readback per attempted step for the step-size controller.  The likelihood sampler (`Sampler.sample_ode_likelihood`)
 integrates the tuple state (x, logp) as one flat f32 buffer with torchdiffeq's mixed norm; each evaluation is one model forward, its input-VJP and one
@@ -24,7 +26,7 @@ import torch as th
 
 from . import ops
 
-FUSED_STATE_UPDATE = True      # False composes the Euler-Maruyama / dopri5 updates from tensor ops (tests/test_gpu_sampler.py, test_gpu_ode_dopri5.py compare)
+FUSED_STATE_UPDATE = True      # False composes the Euler-Maruyama / Heun / last-step / dopri5 updates from tensor ops (tests/test_gpu_sampler*.py, test_gpu_ode_dopri5.py compare)
 
 
 class ModelType(enum.Enum):
@@ -259,11 +261,23 @@ def create_transport(path_type="Linear", prediction="velocity", loss_weight=None
 
 
 # ---- integrators -----------------------------------------------------------------------------------------------------------------------
+def _time_vector(n, t, like=None, device=None):
+    """The model's time vector `th.ones(n).to(x) * t` (integrators.py:28-29,38-39; `.to(device)` at :108): the same values and bits.  For a CUDA state it is
+    filled on the device -- the reference's pageable host-to-device copy of the ones waits for the stream, once per model evaluation."""
+    device, dtype = (like.device, like.dtype) if like is not None else (th.device(device), th.float32)
+    if device.type != "cuda":
+        return (th.ones(n).to(like) if like is not None else th.ones(n).to(device)) * t
+    if th.is_tensor(t) and t.is_cuda:                       # the fixed-grid ODE loop's grid lives on the device: no host read of t either
+        return th.full((n,), 1.0, device=device, dtype=dtype) * t
+    return th.full((n,), float(t), device=device, dtype=dtype)
+
+
 class sde:
     """integrators.py:8-77.  `sampler_type` "Euler" (Euler-Maruyama) or "Heun".
 
-    With `fused` (set by `Sampler.sample_sde` for the Linear path with a velocity model) the Euler step calls the model for the velocity and does
-    the whole update in `ops.sde_euler_step`; otherwise it evaluates the caller's `drift` / `diffusion` callables like the reference."""
+    With `fused` (set by `Sampler.sample_sde` for the Linear path with a velocity model) a step calls the model for the velocity and does the whole
+    update on csrc/sampler.hip -- Euler-Maruyama in `ops.sde_euler_step`, Heun in `ops.sde_heun_perturb` / `sde_heun_predict` / `sde_heun_correct` around its
+    two evaluations --; otherwise it evaluates the caller's `drift` / `diffusion` callables like the reference."""
 
     def __init__(self, drift, diffusion, *, t0, t1, num_steps, sampler_type, fused=None):
         assert t0 < t1, "SDE sampler has to be in forward time"
@@ -304,16 +318,19 @@ class sde:
         diff = diff if th.is_tensor(diff) else th.tensor(float(diff), dtype=th.float32)
         return float(rar), float(var), float(diff), float(th.sqrt(2 * diff))
 
+    def _fused_ok(self, x):
+        return FUSED_STATE_UPDATE and self.fused is not None and x.is_cuda and x.dtype == th.float32
+
     def _euler_maruyama_step(self, x, mean_x, t, model, **model_kwargs):
         w_cur = self._noise(x)
-        if FUSED_STATE_UPDATE and self.fused is not None and x.is_cuda and x.dtype == th.float32 and x.numel() % 4 == 0:
-            tv = th.full((x.size(0),), float(t), device=x.device, dtype=x.dtype)      # == th.ones(B).to(x) * t, without the blocking host copy
+        if self._fused_ok(x) and x.numel() % 4 == 0:
+            tv = _time_vector(x.size(0), t, x)
             v = model(x, tv, **model_kwargs)
             assert v.shape == x.shape, "Output shape from ODE solver must match input shape"
             rar, var, diff, sq2d = self._coeffs(t)
             return ops.sde_euler_step(x.contiguous(), v.contiguous(), w_cur, rar, var, diff, float(self.dt), sq2d, float(th.sqrt(self.dt)),
                                       need_mean=True)
-        t = th.ones(x.size(0)).to(x) * t
+        t = _time_vector(x.size(0), t, x)
         dw = w_cur * th.sqrt(self.dt)
         drift = self.drift(x, t, model, **model_kwargs)
         diffusion = self.diffusion(x, t)
@@ -322,8 +339,20 @@ class sde:
 
     def _heun_step(self, x, _, t, model, **model_kwargs):
         w_cur = self._noise(x)
+        if self._fused_ok(x):
+            # three passes around the two evaluations; the corrector's coefficients and its time vector at the f32 sum t + dt, as `t_cur + self.dt` holds it
+            n, t2 = x.size(0), t + self.dt
+            rar, var, diff, sq2d = self._coeffs(t)
+            rar2, var2, diff2, _ = self._coeffs(t2)
+            xhat = ops.sde_heun_perturb(x.contiguous(), w_cur, sq2d, float(th.sqrt(self.dt)))
+            v1 = model(xhat, _time_vector(n, t, x), **model_kwargs)
+            assert v1.shape == x.shape, "Output shape from ODE solver must match input shape"
+            k1, xp = ops.sde_heun_predict(xhat, v1.contiguous(), rar, var, diff, float(self.dt))      # v1 is consumed here: a graphed model reuses its output buffer
+            v2 = model(xp, _time_vector(n, t2, x), **model_kwargs)
+            assert v2.shape == x.shape, "Output shape from ODE solver must match input shape"
+            return ops.sde_heun_correct(xhat, xp, k1, v2.contiguous(), rar2, var2, diff2, float(0.5 * self.dt)), xhat
         dw = w_cur * th.sqrt(self.dt)
-        t_cur = th.ones(x.size(0)).to(x) * t
+        t_cur = _time_vector(x.size(0), t, x)
         diffusion = self.diffusion(x, t_cur)
         xhat = x + th.sqrt(2 * diffusion) * dw
         k1 = self.drift(xhat, t_cur, model, **model_kwargs)
@@ -643,7 +672,7 @@ class ode:
 
         def fn(t, x):
             n = x[0].size(0) if isinstance(x, tuple) else x.size(0)
-            return self.drift(x, th.ones(n).to(device) * t, model, **model_kwargs)
+            return self.drift(x, _time_vector(n, t, device=device), model, **model_kwargs)
 
         t = self.t.to(device)
         if self.sampler_type not in _FIXED_GRID:
@@ -663,7 +692,7 @@ class ode:
 
             def fn(t, y):
                 out = th.empty_like(y)
-                fn_into(th.ones(batch).to(device) * t, y, out)
+                fn_into(_time_vector(batch, t, device=device), y, out)
                 return out
         out = [x]
         with th.no_grad():
@@ -707,15 +736,18 @@ class Sampler:
 
         return sde_drift, diffusion_fn
 
-    def _last_step(self, sde_drift, *, last_step, last_step_size, fused=None):
+    def _last_step(self, sde_drift, *, last_step, last_step_size, t1, fused=None):
+        """transport.py:275-295.  `t1`: the last step's time as the host knows it; the kernel routes form their coefficients from it, not from the `t` they are
+        called with -- reading that back waits for the model evaluation queued before it and leaves the device idle until the kernel is launched."""
         ps = self.transport.path_sampler
+        te = th.tensor([t1], dtype=th.float32).view(1, 1)      # the value `th.ones(n, device=...) * t1` holds
         if last_step is None:
             return lambda x, t, model, **kw: x
+        on_kernel = lambda x: FUSED_STATE_UPDATE and fused is not None and x.is_cuda and x.dtype == th.float32
         if last_step == "Mean":
             def mean_step(x, t, model, **kw):
-                if FUSED_STATE_UPDATE and fused is not None and x.is_cuda and x.dtype == th.float32 and x.numel() % 4 == 0:
+                if on_kernel(x) and x.numel() % 4 == 0:
                     v = self.drift(x, t, model, **kw)
-                    te = t[:1].float().cpu().view(1, 1)
                     rar, var = ps._score_coeffs(te)
                     diff = float(ps.compute_diffusion(te, te.view(1), form=fused[1], norm=fused[2]))
                     return ops.sde_euler_step(x.contiguous(), v.contiguous(), None, float(rar), float(var), diff, float(last_step_size), 0.0, 0.0)[0]
@@ -723,9 +755,22 @@ class Sampler:
             return mean_step
         if last_step == "Tweedie":
             alpha, sigma = ps.compute_alpha_t, ps.compute_sigma_t
-            return lambda x, t, model, **kw: x / alpha(t)[0][0] + (sigma(t)[0][0] ** 2) / alpha(t)[0][0] * self.score(x, t, model, **kw)
+
+            def tweedie_step(x, t, model, **kw):
+                if on_kernel(x):
+                    v = self.drift(x, t, model, **kw)
+                    rar, var = ps._score_coeffs(te)
+                    a = alpha(te)[0]
+                    return ops.sde_last_step(x.contiguous(), v.contiguous(), ops.LAST_STEP_TWEEDIE, a=float(a), c=float((sigma(te)[0] ** 2) / a), rar=float(rar),
+                                             var=float(var))
+                return x / alpha(t)[0][0] + (sigma(t)[0][0] ** 2) / alpha(t)[0][0] * self.score(x, t, model, **kw)
+            return tweedie_step
         if last_step == "Euler":
-            return lambda x, t, model, **kw: x + self.drift(x, t, model, **kw) * last_step_size
+            def euler_step(x, t, model, **kw):
+                if on_kernel(x):
+                    return ops.sde_last_step(x.contiguous(), self.drift(x, t, model, **kw).contiguous(), ops.LAST_STEP_EULER, h=float(last_step_size))
+                return x + self.drift(x, t, model, **kw) * last_step_size
+            return euler_step
         raise NotImplementedError()
 
     def sample_sde(self, *, sampling_method="Euler", diffusion_form="SBDM", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04, num_steps=250):
@@ -737,7 +782,7 @@ class Sampler:
                                                reverse=False, last_step_size=last_step_size)
         fused = (self.transport.path_sampler, diffusion_form, diffusion_norm) if self.transport.model_type == ModelType.VELOCITY else None
         _sde = sde(sde_drift, sde_diffusion, t0=t0, t1=t1, num_steps=num_steps, sampler_type=sampling_method, fused=fused)
-        last_step_fn = self._last_step(sde_drift, last_step=last_step, last_step_size=last_step_size, fused=fused)
+        last_step_fn = self._last_step(sde_drift, last_step=last_step, last_step_size=last_step_size, t1=t1, fused=fused)
 
         def _sample(init, model, **model_kwargs):
             xs = _sde.sample(init, model, **model_kwargs)

@@ -728,6 +728,33 @@ int dmvae_ode_hutchinson_pack(const void* v, int v_is_bf16, const void* g, const
  * f32, g = bf16(uncond + m) --; an f32 output keeps the three f32 operations apart (no FMA): bit-identical to the PyTorch-CPU result in either type. */
 int dmvae_cfg_combine(const void* out2n, int is_bf16, void* dst, int n, int channels, size_t hw, int k, float scale, const void* t_or_null,
                       float interval_start, dmvae_stream_t stream);
+/* The Heun step of the SDE sampler (sde.__Heun_step, diffusion/transport/integrators.py:37-48, with the drift of transport.py:253-256 and the velocity -> score
+ * conversion of path.py:74-89 folded in), three passes around its two model evaluations.  As in dmvae_sde_euler_step every t-dependent coefficient is the f32
+ * scalar the reference's graph holds, operation order and rounding are the reference's (no FMA contraction, IEEE divide), v1 / v2 are bf16 (v_is_bf16 != 0) or
+ * f32 and every other array is [n] f32; any n (quads when every pointer is aligned for them, a scalar tail otherwise).
+ *   perturb:  xhat = x + sqrt_2diff * (w * sqrt_dt)
+ *   predict:  k1 = v1 + diff * ((rar * v1 - xhat) / var);  xp = xhat + dt * k1                      (coefficients at t)
+ *   correct:  k2 = v2 + diff2 * ((rar2 * v2 - xp) / var2);  x_out = xhat + half_dt * (k1 + k2)       (coefficients at the f32 sum t + dt; half_dt = f32(0.5 * dt)) */
+int dmvae_sde_heun_perturb(const void* x, const void* w, void* xhat, size_t n, float sqrt_2diff, float sqrt_dt, dmvae_stream_t stream);
+int dmvae_sde_heun_predict(const void* xhat, const void* v1, int v_is_bf16, void* k1, void* xp, size_t n, float rar, float var, float diff, float dt,
+                           dmvae_stream_t stream);
+int dmvae_sde_heun_correct(const void* xhat, const void* xp, const void* k1, const void* v2, int v_is_bf16, void* x_out, size_t n, float rar2, float var2,
+                           float diff2, float half_dt, dmvae_stream_t stream);
+/* The "Tweedie" and "Euler" last steps of Sampler.__get_last_step (diffusion/transport/transport.py:279-288) in one pass; x, out [n] f32, v bf16 or f32, any n.
+ *   DMVAE_LAST_STEP_TWEEDIE:  out = x / a + c * ((rar * v - x) / var)      a = alpha(t1), c = sigma(t1)^2 / a, formed by the host in f32
+ *   DMVAE_LAST_STEP_EULER:    out = x + (v * h)                            h = last_step_size; a bf16 v keeps the product in bf16 (tensor * Python float)
+ * Rounding sites are the reference's: bit-identical to the PyTorch-CPU result for the same v. */
+#define DMVAE_LAST_STEP_TWEEDIE 0
+#define DMVAE_LAST_STEP_EULER 1
+int dmvae_sde_last_step(const void* x, const void* v, int v_is_bf16, void* out, size_t n, int mode, float a, float c, float rar, float var, float h,
+                        dmvae_stream_t stream);
+/* Autoguidance on two model outputs (LightningDiT.forward_with_autoguidance, diffusion/lightningdit/lightningdit.py:450-465), one launch: eps [n, c_eps, hw] is
+ * this model's output and ag [n, c_ag, hw] the additional model's, both bf16 (is_bf16 != 0) or both f32; dst [2n, k, hw] of the same type, neither eps nor ag,
+ * receives in BOTH halves the first k channels (k = in_channels; 0 < k <= c_eps, c_ag) of
+ *   g = ag + scale * (eps - ag)   where lo <= ((const float*)t)[0] <= hi (compared on the device; t must not be NULL),   eps itself elsewhere.
+ * Rounding as dmvae_cfg_combine: a bf16 output rounds after each of the three ops, an f32 output keeps them apart (no FMA). */
+int dmvae_autoguidance_combine(const void* eps, int c_eps, const void* ag, int c_ag, int is_bf16, void* dst, int n, size_t hw, int k, float scale, const void* t,
+                               float lo, float hi, dmvae_stream_t stream);
 
 /* ---- fp32 parity mode (DMVAE_PARITY=1; csrc/parity.hip) ---------------------------------------------------------------------------
  * north_star: "match the reference PyTorch-CPU path within 1e-4 relative fp32".  In this mode activations are f32 NHWC and every
