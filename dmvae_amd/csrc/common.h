@@ -85,6 +85,21 @@ __device__ __forceinline__ s16x4 tr_read_ordered(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
+// LDS images of the fused attention kernels' K and V tiles (vit.hip: a whole head resident; attention_stream.hip: 64-key tiles), byte offset of 16-B chunk c of
+// row `key`.  ROW: bytes per row, 128 (head dim 64) or 256 (96).
+// K is read row-wise by ds_read_b128, which is served in four groups of sixteen lanes that are NOT consecutive ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... --
+// MI355X_MICROARCH.md, LDS table), each lane reading key (lane & 31)'s chunk: the sixteen slots of a group must be distinct mod 256 B.  256-B rows: XOR with
+// key & 15 (sixteen distinct values in every group).  128-B rows (two keys per 256 B): XOR with (key >> 1) & 7 -- eight values, each met by one even and one odd key
+// of the group.  (XOR with key & 7, which every group holds twice, was a 2-way conflict on every K read: SQ_LDS_BANK_CONFLICT 37 % of the LDS cycles.)
+template <int ROW>
+__device__ __forceinline__ int att_kslot(int key, int c) { return key * ROW + ((c ^ (ROW == 128 ? (key >> 1) & 7 : key & 15)) << 4); }
+// V is read by ds_read_b64_tr_b16: channel chunk c (8 channels) -> 64-B segment c >> 2, swizzled per key; 16-B slot c & 3 inside it.  128-B rows: two segments swizzled
+// by (key >> 1) & 1 -- the four key rows a transpose-read pass touches then sit in four distinct 64-B bank slots of the 256-B LDS row; 256-B rows: four, by key & 3.
+template <int ROW>
+__device__ __forceinline__ int att_vslot(int key, int c) {
+  return ROW == 128 ? key * 128 + ((((c >> 2) ^ ((key >> 1) & 1))) << 6) + ((c & 3) << 4) : key * 256 + ((((c >> 2) ^ (key & 3))) << 6) + ((c & 3) << 4);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -53,13 +53,13 @@ def frozen_forward_features(vit, x: torch.Tensor) -> torch.Tensor:
         # the PARAMETERS go to `linear`, not their bf16 copies: it serves a frozen one from the K-tile-major pack and one that an optimiser of this build
         # owns (DMDTrainer's encoder between its VAE turns: vae.encode under no_grad) from the live bf16 shadow that optimiser maintains
         qkv = linear(hn, blk.attn.qkv.weight, blk.attn.qkv.bias)                       # [b, s, 3*c] = [b, s, 3, heads, hd]
-        if hd == 64 and s <= 288:
-            o = ops.attention_qkv(qkv, nh, hd ** -0.5)                             # fused: nothing of size s x s reaches HBM
+        if hd == 64:
+            o = ops.attention_qkv(qkv, nh, hd ** -0.5)                             # fused at any s (resident K / V up to 288 tokens, streamed beyond): nothing s x s in HBM
         else:
-            # head dims / sequence lengths the fused kernel does not take (hip_path_supported keeps the reference's shapes off this branch): library batched
-            # GEMMs, only behind the explicit opt-in
+            # head dims the fused kernels do not take (hip_path_supported keeps the reference's shapes off this branch): library batched GEMMs, only behind
+            # the explicit opt-in
             from .._stock import require_opt_in
-            require_opt_in("vit_fast.forward_features (attention)", f"head dim {hd}, {s} tokens: the fused attention kernel takes head dim 64 and <= 288 tokens")
+            require_opt_in("vit_fast.forward_features (attention)", f"head dim {hd}: the fused attention kernels take head dim 64")
             qkv = qkv.reshape(b, s, 3, nh, hd).permute(2, 0, 3, 1, 4)
             att = ops.softmax_rows_bf16(qkv[0] @ qkv[1].transpose(-2, -1), hd ** -0.5)   # scale, f32 softmax and the casts in one pass
             o = (att @ qkv[2]).transpose(1, 2).reshape(b, s, c)
@@ -75,10 +75,12 @@ def frozen_forward_features(vit, x: torch.Tensor) -> torch.Tensor:
 
 def hip_path_supported(vit, seq_len: int) -> bool:
     """Shapes the encoder kernels cover: width 256 / 512 / 768 / 1024 / 1280 / 1536 (LayerNorm kernels; ViT-B = 768 and ViT-L = 1024 are the
-    reference's two sizes, models/vae.py:41-48), head dim 64, at most 288 tokens (fused attention)."""
+    reference's two sizes, models/vae.py:41-48) and head dim 64 (fused attention), at any token count: up to 288 tokens the attention kernel keeps a head's K / V
+    resident in LDS, beyond that (patch 8, 384 px: models/vae.py:38-50) it streams them (csrc/attention_stream.hip).  `seq_len` stays in the signature for the
+    callers; with gradients the attention backward above 288 tokens is the composed one (`functional._attention_bwd`: S x S f32 scratch per (sample, head))."""
     c = vit.embed_dim
     nh = vit.blocks[0].attn.num_heads
-    return c in (256, 512, 768, 1024, 1280, 1536) and c // nh == 64 and seq_len <= 288
+    return c in (256, 512, 768, 1024, 1280, 1536) and c // nh == 64
 
 
 NOGRAD_FUSED = True      # trainable_forward_features under no_grad takes the frozen route's fused kernels (False: the block Functions' forward; tests compare)

@@ -1038,15 +1038,34 @@ def softmax_rows_bf16(s: torch.Tensor, scale: float) -> torch.Tensor:
     return p
 
 
+ATTENTION_RESIDENT_MAX = 288      # tokens the resident fused attention kernels (csrc/vit.hip, attention_bwd.hip) hold in LDS
+
+
 def attention_qkv(qkv: torch.Tensor, heads: int, scale: float, need_lse: bool = False):
     """Fused multi-head self-attention on the qkv Linear's output [B, S, 3*heads*64] (bf16) -> [B, S, heads*64]; with need_lse also the row statistics
-    lse [B*heads, S] f32 (scale * max + log(sum) per query) for `attention_bwd_qkv`."""
+    lse [B*heads, S] f32 (scale * max + log(sum) per query) for `attention_bwd_qkv`.  Up to 288 tokens the kernel that keeps a head's K / V resident in LDS
+    (csrc/vit.hip), beyond that the streaming-softmax kernel (`attention_qkv_stream`): any S."""
+    qkv = _req(qkv, bf16, "qkv")
+    b, s, c3 = qkv.shape
+    if s > ATTENTION_RESIDENT_MAX:
+        return attention_qkv_stream(qkv, heads, scale, need_lse)
+    c = c3 // 3
+    out = torch.empty(b, s, c, dtype=bf16, device=qkv.device)
+    lse = torch.empty(b * heads, s, dtype=f32, device=qkv.device) if need_lse else None
+    check(_lib.lib().dmvae_attention_qkv_lse_bf16(qkv.data_ptr(), out.data_ptr(), _ptr(lse), b, s, heads, c // heads, float(scale), _stream()), "attention_qkv_bf16")
+    return (out, lse) if need_lse else out
+
+
+def attention_qkv_stream(qkv: torch.Tensor, heads: int, scale: float, need_lse: bool = False):
+    """`attention_qkv`'s operands and results at any token count S >= 1, on the kernel that streams 64-key K / V tiles through LDS with an online softmax
+    (csrc/attention_stream.hip; head dim 64): nothing of size S x S reaches HBM, reruns and batch splits are bit-identical."""
     qkv = _req(qkv, bf16, "qkv")
     b, s, c3 = qkv.shape
     c = c3 // 3
     out = torch.empty(b, s, c, dtype=bf16, device=qkv.device)
     lse = torch.empty(b * heads, s, dtype=f32, device=qkv.device) if need_lse else None
-    check(_lib.lib().dmvae_attention_qkv_lse_bf16(qkv.data_ptr(), out.data_ptr(), _ptr(lse), b, s, heads, c // heads, float(scale), _stream()), "attention_qkv_bf16")
+    check(_lib.lib().dmvae_attention_qkv_stream_bf16(qkv.data_ptr(), out.data_ptr(), _ptr(lse), b, s, heads, c // heads, float(scale), _stream()),
+          "attention_qkv_stream_bf16")
     return (out, lse) if need_lse else out
 
 

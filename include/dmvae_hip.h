@@ -419,6 +419,12 @@ int dmvae_softmax_rows_bf16(const void* s, void* p, size_t rows, int cols, float
 int dmvae_attention_qkv_lse_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, dmvae_stream_t stream);
 int dmvae_attention_heads_lse_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
                                    int head_dim_padded, float scale, dmvae_stream_t stream);
+/* The encoder's multi-head self-attention at ANY token count: _qkv's operands and results (qkv [batch][seq][3][heads][64] bf16 -> out [batch][seq][heads*64] bf16,
+ * lse f32 [batch * heads][seq] = scale * max_k(q.k) + log(sum_k exp(scale (q.k - max))), natural log, or NULL), computed by a kernel that streams 64-key K / V tiles
+ * through LDS with an online softmax (csrc/attention_stream.hip) instead of keeping a head resident: nothing of size seq x seq reaches HBM, reruns and batch splits
+ * are bit-identical.  The shapes beyond _qkv's 288 tokens: patch_size 8 at 256 px = 1025 tokens, 384 px at patch 16 = 577.  Any seq >= 1, head_dim 64, scale > 0;
+ * everything else is rejected before any HIP call.  Reference: models/dino_layers/attention.py:56-69 with patch_size / img_size passed through models/vae.py:38-50. */
+int dmvae_attention_qkv_stream_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, dmvae_stream_t stream);
 /* The whole attention of a LightningDiT block from the qkv Linear's output [batch][seq][3][heads][head_dim] bf16: per-head RMSNorm (bf16 result) * weight
  * and the 2-D rotary embedding (the arithmetic of dmvae_qknorm_rope_bf16; cos / sin tables [seq][head_dim] f32) are applied to q and k as they enter the
  * fused kernel -> out [batch][seq][heads*head_dim].  lightningdit.py:66-88 in one launch, no head-major q / k / v in HBM.  head_dim % 8 == 0, <= 96; seq <= 288. */

@@ -1,0 +1,50 @@
+"""CPU: the streaming attention entry (csrc/attention_stream.hip) is exported and bound, and validates its arguments before any HIP call --
+errno-style code plus a message, no GPU touched.  The entry is additive: the ABI version does not move."""
+import ctypes
+import os
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from dmvae_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        subprocess.run(["make", "-C", os.path.join(ROOT, "dmvae_amd", "csrc"), "-j8"], check=True)
+    return _lib.lib()
+
+
+def test_stream_entry_is_exported_and_bound(lib):
+    from dmvae_amd import _lib
+    assert "dmvae_attention_qkv_stream_bf16" in _lib.SIGNATURES
+    assert hasattr(lib, "dmvae_attention_qkv_stream_bf16")
+    assert _lib.SIGNATURES["dmvae_attention_qkv_stream_bf16"] == _lib.SIGNATURES["dmvae_attention_qkv_lse_bf16"]      # same operands as the resident entry
+    assert lib.dmvae_abi_version() == 9
+
+
+def test_stream_entry_rejects_bad_arguments_without_gpu(lib):
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    f = lib.dmvae_attention_qkv_stream_bf16
+    scale = 64 ** -0.5
+
+    def rejected(*args):
+        rc = f(*args)
+        msg = lib.dmvae_last_error()
+        assert rc != 0 and b"attention_qkv_stream_bf16" in msg, (rc, msg)
+        return msg
+
+    assert b"head_dim 64" in rejected(p, p, None, 1, 300, 2, 72, scale, None)       # head_dim 72
+    assert b"seq" in rejected(p, p, None, 1, 0, 2, 64, scale, None)                # seq 0
+    rejected(p, p, None, 1, -5, 2, 64, scale, None)
+    assert b"null" in rejected(None, p, None, 1, 300, 2, 64, scale, None)          # null qkv
+    assert b"null" in rejected(p, None, None, 1, 300, 2, 64, scale, None)          # null out
+    rejected(p, p, None, 0, 300, 2, 64, scale, None)                               # empty batch
+    rejected(p, p, None, 1, 300, 0, 64, scale, None)                               # no heads
+    rejected(p, p, None, 1, 300, 2, 64, 0.0, None)                                 # the row maximum is taken on the raw scores: scale > 0
+    rejected(p, p, None, 1, 300, 2, 64, float("nan"), None)
+    rejected(p, p, None, 1 << 20, 1 << 20, 1 << 10, 64, scale, None)               # more workgroups than a grid dimension holds
+    assert lib.dmvae_abi_version() == 9

@@ -1,6 +1,12 @@
 """Attention kernels at the shapes of the DMD / diffusion stages: LightningDiT-XL/1 heads (16 x 72 channels, 256 tokens, q / k padded to 96) at B = 16 / 64 and
 ViT-L/16's packed qkv (16 x 64, 257 tokens) at B = 16 / 32: forward (+ row statistics) and the backward on those statistics, us per call and the algorithmic
-bytes (every operand once, every result once) over that time."""
+bytes (every operand once, every result once) over that time.
+
+Streaming section (`--stream-only` runs it alone, `--out FILE` also writes its table to FILE): the encoder's attention beyond the resident kernel's 288 tokens
+(csrc/attention_stream.hip) at S = 577 and 1025, B x H = 32 x 16, random data, against the same attention composed from this build's own ops (f32-score GEMM +
+row softmax + GEMM on head-major copies, keys padded to a multiple of 32 and masked) and the resident kernel at S = 288 for scale; rounds interleaved in one
+process, median and minimum; 4 S^2 64 FLOP per head.  Then the frozen ViT-L forward at 1025 tokens (patch 8 at 256 px), B = 8: the HIP route against the stock
+modules under autocast(bf16) -- the only way to run that shape before the streaming kernel."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -22,7 +28,7 @@ def timed(fn, n=50):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-for B in (16, 32, 64):
+for B in (() if "--stream-only" in sys.argv else (16, 32, 64)):
     H, N, D, DP = 16, 256, 72, 96
     q = torch.zeros(B * H, N, DP, device="cuda", dtype=BF); k = torch.zeros_like(q)
     q[..., :D] = torch.randn(B * H, N, D, device="cuda", generator=g).to(BF); k[..., :D] = torch.randn(B * H, N, D, device="cuda", generator=g).to(BF)
@@ -36,7 +42,7 @@ for B in (16, 32, 64):
     bb = (4 * q.numel() + 2 * v.numel() + 2 * out.numel()) * 2 + lse.numel() * 4
     fl = 4 * B * H * N * N * D
     print(f"DiT heads B={B:3d}: fwd+lse {tf:6.1f} us ({fb / tf * 1e-6:5.2f} TB/s, {fl / tf * 1e-6:5.0f} TF/s)   bwd lse {tb:6.1f} us ({bb / tb * 1e-6:5.2f} TB/s, {2.5 * fl / tb * 1e-6:5.0f} TF/s)")
-for B in (16, 32):
+for B in (() if "--stream-only" in sys.argv else (16, 32)):
     H, N, D = 16, 257, 64
     qkv = torch.randn(B, N, 3 * H * D, device="cuda", generator=g).to(BF)
     scale = D ** -0.5
@@ -48,3 +54,68 @@ for B in (16, 32):
     bb = (2 * qkv.numel() + 2 * out.numel()) * 2 + lse.numel() * 4
     fl = 4 * B * H * N * N * D
     print(f"ViT qkv   B={B:3d}: fwd+lse {tf:6.1f} us ({fb / tf * 1e-6:5.2f} TB/s, {fl / tf * 1e-6:5.0f} TF/s)   bwd lse {tb:6.1f} us ({bb / tb * 1e-6:5.2f} TB/s, {2.5 * fl / tb * 1e-6:5.0f} TF/s)")
+
+
+# ---- streaming kernel beyond 288 tokens ------------------------------------------------------------------------------------------------------------------
+def composed(q, k, v, s, scale):
+    """q, k, v: head-major [B*H, sp, 64] bf16 (rows >= s zero) -> [B*H, sp, 64]: what `functional._attention_bwd` / `lightningdit_fast._attention` compose"""
+    sc = ops.gemm_nt(q, k, out_f32=True)
+    if sc.shape[-1] != s:
+        sc[:, :, s:] = float("-inf")
+    return ops.gemm_nt(ops.softmax_rows(sc, scale), ops.transpose_last2(v))
+
+
+def stream_section(out_path):
+    B, H, D, scale = 32, 16, 64, 64 ** -0.5
+    cases = {}
+    for S in (288, 577, 1025):
+        qkv = torch.randn(B, S, 3 * H * D, device="cuda", generator=g).to(BF)
+        if S <= 288:
+            cases[f"resident kernel      S={S:4d}"] = (S, lambda qkv=qkv: ops.attention_qkv(qkv, H, scale, need_lse=True))
+            cases[f"streaming kernel     S={S:4d}"] = (S, lambda qkv=qkv: ops.attention_qkv_stream(qkv, H, scale, need_lse=True))
+            continue
+        sp = (S + 31) // 32 * 32
+        hm = torch.zeros(3, B * H, sp, D, device="cuda", dtype=BF)
+        hm[:, :, :S] = qkv.view(B, S, 3, H, D).permute(2, 0, 3, 1, 4).reshape(3, B * H, S, D)
+        a = ops.attention_qkv_stream(qkv, H, scale).view(B, S, H, D).permute(0, 2, 1, 3).reshape(B * H, S, D).float()
+        c = composed(hm[0], hm[1], hm[2], S, scale)[:, :S].float()
+        print(f"S={S}: streaming vs composed rel-L2 {((a - c).norm() / c.norm()).item():.2e}")
+        cases[f"streaming kernel     S={S:4d}"] = (S, lambda qkv=qkv: ops.attention_qkv_stream(qkv, H, scale, need_lse=True))
+        cases[f"streaming, no lse    S={S:4d}"] = (S, lambda qkv=qkv: ops.attention_qkv_stream(qkv, H, scale))
+        cases[f"composed (own ops)   S={S:4d}"] = (S, lambda hm=hm, S=S: composed(hm[0], hm[1], hm[2], S, scale))
+    times = {k: [] for k in cases}
+    for _ in range(7):                      # interleaved rounds
+        for k, (S, fn) in cases.items():
+            times[k].append(timed(fn, n=20))
+    lines = [f"attention forward, B x H = {B} x {H}, head dim 64, random data, 7 interleaved rounds of 20 calls; TFLOP/s on 4 S^2 64 FLOP per head",
+             f"{'case':32s} {'median us':>10s} {'min us':>10s} {'TF/s (median)':>14s} {'TF/s (min)':>11s}"]
+    for k, (S, _) in cases.items():
+        t = sorted(times[k])
+        med, mn, fl = t[len(t) // 2], t[0], 4.0 * B * H * S * S * D
+        lines.append(f"{k:32s} {med:10.1f} {mn:10.1f} {fl / med * 1e-6:14.1f} {fl / mn * 1e-6:11.1f}")
+    # frozen ViT-L forward at 1025 tokens
+    from dmvae_amd.models.vit import DinoV2ViT
+    torch.manual_seed(0)
+    vit = DinoV2ViT(embed_dim=1024, depth=24, num_heads=16, patch_size=8, img_size=256).cuda().eval()
+    img = torch.randn(8, 3, 256, 256, device="cuda", generator=g)
+    with torch.no_grad(), torch.autocast("cuda", dtype=BF):
+        routes = {"HIP route (streaming attention)": lambda: vit.forward_features(img), "stock modules (autocast bf16)": lambda: vit.forward_features_stock(img)}
+        y0, y1 = (f().float() for f in routes.values())
+        vt = {k: [] for k in routes}
+        for _ in range(5):
+            for k, fn in routes.items():
+                vt[k].append(timed(fn, n=5) * 1e-3)
+    lines.append("")
+    lines.append(f"frozen ViT-L/8 forward at 256 px (1025 tokens), B = 8, ms per call, 5 interleaved rounds of 5 calls; HIP vs stock relative norm {((y0 - y1).norm() / y1.norm()).item():.2e}")
+    for k in routes:
+        t = sorted(vt[k])
+        lines.append(f"{k:32s} median {t[len(t) // 2]:8.2f} ms   min {t[0]:8.2f} ms")
+    text = "\n".join(lines)
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
+stream_section(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
