@@ -66,28 +66,7 @@ struct LayTight {
     return v;
   }
 };
-__device__ __forceinline__ float dot8(const uint4& a, const uint4& b) {
-  const bf16x8 x = *reinterpret_cast<const bf16x8*>(&a), y = *reinterpret_cast<const bf16x8*>(&b);
-  float s = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; e++) s += (float)x[e] * (float)y[e];
-  return s;
-}
-// C-layout registers of a 32 x 32 block (row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31), 16 of them scaled to bf16 -> the two A fragments
-// (reduction index = the block's ROW, 8 consecutive per lane) of its two 16-row halves
-__device__ __forceinline__ void to_afrag(const f32x16& c, bf16x8 out[2]) {
-#pragma unroll
-  for (int half = 0; half < 2; half++) {
-    const unsigned p0 = dmvae_pack_bf16x2(c[half * 8 + 0], c[half * 8 + 1]), p1 = dmvae_pack_bf16x2(c[half * 8 + 2], c[half * 8 + 3]);
-    const unsigned p2 = dmvae_pack_bf16x2(c[half * 8 + 4], c[half * 8 + 5]), p3 = dmvae_pack_bf16x2(c[half * 8 + 6], c[half * 8 + 7]);
-    // lanes < 32 hold rows {0-3, 8-11} of the half, lanes >= 32 rows {4-7, 12-15}: the fragment wants {0-7} / {8-15}
-    const auto s0 = __builtin_amdgcn_permlane32_swap(p0, p2, false, false);
-    const auto s1 = __builtin_amdgcn_permlane32_swap(p1, p3, false, false);
-    union { unsigned u[4]; bf16x8 v; } pa;
-    pa.u[0] = s0[0]; pa.u[1] = s1[0]; pa.u[2] = s0[1]; pa.u[3] = s1[1];
-    out[half] = pa.v;
-  }
-}
+// dot8 and to_afrag (the C-layout -> A-fragment conversion by v_permlane32_swap): common.h, shared with attention_bwd_stream.hip
 
 template <int DP>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(Args a) {

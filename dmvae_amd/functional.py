@@ -1079,8 +1079,8 @@ class VitBlockFn(torch.autograd.Function):
         hn1 = ops.layernorm_bf16(t, n1w, n1b, eps)
         qkv = linear(hn1, qkvw, qkvb)
         lse = None
-        if hd == 64 and s <= 288 and any(ctx.needs_input_grad):
-            o, lse = ops.attention_qkv(qkv, heads, hd ** -0.5, need_lse=True)      # + the row statistics the backward kernel rebuilds P from
+        if hd == 64 and any(ctx.needs_input_grad):
+            o, lse = ops.attention_qkv(qkv, heads, hd ** -0.5, need_lse=True)      # + the row statistics the backward kernels rebuild P from (any S)
         else:
             o = ops.attention_qkv(qkv, heads, hd ** -0.5)
         o2 = linear(o, pw, pb)
@@ -1115,9 +1115,9 @@ class VitBlockFn(torch.autograd.Function):
         # attention branch
         do2, dls1 = ops.layerscale_bwd(dt, o2, ls1, dg_out=_dst(ls1))
         do, dpw, dpb = _lin_grads(do2.view(rows, c), o.view(rows, c), pw, pb, defer=pend)
-        if c // heads == 64 and s <= 288:
-            dqkv = ops.attention_bwd_qkv(qkv, o, do.view(b, s, c), heads, (c // heads) ** -0.5, lse=ctx.lse)      # one kernel, nothing S x S in HBM
-        else:
+        if c // heads == 64:
+            dqkv = ops.attention_bwd_qkv(qkv, o, do.view(b, s, c), heads, (c // heads) ** -0.5, lse=ctx.lse)      # resident or streaming kernels: nothing S x S in HBM
+        else:      # other head dims: the GEMM-composed route
             dqkv = _attention_bwd(qkv, do.view(b, s, c), heads, (c // heads) ** -0.5)
         dhn1, dqkvw, dqkvb = _lin_grads(dqkv.view(rows, 3 * c), hn1.view(rows, c), qkvw, qkvb, defer=pend)
         dn1w, dn1b = ops.layernorm_bwd_(dt, dhn1.view(b, s, c), t, n1w, eps, dg_out=_dst(n1w), db_out=_dst(n1b))

@@ -77,7 +77,7 @@ def hip_path_supported(vit, seq_len: int) -> bool:
     """Shapes the encoder kernels cover: width 256 / 512 / 768 / 1024 / 1280 / 1536 (LayerNorm kernels; ViT-B = 768 and ViT-L = 1024 are the
     reference's two sizes, models/vae.py:41-48) and head dim 64 (fused attention), at any token count: up to 288 tokens the attention kernel keeps a head's K / V
     resident in LDS, beyond that (patch 8, 384 px: models/vae.py:38-50) it streams them (csrc/attention_stream.hip).  `seq_len` stays in the signature for the
-    callers; with gradients the attention backward above 288 tokens is the composed one (`functional._attention_bwd`: S x S f32 scratch per (sample, head))."""
+    callers; with gradients the attention backward above 288 tokens streams as well (csrc/attention_bwd_stream.hip): nothing S x S in HBM at any token count."""
     c = vit.embed_dim
     nh = vit.blocks[0].attn.num_heads
     return c in (256, 512, 768, 1024, 1280, 1536) and c // nh == 64

@@ -1097,16 +1097,37 @@ def attention_qknorm_rope(qkv: torch.Tensor, qw: torch.Tensor, kw: torch.Tensor,
 
 
 def attention_bwd_qkv(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, heads: int, scale: float, lse: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """d(qkv) [B,S,3*C] of `attention_qkv` from its input, its result `out` [B,S,C] and d(out) (bf16): one fused kernel (csrc/attention_bwd.hip); with the forward's
-    `lse` the eight-wave form that rebuilds the probabilities from it."""
+    """d(qkv) [B,S,3*C] of `attention_qkv` from its input, its result `out` [B,S,C] and d(out) (bf16).  Up to 288 tokens one fused kernel with a head resident in LDS
+    (csrc/attention_bwd.hip); with the forward's `lse` the eight-wave form that rebuilds the probabilities from it.  Beyond that the streaming kernels
+    (`attention_bwd_qkv_stream`), which need `lse`."""
     qkv = _req(qkv, bf16, "qkv"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
     b, s, c3 = qkv.shape
+    if s > ATTENTION_RESIDENT_MAX:
+        return attention_bwd_qkv_stream(qkv, out, dout, heads, scale, lse)
     c = c3 // 3
     assert out.shape == (b, s, c) and dout.shape == (b, s, c)
     dqkv = torch.empty_like(qkv)
     assert lse is None or (lse.dtype == f32 and lse.is_contiguous() and lse.shape == (b * heads, s))
     check(_lib.lib().dmvae_attention_bwd_qkv_lse_bf16(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), _ptr(lse), dqkv.data_ptr(), b, s, heads, c // heads, float(scale),
                                                       _stream()), "attention_bwd_qkv_bf16")
+    return dqkv
+
+
+def attention_bwd_qkv_stream(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, heads: int, scale: float, lse: Optional[torch.Tensor]) -> torch.Tensor:
+    """`attention_bwd_qkv`'s operands and result at any token count S >= 1, on the kernels that stream 64-row tiles through LDS (csrc/attention_bwd_stream.hip; head
+    dim 64): a query pass for dQ and a key pass for dK / dV.  `lse` [B*heads, S] f32 from the forward is required.  Nothing of size S x S reaches HBM -- the only
+    scratch is delta [B*heads, S] f32 -- and reruns and batch splits are bit-identical."""
+    if lse is None:
+        raise ValueError("attention_bwd_qkv_stream needs the forward's lse (attention_qkv(..., need_lse=True))")
+    qkv = _req(qkv, bf16, "qkv"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
+    b, s, c3 = qkv.shape
+    c = c3 // 3
+    assert out.shape == (b, s, c) and dout.shape == (b, s, c)
+    assert lse.dtype == f32 and lse.is_contiguous() and lse.shape == (b * heads, s)
+    dqkv = torch.empty_like(qkv)
+    delta = torch.empty(b * heads, s, dtype=f32, device=qkv.device)
+    check(_lib.lib().dmvae_attention_bwd_qkv_stream_bf16(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), b, s, heads,
+                                                         c // heads, float(scale), _stream()), "attention_bwd_qkv_stream_bf16")
     return dqkv
 
 

@@ -444,6 +444,13 @@ int dmvae_attention_bwd_qkv_lse_bf16(const void* qkv, const void* out, const voi
                                      float scale, dmvae_stream_t stream);
 int dmvae_attention_bwd_heads_lse_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq, void* dk,
                                        void* dv, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale, dmvae_stream_t stream);
+/* _bwd_qkv_lse's operands and result at ANY token count (csrc/attention_bwd_stream.hip, the backward of dmvae_attention_qkv_stream_bf16): two kernels on `stream`
+ * that walk 64-row tiles -- a query pass (dQ, and delta_q = dout_q . out_q into `delta`) and a key pass (dK, dV) -- so nothing of size seq x seq reaches HBM.
+ * lse is REQUIRED (f32 [batch * heads][seq], what either forward entry writes); delta is scratch the caller provides, batch * heads * seq floats, overwritten.
+ * Every sum has a fixed order: reruns and batch splits are bit-identical.  Any seq >= 1, head_dim 64, scale > 0; everything else, a NULL lse or delta included, is
+ * rejected before any HIP call.  Reference: autograd of models/dino_layers/attention.py:56-69 at the token counts of models/vae.py:38-50 (train_dmd.py:349,519). */
+int dmvae_attention_bwd_qkv_stream_bf16(const void* qkv, const void* out, const void* dout, const void* lse, void* dqkv, void* delta, int batch, int seq, int heads,
+                                        int head_dim, float scale, dmvae_stream_t stream);
 
 /* Backward side of the same encoder block, for the stages where the encoder trains (train_dmd.py:349,519).  Residual stream f32,
  * Linear operands / results bf16 (autocast).  workspace: dmvae_vit_bwd_workspace(c) bytes.

@@ -6,7 +6,12 @@ Streaming section (`--stream-only` runs it alone, `--out FILE` also writes its t
 (csrc/attention_stream.hip) at S = 577 and 1025, B x H = 32 x 16, random data, against the same attention composed from this build's own ops (f32-score GEMM +
 row softmax + GEMM on head-major copies, keys padded to a multiple of 32 and masked) and the resident kernel at S = 288 for scale; rounds interleaved in one
 process, median and minimum; 4 S^2 64 FLOP per head.  Then the frozen ViT-L forward at 1025 tokens (patch 8 at 256 px), B = 8: the HIP route against the stock
-modules under autocast(bf16) -- the only way to run that shape before the streaming kernel."""
+modules under autocast(bf16) -- the only way to run that shape before the streaming kernel.
+
+`--stream-bwd` runs the backward section alone (`--out FILE` writes its table): `ops.attention_bwd_qkv_stream` (csrc/attention_bwd_stream.hip) against the
+GEMM-composed `functional._attention_bwd` at S = 577 and 1025, B x H = 32 x 16, rounds interleaved in one process, median and minimum; 10 S^2 64 FLOP per head
+(the five products of the minimal form; the kernels run seven).  Then the peak allocation of one trainable ViT-L block's backward at 1025 tokens, B = 16, on
+either attention backward."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -28,7 +33,8 @@ def timed(fn, n=50):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-for B in (() if "--stream-only" in sys.argv else (16, 32, 64)):
+SECTION_ONLY = "--stream-only" in sys.argv or "--stream-bwd" in sys.argv
+for B in (() if SECTION_ONLY else (16, 32, 64)):
     H, N, D, DP = 16, 256, 72, 96
     q = torch.zeros(B * H, N, DP, device="cuda", dtype=BF); k = torch.zeros_like(q)
     q[..., :D] = torch.randn(B * H, N, D, device="cuda", generator=g).to(BF); k[..., :D] = torch.randn(B * H, N, D, device="cuda", generator=g).to(BF)
@@ -42,7 +48,7 @@ for B in (() if "--stream-only" in sys.argv else (16, 32, 64)):
     bb = (4 * q.numel() + 2 * v.numel() + 2 * out.numel()) * 2 + lse.numel() * 4
     fl = 4 * B * H * N * N * D
     print(f"DiT heads B={B:3d}: fwd+lse {tf:6.1f} us ({fb / tf * 1e-6:5.2f} TB/s, {fl / tf * 1e-6:5.0f} TF/s)   bwd lse {tb:6.1f} us ({bb / tb * 1e-6:5.2f} TB/s, {2.5 * fl / tb * 1e-6:5.0f} TF/s)")
-for B in (() if "--stream-only" in sys.argv else (16, 32)):
+for B in (() if SECTION_ONLY else (16, 32)):
     H, N, D = 16, 257, 64
     qkv = torch.randn(B, N, 3 * H * D, device="cuda", generator=g).to(BF)
     scale = D ** -0.5
@@ -118,4 +124,80 @@ def stream_section(out_path):
             f.write(text + "\n")
 
 
-stream_section(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+# ---- streaming backward beyond 288 tokens ------------------------------------------------------------------------------------------------------------------
+def stream_bwd_section(out_path):
+    from dmvae_amd import functional as Fn
+    B, H, D, scale = 32, 16, 64, 64 ** -0.5
+    cases = {}
+    lines = []
+    for S in (577, 1025):
+        qkv = torch.randn(B, S, 3 * H * D, device="cuda", generator=g).to(BF)
+        out, lse = ops.attention_qkv_stream(qkv, H, scale, need_lse=True)
+        dout = torch.randn(out.shape, device="cuda", generator=g).to(BF)
+        a, c = ops.attention_bwd_qkv_stream(qkv, out, dout, H, scale, lse).float(), Fn._attention_bwd(qkv, dout, H, scale).float()
+        lines.append(f"S={S}: streaming vs composed d(qkv) rel-L2 {((a - c).norm() / c.norm()).item():.2e}")
+        del a, c
+        cases[f"streaming kernels    S={S:4d}"] = (S, lambda qkv=qkv, out=out, dout=dout, lse=lse: ops.attention_bwd_qkv_stream(qkv, out, dout, H, scale, lse))
+        cases[f"composed (own ops)   S={S:4d}"] = (S, lambda qkv=qkv, dout=dout: Fn._attention_bwd(qkv, dout, H, scale))
+    times = {k: [] for k in cases}
+    for _ in range(7):                      # interleaved rounds
+        for k, (S, fn) in cases.items():
+            times[k].append(timed(fn, n=10))
+    lines += [f"attention backward, B x H = {B} x {H}, head dim 64, random data, 7 interleaved rounds of 10 calls; TFLOP/s on 10 S^2 64 FLOP per head",
+              f"{'case':32s} {'median us':>10s} {'min us':>10s} {'TF/s (median)':>14s} {'TF/s (min)':>11s}"]
+    med = {}
+    for k, (S, _) in cases.items():
+        t = sorted(times[k])
+        med[k], mn, fl = t[len(t) // 2], t[0], 10.0 * B * H * S * S * D
+        lines.append(f"{k:32s} {med[k]:10.1f} {mn:10.1f} {fl / med[k] * 1e-6:14.1f} {fl / mn * 1e-6:11.1f}")
+    for S in (577, 1025):
+        lines.append(f"S={S}: composed / streaming (median) = {med[f'composed (own ops)   S={S:4d}'] / med[f'streaming kernels    S={S:4d}']:.2f}")
+    del cases
+    torch.cuda.empty_cache()
+    # one trainable ViT-L block, forward + backward at 1025 tokens: peak allocation of the backward over what is allocated when it starts
+    from dmvae_amd.models.vit import DinoV2ViT
+    torch.manual_seed(0)
+    blk = DinoV2ViT(embed_dim=1024, depth=1, num_heads=16, patch_size=8, img_size=256).cuda().blocks[0]
+    Bv, S = 16, 1025
+    t0 = torch.randn(Bv, S, 1024, device="cuda", generator=g)
+    dy = torch.randn(Bv, S, 1024, device="cuda", generator=g)
+
+    def block_backward_peak():
+        t = t0.clone().requires_grad_(True)
+        y = Fn.VitBlockFn.apply(t, blk.norm1.weight, blk.norm1.bias, blk.attn.qkv.weight, blk.attn.qkv.bias, blk.attn.proj.weight, blk.attn.proj.bias, blk.ls1.gamma,
+                                blk.norm2.weight, blk.norm2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.ls2.gamma,
+                                blk.attn.num_heads, blk.norm1.eps)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        y.backward(dy)
+        torch.cuda.synchronize()
+        blk.zero_grad(set_to_none=True)
+        return (torch.cuda.max_memory_allocated() - before) / 2 ** 20
+
+    block_backward_peak()                   # first call: workspaces and parameter gradients' buffers
+    peak_stream = block_backward_peak()
+    kernel_route = ops.attention_bwd_qkv
+    ops.attention_bwd_qkv = lambda qkv, out, dout, heads, scale, lse=None: Fn._attention_bwd(qkv, dout, heads, scale)
+    try:
+        block_backward_peak()
+        peak_comp = block_backward_peak()
+    finally:
+        ops.attention_bwd_qkv = kernel_route
+    lines.append("")
+    lines.append(f"one trainable ViT-L block (VitBlockFn) at {S} tokens, B = {Bv}: peak allocation of the backward above its starting point")
+    lines.append(f"{'streaming attention backward':32s} {peak_stream:10.1f} MiB")
+    lines.append(f"{'composed attention backward':32s} {peak_comp:10.1f} MiB   (difference {peak_comp - peak_stream:.1f} MiB)")
+    text = "\n".join(lines)
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
+OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+if "--stream-bwd" in sys.argv:
+    stream_bwd_section(OUT)
+else:
+    stream_section(OUT)
