@@ -32,44 +32,84 @@
 // pass: a query >= S is staged with L = +inf and delta = 0, so p = exp(-inf) = 0 and dS = 0 exactly: it contributes nothing to dK / dV.  Queries / keys >= S of a
 // workgroup's own block compute on zero fragments and are not stored; a wave whose 32 rows are all >= S only stages and synchronises; a 32-row block of the last tile
 // that lies wholly past S is skipped.
-// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): query pass 159 VGPRs, 0 AGPRs, 44 SGPRs, no scratch, no spill,
-// 48 KiB LDS; key pass 238 VGPRs, 0 AGPRs, 48 SGPRs, no scratch, no spill, 65 KiB LDS.  Both run two waves per SIMD (one 8-wave workgroup of the key pass, LDS-bound;
-// the query pass fits three workgroups' LDS but two workgroups' registers).
+// Resources: one table for all four instantiations at the end of this header.
+//
+// Both kernels are templates on DP, the staged head dim.  DP = 64 is everything above: the encoder's entry dmvae_attention_bwd_qkv_stream_bf16, and head-major
+// operands of head dim 64.  DP = 96 is LightningDiT's head dim 72 on the head-major operands of dmvae_qknorm_rope_bf16 (q, k, dq, dk [B*H][N][72 or 96], v, dv
+// [B*H][N][72]; entry dmvae_attention_bwd_heads_stream_bf16): 256-B rows in the layouts of the 96-wide resident kernel (common.h att_kslot<256> / att_vslot<256>),
+// 16-KiB images.  The channels 72 .. 95 are zeros in LDS and never loaded, the products over channels take five 16-channel steps (upper half of the fifth zero, the
+// sixth skipped), the accumulators are three 32-channel blocks; dV columns >= 72 are not stored and the padded columns of dq / dk (rows of 96) are written as the
+// exact zeros the zero K / Q channels produce.  The operands are described by strides, q / k and v separately (head-major v rows are 72 wide, q / k rows 72 or 96).
+// The 96-wide KEY pass does not fit eight waves: two more 32-channel accumulator blocks (dK, dV: + 32 registers) and the wider fragments put it past 256 registers.
+// Choice: a FOUR-wave workgroup (one wave per SIMD, 512 registers: the accumulators go to AGPRs), 128 keys per workgroup, four staging sweeps per tile; fewer keys per
+// wave or 16-wide accumulator blocks would have kept eight waves at half the matrix work per fragment read.  Its LDS, 2 x (4 x 16 KiB + 512 B) = 129 KiB dynamic,
+// admits one workgroup per CU either way.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; no scratch and no spill in any of the four).  "Waves per SIMD" is the
+// compiler's register-limited figure; a workgroup of 8 waves puts two on each SIMD, so what is resident is whole workgroups within that figure and within LDS.
+//   DP = 64 query pass (8 waves): 161 VGPRs, 0 AGPRs, 48 SGPRs, 48 KiB static LDS; 3 waves per SIMD by registers = ONE resident workgroup per CU (a second would need
+//     4 per SIMD; LDS would admit three).  Before the operands were described by separate q / k and v strides: 159 VGPRs, 44 SGPRs, the same residency.
+//   DP = 64 key pass (8 waves): 238 VGPRs, 0 AGPRs, 54 SGPRs (before: 48), 65 KiB dynamic LDS; 2 waves per SIMD = one workgroup per CU (registers and LDS agree).
+//   DP = 96 query pass (8 waves): 216 VGPRs, 0 AGPRs, 54 SGPRs, 96 KiB dynamic LDS; 2 waves per SIMD = one workgroup per CU.
+//   DP = 96 key pass (4 waves): 234 VGPRs, 128 AGPRs, 59 SGPRs, 129 KiB dynamic LDS; 1 wave per SIMD = one workgroup per CU.
 #include "common.h"
 #include "dmvae_hip.h"
 #include <math.h>
 
 namespace dmvae_attn_bwd_stream {
 
-constexpr int D = 64;            // head dim
-constexpr int NT = 512;          // 8 waves
+constexpr int NTQ = 512;         // query pass: 8 waves
 constexpr int BW = 32;           // rows (queries / keys) a wave owns
-constexpr int BB = BW * NT / 64; // rows a workgroup owns: 256
 constexpr int TT = 64;           // rows per streamed tile
-constexpr int ROW = 128;         // bytes per row in LDS
-constexpr int TILE = TT * ROW;   // 8 KiB
-constexpr int DQ_BUF = 3 * TILE;                                    // K rows | K transposed | V rows
-constexpr int DKDV_BUF = 4 * TILE + 2 * TT * (int)sizeof(float);    // Q rows | Q transposed | dO rows | dO transposed | L [64] | delta [64]
+// DP: head dim as staged.  64: head dim 64, 128-B rows in LDS.  96: head dim 72 (LightningDiT-XL), 256-B rows -- common.h's layouts of the 96-wide resident kernel;
+// the channels 72 .. 95 are zeros in LDS (never loaded), the sixth 16-channel step of the products over channels is skipped, the upper half of the fifth is zero,
+// dV columns >= 72 and dQ / dK columns past the row width are not stored.  NT: threads of the workgroup (the key pass at 96 runs four waves: file header).
+template <int DP, int NT = NTQ> struct Geo {
+  static_assert(DP == 64 || DP == 96, "staged head dim 64 or 96");
+  static constexpr int D = DP == 64 ? 64 : 72;      // real head dim: v / out / dout width, the channels of a q / k row that are read
+  static constexpr int ROW = DP == 64 ? 128 : 256;  // bytes per row in LDS
+  static constexpr int TILE = TT * ROW;             // 8 / 16 KiB
+  static constexpr int KS = DP == 64 ? 4 : 5;       // 16-channel steps of the products over channels
+  static constexpr int DB = DP / 32;                // 32-channel blocks of the accumulators
+  static constexpr int CPR = ROW / 16;              // staging lanes per row: one 16-B chunk each
+  static constexpr int SW = TT * CPR / NT;          // staging sweeps per tile
+  static constexpr int BB = BW * NT / 64;           // rows a workgroup owns
+  static constexpr int DQ_BUF = 3 * TILE;                                    // K rows | K transposed | V rows
+  static constexpr int DKDV_BUF = 4 * TILE + 2 * TT * (int)sizeof(float);    // Q rows | Q transposed | dO rows | dO transposed | L [64] | delta [64]
+};
 
 struct Args {
-  const bf16 *q, *k, *v;     // qkv, qkv + C, qkv + 2 C: per (sample, head) base + b * bs + h * 64, token rows rs elements apart
-  const bf16 *o, *dout;      // [B][S][C]
-  bf16 *dq, *dk, *dv;        // dqkv in the same geometry
+  const bf16 *q, *k, *v;     // per (sample, head) base + b * bs + h * hs, token rows rs elements apart: q and k share one geometry (qk_*), v has its own (v_*)
+  const bf16 *o, *dout;      // [B][S][H * D]
+  bf16 *dq, *dk, *dv;        // dq, dk in q's geometry, dv in v's
   const float* lse;          // [B * H][S]
   float* delta;              // [B * H][S]: written by the query pass, read by the key pass
-  long long bs;              // elements between samples: S * 3 C
-  int rs;                    // 3 C
+  long long qk_bs, qk_hs, v_bs, v_hs;      // elements
+  int qk_rs, v_rs;           // elements between token rows; at DP = 96 qk_rs is also the width of a q / k / dq / dk row (72 or 96)
   int S, H;
-  int nb;                    // 256-row blocks per (sample, head)
+  int nb;                    // row blocks per (sample, head) of the kernel being launched
   float scale;
 };
 
+// the query pass' images: static up to 64 KiB (the 64-wide form, as before), the launch's dynamic LDS beyond
+template <int BYTES>
+__device__ __forceinline__ char* dq_image() {
+  if constexpr (BYTES <= 65536) {
+    __shared__ __attribute__((aligned(256))) char img[BYTES];
+    return img;
+  } else {
+    extern __shared__ __attribute__((aligned(256))) char dyn[];
+    return dyn;
+  }
+}
+
 // transpose-read addressing in an att_vslot image (as attention_stream.hip): the lane supplies 4 channels of row 8 kg + rr (and + 4) of a 16-row step; channel block
 // db is the 64-B segment db ^ swizzle: offset ^ (db << 6)
+template <int ROW>
 __device__ __forceinline__ int tr_off0(int lane) {
   const int kg = lane >> 5, g16 = (lane >> 4) & 1, rr = (lane & 15) >> 2, qq = lane & 3;
-  return (kg * 8 + rr) * ROW + (((rr >> 1) & 1) << 6) + (16 * g16 + 4 * qq) * 2;
+  return (kg * 8 + rr) * ROW + ((ROW == 128 ? (rr >> 1) & 1 : rr) << 6) + (16 * g16 + 4 * qq) * 2;
 }
+template <int ROW>
 __device__ __forceinline__ bf16x8 tr_frag(const char* img, int step16, int off0, int db) {
   union { bf16x8 v; s16x4 hlf[2]; } f;
   f.hlf[0] = tr_read_ordered(img + step16 * (16 * ROW) + (off0 ^ (db << 6)));
@@ -77,16 +117,19 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* img, int step16, int off0,
   return f.v;
 }
 
-__global__ __launch_bounds__(NT) void attention_bwd_stream_dq_kernel(Args a) {
+template <int DP>
+__global__ __launch_bounds__(NTQ) void attention_bwd_stream_dq_kernel(Args a) {
 #if __HIP_DEVICE_COMPILE__
-  __shared__ __attribute__((aligned(256))) char smem[2 * DQ_BUF];
+  using G = Geo<DP>;
+  constexpr int NT = NTQ, D = G::D, ROW = G::ROW, TILE = G::TILE, KS = G::KS, DB = G::DB, CPR = G::CPR, SW = G::SW, BB = G::BB, DQ_BUF = G::DQ_BUF;
+  char* smem = dq_image<2 * DQ_BUF>();
   const int S = a.S, C = a.H * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned item = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = (int)(item / (unsigned)a.nb), blk = (int)(item % (unsigned)a.nb);
   const int b = bh / a.H, h = bh % a.H;
-  const size_t base = (size_t)b * a.bs + h * D;
-  const bf16 *qp = a.q + base, *kp = a.k + base, *vp = a.v + base;
+  const size_t base = (size_t)b * a.qk_bs + h * a.qk_hs, vbase = (size_t)b * a.v_bs + h * a.v_hs;
+  const bf16 *qp = a.q + base, *kp = a.k + base, *vp = a.v + vbase;
   const bf16* og = a.o + (size_t)b * S * C + h * D;
   const bf16* dog = a.dout + (size_t)b * S * C + h * D;
   const int kg = lane >> 5, ql = lane & 31;
@@ -95,35 +138,44 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dq_kernel(Args a) {
   const bool live = q0 < S;                  // wave-uniform
   const int nt = (S + TT - 1) / TT;
 
-  // staging: thread -> key row tid >> 3 of the tile, 16-B chunk tid & 7 of its K row and of its V row
-  const int skey = tid >> 3, sc = tid & 7;
-  const int rsl = att_kslot<ROW>(skey, sc), tsl = att_vslot<ROW>(skey, sc);
-  uint4 kreg, vreg;
+  // staging: thread -> key row tid / CPR (+ NT / CPR per sweep) of the tile, 16-B chunk tid % CPR of its K row and of its V row; a chunk past the D real channels
+  // is not loaded (zeros in LDS)
+  const int skey = tid / CPR, sc = tid % CPR;
+  int rsl[SW], tsl[SW];
+#pragma unroll
+  for (int it = 0; it < SW; it++) { rsl[it] = att_kslot<ROW>(skey + it * (NT / CPR), sc); tsl[it] = att_vslot<ROW>(skey + it * (NT / CPR), sc); }
+  uint4 kreg[SW], vreg[SW];
   auto load_tile = [&](int t) {
-    const int key = t * TT + skey;
-    kreg = uint4{0, 0, 0, 0}; vreg = uint4{0, 0, 0, 0};
-    if (key < S) {
-      kreg = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.rs + sc * 8);
-      vreg = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.rs + sc * 8);
+#pragma unroll
+    for (int it = 0; it < SW; it++) {
+      const int key = t * TT + skey + it * (NT / CPR);
+      kreg[it] = uint4{0, 0, 0, 0}; vreg[it] = uint4{0, 0, 0, 0};
+      if (key < S && (DP == 64 || sc < D / 8)) {
+        kreg[it] = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.qk_rs + sc * 8);
+        vreg[it] = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.v_rs + sc * 8);
+      }
     }
   };
   auto store_tile = [&](int buf) {
     char* img = smem + buf * DQ_BUF;
-    *reinterpret_cast<uint4*>(img + rsl) = kreg;
-    *reinterpret_cast<uint4*>(img + TILE + tsl) = kreg;
-    *reinterpret_cast<uint4*>(img + 2 * TILE + rsl) = vreg;
+#pragma unroll
+    for (int it = 0; it < SW; it++) {
+      *reinterpret_cast<uint4*>(img + rsl[it]) = kreg[it];
+      *reinterpret_cast<uint4*>(img + TILE + tsl[it]) = kreg[it];
+      *reinterpret_cast<uint4*>(img + 2 * TILE + rsl[it]) = vreg[it];
+    }
   };
   load_tile(0);
 
   // the wave's Q / dO fragments (column operands: query on the lane, 8 channels per lane per 16-channel step) and delta
-  bf16x8 qf[4], dof[4];
+  bf16x8 qf[KS], dof[KS];
   float delta = 0.f;
 #pragma unroll
-  for (int kk = 0; kk < 4; kk++) {
+  for (int kk = 0; kk < KS; kk++) {
     uint4 tq = {0, 0, 0, 0}, td = {0, 0, 0, 0}, to = {0, 0, 0, 0};
     const int d0 = kk * 16 + kg * 8;
-    if (q < S) {
-      tq = *reinterpret_cast<const uint4*>(qp + (size_t)q * a.rs + d0);
+    if (q < S && (DP == 64 || d0 < D)) {
+      tq = *reinterpret_cast<const uint4*>(qp + (size_t)q * a.qk_rs + d0);
       td = *reinterpret_cast<const uint4*>(dog + (size_t)q * C + d0);
       to = *reinterpret_cast<const uint4*>(og + (size_t)q * C + d0);
     }
@@ -137,13 +189,13 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dq_kernel(Args a) {
     Lq = a.lse[(size_t)bh * S + q];
     if (kg == 0) a.delta[(size_t)bh * S + q] = delta;
   }
-  const int toff = tr_off0(lane);
+  const int toff = tr_off0<ROW>(lane);
   const float scale = a.scale;
   store_tile(0);
 
-  f32x16 dq[2];
+  f32x16 dq[DB];
 #pragma unroll
-  for (int db = 0; db < 2; db++)
+  for (int db = 0; db < DB; db++)
 #pragma unroll
     for (int r = 0; r < 16; r++) dq[db][r] = 0.f;
 
@@ -159,9 +211,9 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dq_kernel(Args a) {
         const int key0 = t * TT + kb * 32;
         if (kb == 1 && key0 >= S) break;      // the last tile's second block wholly past S (wave-uniform)
         // st[r] = score(key key0 + (r&3) + 8 (r>>2) + 4 kg, query q), dpt likewise: every row fragment of the block ahead of its products
-        bf16x8 kf[4], vf[4];
+        bf16x8 kf[KS], vf[KS];
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
+        for (int kk = 0; kk < KS; kk++) {
           const int off = att_kslot<ROW>(kb * 32 + ql, kk * 2 + kg);
           kf[kk] = *reinterpret_cast<const bf16x8*>(ks + off);
           vf[kk] = *reinterpret_cast<const bf16x8*>(vs + off);
@@ -171,16 +223,16 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dq_kernel(Args a) {
 #pragma unroll
         for (int r = 0; r < 16; r++) { st[r] = 0.f; dpt[r] = 0.f; }
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
+        for (int kk = 0; kk < KS; kk++) {
           st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kk], qf[kk], st, 0, 0, 0);
           dpt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[kk], dof[kk], dpt, 0, 0, 0);
         }
         // behind the products: the K^T fragments of the dQ product (they land under the exponentials), and the next tile's global loads
-        bf16x8 ktr[2][2];
+        bf16x8 ktr[2][DB];
 #pragma unroll
         for (int half = 0; half < 2; half++)
 #pragma unroll
-          for (int db = 0; db < 2; db++) ktr[half][db] = tr_frag(kt, kb * 2 + half, toff, db);
+          for (int db = 0; db < DB; db++) ktr[half][db] = tr_frag<ROW>(kt, kb * 2 + half, toff, db);
         if (kb == 0 && more) load_tile(t + 1);
         __builtin_amdgcn_sched_barrier(0);
         if (key0 + 32 > S) {      // only the last live block can hold keys past S: a wave-uniform branch
@@ -202,7 +254,7 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dq_kernel(Args a) {
 #pragma unroll
         for (int half = 0; half < 2; half++)
 #pragma unroll
-          for (int db = 0; db < 2; db++) dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[half], ktr[half][db], dq[db], 0, 0, 0);
+          for (int db = 0; db < DB; db++) dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[half], ktr[half][db], dq[db], 0, 0, 0);
       }
     } else if (more) {
       load_tile(t + 1);
@@ -213,25 +265,28 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dq_kernel(Args a) {
   // registers r are queries q0 + (r&3) + 8 (r>>2) + 4 kg, the lane is channel db*32 + ql: 32 lanes write 64 consecutive bytes of a row
   bf16* dqg = a.dq + base;
 #pragma unroll
-  for (int db = 0; db < 2; db++)
+  for (int db = 0; db < DB; db++)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
       const int qo = q0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-      if (qo < S) dqg[(size_t)qo * a.rs + db * 32 + ql] = (bf16)dq[db][r];
+      if (qo < S && (DP == 64 || db * 32 + ql < a.qk_rs)) dqg[(size_t)qo * a.qk_rs + db * 32 + ql] = (bf16)dq[db][r];
     }
 #endif
 }
 
+template <int DP, int NT>
 __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
 #if __HIP_DEVICE_COMPILE__
+  using G = Geo<DP, NT>;
+  constexpr int D = G::D, ROW = G::ROW, TILE = G::TILE, KS = G::KS, DB = G::DB, CPR = G::CPR, SW = G::SW, BB = G::BB, DKDV_BUF = G::DKDV_BUF;
   extern __shared__ __attribute__((aligned(256))) char smem[];      // 2 x DKDV_BUF
   const int S = a.S, C = a.H * D;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned item = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = (int)(item / (unsigned)a.nb), blk = (int)(item % (unsigned)a.nb);
   const int b = bh / a.H, h = bh % a.H;
-  const size_t base = (size_t)b * a.bs + h * D;
-  const bf16 *qp = a.q + base, *kp = a.k + base, *vp = a.v + base;
+  const size_t base = (size_t)b * a.qk_bs + h * a.qk_hs, vbase = (size_t)b * a.v_bs + h * a.v_hs;
+  const bf16 *qp = a.q + base, *kp = a.k + base, *vp = a.v + vbase;
   const bf16* dog = a.dout + (size_t)b * S * C + h * D;
   const float* lse = a.lse + (size_t)bh * S;
   const float* dlt = a.delta + (size_t)bh * S;
@@ -241,17 +296,23 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
   const bool live = key0 < S;                // wave-uniform
   const int nt = (S + TT - 1) / TT;
 
-  // staging: thread -> query row tid >> 3 of the tile, 16-B chunk tid & 7 of its Q row and of its dO row; threads 0-63 its L, threads 64-127 its delta
-  const int srow = tid >> 3, sc = tid & 7;
-  const int rsl = att_kslot<ROW>(srow, sc), tsl = att_vslot<ROW>(srow, sc);
-  uint4 qreg, dreg;
+  // staging: thread -> query row tid / CPR (+ NT / CPR per sweep) of the tile, 16-B chunk tid % CPR of its Q row and of its dO row (a chunk past the D real channels
+  // is not loaded: zeros in LDS); threads 0-63 its L, threads 64-127 its delta
+  const int srow = tid / CPR, sc = tid % CPR;
+  int rsl[SW], tsl[SW];
+#pragma unroll
+  for (int it = 0; it < SW; it++) { rsl[it] = att_kslot<ROW>(srow + it * (NT / CPR), sc); tsl[it] = att_vslot<ROW>(srow + it * (NT / CPR), sc); }
+  uint4 qreg[SW], dreg[SW];
   float sreg = 0.f;
   auto load_tile = [&](int t) {
-    const int row = t * TT + srow;
-    qreg = uint4{0, 0, 0, 0}; dreg = uint4{0, 0, 0, 0};
-    if (row < S) {
-      qreg = *reinterpret_cast<const uint4*>(qp + (size_t)row * a.rs + sc * 8);
-      dreg = *reinterpret_cast<const uint4*>(dog + (size_t)row * C + sc * 8);
+#pragma unroll
+    for (int it = 0; it < SW; it++) {
+      const int row = t * TT + srow + it * (NT / CPR);
+      qreg[it] = uint4{0, 0, 0, 0}; dreg[it] = uint4{0, 0, 0, 0};
+      if (row < S && (DP == 64 || sc < D / 8)) {
+        qreg[it] = *reinterpret_cast<const uint4*>(qp + (size_t)row * a.qk_rs + sc * 8);
+        dreg[it] = *reinterpret_cast<const uint4*>(dog + (size_t)row * C + sc * 8);
+      }
     }
     if (tid < 2 * TT) {
       const int sq = t * TT + (tid & (TT - 1));
@@ -261,34 +322,37 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
   };
   auto store_tile = [&](int buf) {
     char* img = smem + buf * DKDV_BUF;
-    *reinterpret_cast<uint4*>(img + rsl) = qreg;
-    *reinterpret_cast<uint4*>(img + TILE + tsl) = qreg;
-    *reinterpret_cast<uint4*>(img + 2 * TILE + rsl) = dreg;
-    *reinterpret_cast<uint4*>(img + 3 * TILE + tsl) = dreg;
+#pragma unroll
+    for (int it = 0; it < SW; it++) {
+      *reinterpret_cast<uint4*>(img + rsl[it]) = qreg[it];
+      *reinterpret_cast<uint4*>(img + TILE + tsl[it]) = qreg[it];
+      *reinterpret_cast<uint4*>(img + 2 * TILE + rsl[it]) = dreg[it];
+      *reinterpret_cast<uint4*>(img + 3 * TILE + tsl[it]) = dreg[it];
+    }
     if (tid < 2 * TT) reinterpret_cast<float*>(img + 4 * TILE)[tid] = sreg;
   };
   load_tile(0);
 
   // the wave's K / V fragments (column operands: key on the lane)
-  bf16x8 kfb[4], vfb[4];
+  bf16x8 kfb[KS], vfb[KS];
 #pragma unroll
-  for (int kk = 0; kk < 4; kk++) {
+  for (int kk = 0; kk < KS; kk++) {
     uint4 tk = {0, 0, 0, 0}, tv = {0, 0, 0, 0};
     const int d0 = kk * 16 + kg * 8;
-    if (key < S) {
-      tk = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.rs + d0);
-      tv = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.rs + d0);
+    if (key < S && (DP == 64 || d0 < D)) {
+      tk = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.qk_rs + d0);
+      tv = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.v_rs + d0);
     }
     kfb[kk] = *reinterpret_cast<bf16x8*>(&tk);
     vfb[kk] = *reinterpret_cast<bf16x8*>(&tv);
   }
-  const int toff = tr_off0(lane);
+  const int toff = tr_off0<ROW>(lane);
   const float scale = a.scale;
   store_tile(0);
 
-  f32x16 dk[2], dv[2];
+  f32x16 dk[DB], dv[DB];
 #pragma unroll
-  for (int db = 0; db < 2; db++)
+  for (int db = 0; db < DB; db++)
 #pragma unroll
     for (int r = 0; r < 16; r++) { dk[db][r] = 0.f; dv[db][r] = 0.f; }
 
@@ -306,9 +370,9 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
       for (int qb = 0; qb < 2; qb++) {
         if (qb == 1 && t * TT + 32 >= S) break;      // the last tile's second block wholly past S (wave-uniform): all its P and dS are zero
         // s[r] = score(query qb*32 + (r&3) + 8 (r>>2) + 4 kg of the tile, this lane's key), dp likewise
-        bf16x8 qfr[4], dor[4];
+        bf16x8 qfr[KS], dor[KS];
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
+        for (int kk = 0; kk < KS; kk++) {
           const int off = att_kslot<ROW>(qb * 32 + ql, kk * 2 + kg);
           qfr[kk] = *reinterpret_cast<const bf16x8*>(qs + off);
           dor[kk] = *reinterpret_cast<const bf16x8*>(ds + off);
@@ -318,7 +382,7 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
 #pragma unroll
         for (int r = 0; r < 16; r++) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) {
+        for (int kk = 0; kk < KS; kk++) {
           s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qfr[kk], kfb[kk], s, 0, 0, 0);
           dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dor[kk], vfb[kk], dp, 0, 0, 0);
         }
@@ -330,13 +394,13 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
           Lv[r4] = *reinterpret_cast<const f32x4*>(Ls + qb * 32 + 8 * r4 + 4 * kg);
           Dv[r4] = *reinterpret_cast<const f32x4*>(Ds + qb * 32 + 8 * r4 + 4 * kg);
         }
-        bf16x8 dft[2][2], qft[2][2];
+        bf16x8 dft[2][DB], qft[2][DB];
 #pragma unroll
         for (int half = 0; half < 2; half++)
 #pragma unroll
-          for (int db = 0; db < 2; db++) {
-            dft[half][db] = tr_frag(dt, qb * 2 + half, toff, db);
-            qft[half][db] = tr_frag(qt, qb * 2 + half, toff, db);
+          for (int db = 0; db < DB; db++) {
+            dft[half][db] = tr_frag<ROW>(dt, qb * 2 + half, toff, db);
+            qft[half][db] = tr_frag<ROW>(qt, qb * 2 + half, toff, db);
           }
         if (qb == 0 && more) load_tile(t + 1);
         __builtin_amdgcn_sched_barrier(0);
@@ -354,7 +418,7 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
 #pragma unroll
         for (int half = 0; half < 2; half++)
 #pragma unroll
-          for (int db = 0; db < 2; db++) {
+          for (int db = 0; db < DB; db++) {
             dv[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[half], dft[half][db], dv[db], 0, 0, 0);
             dk[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsf[half], qft[half][db], dk[db], 0, 0, 0);
           }
@@ -367,15 +431,15 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
   if (!live) return;
   // registers r are keys key0 + (r&3) + 8 (r>>2) + 4 kg, the lane is channel db*32 + ql
   bf16* dkg = a.dk + base;
-  bf16* dvg = a.dv + base;
+  bf16* dvg = a.dv + vbase;
 #pragma unroll
-  for (int db = 0; db < 2; db++)
+  for (int db = 0; db < DB; db++)
 #pragma unroll
     for (int r = 0; r < 16; r++) {
       const int ko = key0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
       if (ko < S) {
-        dkg[(size_t)ko * a.rs + db * 32 + ql] = (bf16)dk[db][r];
-        dvg[(size_t)ko * a.rs + db * 32 + ql] = (bf16)dv[db][r];
+        if (DP == 64 || db * 32 + ql < a.qk_rs) dkg[(size_t)ko * a.qk_rs + db * 32 + ql] = (bf16)dk[db][r];
+        if (DP == 64 || db * 32 + ql < D) dvg[(size_t)ko * a.v_rs + db * 32 + ql] = (bf16)dv[db][r];
       }
     }
 #endif
@@ -386,6 +450,8 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
 extern "C" int dmvae_attention_bwd_qkv_stream_bf16(const void* qkv, const void* out, const void* dout, const void* lse, void* dqkv, void* delta, int batch, int seq,
                                                    int heads, int head_dim, float scale, hipStream_t stream) {
   using namespace dmvae_attn_bwd_stream;
+  using G = Geo<64>;
+  constexpr int D = G::D, NT = NTQ, BB = G::BB, DKDV_BUF = G::DKDV_BUF;
   DMVAE_CHECK_ARG(qkv && out && dout && dqkv, "attention_bwd_qkv_stream_bf16: null qkv, out, dout or dqkv");
   DMVAE_CHECK_ARG(lse, "attention_bwd_qkv_stream_bf16: null lse (the forward's row statistics are required)");
   DMVAE_CHECK_ARG(delta, "attention_bwd_qkv_stream_bf16: null delta scratch (batch * heads * seq floats)");
@@ -401,12 +467,59 @@ extern "C" int dmvae_attention_bwd_qkv_stream_bf16(const void* qkv, const void* 
   a.q = (const bf16*)qkv; a.k = a.q + C; a.v = a.q + 2 * C;
   a.dq = (bf16*)dqkv; a.dk = a.dq + C; a.dv = a.dq + 2 * C;
   a.o = (const bf16*)out; a.dout = (const bf16*)dout; a.lse = (const float*)lse; a.delta = (float*)delta;
-  a.bs = (long long)seq * 3 * C; a.rs = (int)(3 * C);
+  a.qk_bs = a.v_bs = (long long)seq * 3 * C; a.qk_hs = a.v_hs = head_dim; a.qk_rs = a.v_rs = (int)(3 * C);
   a.S = seq; a.H = heads; a.nb = (int)nb; a.scale = scale;
-  DMVAE_LDS_OPTIN(2 * DKDV_BUF, attention_bwd_stream_dkdv_kernel);
-  hipLaunchKernelGGL(attention_bwd_stream_dq_kernel, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+  DMVAE_LDS_OPTIN(2 * DKDV_BUF, attention_bwd_stream_dkdv_kernel<64, NTQ>);
+  hipLaunchKernelGGL(attention_bwd_stream_dq_kernel<64>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
   DMVAE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(attention_bwd_stream_dkdv_kernel, dim3((unsigned)blocks), dim3(NT), 2 * DKDV_BUF, stream, a);
+  hipLaunchKernelGGL((attention_bwd_stream_dkdv_kernel<64, NTQ>), dim3((unsigned)blocks), dim3(NT), 2 * DKDV_BUF, stream, a);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The same two passes on head-major operands (q, k, dq, dk: [B*H][N][QD], v, dv: [B*H][N][D]: what dmvae_attention_bwd_heads_lse_bf16 takes) at any token count.
+// head_dim 64 or 72; QD = head_dim (unpadded rows) or its round-up to 32 (rows zero-padded by the producer; the padded columns of dq / dk are written as zeros).
+extern "C" int dmvae_attention_bwd_heads_stream_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq, void* dk,
+                                                     void* dv, void* delta, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale,
+                                                     hipStream_t stream) {
+  using namespace dmvae_attn_bwd_stream;
+  DMVAE_CHECK_ARG(q && k && v && out && dout && dq && dk && dv, "attention_bwd_heads_stream_bf16: null q, k, v, out, dout, dq, dk or dv");
+  DMVAE_CHECK_ARG(lse, "attention_bwd_heads_stream_bf16: null lse (the forward's row statistics are required)");
+  DMVAE_CHECK_ARG(delta, "attention_bwd_heads_stream_bf16: null delta scratch (batch * heads * seq floats)");
+  DMVAE_CHECK_ARG(batch > 0 && heads > 0 && seq >= 1, "attention_bwd_heads_stream_bf16: needs batch, heads, seq >= 1 (got %d, %d, %d)", batch, heads, seq);
+  DMVAE_CHECK_ARG(head_dim == 64 || head_dim == 72, "attention_bwd_heads_stream_bf16: needs head_dim 64 or 72 (got %d)", head_dim);
+  DMVAE_CHECK_ARG(head_dim_padded == head_dim || head_dim_padded == (head_dim + 31) / 32 * 32,
+                  "attention_bwd_heads_stream_bf16: q / k rows hold head_dim channels or head_dim rounded up to 32 (got %d for head_dim %d)", head_dim_padded, head_dim);
+  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "attention_bwd_heads_stream_bf16: needs a finite scale > 0 (got %g)", (double)scale);
+  constexpr int NTK96 = 256;      // the 96-wide key pass: four waves, 128 keys per workgroup (file header)
+  constexpr int lds_dq96 = 2 * Geo<96>::DQ_BUF, lds_dkdv64 = 2 * Geo<64>::DKDV_BUF, lds_dkdv96 = 2 * Geo<96, NTK96>::DKDV_BUF;
+  const long long nbq = ((long long)seq + Geo<64>::BB - 1) / Geo<64>::BB;
+  const long long nbk = head_dim == 64 ? nbq : ((long long)seq + Geo<96, NTK96>::BB - 1) / Geo<96, NTK96>::BB;
+  // the (sample, head) count is an int in the kernels; the flat grids are one dimension
+  DMVAE_CHECK_ARG((long long)batch * heads <= 0x7fffffffLL && (long long)batch * heads * nbk <= 0x7fffffffLL,
+                  "attention_bwd_heads_stream_bf16: %d x %d heads x %d tokens does not fit the grid", batch, heads, seq);
+  Args a = {};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)out; a.dout = (const bf16*)dout;
+  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.lse = (const float*)lse; a.delta = (float*)delta;
+  a.qk_hs = (long long)seq * head_dim_padded; a.qk_bs = a.qk_hs * heads; a.qk_rs = head_dim_padded;
+  a.v_hs = (long long)seq * head_dim; a.v_bs = a.v_hs * heads; a.v_rs = head_dim;
+  a.S = seq; a.H = heads; a.scale = scale;
+  const unsigned bh = (unsigned)(batch * heads);
+  if (head_dim == 64) {
+    DMVAE_LDS_OPTIN(lds_dkdv64, attention_bwd_stream_dkdv_kernel<64, NTQ>);
+    a.nb = (int)nbq;
+    hipLaunchKernelGGL(attention_bwd_stream_dq_kernel<64>, dim3(bh * (unsigned)nbq), dim3(NTQ), 0, stream, a);
+    DMVAE_CHECK_LAUNCH();
+    hipLaunchKernelGGL((attention_bwd_stream_dkdv_kernel<64, NTQ>), dim3(bh * (unsigned)nbq), dim3(NTQ), lds_dkdv64, stream, a);
+  } else {
+    DMVAE_LDS_OPTIN(lds_dq96, attention_bwd_stream_dq_kernel<96>);
+    DMVAE_LDS_OPTIN(lds_dkdv96, attention_bwd_stream_dkdv_kernel<96, NTK96>);
+    a.nb = (int)nbq;
+    hipLaunchKernelGGL(attention_bwd_stream_dq_kernel<96>, dim3(bh * (unsigned)nbq), dim3(NTQ), lds_dq96, stream, a);
+    DMVAE_CHECK_LAUNCH();
+    a.nb = (int)nbk;
+    hipLaunchKernelGGL((attention_bwd_stream_dkdv_kernel<96, NTK96>), dim3(bh * (unsigned)nbk), dim3(NTK96), lds_dkdv96, stream, a);
+  }
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

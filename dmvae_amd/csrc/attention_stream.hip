@@ -30,18 +30,36 @@
 // not stored.  A wave whose 32 queries are all >= S skips the matrix work and only stages and synchronises.
 // Determinism: every reduction has a fixed order and every operation is per (sample, head): reruns are bit-identical and a 2B-sample call equals two B-sample calls.
 // Grid: one flat dimension of B * H * ceil(S / 256) workgroups through xcd_remap, so that the query blocks of one head run on one XCD and share its L2 for K / V.
+//
+// Two instantiations of the one kernel (template parameter DP, the staged head dim).  DP = 64: everything above -- the encoder's entry dmvae_attention_qkv_stream_bf16
+// and head-major operands of head dim 64.  DP = 96: LightningDiT's head dim 72 on the head-major operands of dmvae_qknorm_rope_bf16 (q, k [B*H][N][72 or 96],
+// v [B*H][N][72]; entry dmvae_attention_heads_stream_bf16): K / V tiles of 256-B rows in the layouts the 96-wide resident kernel uses (common.h att_kslot<256> /
+// att_vslot<256>), 2 x 2 x 16 KiB = 64 KiB static, two staging sweeps per tile (sixteen lanes per key row, nine of them load).  As in the resident kernels the channels
+// 72 .. 95 are zeros in LDS and never loaded -- rows padded to 96 by the producer and rows of 72 channels give the same bits --, q k^T takes five 16-channel steps (the
+// upper half of the fifth is zero, the sixth is skipped), the output accumulators are three 32-channel blocks and channels >= 72 are not stored.
+// Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DP = 64: 137 VGPRs, 0 AGPRs, 50 SGPRs, no scratch, no spill, 32 KiB LDS, 3 waves per
+// SIMD -- the numbers of the kernel before it was a template.  DP = 96: 186 VGPRs, 0 AGPRs, 56 SGPRs, no scratch, no spill, 64 KiB LDS, 2 waves per SIMD.
 #include "common.h"
 #include <math.h>
 
 namespace dmvae_attn_stream {
 
-constexpr int D = 64;            // head dim
 constexpr int NT = 512;          // 8 waves
 constexpr int QW = 32;           // queries per wave
 constexpr int QB = QW * NT / 64; // queries per workgroup: 256
 constexpr int KT = 64;           // keys per tile
-constexpr int ROW = 128;         // bytes per K / V row in LDS
-constexpr int TILE = KT * ROW;   // 8 KiB
+// DP: head dim as staged.  64: head dim 64, 128-B rows in LDS.  96: head dim 72 (LightningDiT-XL), 256-B rows -- common.h's layouts of the 96-wide resident kernel;
+// the channels 72 .. 95 are zeros in LDS (never loaded), the sixth 16-channel K step is skipped, the upper half of the fifth is zero, output channels >= 72 are not stored.
+template <int DP> struct Geo {
+  static_assert(DP == 64 || DP == 96, "staged head dim 64 or 96");
+  static constexpr int D = DP == 64 ? 64 : 72;      // real head dim: V / output width, the channels of a q / k row that are read
+  static constexpr int ROW = DP == 64 ? 128 : 256;  // bytes per K / V row in LDS
+  static constexpr int TILE = KT * ROW;             // 8 / 16 KiB
+  static constexpr int KS = DP == 64 ? 4 : 5;       // 16-channel steps of q k^T
+  static constexpr int DB = DP / 32;                // 32-channel blocks of the output accumulators
+  static constexpr int CPR = ROW / 16;              // staging lanes per row: one 16-B chunk each
+  static constexpr int SW = KT * CPR / NT;          // staging sweeps per tile: 1 / 2
+};
 
 struct StreamArgs {
   const bf16 *q, *k, *v;
@@ -64,9 +82,12 @@ __device__ __forceinline__ float xhalf_sum(float x) {    // r[0] is the low half
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
+template <int DP>
 __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
 #if __HIP_DEVICE_COMPILE__
-  __shared__ __attribute__((aligned(256))) char smem[2 * 2 * TILE];     // [buffer][K | V][64 keys][128 B]
+  using G = Geo<DP>;
+  constexpr int D = G::D, ROW = G::ROW, TILE = G::TILE, KS = G::KS, DB = G::DB, CPR = G::CPR, SW = G::SW;
+  __shared__ __attribute__((aligned(256))) char smem[2 * 2 * TILE];     // [buffer][K | V][64 keys][ROW B]
   const int S = a.S;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const unsigned item = xcd_remap(blockIdx.x, gridDim.x);
@@ -81,44 +102,54 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
   const bool live = q0 < S;                  // wave-uniform
   const int nt = (S + KT - 1) / KT;
 
-  // staging: thread -> key row tid >> 3 of the tile, 16-B chunk tid & 7 of its K row and of its V row
-  const int skey = tid >> 3, sc = tid & 7;
-  const int ksl = att_kslot<ROW>(skey, sc), vsl = att_vslot<ROW>(skey, sc);
-  uint4 kreg, vreg;
+  // staging: thread -> key row tid / CPR (+ NT / CPR per sweep) of the tile, 16-B chunk tid % CPR of its K row and of its V row; a chunk past the D real channels
+  // is not loaded (zeros in LDS)
+  const int skey = tid / CPR, sc = tid % CPR;
+  int ksl[SW], vsl[SW];
+#pragma unroll
+  for (int it = 0; it < SW; it++) { ksl[it] = att_kslot<ROW>(skey + it * (NT / CPR), sc); vsl[it] = att_vslot<ROW>(skey + it * (NT / CPR), sc); }
+  uint4 kreg[SW], vreg[SW];
   auto load_tile = [&](int t) {
-    const int key = t * KT + skey;
-    kreg = uint4{0, 0, 0, 0}; vreg = uint4{0, 0, 0, 0};
-    if (key < S) {
-      kreg = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.k_rs + sc * 8);
-      vreg = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.v_rs + sc * 8);
+#pragma unroll
+    for (int it = 0; it < SW; it++) {
+      const int key = t * KT + skey + it * (NT / CPR);
+      kreg[it] = uint4{0, 0, 0, 0}; vreg[it] = uint4{0, 0, 0, 0};
+      if (key < S && (DP == 64 || sc < D / 8)) {
+        kreg[it] = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.k_rs + sc * 8);
+        vreg[it] = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.v_rs + sc * 8);
+      }
     }
   };
   auto store_tile = [&](int buf) {
     char* base = smem + buf * 2 * TILE;
-    *reinterpret_cast<uint4*>(base + ksl) = kreg;
-    *reinterpret_cast<uint4*>(base + TILE + vsl) = vreg;
+#pragma unroll
+    for (int it = 0; it < SW; it++) {
+      *reinterpret_cast<uint4*>(base + ksl[it]) = kreg[it];
+      *reinterpret_cast<uint4*>(base + TILE + vsl[it]) = vreg[it];
+    }
   };
   load_tile(0);
 
   // Q fragments (column operand of the swapped product): 8 channels per lane per 16-channel step
-  bf16x8 qf[4];
+  bf16x8 qf[KS];
 #pragma unroll
-  for (int kk = 0; kk < 4; kk++) {
+  for (int kk = 0; kk < KS; kk++) {
     uint4 t = {0, 0, 0, 0};
-    if (q < S) t = *reinterpret_cast<const uint4*>(qp + (size_t)q * a.q_rs + kk * 16 + kg * 8);
+    if (q < S && (DP == 64 || kk * 16 + kg * 8 < D)) t = *reinterpret_cast<const uint4*>(qp + (size_t)q * a.q_rs + kk * 16 + kg * 8);
     qf[kk] = *reinterpret_cast<bf16x8*>(&t);
   }
   // V transpose-read addressing (as vit.hip): the lane supplies 4 channels of one key row of a 16-key step
   const int g16 = (lane >> 4) & 1, rr = (lane & 15) >> 2, qq = lane & 3;
-  // channel block db is the 64-B segment db ^ swizzle: the second block's address is the first's with bit 6 flipped (one address register, not two)
-  const int voff0 = (kg * 8 + rr) * ROW + (((rr >> 1) & 1) << 6) + (16 * g16 + 4 * qq) * 2;
+  // channel block db is the 64-B segment db ^ swizzle (att_vslot: (key >> 1) & 1 in 128-B rows, key & 3 in 256-B rows): another block's address is the first's with
+  // db << 6 XOR-ed in (one address register; the bits below 6 and the row offset above them do not overlap the segment bits)
+  const int voff0 = (kg * 8 + rr) * ROW + ((ROW == 128 ? (rr >> 1) & 1 : rr) << 6) + (16 * g16 + 4 * qq) * 2;
   store_tile(0);
 
   const float ec = a.scale * 1.4426950408889634f;     // scale > 0 (checked on the host): the maximum of the raw scores is the maximum of the scaled ones
   float m = -INFINITY, l = 0.f;
-  f32x16 o[2];
+  f32x16 o[DB];
 #pragma unroll
-  for (int db = 0; db < 2; db++)
+  for (int db = 0; db < DB; db++)
 #pragma unroll
     for (int r = 0; r < 16; r++) o[db][r] = 0.f;
 
@@ -132,14 +163,14 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
       f32x16 st[2];
 #pragma unroll
       for (int kb = 0; kb < 2; kb++) {
-        bf16x8 kf[4];      // every fragment read of the block ahead of its products
+        bf16x8 kf[KS];     // every fragment read of the block ahead of its products
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) kf[kk] = *reinterpret_cast<const bf16x8*>(ks + att_kslot<ROW>(kb * 32 + ql, kk * 2 + kg));
+        for (int kk = 0; kk < KS; kk++) kf[kk] = *reinterpret_cast<const bf16x8*>(ks + att_kslot<ROW>(kb * 32 + ql, kk * 2 + kg));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < 16; r++) st[kb][r] = 0.f;
 #pragma unroll
-        for (int kk = 0; kk < 4; kk++) st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kk], qf[kk], st[kb], 0, 0, 0);
+        for (int kk = 0; kk < KS; kk++) st[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kk], qf[kk], st[kb], 0, 0, 0);
       }
       if (more) load_tile(t + 1);      // in flight under the softmax and the PV products
       if (t * KT + KT > S) {           // the last tile of a ragged S: register r of block kb is key t*64 + kb*32 + (r&3) + 8*(r>>2) + 4*kg
@@ -161,17 +192,17 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
       m = mn;
       l *= alpha;
 #pragma unroll
-      for (int db = 0; db < 2; db++)
+      for (int db = 0; db < DB; db++)
 #pragma unroll
         for (int r = 0; r < 16; r++) o[db][r] *= alpha;
 #pragma unroll
       for (int kb = 0; kb < 2; kb++) {
-        // the block's V^T fragments (two 16-key steps x two 32-channel blocks) are on their way while its exponentials run
-        union { bf16x8 v; s16x4 hlf[2]; } vf[2][2];
+        // the block's V^T fragments (two 16-key steps x DB 32-channel blocks) are on their way while its exponentials run
+        union { bf16x8 v; s16x4 hlf[2]; } vf[2][DB];
 #pragma unroll
         for (int half = 0; half < 2; half++)
 #pragma unroll
-          for (int db = 0; db < 2; db++) {
+          for (int db = 0; db < DB; db++) {
             vf[half][db].hlf[0] = tr_read_ordered(vs + (kb * 2 + half) * (16 * ROW) + (voff0 ^ (db << 6)));
             vf[half][db].hlf[1] = tr_read_ordered(vs + (kb * 2 + half) * (16 * ROW) + (voff0 ^ (db << 6)) + 4 * ROW);
           }
@@ -189,7 +220,7 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
           union { unsigned u[4]; bf16x8 v; } pa;
           pa.u[0] = s0[0]; pa.u[1] = s1[0]; pa.u[2] = s0[1]; pa.u[3] = s1[1];
 #pragma unroll
-          for (int db = 0; db < 2; db++) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[half][db].v, pa.v, o[db], 0, 0, 0);
+          for (int db = 0; db < DB; db++) o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[half][db].v, pa.v, o[db], 0, 0, 0);
         }
       }
     } else if (more) {
@@ -205,9 +236,10 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
     // lane = query q; registers r = 4 r4 .. 4 r4 + 3 are channels db*32 + 8 r4 + 4 kg + 0..3: 8-byte stores
     bf16* orow = a.out + ((size_t)b * S + q) * ((size_t)a.H * D) + h * D;
 #pragma unroll
-    for (int db = 0; db < 2; db++)
+    for (int db = 0; db < DB; db++)
 #pragma unroll
       for (int r4 = 0; r4 < 4; r4++) {
+        if (DP != 64 && db * 32 + 8 * r4 + 4 * kg >= D) continue;      // D % 8 == 0: the four channels are inside together
         uint2 pk;
         pk.x = dmvae_pack_bf16x2(o[db][4 * r4 + 0] * inv, o[db][4 * r4 + 1] * inv);
         pk.y = dmvae_pack_bf16x2(o[db][4 * r4 + 2] * inv, o[db][4 * r4 + 3] * inv);
@@ -221,6 +253,7 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
 
 extern "C" int dmvae_attention_qkv_stream_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, hipStream_t stream) {
   using namespace dmvae_attn_stream;
+  constexpr int D = Geo<64>::D;
   DMVAE_CHECK_ARG(qkv && out, "attention_qkv_stream_bf16: null qkv or out");
   DMVAE_CHECK_ARG(batch > 0 && heads > 0 && seq >= 1, "attention_qkv_stream_bf16: needs batch, heads, seq >= 1 (got %d, %d, %d)", batch, heads, seq);
   DMVAE_CHECK_ARG(head_dim == D, "attention_qkv_stream_bf16: needs head_dim 64 (got %d)", head_dim);
@@ -235,7 +268,35 @@ extern "C" int dmvae_attention_qkv_stream_bf16(const void* qkv, void* out, void*
   a.q_bs = a.k_bs = a.v_bs = (long long)seq * 3 * C; a.q_hs = a.k_hs = a.v_hs = head_dim;
   a.q_rs = a.k_rs = a.v_rs = (int)(3 * C);
   a.S = seq; a.H = heads; a.nqb = (int)nqb; a.scale = scale; a.lse = (float*)lse;
-  hipLaunchKernelGGL(attention_stream_kernel, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+  hipLaunchKernelGGL(attention_stream_kernel<64>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+// The same kernel on head-major operands (q, k: [B*H][N][QD], v: [B*H][N][D]; LightningDiT after QK-norm + RoPE: what dmvae_attention_heads_lse_bf16 takes) at any
+// token count.  head_dim 64 or 72; QD = head_dim (unpadded rows) or its round-up to 32 (rows zero-padded by the producer): the kernel reads the head_dim real channels
+// of a row either way, so both forms give the same bits.
+extern "C" int dmvae_attention_heads_stream_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
+                                                 int head_dim_padded, float scale, hipStream_t stream) {
+  using namespace dmvae_attn_stream;
+  DMVAE_CHECK_ARG(q && k && v && out, "attention_heads_stream_bf16: null q, k, v or out");
+  DMVAE_CHECK_ARG(batch > 0 && heads > 0 && seq >= 1, "attention_heads_stream_bf16: needs batch, heads, seq >= 1 (got %d, %d, %d)", batch, heads, seq);
+  DMVAE_CHECK_ARG(head_dim == 64 || head_dim == 72, "attention_heads_stream_bf16: needs head_dim 64 or 72 (got %d)", head_dim);
+  DMVAE_CHECK_ARG(head_dim_padded == head_dim || head_dim_padded == (head_dim + 31) / 32 * 32,
+                  "attention_heads_stream_bf16: q / k rows hold head_dim channels or head_dim rounded up to 32 (got %d for head_dim %d)", head_dim_padded, head_dim);
+  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "attention_heads_stream_bf16: needs a finite scale > 0 (got %g)", (double)scale);
+  const long long nqb = ((long long)seq + QB - 1) / QB, blocks = (long long)batch * heads * nqb;
+  // the (sample, head) count is an int in the kernel; the flat grid is one dimension
+  DMVAE_CHECK_ARG((long long)batch * heads <= 0x7fffffffLL && blocks <= 0x7fffffffLL,
+                  "attention_heads_stream_bf16: %d x %d heads x %d tokens does not fit the grid", batch, heads, seq);
+  StreamArgs a = {};
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out;
+  a.q_hs = a.k_hs = (long long)seq * head_dim_padded; a.q_bs = a.k_bs = a.q_hs * heads;
+  a.v_hs = (long long)seq * head_dim; a.v_bs = a.v_hs * heads;
+  a.q_rs = a.k_rs = head_dim_padded; a.v_rs = head_dim;
+  a.S = seq; a.H = heads; a.nqb = (int)nqb; a.scale = scale; a.lse = (float*)lse;
+  if (head_dim == 64) hipLaunchKernelGGL(attention_stream_kernel<64>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+  else hipLaunchKernelGGL(attention_stream_kernel<96>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

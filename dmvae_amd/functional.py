@@ -1161,9 +1161,13 @@ class DitBlockFn(torch.autograd.Function):
         qkv = linear(a1, qkvw, qkvb)
         q, k, v = ops.qknorm_rope(qkv, qnw, knw, cos, sin, heads, eps)
         fused = ops.attention_heads_supported(n, d)
-        if fused:       # the inference kernel; its backward recomputes the probabilities in registers (csrc/attention_bwd.hip)
+        lse = None
+        if fused:       # the inference kernel; its backward recomputes the probabilities in registers (csrc/attention_bwd.hip); no P is saved
             p = None
-            o = ops.attention_heads(q, k, v, b, d ** -0.5)
+            if n > ops.ATTENTION_RESIDENT_MAX:      # the streaming kernels: the backward rebuilds the probabilities from the forward's row statistics
+                o, lse = ops.attention_heads(q, k, v, b, d ** -0.5, need_lse=True)
+            else:
+                o = ops.attention_heads(q, k, v, b, d ** -0.5)
         else:
             p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), d ** -0.5)
             o = ops.gemm_nt(p, ops.transpose_last2(v)).view(b, heads, n, d).permute(0, 2, 1, 3).reshape(b, n, c)
@@ -1175,6 +1179,7 @@ class DitBlockFn(torch.autograd.Function):
         ctx.save_for_backward(h, mod, a1, qkv, q, k, v, p, o, o2, h_mid, a2, x12, g, o3, n1w, qkvw, qnw, knw, pw, n2w, w12w, w3w, cos, sin)
         ctx.others = (qkvb, pb, w12b, w3b, heads, eps)
         ctx.fused_attn = fused
+        ctx.lse = lse
         return h_out
 
     @staticmethod
@@ -1197,7 +1202,7 @@ class DitBlockFn(torch.autograd.Function):
         do2 = ops.gated_residual_bwd(dt, o2, mod, dmod, 2 * c)
         do, dpw, dpb = _lin_grads(do2.view(rows, c), o.view(rows, c), pw, pb)
         if ctx.fused_attn:
-            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5)
+            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=ctx.lse)
         else:
             do_h = do.view(b, n, heads, d).permute(0, 2, 1, 3).reshape(b * heads, n, d)
             pad = dp_ - d                                                   # head dim padded to the GEMM kernel's 32-wide K step (72 -> 96)

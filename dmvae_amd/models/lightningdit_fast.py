@@ -3,7 +3,8 @@
 
 Same arithmetic as `forward_stock` under autocast(bf16), with bf16 rounding at the sites where the reference's autocast graph rounds (see
 csrc/dit.hip); per block: 1 fused (gated residual +) RMSNorm+modulate, qkv GEMM, 1 fused QK-norm+RoPE+head split, attention in one fused kernel (csrc/vit.hip, head dims 64 and 72
-alike: the staged head dim pads to 96; composed batched QK^T GEMM / f32 softmax / PV GEMM beyond 288 tokens), proj GEMM, 1 gated residual, RMSNorm+modulate, w12 GEMM, SwiGLU gate, w3 GEMM,
+alike: the staged head dim pads to 96; beyond 288 tokens QK-norm + RoPE as their own kernel and the streaming-softmax kernel of csrc/attention_stream.hip -- nothing N x N in
+HBM at any token count; other head dims beyond 288 tokens: composed batched QK^T GEMM / f32 softmax / PV GEMM), proj GEMM, 1 gated residual, RMSNorm+modulate, w12 GEMM, SwiGLU gate, w3 GEMM,
 gated residual -- every token-level Linear on this build's GEMM kernel (`functional.linear`: csrc/gemm_pp.hip).
 The per-sample pieces (timestep / label embedding, adaLN Linear: one row per sample) stay stock PyTorch under autocast."""
 import os
@@ -57,7 +58,7 @@ def _attention(qkv, blk, rope, heads):
     b, n, c3 = qkv.shape
     c = c3 // 3
     d = c // heads
-    if _FUSED_ATTN and _FUSED_QKNORM and ops.attention_heads_supported(n, d):
+    if _FUSED_ATTN and _FUSED_QKNORM and n <= ops.ATTENTION_RESIDENT_MAX and ops.attention_heads_supported(n, d):      # the QK-norm variant is resident-only
         return ops.attention_qknorm_rope(qkv, blk.attn.q_norm.weight, blk.attn.k_norm.weight, rope.freqs_cos, rope.freqs_sin, heads, blk.attn.q_norm.eps, d ** -0.5)
     q, k, v = ops.qknorm_rope(qkv, blk.attn.q_norm.weight, blk.attn.k_norm.weight, rope.freqs_cos, rope.freqs_sin, heads, blk.attn.q_norm.eps)
     if _FUSED_ATTN and ops.attention_heads_supported(n, d):

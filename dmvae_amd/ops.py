@@ -1071,15 +1071,34 @@ def attention_qkv_stream(qkv: torch.Tensor, heads: int, scale: float, need_lse: 
 
 def attention_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, scale: float, need_lse: bool = False):
     """q, k [B*H, N, Dp], v [B*H, N, D] (bf16, as `qknorm_rope` returns them) -> softmax(scale q k^T) v as [B, N, H*D] bf16, one fused kernel; with need_lse also
-    lse [B*H, N] f32 for `attention_bwd_heads`."""
+    lse [B*H, N] f32 for `attention_bwd_heads`.  Up to 288 tokens the kernel that keeps a head's K / V resident in LDS (csrc/vit.hip), beyond that the
+    streaming-softmax kernel (`attention_heads_stream`: head dims 64 and 72)."""
     q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v")
     bh, n, dp = q.shape
+    if n > ATTENTION_RESIDENT_MAX:
+        return attention_heads_stream(q, k, v, batch, scale, need_lse)
     d = v.shape[-1]
     heads = bh // batch
     out = torch.empty(batch, n, heads * d, dtype=bf16, device=q.device)
     lse = torch.empty(bh, n, dtype=f32, device=q.device) if need_lse else None
     check(_lib.lib().dmvae_attention_heads_lse_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), batch, n, heads, d, dp, float(scale),
                                                     _stream()), "attention_heads_bf16")
+    return (out, lse) if need_lse else out
+
+
+def attention_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, scale: float, need_lse: bool = False):
+    """`attention_heads`' operands and results at any token count N >= 1, on the kernel that streams 64-key K / V tiles through LDS with an online softmax
+    (csrc/attention_stream.hip; head dim 64 or 72, q / k rows of D channels or D rounded up to 32): nothing of size N x N reaches HBM, reruns and batch splits
+    are bit-identical."""
+    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v")
+    bh, n, dp = q.shape
+    d = v.shape[-1]
+    heads = bh // batch
+    assert k.shape == q.shape and v.shape == (bh, n, d) and heads * batch == bh
+    out = torch.empty(batch, n, heads * d, dtype=bf16, device=q.device)
+    lse = torch.empty(bh, n, dtype=f32, device=q.device) if need_lse else None
+    check(_lib.lib().dmvae_attention_heads_stream_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), batch, n, heads, d, dp, float(scale),
+                                                       _stream()), "attention_heads_stream_bf16")
     return (out, lse) if need_lse else out
 
 
@@ -1133,9 +1152,12 @@ def attention_bwd_qkv_stream(qkv: torch.Tensor, out: torch.Tensor, dout: torch.T
 
 def attention_bwd_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, batch: int, scale: float,
                         lse: Optional[torch.Tensor] = None):
-    """(dq, dk [B*H,N,Dp], dv [B*H,N,D]) of `attention_heads` from its operands, its result `out` [B,N,H*D] and d(out)."""
+    """(dq, dk [B*H,N,Dp], dv [B*H,N,D]) of `attention_heads` from its operands, its result `out` [B,N,H*D] and d(out).  Up to 288 tokens one fused kernel with a
+    head resident in LDS (csrc/attention_bwd.hip); beyond that the streaming kernels (`attention_bwd_heads_stream`), which need `lse`."""
     q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
     bh, n, dp = q.shape
+    if n > ATTENTION_RESIDENT_MAX:
+        return attention_bwd_heads_stream(q, k, v, out, dout, batch, scale, lse)
     d = v.shape[-1]
     heads = bh // batch
     assert out.shape == (batch, n, heads * d) and dout.shape == out.shape
@@ -1146,8 +1168,34 @@ def attention_bwd_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: 
     return dq, dk, dv
 
 
+def attention_bwd_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, batch: int, scale: float,
+                               lse: Optional[torch.Tensor]):
+    """`attention_bwd_heads`' operands and results at any token count N >= 1, on the kernels that stream 64-row tiles through LDS (csrc/attention_bwd_stream.hip;
+    head dim 64 or 72): a query pass for dQ and a key pass for dK / dV.  `lse` [B*H, N] f32 from the forward is required.  Nothing of size N x N reaches HBM -- the
+    only scratch is delta [B*H, N] f32 -- and reruns and batch splits are bit-identical."""
+    if lse is None:
+        raise ValueError("attention_bwd_heads_stream needs the forward's lse (attention_heads(..., need_lse=True))")
+    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
+    bh, n, dp = q.shape
+    d = v.shape[-1]
+    heads = bh // batch
+    assert k.shape == q.shape and v.shape == (bh, n, d) and heads * batch == bh
+    assert out.shape == (batch, n, heads * d) and dout.shape == out.shape
+    assert lse.dtype == f32 and lse.is_contiguous() and lse.shape == (bh, n)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty(bh, n, dtype=f32, device=q.device)
+    check(_lib.lib().dmvae_attention_bwd_heads_stream_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dq.data_ptr(),
+                                                           dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), batch, n, heads, d, dp, float(scale), _stream()),
+          "attention_bwd_heads_stream_bf16")
+    return dq, dk, dv
+
+
 def attention_heads_supported(n: int, d: int) -> bool:
-    return n <= 288 and d % 8 == 0 and (d + 31) // 32 * 32 in (64, 96)
+    """Whether `attention_heads` / `attention_bwd_heads` take n tokens at head dim d: head dims 64 and 72 at any token count (resident kernels up to 288 tokens,
+    streaming beyond), the other head dims of the resident kernels' staged widths (40, 48, ... 96) up to 288 tokens."""
+    if d in (64, 72):
+        return n >= 1
+    return n <= ATTENTION_RESIDENT_MAX and d % 8 == 0 and (d + 31) // 32 * 32 in (64, 96)
 
 
 def scale_residual_layernorm_(x: torch.Tensor, r: torch.Tensor, ls_gamma: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:

@@ -425,6 +425,12 @@ int dmvae_attention_heads_lse_bf16(const void* q, const void* k, const void* v, 
  * are bit-identical.  The shapes beyond _qkv's 288 tokens: patch_size 8 at 256 px = 1025 tokens, 384 px at patch 16 = 577.  Any seq >= 1, head_dim 64, scale > 0;
  * everything else is rejected before any HIP call.  Reference: models/dino_layers/attention.py:56-69 with patch_size / img_size passed through models/vae.py:38-50. */
 int dmvae_attention_qkv_stream_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, dmvae_stream_t stream);
+/* _heads' operands and results at ANY token count, on the same streaming kernel (csrc/attention_stream.hip, instantiated at the staged head dims 64 and 96):
+ * LightningDiT's attention after QK-norm + RoPE beyond 288 tokens -- a 32 x 32 latent grid at patch 1 is 1024 tokens, 24 x 24 is 576.  head_dim 64 or 72;
+ * head_dim_padded = head_dim (rows without padding) or head_dim rounded up to 32 (rows zero-padded by the producer): the kernel reads the head_dim real channels of
+ * a row either way and computes the same bits.  lse as above, or NULL.  Any seq >= 1, scale > 0; everything else is rejected before any HIP call. */
+int dmvae_attention_heads_stream_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
+                                      int head_dim_padded, float scale, dmvae_stream_t stream);
 /* The whole attention of a LightningDiT block from the qkv Linear's output [batch][seq][3][heads][head_dim] bf16: per-head RMSNorm (bf16 result) * weight
  * and the 2-D rotary embedding (the arithmetic of dmvae_qknorm_rope_bf16; cos / sin tables [seq][head_dim] f32) are applied to q and k as they enter the
  * fused kernel -> out [batch][seq][heads*head_dim].  lightningdit.py:66-88 in one launch, no head-major q / k / v in HBM.  head_dim % 8 == 0, <= 96; seq <= 288. */
@@ -451,6 +457,12 @@ int dmvae_attention_bwd_heads_lse_bf16(const void* q, const void* k, const void*
  * rejected before any HIP call.  Reference: autograd of models/dino_layers/attention.py:56-69 at the token counts of models/vae.py:38-50 (train_dmd.py:349,519). */
 int dmvae_attention_bwd_qkv_stream_bf16(const void* qkv, const void* out, const void* dout, const void* lse, void* dqkv, void* delta, int batch, int seq, int heads,
                                         int head_dim, float scale, dmvae_stream_t stream);
+/* _bwd_heads_lse's operands and results at ANY token count, on the same two streaming passes (the backward of dmvae_attention_heads_stream_bf16): head_dim 64 or 72,
+ * head_dim_padded = head_dim or head_dim rounded up to 32 (the padded columns of dq / dk are written as zeros).  lse REQUIRED, delta = batch * heads * seq floats of
+ * caller-provided scratch, overwritten.  Fixed summation order: reruns and batch splits are bit-identical.  Everything else is rejected before any HIP call. */
+int dmvae_attention_bwd_heads_stream_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq, void* dk,
+                                          void* dv, void* delta, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale,
+                                          dmvae_stream_t stream);
 
 /* Backward side of the same encoder block, for the stages where the encoder trains (train_dmd.py:349,519).  Residual stream f32,
  * Linear operands / results bf16 (autocast).  workspace: dmvae_vit_bwd_workspace(c) bytes.

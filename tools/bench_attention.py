@@ -11,7 +11,12 @@ modules under autocast(bf16) -- the only way to run that shape before the stream
 `--stream-bwd` runs the backward section alone (`--out FILE` writes its table): `ops.attention_bwd_qkv_stream` (csrc/attention_bwd_stream.hip) against the
 GEMM-composed `functional._attention_bwd` at S = 577 and 1025, B x H = 32 x 16, rounds interleaved in one process, median and minimum; 10 S^2 64 FLOP per head
 (the five products of the minimal form; the kernels run seven).  Then the peak allocation of one trainable ViT-L block's backward at 1025 tokens, B = 16, on
-either attention backward."""
+either attention backward.
+
+`--heads-stream` / `--heads-stream-bwd` (either or both in one run; `--out FILE` writes their tables): LightningDiT's attention beyond 288 tokens on head-major
+operands -- `ops.attention_heads_stream` / `ops.attention_bwd_heads_stream` (the same two source files, instantiated at the staged head dims 64 and 96) against the
+composed route of `lightningdit_fast._attention` / `functional.DitBlockFn` built from this build's own ops (f32-score GEMM + row softmax + GEMM, P saved for the
+backward), at B x H = 16 x 16, N = 576 and 1024, D = 72 and 64; rounds interleaved in one process, median, minimum and spread."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -33,7 +38,7 @@ def timed(fn, n=50):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-SECTION_ONLY = "--stream-only" in sys.argv or "--stream-bwd" in sys.argv
+SECTION_ONLY = any(f in sys.argv for f in ("--stream-only", "--stream-bwd", "--heads-stream", "--heads-stream-bwd"))
 for B in (() if SECTION_ONLY else (16, 32, 64)):
     H, N, D, DP = 16, 256, 72, 96
     q = torch.zeros(B * H, N, DP, device="cuda", dtype=BF); k = torch.zeros_like(q)
@@ -196,8 +201,73 @@ def stream_bwd_section(out_path):
             f.write(text + "\n")
 
 
+# ---- LightningDiT's head-major attention beyond 288 tokens ----------------------------------------------------------------------------------------------
+def heads_stream_section(fwd, bwd, out_path):
+    import torch.nn.functional as F
+    B, H = 16, 16
+    cases, lines = {}, []
+    for D in (72, 64):
+        DP, scale = (D + 31) // 32 * 32, D ** -0.5
+        for N in (576, 1024):
+            q, k = (F.pad(torch.randn(B * H, N, D, device="cuda", generator=g), (0, DP - D)).to(BF).contiguous() for _ in range(2))
+            v = torch.randn(B * H, N, D, device="cuda", generator=g).to(BF)
+            out, lse = ops.attention_heads_stream(q, k, v, B, scale, need_lse=True)
+            tag = f"D={D} N={N:4d}"
+
+            def comp_fwd(q=q, k=k, v=v, scale=scale):      # lightningdit_fast._attention / DitBlockFn.forward above the cap before the streaming kernels
+                p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), scale)
+                return p, ops.gemm_nt(p, ops.transpose_last2(v))
+            p, oc = comp_fwd()
+            a = out.view(B, N, H, D).permute(0, 2, 1, 3).reshape(B * H, N, D).float()
+            lines.append(f"{tag}: streaming vs composed out rel-L2 {((a - oc.float()).norm() / oc.float().norm()).item():.2e}")
+            if fwd:
+                cases[f"fwd streaming + lse  {tag}"] = (4.0, D, N, lambda q=q, k=k, v=v, scale=scale: ops.attention_heads_stream(q, k, v, B, scale, need_lse=True))
+                cases[f"fwd composed         {tag}"] = (4.0, D, N, comp_fwd)
+            if bwd:
+                dout = torch.randn(out.shape, device="cuda", generator=g).to(BF)
+                do_h = dout.view(B, N, H, D).permute(0, 2, 1, 3).reshape(B * H, N, D).contiguous()
+                do_p, v_p = (F.pad(do_h, (0, DP - D)), F.pad(v, (0, DP - D))) if DP > D else (do_h, v)
+
+                def comp_bwd(q=q, k=k, p=p, do_h=do_h, do_p=do_p, v_p=v_p, scale=scale):      # DitBlockFn.backward's composed branch on the saved P
+                    ds = ops.softmax_rows_bwd(ops.gemm_nt(do_p, v_p, out_f32=True), p, scale)
+                    return ops.gemm_nt(ds, ops.transpose_last2(k)), ops.gemm_tn(ds, q), ops.gemm_tn(p, do_h)
+                gs, gc = ops.attention_bwd_heads_stream(q, k, v, out, dout, B, scale, lse), comp_bwd()
+                lines.append(f"{tag}: streaming vs composed " + "  ".join(f"{n_} rel-L2 {((x.float() - y.float()).norm() / y.float().norm()).item():.2e}"
+                                                                            for n_, x, y in zip(("dq", "dk", "dv"), gs, gc)))
+                del gs, gc
+                cases[f"bwd streaming        {tag}"] = (10.0, D, N, lambda q=q, k=k, v=v, out=out, dout=dout, lse=lse, scale=scale:
+                                                        ops.attention_bwd_heads_stream(q, k, v, out, dout, B, scale, lse))
+                cases[f"bwd composed         {tag}"] = (10.0, D, N, comp_bwd)
+            del p, oc, a
+    rounds, calls = 7, 10
+    times = {k_: [] for k_ in cases}
+    for _ in range(rounds):                 # interleaved rounds
+        for k_, (_, _, _, fn) in cases.items():
+            times[k_].append(timed(fn, n=calls))
+    lines += [f"LightningDiT attention on head-major operands, B x H = {B} x {H}, random data, {rounds} interleaved rounds of {calls} calls; TFLOP/s on 4 (forward) / 10 "
+              f"(backward) N^2 D FLOP per head; composed = f32-score GEMM + row softmax + GEMM from this build's own ops, P saved for its backward",
+              f"{'case':36s} {'median us':>10s} {'min us':>10s} {'max us':>10s} {'TF/s (median)':>14s}"]
+    med = {}
+    for k_, (fpp, D, N, _) in cases.items():
+        t = sorted(times[k_])
+        med[k_] = t[len(t) // 2]
+        lines.append(f"{k_:36s} {med[k_]:10.1f} {t[0]:10.1f} {t[-1]:10.1f} {fpp * B * H * N * N * D / med[k_] * 1e-6:14.1f}")
+    for k_ in cases:
+        if "streaming" in k_:
+            twin = k_.replace("streaming + lse", "composed       ").replace("streaming", "composed ")
+            lines.append(f"{k_[:3]} {k_[-13:]}: composed / streaming (median) = {med[twin] / med[k_]:.2f}")
+    text = "\n".join(lines)
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
-if "--stream-bwd" in sys.argv:
+if "--heads-stream" in sys.argv or "--heads-stream-bwd" in sys.argv:
+    heads_stream_section("--heads-stream" in sys.argv, "--heads-stream-bwd" in sys.argv, OUT)
+elif "--stream-bwd" in sys.argv:
     stream_bwd_section(OUT)
 else:
     stream_section(OUT)
