@@ -1,4 +1,4 @@
-// Backward of the fused multi-head self-attention of vit.hip (timm Attention / dino_layers/attention.py:56-69 for the trainable ViT encoder of
+// Backward of the fused multi-head self-attention of attention.hip (timm Attention / dino_layers/attention.py:56-69 for the trainable ViT encoder of
 // train_dmd.py:349,519; LightningDiT's Attention, diffusion/lightningdit/lightningdit.py:76-88, for the student's training turn) -- S <= 288 tokens,
 // head dim 64 (ViT) or 72 zero-padded to 96 (LightningDiT-XL).  Replaces autograd's SDPA backward; the GEMM-composed version this build used before
 // moved the S x S scores / probabilities through HBM four times per block.
@@ -19,16 +19,16 @@
 //     (row * 12 mod 16 cycles through {0, 12, 8, 4}, the XOR through the other two bits);
 //   transpose reads (ds_read_b64_tr_b16, B fragments with the reduction along tokens): the four rows of a pass start 48 banks apart, i.e. in four
 //     different 16-bank quarters, and a pass reads one whole 64-B segment of each -- the XOR only permutes inside it.
-#include "common.h"
+#include "attention_common.h"
 #include "dmvae_hip.h"
 
 namespace dmvae_attn_bwd {
 
-constexpr int KEYS = 288, NB = KEYS / 32, PITCH = 192;
+constexpr int KEYS = ATT_RESIDENT_KEYS, NB = KEYS / 32, PITCH = 192;
 constexpr int BUF = KEYS * PITCH;
 
 struct Args {
-  const bf16 *q, *k, *v;         // per (batch, head): base + b * bs + h * hs, token rows rs elements apart; q / k rows hold DP (padded) channels
+  const bf16 *q, *k, *v;         // the operand fields, named as attention_common.h says; q / k rows hold DP (padded) channels
   const bf16 *o, *dout;          // [B][S][H * D]
   bf16 *dq, *dk, *dv;            // same geometry as q / k / v
   long long q_bs, q_hs, k_bs, k_hs, v_bs, v_hs;
@@ -37,7 +37,7 @@ struct Args {
   int QD;                        // channels a q / k / dq / dk row holds: DP (zero-padded by the producer) or D itself (rows 2 D bytes apart: chunks past QD are neither loaded nor stored)
   float scale;
   const float* lse;              // attention_bwd_lse_kernel: [B * H][S] f32, scale * max + log(sum) of every query's scaled scores (the forward kernel writes it)
-  int xcd;                       // 1: block -> (batch, head) through xcd_remap (vit.hip::AttnArgs::xcd)
+  int xcd;                       // 1: block -> (batch, head) through xcd_remap (attention.hip::AttnArgs::xcd)
 };
 
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * PITCH + (((chunk & ~3) | ((chunk & 3) ^ ((row >> 2) & 3))) << 4); }
@@ -66,7 +66,7 @@ struct LayTight {
     return v;
   }
 };
-// dot8 and to_afrag (the C-layout -> A-fragment conversion by v_permlane32_swap): common.h, shared with attention_bwd_stream.hip
+// dot8 and to_afrag (the C-layout -> A-fragment conversion by v_permlane32_swap): attention_common.h, shared with attention_bwd_stream.hip
 
 template <int DP>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(Args a) {
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(512) void attention_bwd_lse_kernel(Args a) {
   const int nblk = (S + 31) >> 5;
   const int rows_staged = nblk * 32;
 
-  // every global load of a staging is issued before its first LDS store (vit.hip's forward staging: the loop form waits for each sweep's loads before issuing the
+  // every global load of a staging is issued before its first LDS store (attention.hip's forward staging: the loop form waits for each sweep's loads before issuing the
   // next sweep's -- seven serial memory round trips per staging at DP = 96)
   constexpr int SWEEPS = (KEYS * CH + NT - 1) / NT;
   auto stage = [&](const bf16* s0, int rs0, int ch0, const bf16* s1, int rs1, int ch1) {
@@ -939,15 +939,11 @@ extern "C" int dmvae_attention_bwd_qkv_lse_bf16(const void* qkv, const void* out
                                                 int head_dim, float scale, hipStream_t stream) {
   using namespace dmvae_attn_bwd;
   DMVAE_CHECK_ARG(qkv && out && dout && dqkv && batch > 0 && heads > 0 && seq > 0, "attention_bwd_qkv_bf16: bad argument");
-  DMVAE_CHECK_ARG(head_dim == 64 && seq <= KEYS, "attention_bwd_qkv_bf16: needs head_dim 64 and seq <= 288 (got %d, %d)", head_dim, seq);
-  const long long C = (long long)heads * head_dim;
+  DMVAE_CHECK_ARG(head_dim == 64 && seq <= KEYS, "attention_bwd_qkv_bf16: needs head_dim 64 and seq <= %d (got %d, %d)", KEYS, head_dim, seq);
   Args a = {};
-  a.q = (const bf16*)qkv; a.k = a.q + C; a.v = a.q + 2 * C;
-  a.dq = (bf16*)dqkv; a.dk = a.dq + C; a.dv = a.dq + 2 * C;
-  a.o = (const bf16*)out; a.dout = (const bf16*)dout;
-  a.q_bs = a.k_bs = a.v_bs = (long long)seq * 3 * C; a.q_hs = a.k_hs = a.v_hs = head_dim;
-  a.q_rs = a.k_rs = a.v_rs = (int)(3 * C);
-  a.S = seq; a.H = heads; a.D = head_dim; a.QD = head_dim; a.scale = scale; a.lse = (const float*)lse;
+  attn_operands_qkv(a, qkv, seq, heads, head_dim);
+  attn_grads_qkv(a, dqkv, heads, head_dim);
+  a.o = (const bf16*)out; a.dout = (const bf16*)dout; a.D = head_dim; a.QD = head_dim; a.scale = scale; a.lse = (const float*)lse;
   return launch<64>(a, batch, stream);
 }
 
@@ -955,16 +951,11 @@ extern "C" int dmvae_attention_bwd_heads_lse_bf16(const void* q, const void* k, 
                                                   void* dv, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale, hipStream_t stream) {
   using namespace dmvae_attn_bwd;
   DMVAE_CHECK_ARG(q && k && v && out && dout && dq && dk && dv && batch > 0 && heads > 0 && seq > 0, "attention_bwd_heads_bf16: bad argument");
-  const int dpc = (head_dim_padded + 31) / 32 * 32;      // q / k / dq / dk rows of 64 / 96 channels (zero-padded) or of head_dim channels (vit.hip: dmvae_attention_heads_lse_bf16)
-  DMVAE_CHECK_ARG(seq <= KEYS && head_dim % 8 == 0 && head_dim <= head_dim_padded && (head_dim_padded == 64 || head_dim_padded == 96 || head_dim_padded == head_dim) &&
-                  (dpc == 64 || dpc == 96),
-                  "attention_bwd_heads_bf16: needs seq <= 288, head_dim %% 8 == 0, q / k rows of 64, 96 or head_dim <= 96 channels (got %d, %d, %d)", seq, head_dim, head_dim_padded);
+  const int dpc = attn_resident_heads_check("attention_bwd_heads_bf16", seq, head_dim, head_dim_padded);      // the staged width (q / k / dq / dk rows as attention.hip's entry takes them)
+  if (dpc < 0) return dpc;
   Args a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)out; a.dout = (const bf16*)dout;
-  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv;
-  a.q_hs = a.k_hs = (long long)seq * head_dim_padded; a.q_bs = a.k_bs = a.q_hs * heads;
-  a.v_hs = (long long)seq * head_dim; a.v_bs = a.v_hs * heads;
-  a.q_rs = a.k_rs = head_dim_padded; a.v_rs = head_dim;
-  a.S = seq; a.H = heads; a.D = head_dim; a.QD = head_dim_padded; a.scale = scale; a.lse = (const float*)lse;
+  attn_operands_heads(a, q, k, v, seq, heads, head_dim, head_dim_padded);
+  attn_grads_heads(a, dq, dk, dv);
+  a.o = (const bf16*)out; a.dout = (const bf16*)dout; a.D = head_dim; a.QD = head_dim_padded; a.scale = scale; a.lse = (const float*)lse;
   return dpc == 64 ? launch<64>(a, batch, stream) : launch<96>(a, batch, stream);
 }

@@ -6,7 +6,7 @@
 //   P = exp(scale s - L)      dV = P^T dO      dP = dO V^T      dS = P o (dP - delta),  delta_q = dO_q . O_q      dQ = scale dS K      dK = scale dS^T Q
 //
 // Operands: qkv [B][S][3][H][64] bf16 (the qkv Linear's output), out / dout [B][S][H*64] bf16, lse [B*H][S] f32 = scale * max + log(sum) of a query's scaled scores
-// (what attention_stream.hip and vit.hip write), dqkv in qkv's layout.
+// (what attention_stream.hip and attention.hip write), dqkv in qkv's layout.
 //
 // Two passes on one stream, the two-orientation form of attention_bwd.hip (seven S x S x 64 contractions instead of five: S and dP are formed with the queries on the
 // lanes AND with the keys on the lanes).  The alternatives sum dQ across workgroups -- float atomics (no fixed order) or an ordered hand-off between resident workgroups
@@ -21,7 +21,7 @@
 //     dV += P^T dO and dK += dS^T Q through transpose reads of dO / Q.  L and delta of a tile's 64 queries travel with it.
 // Tile walk as attention_stream.hip: tiles double-buffered in LDS through register staging (every thread carries one 16-B piece of each of the next tile's two operands,
 // loaded behind the first block's products, written to the OTHER buffer at the end of the iteration), one barrier per tile, one flat grid through xcd_remap so that
-// the blocks of one head share an XCD's L2.  An operand that is read by rows AND transposed is staged twice, once per layout of common.h (att_kslot: conflict-free
+// the blocks of one head share an XCD's L2.  An operand that is read by rows AND transposed is staged twice, once per layout of attention_common.h (att_kslot: conflict-free
 // ds_read_b128 rows; att_vslot: ds_read_b64_tr_b16): query pass K rows | K transposed | V rows = 24 KiB per buffer, 48 KiB static; key pass Q rows | Q transposed |
 // dO rows | dO transposed | L, delta = 32.5 KiB per buffer, 65 KiB dynamic (opt-in).
 //
@@ -36,7 +36,7 @@
 //
 // Both kernels are templates on DP, the staged head dim.  DP = 64 is everything above: the encoder's entry dmvae_attention_bwd_qkv_stream_bf16, and head-major
 // operands of head dim 64.  DP = 96 is LightningDiT's head dim 72 on the head-major operands of dmvae_qknorm_rope_bf16 (q, k, dq, dk [B*H][N][72 or 96], v, dv
-// [B*H][N][72]; entry dmvae_attention_bwd_heads_stream_bf16): 256-B rows in the layouts of the 96-wide resident kernel (common.h att_kslot<256> / att_vslot<256>),
+// [B*H][N][72]; entry dmvae_attention_bwd_heads_stream_bf16): 256-B rows in the layouts of the 96-wide resident kernel (attention_common.h att_kslot<256> / att_vslot<256>),
 // 16-KiB images.  The channels 72 .. 95 are zeros in LDS and never loaded, the products over channels take five 16-channel steps (upper half of the fifth zero, the
 // sixth skipped), the accumulators are three 32-channel blocks; dV columns >= 72 are not stored and the padded columns of dq / dk (rows of 96) are written as the
 // exact zeros the zero K / Q channels produce.  The operands are described by strides, q / k and v separately (head-major v rows are 72 wide, q / k rows 72 or 96).
@@ -51,43 +51,36 @@
 //   DP = 64 key pass (8 waves): 238 VGPRs, 0 AGPRs, 54 SGPRs (before: 48), 65 KiB dynamic LDS; 2 waves per SIMD = one workgroup per CU (registers and LDS agree).
 //   DP = 96 query pass (8 waves): 216 VGPRs, 0 AGPRs, 54 SGPRs, 96 KiB dynamic LDS; 2 waves per SIMD = one workgroup per CU.
 //   DP = 96 key pass (4 waves): 234 VGPRs, 128 AGPRs, 59 SGPRs, 129 KiB dynamic LDS; 1 wave per SIMD = one workgroup per CU.
-#include "common.h"
+#include "attention_common.h"
 #include "dmvae_hip.h"
-#include <math.h>
 
 namespace dmvae_attn_bwd_stream {
 
 constexpr int NTQ = 512;         // query pass: 8 waves
 constexpr int BW = 32;           // rows (queries / keys) a wave owns
-constexpr int TT = 64;           // rows per streamed tile
-// DP: head dim as staged.  64: head dim 64, 128-B rows in LDS.  96: head dim 72 (LightningDiT-XL), 256-B rows -- common.h's layouts of the 96-wide resident kernel;
-// the channels 72 .. 95 are zeros in LDS (never loaded), the sixth 16-channel step of the products over channels is skipped, the upper half of the fifth is zero,
-// dV columns >= 72 and dQ / dK columns past the row width are not stored.  NT: threads of the workgroup (the key pass at 96 runs four waves: file header).
-template <int DP, int NT = NTQ> struct Geo {
-  static_assert(DP == 64 || DP == 96, "staged head dim 64 or 96");
-  static constexpr int D = DP == 64 ? 64 : 72;      // real head dim: v / out / dout width, the channels of a q / k row that are read
-  static constexpr int ROW = DP == 64 ? 128 : 256;  // bytes per row in LDS
-  static constexpr int TILE = TT * ROW;             // 8 / 16 KiB
-  static constexpr int KS = DP == 64 ? 4 : 5;       // 16-channel steps of the products over channels
-  static constexpr int DB = DP / 32;                // 32-channel blocks of the accumulators
-  static constexpr int CPR = ROW / 16;              // staging lanes per row: one 16-B chunk each
-  static constexpr int SW = TT * CPR / NT;          // staging sweeps per tile
-  static constexpr int BB = BW * NT / 64;           // rows a workgroup owns
-  static constexpr int DQ_BUF = 3 * TILE;                                    // K rows | K transposed | V rows
-  static constexpr int DKDV_BUF = 4 * TILE + 2 * TT * (int)sizeof(float);    // Q rows | Q transposed | dO rows | dO transposed | L [64] | delta [64]
+constexpr int TT = ATT_STREAM_TILE;       // rows per streamed tile
+// attention_common.h's tile geometry (dV columns >= 72 and dQ / dK columns past the row width are not stored) plus the two passes' LDS images.  NT: threads of the
+// workgroup (the key pass at 96 runs four waves: file header).
+template <int DP, int NT = NTQ> struct Geo : AttnStreamGeo<DP, NT> {
+  static constexpr int DQ_BUF = 3 * Geo::TILE;                                    // K rows | K transposed | V rows
+  static constexpr int DKDV_BUF = 4 * Geo::TILE + 2 * TT * (int)sizeof(float);    // Q rows | Q transposed | dO rows | dO transposed | L [64] | delta [64]
 };
 
+// The operand fields, named as attention_common.h says.  Both passes address q AND k (and dq, dk) through q's geometry (q_*): the two always share one (packed qkv: the
+// same strides; head-major: the same row width).  v and dv have their own (v_*).  At DP = 96 q_rs is also the width of a q / k / dq / dk row (72 or 96).
 struct Args {
-  const bf16 *q, *k, *v;     // per (sample, head) base + b * bs + h * hs, token rows rs elements apart: q and k share one geometry (qk_*), v has its own (v_*)
+  const bf16 *q, *k, *v;
   const bf16 *o, *dout;      // [B][S][H * D]
   bf16 *dq, *dk, *dv;        // dq, dk in q's geometry, dv in v's
   const float* lse;          // [B * H][S]
   float* delta;              // [B * H][S]: written by the query pass, read by the key pass
-  long long qk_bs, qk_hs, v_bs, v_hs;      // elements
-  int qk_rs, v_rs;           // elements between token rows; at DP = 96 qk_rs is also the width of a q / k / dq / dk row (72 or 96)
+  long long q_bs, q_hs, v_bs, v_hs;      // elements
+  int q_rs, v_rs;            // elements between token rows
   int S, H;
   int nb;                    // row blocks per (sample, head) of the kernel being launched
   float scale;
+  long long k_bs, k_hs;      // k's geometry as the shared recipes fill it: equal to q's, and read by neither kernel (behind everything they load, so the loads keep their places)
+  int k_rs;
 };
 
 // the query pass' images: static up to 64 KiB (the 64-wide form, as before), the launch's dynamic LDS beyond
@@ -102,21 +95,6 @@ __device__ __forceinline__ char* dq_image() {
   }
 }
 
-// transpose-read addressing in an att_vslot image (as attention_stream.hip): the lane supplies 4 channels of row 8 kg + rr (and + 4) of a 16-row step; channel block
-// db is the 64-B segment db ^ swizzle: offset ^ (db << 6)
-template <int ROW>
-__device__ __forceinline__ int tr_off0(int lane) {
-  const int kg = lane >> 5, g16 = (lane >> 4) & 1, rr = (lane & 15) >> 2, qq = lane & 3;
-  return (kg * 8 + rr) * ROW + ((ROW == 128 ? (rr >> 1) & 1 : rr) << 6) + (16 * g16 + 4 * qq) * 2;
-}
-template <int ROW>
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int step16, int off0, int db) {
-  union { bf16x8 v; s16x4 hlf[2]; } f;
-  f.hlf[0] = tr_read_ordered(img + step16 * (16 * ROW) + (off0 ^ (db << 6)));
-  f.hlf[1] = tr_read_ordered(img + step16 * (16 * ROW) + (off0 ^ (db << 6)) + 4 * ROW);
-  return f.v;
-}
-
 template <int DP>
 __global__ __launch_bounds__(NTQ) void attention_bwd_stream_dq_kernel(Args a) {
 #if __HIP_DEVICE_COMPILE__
@@ -128,7 +106,7 @@ __global__ __launch_bounds__(NTQ) void attention_bwd_stream_dq_kernel(Args a) {
   const unsigned item = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = (int)(item / (unsigned)a.nb), blk = (int)(item % (unsigned)a.nb);
   const int b = bh / a.H, h = bh % a.H;
-  const size_t base = (size_t)b * a.qk_bs + h * a.qk_hs, vbase = (size_t)b * a.v_bs + h * a.v_hs;
+  const size_t base = (size_t)b * a.q_bs + h * a.q_hs, vbase = (size_t)b * a.v_bs + h * a.v_hs;
   const bf16 *qp = a.q + base, *kp = a.k + base, *vp = a.v + vbase;
   const bf16* og = a.o + (size_t)b * S * C + h * D;
   const bf16* dog = a.dout + (size_t)b * S * C + h * D;
@@ -151,7 +129,7 @@ __global__ __launch_bounds__(NTQ) void attention_bwd_stream_dq_kernel(Args a) {
       const int key = t * TT + skey + it * (NT / CPR);
       kreg[it] = uint4{0, 0, 0, 0}; vreg[it] = uint4{0, 0, 0, 0};
       if (key < S && (DP == 64 || sc < D / 8)) {
-        kreg[it] = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.qk_rs + sc * 8);
+        kreg[it] = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.q_rs + sc * 8);
         vreg[it] = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.v_rs + sc * 8);
       }
     }
@@ -175,7 +153,7 @@ __global__ __launch_bounds__(NTQ) void attention_bwd_stream_dq_kernel(Args a) {
     uint4 tq = {0, 0, 0, 0}, td = {0, 0, 0, 0}, to = {0, 0, 0, 0};
     const int d0 = kk * 16 + kg * 8;
     if (q < S && (DP == 64 || d0 < D)) {
-      tq = *reinterpret_cast<const uint4*>(qp + (size_t)q * a.qk_rs + d0);
+      tq = *reinterpret_cast<const uint4*>(qp + (size_t)q * a.q_rs + d0);
       td = *reinterpret_cast<const uint4*>(dog + (size_t)q * C + d0);
       to = *reinterpret_cast<const uint4*>(og + (size_t)q * C + d0);
     }
@@ -269,7 +247,7 @@ __global__ __launch_bounds__(NTQ) void attention_bwd_stream_dq_kernel(Args a) {
 #pragma unroll
     for (int r = 0; r < 16; r++) {
       const int qo = q0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-      if (qo < S && (DP == 64 || db * 32 + ql < a.qk_rs)) dqg[(size_t)qo * a.qk_rs + db * 32 + ql] = (bf16)dq[db][r];
+      if (qo < S && (DP == 64 || db * 32 + ql < a.q_rs)) dqg[(size_t)qo * a.q_rs + db * 32 + ql] = (bf16)dq[db][r];
     }
 #endif
 }
@@ -285,7 +263,7 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
   const unsigned item = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = (int)(item / (unsigned)a.nb), blk = (int)(item % (unsigned)a.nb);
   const int b = bh / a.H, h = bh % a.H;
-  const size_t base = (size_t)b * a.qk_bs + h * a.qk_hs, vbase = (size_t)b * a.v_bs + h * a.v_hs;
+  const size_t base = (size_t)b * a.q_bs + h * a.q_hs, vbase = (size_t)b * a.v_bs + h * a.v_hs;
   const bf16 *qp = a.q + base, *kp = a.k + base, *vp = a.v + vbase;
   const bf16* dog = a.dout + (size_t)b * S * C + h * D;
   const float* lse = a.lse + (size_t)bh * S;
@@ -310,7 +288,7 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
       const int row = t * TT + srow + it * (NT / CPR);
       qreg[it] = uint4{0, 0, 0, 0}; dreg[it] = uint4{0, 0, 0, 0};
       if (row < S && (DP == 64 || sc < D / 8)) {
-        qreg[it] = *reinterpret_cast<const uint4*>(qp + (size_t)row * a.qk_rs + sc * 8);
+        qreg[it] = *reinterpret_cast<const uint4*>(qp + (size_t)row * a.q_rs + sc * 8);
         dreg[it] = *reinterpret_cast<const uint4*>(dog + (size_t)row * C + sc * 8);
       }
     }
@@ -340,7 +318,7 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
     uint4 tk = {0, 0, 0, 0}, tv = {0, 0, 0, 0};
     const int d0 = kk * 16 + kg * 8;
     if (key < S && (DP == 64 || d0 < D)) {
-      tk = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.qk_rs + d0);
+      tk = *reinterpret_cast<const uint4*>(kp + (size_t)key * a.q_rs + d0);
       tv = *reinterpret_cast<const uint4*>(vp + (size_t)key * a.v_rs + d0);
     }
     kfb[kk] = *reinterpret_cast<bf16x8*>(&tk);
@@ -438,7 +416,7 @@ __global__ __launch_bounds__(NT) void attention_bwd_stream_dkdv_kernel(Args a) {
     for (int r = 0; r < 16; r++) {
       const int ko = key0 + (r & 3) + 8 * (r >> 2) + 4 * kg;
       if (ko < S) {
-        if (DP == 64 || db * 32 + ql < a.qk_rs) dkg[(size_t)ko * a.qk_rs + db * 32 + ql] = (bf16)dk[db][r];
+        if (DP == 64 || db * 32 + ql < a.q_rs) dkg[(size_t)ko * a.q_rs + db * 32 + ql] = (bf16)dk[db][r];
         if (DP == 64 || db * 32 + ql < D) dvg[(size_t)ko * a.v_rs + db * 32 + ql] = (bf16)dv[db][r];
       }
     }
@@ -451,28 +429,18 @@ extern "C" int dmvae_attention_bwd_qkv_stream_bf16(const void* qkv, const void* 
                                                    int heads, int head_dim, float scale, hipStream_t stream) {
   using namespace dmvae_attn_bwd_stream;
   using G = Geo<64>;
-  constexpr int D = G::D, NT = NTQ, BB = G::BB, DKDV_BUF = G::DKDV_BUF;
-  DMVAE_CHECK_ARG(qkv && out && dout && dqkv, "attention_bwd_qkv_stream_bf16: null qkv, out, dout or dqkv");
-  DMVAE_CHECK_ARG(lse, "attention_bwd_qkv_stream_bf16: null lse (the forward's row statistics are required)");
-  DMVAE_CHECK_ARG(delta, "attention_bwd_qkv_stream_bf16: null delta scratch (batch * heads * seq floats)");
-  DMVAE_CHECK_ARG(batch > 0 && heads > 0 && seq >= 1, "attention_bwd_qkv_stream_bf16: needs batch, heads, seq >= 1 (got %d, %d, %d)", batch, heads, seq);
-  DMVAE_CHECK_ARG(head_dim == D, "attention_bwd_qkv_stream_bf16: needs head_dim 64 (got %d)", head_dim);
-  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "attention_bwd_qkv_stream_bf16: needs a finite scale > 0 (got %g)", (double)scale);
-  const long long C = (long long)heads * head_dim;
-  const long long nb = ((long long)seq + BB - 1) / BB, blocks = (long long)batch * heads * nb;
-  // the row stride and the (sample, head) count are ints in the kernels; the flat grid is one dimension
-  DMVAE_CHECK_ARG(3 * C <= 0x7fffffffLL && (long long)batch * heads <= 0x7fffffffLL && blocks <= 0x7fffffffLL,
-                  "attention_bwd_qkv_stream_bf16: %d x %d heads x %d tokens does not fit the grid", batch, heads, seq);
+  if (int e = attn_stream_check("attention_bwd_qkv_stream_bf16", "qkv, out, dout or dqkv", qkv && out && dout && dqkv, ATTN_PACKED, ATTN_BWD, lse, delta, batch, seq, heads, head_dim, 0,
+                                scale, G::BB)) return e;
   Args a = {};
-  a.q = (const bf16*)qkv; a.k = a.q + C; a.v = a.q + 2 * C;
-  a.dq = (bf16*)dqkv; a.dk = a.dq + C; a.dv = a.dq + 2 * C;
+  attn_operands_qkv(a, qkv, seq, heads, head_dim);
+  attn_grads_qkv(a, dqkv, heads, head_dim);
   a.o = (const bf16*)out; a.dout = (const bf16*)dout; a.lse = (const float*)lse; a.delta = (float*)delta;
-  a.qk_bs = a.v_bs = (long long)seq * 3 * C; a.qk_hs = a.v_hs = head_dim; a.qk_rs = a.v_rs = (int)(3 * C);
-  a.S = seq; a.H = heads; a.nb = (int)nb; a.scale = scale;
-  DMVAE_LDS_OPTIN(2 * DKDV_BUF, attention_bwd_stream_dkdv_kernel<64, NTQ>);
-  hipLaunchKernelGGL(attention_bwd_stream_dq_kernel<64>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+  a.nb = attn_row_blocks(seq, G::BB); a.scale = scale;
+  const dim3 grid((unsigned)(batch * heads * a.nb));
+  DMVAE_LDS_OPTIN(2 * G::DKDV_BUF, attention_bwd_stream_dkdv_kernel<64, NTQ>);
+  hipLaunchKernelGGL(attention_bwd_stream_dq_kernel<64>, grid, dim3(NTQ), 0, stream, a);
   DMVAE_CHECK_LAUNCH();
-  hipLaunchKernelGGL((attention_bwd_stream_dkdv_kernel<64, NTQ>), dim3((unsigned)blocks), dim3(NT), 2 * DKDV_BUF, stream, a);
+  hipLaunchKernelGGL((attention_bwd_stream_dkdv_kernel<64, NTQ>), grid, dim3(NTQ), 2 * G::DKDV_BUF, stream, a);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -483,41 +451,31 @@ extern "C" int dmvae_attention_bwd_heads_stream_bf16(const void* q, const void* 
                                                      void* dv, void* delta, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale,
                                                      hipStream_t stream) {
   using namespace dmvae_attn_bwd_stream;
-  DMVAE_CHECK_ARG(q && k && v && out && dout && dq && dk && dv, "attention_bwd_heads_stream_bf16: null q, k, v, out, dout, dq, dk or dv");
-  DMVAE_CHECK_ARG(lse, "attention_bwd_heads_stream_bf16: null lse (the forward's row statistics are required)");
-  DMVAE_CHECK_ARG(delta, "attention_bwd_heads_stream_bf16: null delta scratch (batch * heads * seq floats)");
-  DMVAE_CHECK_ARG(batch > 0 && heads > 0 && seq >= 1, "attention_bwd_heads_stream_bf16: needs batch, heads, seq >= 1 (got %d, %d, %d)", batch, heads, seq);
-  DMVAE_CHECK_ARG(head_dim == 64 || head_dim == 72, "attention_bwd_heads_stream_bf16: needs head_dim 64 or 72 (got %d)", head_dim);
-  DMVAE_CHECK_ARG(head_dim_padded == head_dim || head_dim_padded == (head_dim + 31) / 32 * 32,
-                  "attention_bwd_heads_stream_bf16: q / k rows hold head_dim channels or head_dim rounded up to 32 (got %d for head_dim %d)", head_dim_padded, head_dim);
-  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "attention_bwd_heads_stream_bf16: needs a finite scale > 0 (got %g)", (double)scale);
   constexpr int NTK96 = 256;      // the 96-wide key pass: four waves, 128 keys per workgroup (file header)
   constexpr int lds_dq96 = 2 * Geo<96>::DQ_BUF, lds_dkdv64 = 2 * Geo<64>::DKDV_BUF, lds_dkdv96 = 2 * Geo<96, NTK96>::DKDV_BUF;
-  const long long nbq = ((long long)seq + Geo<64>::BB - 1) / Geo<64>::BB;
-  const long long nbk = head_dim == 64 ? nbq : ((long long)seq + Geo<96, NTK96>::BB - 1) / Geo<96, NTK96>::BB;
-  // the (sample, head) count is an int in the kernels; the flat grids are one dimension
-  DMVAE_CHECK_ARG((long long)batch * heads <= 0x7fffffffLL && (long long)batch * heads * nbk <= 0x7fffffffLL,
-                  "attention_bwd_heads_stream_bf16: %d x %d heads x %d tokens does not fit the grid", batch, heads, seq);
+  if (int e = attn_stream_check("attention_bwd_heads_stream_bf16", "q, k, v, out, dout, dq, dk or dv", q && k && v && out && dout && dq && dk && dv, ATTN_HEADS, ATTN_BWD, lse, delta,
+                                batch, seq, heads, head_dim, head_dim_padded, scale, head_dim == 64 ? Geo<64>::BB : Geo<96, NTK96>::BB)) return e;
+  const int nbq = attn_row_blocks(seq, Geo<64>::BB);
+  const int nbk = head_dim == 64 ? nbq : attn_row_blocks(seq, Geo<96, NTK96>::BB);
   Args a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.o = (const bf16*)out; a.dout = (const bf16*)dout;
-  a.dq = (bf16*)dq; a.dk = (bf16*)dk; a.dv = (bf16*)dv; a.lse = (const float*)lse; a.delta = (float*)delta;
-  a.qk_hs = (long long)seq * head_dim_padded; a.qk_bs = a.qk_hs * heads; a.qk_rs = head_dim_padded;
-  a.v_hs = (long long)seq * head_dim; a.v_bs = a.v_hs * heads; a.v_rs = head_dim;
-  a.S = seq; a.H = heads; a.scale = scale;
+  attn_operands_heads(a, q, k, v, seq, heads, head_dim, head_dim_padded);
+  attn_grads_heads(a, dq, dk, dv);
+  a.o = (const bf16*)out; a.dout = (const bf16*)dout; a.lse = (const float*)lse; a.delta = (float*)delta;
+  a.scale = scale;
   const unsigned bh = (unsigned)(batch * heads);
   if (head_dim == 64) {
     DMVAE_LDS_OPTIN(lds_dkdv64, attention_bwd_stream_dkdv_kernel<64, NTQ>);
-    a.nb = (int)nbq;
+    a.nb = nbq;
     hipLaunchKernelGGL(attention_bwd_stream_dq_kernel<64>, dim3(bh * (unsigned)nbq), dim3(NTQ), 0, stream, a);
     DMVAE_CHECK_LAUNCH();
     hipLaunchKernelGGL((attention_bwd_stream_dkdv_kernel<64, NTQ>), dim3(bh * (unsigned)nbq), dim3(NTQ), lds_dkdv64, stream, a);
   } else {
     DMVAE_LDS_OPTIN(lds_dq96, attention_bwd_stream_dq_kernel<96>);
     DMVAE_LDS_OPTIN(lds_dkdv96, attention_bwd_stream_dkdv_kernel<96, NTK96>);
-    a.nb = (int)nbq;
+    a.nb = nbq;
     hipLaunchKernelGGL(attention_bwd_stream_dq_kernel<96>, dim3(bh * (unsigned)nbq), dim3(NTQ), lds_dq96, stream, a);
     DMVAE_CHECK_LAUNCH();
-    a.nb = (int)nbk;
+    a.nb = nbk;
     hipLaunchKernelGGL((attention_bwd_stream_dkdv_kernel<96, NTK96>), dim3(bh * (unsigned)nbk), dim3(NTK96), lds_dkdv96, stream, a);
   }
   DMVAE_CHECK_LAUNCH();

@@ -1,9 +1,9 @@
 // Streaming-softmax multi-head self-attention forward for gfx950 (MI355X): the encoder's attention at ANY token count -- patch 8 at 256 px is 1025 tokens, 384 px at
 // patch 16 is 577 (reference: models/dino_layers/attention.py:56-69, reached with patch_size / img_size through models/vae.py:38-50 and train_diffusion.py:54,224).
-// csrc/vit.hip's attention_kernel keeps a whole head's K and V resident in LDS and therefore stops at 288 tokens; this kernel walks 64-key tiles with an online
+// csrc/attention.hip's attention_kernel keeps a whole head's K and V resident in LDS and therefore stops at 288 tokens; this kernel walks 64-key tiles with an online
 // softmax instead.  Nothing of size S x S reaches HBM.
 //
-// Operands: the qkv Linear's output [B][S][3][H][64] bf16 described by strides (StreamArgs: per-(sample, head) base = ptr + b * bs + h * hs, token rows rs elements
+// Operands: the qkv Linear's output [B][S][3][H][64] bf16 described by strides (attention_common.h's operand fields: per-(sample, head) base = ptr + b * bs + h * hs, token rows rs elements
 // apart -- head-major operands fit the same struct), out [B][S][H*64] bf16, optional lse [B*H][S] f32 = scale * max + log(sum) of a query's scaled scores (natural
 // log: the definition of dmvae_attention_*_lse_bf16, what the LSE-consuming backward kernels rebuild P from).
 //
@@ -33,36 +33,24 @@
 //
 // Two instantiations of the one kernel (template parameter DP, the staged head dim).  DP = 64: everything above -- the encoder's entry dmvae_attention_qkv_stream_bf16
 // and head-major operands of head dim 64.  DP = 96: LightningDiT's head dim 72 on the head-major operands of dmvae_qknorm_rope_bf16 (q, k [B*H][N][72 or 96],
-// v [B*H][N][72]; entry dmvae_attention_heads_stream_bf16): K / V tiles of 256-B rows in the layouts the 96-wide resident kernel uses (common.h att_kslot<256> /
+// v [B*H][N][72]; entry dmvae_attention_heads_stream_bf16): K / V tiles of 256-B rows in the layouts the 96-wide resident kernel uses (attention_common.h att_kslot<256> /
 // att_vslot<256>), 2 x 2 x 16 KiB = 64 KiB static, two staging sweeps per tile (sixteen lanes per key row, nine of them load).  As in the resident kernels the channels
 // 72 .. 95 are zeros in LDS and never loaded -- rows padded to 96 by the producer and rows of 72 channels give the same bits --, q k^T takes five 16-channel steps (the
 // upper half of the fifth is zero, the sixth is skipped), the output accumulators are three 32-channel blocks and channels >= 72 are not stored.
 // Resources (hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage): DP = 64: 137 VGPRs, 0 AGPRs, 50 SGPRs, no scratch, no spill, 32 KiB LDS, 3 waves per
 // SIMD -- the numbers of the kernel before it was a template.  DP = 96: 186 VGPRs, 0 AGPRs, 56 SGPRs, no scratch, no spill, 64 KiB LDS, 2 waves per SIMD.
-#include "common.h"
-#include <math.h>
+#include "attention_common.h"
 
 namespace dmvae_attn_stream {
 
 constexpr int NT = 512;          // 8 waves
 constexpr int QW = 32;           // queries per wave
-constexpr int QB = QW * NT / 64; // queries per workgroup: 256
-constexpr int KT = 64;           // keys per tile
-// DP: head dim as staged.  64: head dim 64, 128-B rows in LDS.  96: head dim 72 (LightningDiT-XL), 256-B rows -- common.h's layouts of the 96-wide resident kernel;
-// the channels 72 .. 95 are zeros in LDS (never loaded), the sixth 16-channel K step is skipped, the upper half of the fifth is zero, output channels >= 72 are not stored.
-template <int DP> struct Geo {
-  static_assert(DP == 64 || DP == 96, "staged head dim 64 or 96");
-  static constexpr int D = DP == 64 ? 64 : 72;      // real head dim: V / output width, the channels of a q / k row that are read
-  static constexpr int ROW = DP == 64 ? 128 : 256;  // bytes per K / V row in LDS
-  static constexpr int TILE = KT * ROW;             // 8 / 16 KiB
-  static constexpr int KS = DP == 64 ? 4 : 5;       // 16-channel steps of q k^T
-  static constexpr int DB = DP / 32;                // 32-channel blocks of the output accumulators
-  static constexpr int CPR = ROW / 16;              // staging lanes per row: one 16-B chunk each
-  static constexpr int SW = KT * CPR / NT;          // staging sweeps per tile: 1 / 2
-};
+constexpr int KT = ATT_STREAM_TILE;       // keys per tile
+template <int DP> using Geo = AttnStreamGeo<DP, NT>;      // attention_common.h; staging sweeps per tile (SW): 1 / 2
+constexpr int QB = Geo<64>::BB;  // queries per workgroup: 256
 
 struct StreamArgs {
-  const bf16 *q, *k, *v;
+  const bf16 *q, *k, *v;      // the operand fields, named as attention_common.h says
   bf16* out;
   long long q_bs, q_hs, k_bs, k_hs, v_bs, v_hs;   // elements
   int q_rs, k_rs, v_rs;                           // elements between token rows
@@ -71,16 +59,6 @@ struct StreamArgs {
   float scale;
   float* lse;      // optional [B * H][S]
 };
-
-// max / sum of a value with its partner in lane ^ 32 (the other half of a query's keys); both lanes get the same bits
-__device__ __forceinline__ float xhalf_max(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float x) {    // r[0] is the low half's value in both lanes, r[1] the high half's: low + high everywhere
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 
 template <int DP>
 __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
@@ -138,10 +116,8 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
     if (q < S && (DP == 64 || kk * 16 + kg * 8 < D)) t = *reinterpret_cast<const uint4*>(qp + (size_t)q * a.q_rs + kk * 16 + kg * 8);
     qf[kk] = *reinterpret_cast<bf16x8*>(&t);
   }
-  // V transpose-read addressing (as vit.hip): the lane supplies 4 channels of one key row of a 16-key step
+  // V transpose-read addressing: attention_common.h's tr_off0 / tr_frag, spelled out (calling them here changes this kernel's instruction stream)
   const int g16 = (lane >> 4) & 1, rr = (lane & 15) >> 2, qq = lane & 3;
-  // channel block db is the 64-B segment db ^ swizzle (att_vslot: (key >> 1) & 1 in 128-B rows, key & 3 in 256-B rows): another block's address is the first's with
-  // db << 6 XOR-ed in (one address register; the bits below 6 and the row offset above them do not overlap the segment bits)
   const int voff0 = (kg * 8 + rr) * ROW + ((ROW == 128 ? (rr >> 1) & 1 : rr) << 6) + (16 * g16 + 4 * qq) * 2;
   store_tile(0);
 
@@ -214,7 +190,7 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
           const unsigned p1 = dmvae_pack_bf16x2(st[kb][half * 8 + 2], st[kb][half * 8 + 3]);
           const unsigned p2 = dmvae_pack_bf16x2(st[kb][half * 8 + 4], st[kb][half * 8 + 5]);
           const unsigned p3 = dmvae_pack_bf16x2(st[kb][half * 8 + 6], st[kb][half * 8 + 7]);
-          // lanes < 32 hold keys {0-3, 8-11} of the step, lanes >= 32 {4-7, 12-15}: the fragment wants {0-7} / {8-15}
+          // lanes < 32 hold keys {0-3, 8-11} of the step, lanes >= 32 {4-7, 12-15}: the fragment wants {0-7} / {8-15} (to_afrag's swaps, spelled out: see there)
           const auto s0 = __builtin_amdgcn_permlane32_swap(p0, p2, false, false);
           const auto s1 = __builtin_amdgcn_permlane32_swap(p1, p3, false, false);
           union { unsigned u[4]; bf16x8 v; } pa;
@@ -253,22 +229,11 @@ __global__ __launch_bounds__(NT) void attention_stream_kernel(StreamArgs a) {
 
 extern "C" int dmvae_attention_qkv_stream_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, hipStream_t stream) {
   using namespace dmvae_attn_stream;
-  constexpr int D = Geo<64>::D;
-  DMVAE_CHECK_ARG(qkv && out, "attention_qkv_stream_bf16: null qkv or out");
-  DMVAE_CHECK_ARG(batch > 0 && heads > 0 && seq >= 1, "attention_qkv_stream_bf16: needs batch, heads, seq >= 1 (got %d, %d, %d)", batch, heads, seq);
-  DMVAE_CHECK_ARG(head_dim == D, "attention_qkv_stream_bf16: needs head_dim 64 (got %d)", head_dim);
-  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "attention_qkv_stream_bf16: needs a finite scale > 0 (got %g)", (double)scale);
-  const long long C = (long long)heads * head_dim;
-  const long long nqb = ((long long)seq + QB - 1) / QB, blocks = (long long)batch * heads * nqb;
-  // the row stride and the (sample, head) count are ints in the kernel; the flat grid is one dimension
-  DMVAE_CHECK_ARG(3 * C <= 0x7fffffffLL && (long long)batch * heads <= 0x7fffffffLL && blocks <= 0x7fffffffLL,
-                  "attention_qkv_stream_bf16: %d x %d heads x %d tokens does not fit the grid", batch, heads, seq);
+  if (int e = attn_stream_check("attention_qkv_stream_bf16", "qkv or out", qkv && out, ATTN_PACKED, ATTN_FWD, nullptr, nullptr, batch, seq, heads, head_dim, 0, scale, QB)) return e;
   StreamArgs a = {};
-  a.q = (const bf16*)qkv; a.k = a.q + C; a.v = a.q + 2 * C; a.out = (bf16*)out;
-  a.q_bs = a.k_bs = a.v_bs = (long long)seq * 3 * C; a.q_hs = a.k_hs = a.v_hs = head_dim;
-  a.q_rs = a.k_rs = a.v_rs = (int)(3 * C);
-  a.S = seq; a.H = heads; a.nqb = (int)nqb; a.scale = scale; a.lse = (float*)lse;
-  hipLaunchKernelGGL(attention_stream_kernel<64>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+  attn_operands_qkv(a, qkv, seq, heads, head_dim);
+  a.out = (bf16*)out; a.nqb = attn_row_blocks(seq, QB); a.scale = scale; a.lse = (float*)lse;
+  hipLaunchKernelGGL(attention_stream_kernel<64>, dim3((unsigned)(batch * heads * a.nqb)), dim3(NT), 0, stream, a);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -279,24 +244,14 @@ extern "C" int dmvae_attention_qkv_stream_bf16(const void* qkv, void* out, void*
 extern "C" int dmvae_attention_heads_stream_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
                                                  int head_dim_padded, float scale, hipStream_t stream) {
   using namespace dmvae_attn_stream;
-  DMVAE_CHECK_ARG(q && k && v && out, "attention_heads_stream_bf16: null q, k, v or out");
-  DMVAE_CHECK_ARG(batch > 0 && heads > 0 && seq >= 1, "attention_heads_stream_bf16: needs batch, heads, seq >= 1 (got %d, %d, %d)", batch, heads, seq);
-  DMVAE_CHECK_ARG(head_dim == 64 || head_dim == 72, "attention_heads_stream_bf16: needs head_dim 64 or 72 (got %d)", head_dim);
-  DMVAE_CHECK_ARG(head_dim_padded == head_dim || head_dim_padded == (head_dim + 31) / 32 * 32,
-                  "attention_heads_stream_bf16: q / k rows hold head_dim channels or head_dim rounded up to 32 (got %d for head_dim %d)", head_dim_padded, head_dim);
-  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "attention_heads_stream_bf16: needs a finite scale > 0 (got %g)", (double)scale);
-  const long long nqb = ((long long)seq + QB - 1) / QB, blocks = (long long)batch * heads * nqb;
-  // the (sample, head) count is an int in the kernel; the flat grid is one dimension
-  DMVAE_CHECK_ARG((long long)batch * heads <= 0x7fffffffLL && blocks <= 0x7fffffffLL,
-                  "attention_heads_stream_bf16: %d x %d heads x %d tokens does not fit the grid", batch, heads, seq);
+  if (int e = attn_stream_check("attention_heads_stream_bf16", "q, k, v or out", q && k && v && out, ATTN_HEADS, ATTN_FWD, nullptr, nullptr, batch, seq, heads, head_dim,
+                                head_dim_padded, scale, QB)) return e;
   StreamArgs a = {};
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v; a.out = (bf16*)out;
-  a.q_hs = a.k_hs = (long long)seq * head_dim_padded; a.q_bs = a.k_bs = a.q_hs * heads;
-  a.v_hs = (long long)seq * head_dim; a.v_bs = a.v_hs * heads;
-  a.q_rs = a.k_rs = head_dim_padded; a.v_rs = head_dim;
-  a.S = seq; a.H = heads; a.nqb = (int)nqb; a.scale = scale; a.lse = (float*)lse;
-  if (head_dim == 64) hipLaunchKernelGGL(attention_stream_kernel<64>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
-  else hipLaunchKernelGGL(attention_stream_kernel<96>, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+  attn_operands_heads(a, q, k, v, seq, heads, head_dim, head_dim_padded);
+  a.out = (bf16*)out; a.nqb = attn_row_blocks(seq, QB); a.scale = scale; a.lse = (float*)lse;
+  const dim3 grid((unsigned)(batch * heads * a.nqb));
+  if (head_dim == 64) hipLaunchKernelGGL(attention_stream_kernel<64>, grid, dim3(NT), 0, stream, a);
+  else hipLaunchKernelGGL(attention_stream_kernel<96>, grid, dim3(NT), 0, stream, a);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -85,21 +85,6 @@ __device__ __forceinline__ s16x4 tr_read_ordered(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
 }
 
-// LDS images of the fused attention kernels' K and V tiles (vit.hip: a whole head resident; attention_stream.hip: 64-key tiles), byte offset of 16-B chunk c of
-// row `key`.  ROW: bytes per row, 128 (head dim 64) or 256 (96).
-// K is read row-wise by ds_read_b128, which is served in four groups of sixteen lanes that are NOT consecutive ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... --
-// MI355X_MICROARCH.md, LDS table), each lane reading key (lane & 31)'s chunk: the sixteen slots of a group must be distinct mod 256 B.  256-B rows: XOR with
-// key & 15 (sixteen distinct values in every group).  128-B rows (two keys per 256 B): XOR with (key >> 1) & 7 -- eight values, each met by one even and one odd key
-// of the group.  (XOR with key & 7, which every group holds twice, was a 2-way conflict on every K read: SQ_LDS_BANK_CONFLICT 37 % of the LDS cycles.)
-template <int ROW>
-__device__ __forceinline__ int att_kslot(int key, int c) { return key * ROW + ((c ^ (ROW == 128 ? (key >> 1) & 7 : key & 15)) << 4); }
-// V is read by ds_read_b64_tr_b16: channel chunk c (8 channels) -> 64-B segment c >> 2, swizzled per key; 16-B slot c & 3 inside it.  128-B rows: two segments swizzled
-// by (key >> 1) & 1 -- the four key rows a transpose-read pass touches then sit in four distinct 64-B bank slots of the 256-B LDS row; 256-B rows: four, by key & 3.
-template <int ROW>
-__device__ __forceinline__ int att_vslot(int key, int c) {
-  return ROW == 128 ? key * 128 + ((((c >> 2) ^ ((key >> 1) & 1))) << 6) + ((c & 3) << 4) : key * 256 + ((((c >> 2) ^ (key & 3))) << 6) + ((c & 3) << 4);
-}
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -146,29 +131,6 @@ __device__ __forceinline__ bf16x8 dmvae_ldnt8(const bf16* p) {
 __device__ __forceinline__ unsigned dmvae_pack_bf16x2(float a, float b) {
   bf16x2 t = {(bf16)a, (bf16)b};
   return *reinterpret_cast<unsigned*>(&t);
-}
-// ---- the attention backward kernels' fragment helpers (attention_bwd.hip, attention_bwd_stream.hip) ----
-__device__ __forceinline__ float dot8(const uint4& a, const uint4& b) {
-  const bf16x8 x = *reinterpret_cast<const bf16x8*>(&a), y = *reinterpret_cast<const bf16x8*>(&b);
-  float s = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; e++) s += (float)x[e] * (float)y[e];
-  return s;
-}
-// C-layout registers of a 32 x 32 block (row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31), 16 of them scaled to bf16 -> the two A fragments
-// (reduction index = the block's ROW, 8 consecutive per lane) of its two 16-row halves
-__device__ __forceinline__ void to_afrag(const f32x16& c, bf16x8 out[2]) {
-#pragma unroll
-  for (int half = 0; half < 2; half++) {
-    const unsigned p0 = dmvae_pack_bf16x2(c[half * 8 + 0], c[half * 8 + 1]), p1 = dmvae_pack_bf16x2(c[half * 8 + 2], c[half * 8 + 3]);
-    const unsigned p2 = dmvae_pack_bf16x2(c[half * 8 + 4], c[half * 8 + 5]), p3 = dmvae_pack_bf16x2(c[half * 8 + 6], c[half * 8 + 7]);
-    // lanes < 32 hold rows {0-3, 8-11} of the half, lanes >= 32 rows {4-7, 12-15}: the fragment wants {0-7} / {8-15}
-    const auto s0 = __builtin_amdgcn_permlane32_swap(p0, p2, false, false);
-    const auto s1 = __builtin_amdgcn_permlane32_swap(p1, p3, false, false);
-    union { unsigned u[4]; bf16x8 v; } pa;
-    pa.u[0] = s0[0]; pa.u[1] = s1[0]; pa.u[2] = s0[1]; pa.u[3] = s1[1];
-    out[half] = pa.v;
-  }
 }
 // RMSNorm + RoPE of 8 consecutive channels d0..d0+7 of token `tok` (csrc/dit.hip::qknorm_rope_kernel's arithmetic: the normalised value is rounded to
 // bf16 before the f32 weight multiplies; pairs (2i, 2i+1) rotate with their own table entries)

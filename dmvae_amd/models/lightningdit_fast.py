@@ -2,7 +2,7 @@
 (the teacher's and the student's evaluations inside the DMD loss, train_dmd.py:211-217: four DiT-XL/1 forwards per VAE turn).
 
 Same arithmetic as `forward_stock` under autocast(bf16), with bf16 rounding at the sites where the reference's autocast graph rounds (see
-csrc/dit.hip); per block: 1 fused (gated residual +) RMSNorm+modulate, qkv GEMM, 1 fused QK-norm+RoPE+head split, attention in one fused kernel (csrc/vit.hip, head dims 64 and 72
+csrc/dit.hip); per block: 1 fused (gated residual +) RMSNorm+modulate, qkv GEMM, 1 fused QK-norm+RoPE+head split, attention in one fused kernel (csrc/attention.hip, head dims 64 and 72
 alike: the staged head dim pads to 96; beyond 288 tokens QK-norm + RoPE as their own kernel and the streaming-softmax kernel of csrc/attention_stream.hip -- nothing N x N in
 HBM at any token count; other head dims beyond 288 tokens: composed batched QK^T GEMM / f32 softmax / PV GEMM), proj GEMM, 1 gated residual, RMSNorm+modulate, w12 GEMM, SwiGLU gate, w3 GEMM,
 gated residual -- every token-level Linear on this build's GEMM kernel (`functional.linear`: csrc/gemm_pp.hip).

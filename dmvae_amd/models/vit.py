@@ -6,7 +6,7 @@ models/dinov2.py + models/dino_layers (LayerNorm eps 1e-6, MHA, LayerScale, GELU
 (blocks.N.{norm1,attn.qkv,attn.proj,ls1.gamma,norm2,mlp.fc1,mlp.fc2,ls2.gamma}) so reference `vae.pt` files load.
 SURVEY.md section-8(f) rank 3.  Three ways through it: frozen (tokenizer stage, train_tokenizer.py:295-297) -> the step harness runs
 `vit_fast.frozen_forward_features` on a bf16 shadow; trainable on the GPU at a width the kernels cover -> `vit_fast.trainable_forward_features`
-(autograd Functions over csrc/vit.hip + vit_bwd.hip, library GEMMs for the Linear layers); anything else (CPU construction / state_dict
+(autograd Functions over csrc/vit.hip + vit_bwd.hip + the attention kernels, library GEMMs for the Linear layers); anything else (CPU construction / state_dict
 work, unusual widths) -> the stock PyTorch modules below, which also define the parameter names.
 """
 import math
@@ -107,7 +107,7 @@ class DinoV2ViT(nn.Module):
                 return parity_forward_features(self, x)
             if hip_path_supported(self, self.pos_embed.shape[1]):
                 if torch.is_grad_enabled() and self.pos_embed.requires_grad:
-                    return trainable_forward_features(self, x)    # trainable encoder on the HIP kernels (csrc/vit.hip, vit_bwd.hip)
+                    return trainable_forward_features(self, x)    # trainable encoder on the HIP kernels (csrc/vit.hip, vit_bwd.hip, attention*.hip)
                 needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
                 if not needs_grad and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16:
                     # frozen / no-grad use under autocast(bf16) -- `vae.encode`, `vae(x, freeze_encoder=True)`: the fused inference route on cached

@@ -1,7 +1,7 @@
 """Inference-only forward of the frozen DINOv2 ViT encoder (models/vae.py:52-53 in the tokenizer stage, where the encoder is
 frozen and runs under no_grad, train_tokenizer.py:295-297): same arithmetic as `vit.DinoV2ViT.forward_features` under
 autocast(bf16), with the elementwise chain on the HIP kernels of csrc/vit.hip -- LayerNorm straight to bf16, LayerScale +
-residual add fused on the f32 residual stream, multi-head attention as one fused MFMA kernel -- and the four Linear GEMMs
+residual add fused on the f32 residual stream --, multi-head attention as one fused MFMA kernel (csrc/attention.hip) and the four Linear GEMMs
 per block (and the patch embedding) on the hand-written GEMM of csrc/gemm_pp.hip through the bf16 weight shadow, fc1 with its
 GELU in the epilogue (`functional.linear`; tools/bench_gemm.py has the per-call comparison with the vendor library it replaced).
 SURVEY.md 8(f) rank 3 ("next")."""

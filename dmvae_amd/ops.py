@@ -1038,58 +1038,22 @@ def softmax_rows_bf16(s: torch.Tensor, scale: float) -> torch.Tensor:
     return p
 
 
-ATTENTION_RESIDENT_MAX = 288      # tokens the resident fused attention kernels (csrc/vit.hip, attention_bwd.hip) hold in LDS
+ATTENTION_RESIDENT_MAX = 288      # tokens the resident fused attention kernels (csrc/attention.hip, attention_bwd.hip) hold in LDS: csrc/attention_common.h's ATT_RESIDENT_KEYS
 
 
-def attention_qkv(qkv: torch.Tensor, heads: int, scale: float, need_lse: bool = False):
-    """Fused multi-head self-attention on the qkv Linear's output [B, S, 3*heads*64] (bf16) -> [B, S, heads*64]; with need_lse also the row statistics
-    lse [B*heads, S] f32 (scale * max + log(sum) per query) for `attention_bwd_qkv`.  Up to 288 tokens the kernel that keeps a head's K / V resident in LDS
-    (csrc/vit.hip), beyond that the streaming-softmax kernel (`attention_qkv_stream`): any S."""
-    qkv = _req(qkv, bf16, "qkv")
-    b, s, c3 = qkv.shape
-    if s > ATTENTION_RESIDENT_MAX:
-        return attention_qkv_stream(qkv, heads, scale, need_lse)
-    c = c3 // 3
-    out = torch.empty(b, s, c, dtype=bf16, device=qkv.device)
-    lse = torch.empty(b * heads, s, dtype=f32, device=qkv.device) if need_lse else None
-    check(_lib.lib().dmvae_attention_qkv_lse_bf16(qkv.data_ptr(), out.data_ptr(), _ptr(lse), b, s, heads, c // heads, float(scale), _stream()), "attention_qkv_bf16")
-    return (out, lse) if need_lse else out
-
-
-def attention_qkv_stream(qkv: torch.Tensor, heads: int, scale: float, need_lse: bool = False):
-    """`attention_qkv`'s operands and results at any token count S >= 1, on the kernel that streams 64-key K / V tiles through LDS with an online softmax
-    (csrc/attention_stream.hip; head dim 64): nothing of size S x S reaches HBM, reruns and batch splits are bit-identical."""
+# The bodies of the eight attention wrappers below: operand requirements, shapes, output / lse / delta allocation, the call.  `entry` is the C symbol, `label` the
+# name check() reports.  The public functions alone decide resident versus streaming (ATTENTION_RESIDENT_MAX).
+def _attention_fwd_qkv(entry: str, label: str, qkv, heads, scale, need_lse):
     qkv = _req(qkv, bf16, "qkv")
     b, s, c3 = qkv.shape
     c = c3 // 3
     out = torch.empty(b, s, c, dtype=bf16, device=qkv.device)
     lse = torch.empty(b * heads, s, dtype=f32, device=qkv.device) if need_lse else None
-    check(_lib.lib().dmvae_attention_qkv_stream_bf16(qkv.data_ptr(), out.data_ptr(), _ptr(lse), b, s, heads, c // heads, float(scale), _stream()),
-          "attention_qkv_stream_bf16")
+    check(getattr(_lib.lib(), entry)(qkv.data_ptr(), out.data_ptr(), _ptr(lse), b, s, heads, c // heads, float(scale), _stream()), label)
     return (out, lse) if need_lse else out
 
 
-def attention_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, scale: float, need_lse: bool = False):
-    """q, k [B*H, N, Dp], v [B*H, N, D] (bf16, as `qknorm_rope` returns them) -> softmax(scale q k^T) v as [B, N, H*D] bf16, one fused kernel; with need_lse also
-    lse [B*H, N] f32 for `attention_bwd_heads`.  Up to 288 tokens the kernel that keeps a head's K / V resident in LDS (csrc/vit.hip), beyond that the
-    streaming-softmax kernel (`attention_heads_stream`: head dims 64 and 72)."""
-    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v")
-    bh, n, dp = q.shape
-    if n > ATTENTION_RESIDENT_MAX:
-        return attention_heads_stream(q, k, v, batch, scale, need_lse)
-    d = v.shape[-1]
-    heads = bh // batch
-    out = torch.empty(batch, n, heads * d, dtype=bf16, device=q.device)
-    lse = torch.empty(bh, n, dtype=f32, device=q.device) if need_lse else None
-    check(_lib.lib().dmvae_attention_heads_lse_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), batch, n, heads, d, dp, float(scale),
-                                                    _stream()), "attention_heads_bf16")
-    return (out, lse) if need_lse else out
-
-
-def attention_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, scale: float, need_lse: bool = False):
-    """`attention_heads`' operands and results at any token count N >= 1, on the kernel that streams 64-key K / V tiles through LDS with an online softmax
-    (csrc/attention_stream.hip; head dim 64 or 72, q / k rows of D channels or D rounded up to 32): nothing of size N x N reaches HBM, reruns and batch splits
-    are bit-identical."""
+def _attention_fwd_heads(entry: str, label: str, q, k, v, batch, scale, need_lse):
     q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v")
     bh, n, dp = q.shape
     d = v.shape[-1]
@@ -1097,9 +1061,67 @@ def attention_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ba
     assert k.shape == q.shape and v.shape == (bh, n, d) and heads * batch == bh
     out = torch.empty(batch, n, heads * d, dtype=bf16, device=q.device)
     lse = torch.empty(bh, n, dtype=f32, device=q.device) if need_lse else None
-    check(_lib.lib().dmvae_attention_heads_stream_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), batch, n, heads, d, dp, float(scale),
-                                                       _stream()), "attention_heads_stream_bf16")
+    check(getattr(_lib.lib(), entry)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), batch, n, heads, d, dp, float(scale), _stream()), label)
     return (out, lse) if need_lse else out
+
+
+def _attention_bwd_qkv(entry: str, label: str, qkv, out, dout, heads, scale, lse, need_delta: bool):
+    qkv = _req(qkv, bf16, "qkv"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
+    b, s, c3 = qkv.shape
+    c = c3 // 3
+    assert out.shape == (b, s, c) and dout.shape == (b, s, c)
+    assert lse is None or (lse.dtype == f32 and lse.is_contiguous() and lse.shape == (b * heads, s))
+    dqkv = torch.empty_like(qkv)
+    delta = (torch.empty(b * heads, s, dtype=f32, device=qkv.device),) if need_delta else ()      # the streaming kernels' only scratch
+    check(getattr(_lib.lib(), entry)(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), _ptr(lse), dqkv.data_ptr(), *(t.data_ptr() for t in delta), b, s, heads,
+                                     c // heads, float(scale), _stream()), label)
+    return dqkv
+
+
+def _attention_bwd_heads(entry: str, label: str, q, k, v, out, dout, batch, scale, lse, need_delta: bool):
+    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
+    bh, n, dp = q.shape
+    d = v.shape[-1]
+    heads = bh // batch
+    assert k.shape == q.shape and v.shape == (bh, n, d) and heads * batch == bh
+    assert out.shape == (batch, n, heads * d) and dout.shape == out.shape
+    assert lse is None or (lse.dtype == f32 and lse.is_contiguous() and lse.shape == (bh, n))
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = (torch.empty(bh, n, dtype=f32, device=q.device),) if need_delta else ()
+    check(getattr(_lib.lib(), entry)(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), _ptr(lse), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                                     *(t.data_ptr() for t in delta), batch, n, heads, d, dp, float(scale), _stream()), label)
+    return dq, dk, dv
+
+
+def attention_qkv(qkv: torch.Tensor, heads: int, scale: float, need_lse: bool = False):
+    """Fused multi-head self-attention on the qkv Linear's output [B, S, 3*heads*64] (bf16) -> [B, S, heads*64]; with need_lse also the row statistics
+    lse [B*heads, S] f32 (scale * max + log(sum) per query) for `attention_bwd_qkv`.  Up to 288 tokens the kernel that keeps a head's K / V resident in LDS
+    (csrc/attention.hip), beyond that the streaming-softmax kernel (`attention_qkv_stream`): any S."""
+    if qkv.shape[1] > ATTENTION_RESIDENT_MAX:
+        return attention_qkv_stream(qkv, heads, scale, need_lse)
+    return _attention_fwd_qkv("dmvae_attention_qkv_lse_bf16", "attention_qkv_bf16", qkv, heads, scale, need_lse)
+
+
+def attention_qkv_stream(qkv: torch.Tensor, heads: int, scale: float, need_lse: bool = False):
+    """`attention_qkv`'s operands and results at any token count S >= 1, on the kernel that streams 64-key K / V tiles through LDS with an online softmax
+    (csrc/attention_stream.hip; head dim 64): nothing of size S x S reaches HBM, reruns and batch splits are bit-identical."""
+    return _attention_fwd_qkv("dmvae_attention_qkv_stream_bf16", "attention_qkv_stream_bf16", qkv, heads, scale, need_lse)
+
+
+def attention_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, scale: float, need_lse: bool = False):
+    """q, k [B*H, N, Dp], v [B*H, N, D] (bf16, as `qknorm_rope` returns them) -> softmax(scale q k^T) v as [B, N, H*D] bf16, one fused kernel; with need_lse also
+    lse [B*H, N] f32 for `attention_bwd_heads`.  Up to 288 tokens the kernel that keeps a head's K / V resident in LDS (csrc/attention.hip), beyond that the
+    streaming-softmax kernel (`attention_heads_stream`: head dims 64 and 72)."""
+    if q.shape[1] > ATTENTION_RESIDENT_MAX:
+        return attention_heads_stream(q, k, v, batch, scale, need_lse)
+    return _attention_fwd_heads("dmvae_attention_heads_lse_bf16", "attention_heads_bf16", q, k, v, batch, scale, need_lse)
+
+
+def attention_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, scale: float, need_lse: bool = False):
+    """`attention_heads`' operands and results at any token count N >= 1, on the kernel that streams 64-key K / V tiles through LDS with an online softmax
+    (csrc/attention_stream.hip; head dim 64 or 72, q / k rows of D channels or D rounded up to 32): nothing of size N x N reaches HBM, reruns and batch splits
+    are bit-identical."""
+    return _attention_fwd_heads("dmvae_attention_heads_stream_bf16", "attention_heads_stream_bf16", q, k, v, batch, scale, need_lse)
 
 
 def attention_qknorm_rope(qkv: torch.Tensor, qw: torch.Tensor, kw: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, eps: float,
@@ -1119,17 +1141,9 @@ def attention_bwd_qkv(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, 
     """d(qkv) [B,S,3*C] of `attention_qkv` from its input, its result `out` [B,S,C] and d(out) (bf16).  Up to 288 tokens one fused kernel with a head resident in LDS
     (csrc/attention_bwd.hip); with the forward's `lse` the eight-wave form that rebuilds the probabilities from it.  Beyond that the streaming kernels
     (`attention_bwd_qkv_stream`), which need `lse`."""
-    qkv = _req(qkv, bf16, "qkv"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
-    b, s, c3 = qkv.shape
-    if s > ATTENTION_RESIDENT_MAX:
+    if qkv.shape[1] > ATTENTION_RESIDENT_MAX:
         return attention_bwd_qkv_stream(qkv, out, dout, heads, scale, lse)
-    c = c3 // 3
-    assert out.shape == (b, s, c) and dout.shape == (b, s, c)
-    dqkv = torch.empty_like(qkv)
-    assert lse is None or (lse.dtype == f32 and lse.is_contiguous() and lse.shape == (b * heads, s))
-    check(_lib.lib().dmvae_attention_bwd_qkv_lse_bf16(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), _ptr(lse), dqkv.data_ptr(), b, s, heads, c // heads, float(scale),
-                                                      _stream()), "attention_bwd_qkv_bf16")
-    return dqkv
+    return _attention_bwd_qkv("dmvae_attention_bwd_qkv_lse_bf16", "attention_bwd_qkv_bf16", qkv, out, dout, heads, scale, lse, False)
 
 
 def attention_bwd_qkv_stream(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, heads: int, scale: float, lse: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1138,34 +1152,16 @@ def attention_bwd_qkv_stream(qkv: torch.Tensor, out: torch.Tensor, dout: torch.T
     scratch is delta [B*heads, S] f32 -- and reruns and batch splits are bit-identical."""
     if lse is None:
         raise ValueError("attention_bwd_qkv_stream needs the forward's lse (attention_qkv(..., need_lse=True))")
-    qkv = _req(qkv, bf16, "qkv"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
-    b, s, c3 = qkv.shape
-    c = c3 // 3
-    assert out.shape == (b, s, c) and dout.shape == (b, s, c)
-    assert lse.dtype == f32 and lse.is_contiguous() and lse.shape == (b * heads, s)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(b * heads, s, dtype=f32, device=qkv.device)
-    check(_lib.lib().dmvae_attention_bwd_qkv_stream_bf16(qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), b, s, heads,
-                                                         c // heads, float(scale), _stream()), "attention_bwd_qkv_stream_bf16")
-    return dqkv
+    return _attention_bwd_qkv("dmvae_attention_bwd_qkv_stream_bf16", "attention_bwd_qkv_stream_bf16", qkv, out, dout, heads, scale, lse, True)
 
 
 def attention_bwd_heads(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, batch: int, scale: float,
                         lse: Optional[torch.Tensor] = None):
     """(dq, dk [B*H,N,Dp], dv [B*H,N,D]) of `attention_heads` from its operands, its result `out` [B,N,H*D] and d(out).  Up to 288 tokens one fused kernel with a
     head resident in LDS (csrc/attention_bwd.hip); beyond that the streaming kernels (`attention_bwd_heads_stream`), which need `lse`."""
-    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
-    bh, n, dp = q.shape
-    if n > ATTENTION_RESIDENT_MAX:
+    if q.shape[1] > ATTENTION_RESIDENT_MAX:
         return attention_bwd_heads_stream(q, k, v, out, dout, batch, scale, lse)
-    d = v.shape[-1]
-    heads = bh // batch
-    assert out.shape == (batch, n, heads * d) and dout.shape == out.shape
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    assert lse is None or (lse.dtype == f32 and lse.is_contiguous() and lse.shape == (bh, n))
-    check(_lib.lib().dmvae_attention_bwd_heads_lse_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), _ptr(lse), dq.data_ptr(),
-                                                        dk.data_ptr(), dv.data_ptr(), batch, n, heads, d, dp, float(scale), _stream()), "attention_bwd_heads_bf16")
-    return dq, dk, dv
+    return _attention_bwd_heads("dmvae_attention_bwd_heads_lse_bf16", "attention_bwd_heads_bf16", q, k, v, out, dout, batch, scale, lse, False)
 
 
 def attention_bwd_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, dout: torch.Tensor, batch: int, scale: float,
@@ -1175,19 +1171,7 @@ def attention_bwd_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     only scratch is delta [B*H, N] f32 -- and reruns and batch splits are bit-identical."""
     if lse is None:
         raise ValueError("attention_bwd_heads_stream needs the forward's lse (attention_heads(..., need_lse=True))")
-    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v"); out = _req(out, bf16, "out"); dout = _req(dout, bf16, "dout")
-    bh, n, dp = q.shape
-    d = v.shape[-1]
-    heads = bh // batch
-    assert k.shape == q.shape and v.shape == (bh, n, d) and heads * batch == bh
-    assert out.shape == (batch, n, heads * d) and dout.shape == out.shape
-    assert lse.dtype == f32 and lse.is_contiguous() and lse.shape == (bh, n)
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    delta = torch.empty(bh, n, dtype=f32, device=q.device)
-    check(_lib.lib().dmvae_attention_bwd_heads_stream_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dq.data_ptr(),
-                                                           dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), batch, n, heads, d, dp, float(scale), _stream()),
-          "attention_bwd_heads_stream_bf16")
-    return dq, dk, dv
+    return _attention_bwd_heads("dmvae_attention_bwd_heads_stream_bf16", "attention_bwd_heads_stream_bf16", q, k, v, out, dout, batch, scale, lse, True)
 
 
 def attention_heads_supported(n: int, d: int) -> bool:

@@ -8,7 +8,7 @@ hipcc (ROCm 7.2) pads no wait states between the two and the hardware does not i
 the destination of one of the previous 8 MFMAs of a DIFFERENT opcode with fewer than 11 wait states between them (an 8-pass producer + 3; s_nop N = N + 1,
 an intervening MFMA = 4, the shortest one's passes, any other instruction = 1).  The -S output carries inline assembly expanded, so the hand-ordered block of
 convout_bwd_kernel (four 16x16x32 products, then their four 16x16x16 accumulations: 3 MFMAs = 12 states between every pair) is audited like compiler output:
-reordering or shrinking that block below the distance fails here before it fails on the GPU.  (A destination on top of the A / B operand, which the same build also had, is legal and common: vit.hip, linear_rows.hip.)
+reordering or shrinking that block below the distance fails here before it fails on the GPU.  (A destination on top of the A / B operand, which the same build also had, is legal and common: attention.hip, linear_rows.hip.)
 usage: python tools/check_mfma_chain.py [files...]   (exit 1 on a finding)"""
 import glob
 import os
