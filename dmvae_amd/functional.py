@@ -245,40 +245,92 @@ class ResnetBlockFn(torch.autograd.Function):
         return dx, dn1w, dn1b, dc1w, dc1b, dn2w, dn2b, dc2w, dc2b, dsw, dsb
 
 
+ATTN_WIDE_STREAM = None      # None: the default below; True / False: tests force a route (tests/test_gpu_attention_wide.py)
+
+
+def _attn_wide_stream(s: int, c: int) -> bool:
+    """AttnBlock's attention on the streaming d = 512 kernel (csrc/attention_wide.hip) -- above ops.ATTNBLOCK_COMPOSED_MAX tokens at 512 channels, except in the fp32
+    parity mode (bf16 operands only).  Up to 1024 tokens (the 256-px training shape is exactly 1024), at other widths and in parity mode: the composed route."""
+    if ATTN_WIDE_STREAM is None:
+        return s > ops.ATTNBLOCK_COMPOSED_MAX and ops.attention_wide_supported(s, c) and not parity.on()
+    return bool(ATTN_WIDE_STREAM)
+
+
+def _attn_pad(t: torch.Tensor, sp: int) -> torch.Tensor:
+    """[n, s, c] -> [n, sp, c] with zero rows appended (the same tensor when sp == s)"""
+    n, s, c = t.shape
+    if s == sp:
+        return t
+    out = t.new_zeros(n, sp, c)
+    out[:, :s] = t
+    return out
+
+
+def _attn_probs(q: torch.Tensor, k: torch.Tensor, scale: float, s: int) -> torch.Tensor:
+    """P [n, sp, sp] of the composed route from q, k [n, sp, c] whose rows >= s are `_attn_pad`'s zeros: the padded keys score -inf, so their p is exactly 0 (the
+    padded queries' rows are uniform over the live keys and meet zero gradient rows in backward)."""
+    sc = ops.gemm_nt(q, k, out_f32=True)
+    if q.shape[1] != s:
+        sc[:, :, s:] = float("-inf")
+    return ops.softmax_rows(sc, scale)
+
+
 class AttnBlockFn(torch.autograd.Function):
-    """x + proj_out(SDPA(q,k,v)) over (h w) tokens, single head, d = C (flux_ae.py:37-52)."""
+    """x + proj_out(SDPA(q,k,v)) over (h w) tokens, single head, d = C (flux_ae.py:37-52).  Up to 1024 tokens the attention is composed from GEMMs with P [n, s, s]
+    saved for backward; above it (`_attn_wide_stream`) the forward is one streaming kernel that saves nothing s x s, and backward recomputes P on the composed ops.
+    The composed GEMMs that reduce over tokens take multiples of 32 (gemm_nt: K % 32; gemm_tn: M % 8): another token count (18 x 18 latents give a 36 x 36 = 1296
+    token grid) runs them on operands padded with zero rows to the next multiple -- with s % 32 == 0, every shape up to here, the calls are the unpadded ones."""
 
     @staticmethod
     def forward(ctx, x, nw, nb, qw, qb, kw, kb, vw, vb, pw, pb):
         n, h, w, c = x.shape
         s = h * w
+        sp = (s + 31) // 32 * 32
         st, hn = _gn_swish(x, nw, nb, swish=False)
         q = ops.conv2d_nhwc(hn, packed(qw), qb, ks=1).view(n, s, c)
         k = ops.conv2d_nhwc(hn, packed(kw), kb, ks=1).view(n, s, c)
         v = ops.conv2d_nhwc(hn, packed(vw), vb, ks=1).view(n, s, c)
         scale = float(c) ** -0.5
-        p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), scale)          # [n, s, s] bf16
-        o = ops.gemm_nt(p, ops.transpose_last2(v))                            # [n, s, c]
+        ctx.stream = _attn_wide_stream(s, c)
+        if ctx.stream:       # above 1024 tokens: one streaming kernel (csrc/attention_wide.hip), no [n, s, s] tensor written or saved; backward recomputes P
+            o = ops.attention_wide_stream(q, k, v, scale)      # without lse: backward recomputes P, nothing reads the row statistics yet
+        else:
+            p = _attn_probs(_attn_pad(q, sp), _attn_pad(k, sp), scale, s)         # [n, sp, sp] bf16
+            o = ops.gemm_nt(p, ops.transpose_last2(_attn_pad(v, sp)))             # [n, sp, c]
+            if sp != s:
+                o = o[:, :s].contiguous()
         y, sty = ops.conv2d_nhwc_gnstats(o.view(n, h, w, c), packed(pw), pb, residual=x, ks=1)
-        ctx.save_for_backward(x, st, hn, q, k, v, p, o, nw, nb, qw, kw, vw, pw)
+        if ctx.stream:
+            ctx.save_for_backward(x, st, hn, q, k, v, o, nw, nb, qw, kw, vw, pw)
+        else:
+            ctx.save_for_backward(x, st, hn, q, k, v, p, o, nw, nb, qw, kw, vw, pw)
         ctx.bias_params = (qb, kb, vb, pb)
         ctx.scale = scale
         return _tag_stats(y, sty)
 
     @staticmethod
     def backward(ctx, dy):
-        x, st, hn, q, k, v, p, o, nw, nb, qw, kw, vw, pw = ctx.saved_tensors
+        if ctx.stream:
+            x, st, hn, q, k, v, o, nw, nb, qw, kw, vw, pw = ctx.saved_tensors
+        else:
+            x, st, hn, q, k, v, p, o, nw, nb, qw, kw, vw, pw = ctx.saved_tensors
         n, h, w, c = x.shape
         s = h * w
+        sp = (s + 31) // 32 * 32
+        q, k, v = _attn_pad(q, sp), _attn_pad(k, sp), _attn_pad(v, sp)
+        if ctx.stream:       # P from the two calls the composed forward makes: the [n, s, s] tensors exist only inside this backward
+            p = _attn_probs(q, k, ctx.scale, s)
         dy = _c(dy)
         qb, kb, vb, pb = ctx.bias_params
         dpw, dpb = ops.conv2d_nhwc_wgrad(dy, o.view(n, h, w, c), 1, dw_out=_dst(pw), db_out=_dst(pb))
-        do = ops.conv2d_nhwc(dy, packed(pw, True), ks=1).view(n, s, c)
+        do = _attn_pad(ops.conv2d_nhwc(dy, packed(pw, True), ks=1).view(n, s, c), sp)
         dp = ops.gemm_nt(do, v, out_f32=True)                                  # dP[q][key] = do[q].v[key]
         ds = ops.softmax_rows_bwd(dp, p, ctx.scale)                            # bf16, includes the scale
         dv = ops.gemm_tn(p, do)                                                # [n, key, c]
         dq = ops.gemm_nt(ds, ops.transpose_last2(k))                           # [n, q, c]
         dk = ops.gemm_tn(ds, q)                                                # [n, key, c]
+        if sp != s:
+            dq, dk, dv = dq[:, :s].contiguous(), dk[:, :s].contiguous(), dv[:, :s].contiguous()
         dq4, dk4, dv4 = dq.view(n, h, w, c), dk.view(n, h, w, c), dv.view(n, h, w, c)
         dqw, dqb = ops.conv2d_nhwc_wgrad(dq4, hn, 1, dw_out=_dst(qw), db_out=_dst(qb))
         dkw, dkb = ops.conv2d_nhwc_wgrad(dk4, hn, 1, dw_out=_dst(kw), db_out=_dst(kb))

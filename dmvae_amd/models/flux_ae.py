@@ -9,6 +9,7 @@ with strict=True), but ``forward`` never calls them: it dispatches to dmvae_amd.
 Public ``forward`` takes/returns NCHW like the reference; ``forward_nhwc`` is the internal
 channels-last bf16 path the Decoder chains without layout round-trips.
 """
+import math
 from dataclasses import dataclass
 
 import torch
@@ -184,7 +185,8 @@ class Decoder(nn.Module):
         self.conv_out = nn.Conv2d(widths[0], out_ch, kernel_size=3, stride=1, padding=1)
 
     def forward(self, z: Tensor, grad_ckpt=False) -> Tensor:
-        """z: [B, 256, C] tokens (the reference hard-codes the 16x16 grid, :244-245) or NCHW [B, C, h, w].
+        """z: [B, T, C] tokens of a square g x g grid, T = g * g (the reference hard-codes the 16x16 grid of 256 px, :244-245; 288 px is 18x18 = 324
+        tokens, 512 px 32x32 = 1024; any other T raises ValueError) or NCHW [B, C, h, w].
         Returns the NCHW image; f32 (the reference returns bf16 under autocast and VAE.forward casts to float)."""
         h = self._body_nhwc(z)
         return Fn.NormConvOutFn.apply(h, self.norm_out.weight, self.norm_out.bias, self.conv_out.weight, self.conv_out.bias)
@@ -205,9 +207,10 @@ class Decoder(nn.Module):
     def _body_nhwc(self, z: Tensor) -> Tensor:
         if z.ndim == 3:
             b, t, c = z.shape
-            if t != 256:
-                raise ValueError("Decoder expects 256 tokens (16x16) like the reference (flux_ae.py:245)")
-            h = z.reshape(b, 16, 16, c).to(Fn.parity.act_dtype()).contiguous()      # tokens are already channels-last (bf16; f32 in the parity mode)
+            g = math.isqrt(t)
+            if g * g != t:
+                raise ValueError(f"Decoder expects a square grid of tokens (the reference hard-codes 256 = 16x16, flux_ae.py:245); got {t}")
+            h = z.reshape(b, g, g, c).to(Fn.parity.act_dtype()).contiguous()        # tokens are already channels-last (bf16; f32 in the parity mode)
         else:
             h = Fn.to_nhwc_bf16(z)
         if isinstance(self.conv_in, nn.Sequential):

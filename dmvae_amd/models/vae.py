@@ -61,11 +61,13 @@ class Denormalize(_PerChannelStats):
 
 class DINOEncoder(nn.Module):
     """[-1, 1] images -> patch tokens of a DINOv2 ViT (prefix tokens dropped).  `vit_kw` (embed_dim, depth, num_heads ...) builds reduced
-    encoders for tests; the reference always instantiates the checkpoint geometry."""
+    encoders for tests; the reference always instantiates the checkpoint geometry.  `img_size` among them (the ViT's own spelling) is `image_size`: the
+    encoder of another resolution -- 288 px is 18 x 18 tokens at patch 16."""
 
     def __init__(self, model_size="base", patch_size=16, image_size=256, pretrained=True, **vit_kw):
         super().__init__()
         width, ckpt_name = _ENCODERS[model_size]
+        image_size = vit_kw.pop("img_size", image_size)
         self.dim = vit_kw.get("embed_dim", width)
         self.de_scale = Denormalize(mean=_HALF, std=_HALF)                      # [-1, 1] -> [0, 1]
         self.scale = Normalize(mean=_IMAGENET_MEAN, std=_IMAGENET_STD)          # [0, 1] -> ImageNet-normalised
@@ -116,7 +118,8 @@ class VAE(nn.Module):
         self.posterior_kl_per_latent = None
         self.reparam_generator = None          # optional torch.Generator (device) for eps
         # construction order = the reference's (encoder, decoder, post_init, bottleneck, three init_weights calls): under a fixed seed the random
-        # initialisation then consumes the generator identically.  As there, `image_size` does not reach the encoder.
+        # initialisation then consumes the generator identically.  As there (vae.py:81), `image_size` does not reach the encoder: another resolution is
+        # built with encoder_kwargs=dict(img_size=...); the decoder takes whatever square token grid arrives (Decoder._body_nhwc).
         self.encoder = DINOEncoder(model_size, patch_size=patch_size, **(encoder_kwargs or {}))
         self.decoder = Decoder(**_DECODER_CFG)
         self.decoder.post_init(z_channels=z_channels)
@@ -126,7 +129,7 @@ class VAE(nn.Module):
 
     # ---- training-time forward --------------------------------------------------------------------------------------------------
     def tokens(self, x, freeze_encoder=False):
-        """Latent tokens [B, 256, z]; with `freeze_encoder` the ViT runs without a graph (train_tokenizer.py keeps it frozen)."""
+        """Latent tokens [B, T, z] (T = 256 at 256 px and patch 16); with `freeze_encoder` the ViT runs without a graph (train_tokenizer.py keeps it frozen)."""
         with torch.set_grad_enabled(torch.is_grad_enabled() and not freeze_encoder):
             feats = self.encoder(x)
         return self.latent(feats)

@@ -1124,6 +1124,28 @@ def attention_heads_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, ba
     return _attention_fwd_heads("dmvae_attention_heads_stream_bf16", "attention_heads_stream_bf16", q, k, v, batch, scale, need_lse)
 
 
+ATTNBLOCK_COMPOSED_MAX = 1024     # tokens up to which the decoder AttnBlock composes its attention from GEMMs (functional.AttnBlockFn); beyond it `attention_wide_stream`
+
+
+def attention_wide_supported(s: int, c: int) -> bool:
+    """Whether `attention_wide_stream` takes S tokens of C channels: one head of 512 channels, any S >= 1."""
+    return c == 512 and s >= 1
+
+
+def attention_wide_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, need_lse: bool = False):
+    """Single-head self-attention at head dim 512: q, k, v [B, S, 512] bf16 contiguous (the decoder AttnBlock's three 1x1 conv outputs) -> softmax(scale q k^T) v as
+    [B, S, 512] bf16; with need_lse also lse [B, S] f32 (scale * max + log(sum) per query).  Any S >= 1, on the kernel that streams 32-key K / V tiles through LDS
+    with an online softmax (csrc/attention_wide.hip): nothing of size S x S reaches HBM, reruns and batch splits are bit-identical."""
+    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v")
+    b, s, c = q.shape
+    assert k.shape == q.shape and v.shape == q.shape
+    out = torch.empty(b, s, c, dtype=bf16, device=q.device)
+    lse = torch.empty(b, s, dtype=f32, device=q.device) if need_lse else None
+    check(_lib.lib().dmvae_attention_wide_stream_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), b, s, c, float(scale), _stream()),
+          "attention_wide_stream_bf16")
+    return (out, lse) if need_lse else out
+
+
 def attention_qknorm_rope(qkv: torch.Tensor, qw: torch.Tensor, kw: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, eps: float,
                           scale: float) -> torch.Tensor:
     """qkv [B,N,3*H*D] bf16 -> softmax(scale rope(norm(q)) rope(norm(k))^T) v as [B,N,H*D] bf16: `qknorm_rope` + `attention_heads` in one kernel."""

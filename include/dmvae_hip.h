@@ -428,9 +428,18 @@ int dmvae_attention_qkv_stream_bf16(const void* qkv, void* out, void* lse, int b
 /* _heads' operands and results at ANY token count, on the same streaming kernel (csrc/attention_stream.hip, instantiated at the staged head dims 64 and 96):
  * LightningDiT's attention after QK-norm + RoPE beyond 288 tokens -- a 32 x 32 latent grid at patch 1 is 1024 tokens, 24 x 24 is 576.  head_dim 64 or 72;
  * head_dim_padded = head_dim (rows without padding) or head_dim rounded up to 32 (rows zero-padded by the producer): the kernel reads the head_dim real channels of
- * a row either way and computes the same bits.  lse as above, or NULL.  Any seq >= 1, scale > 0; everything else is rejected before any HIP call. */
+ * a row either way and computes the same bits.  lse as above, or NULL.  Any seq >= 1, scale > 0; everything else is rejected before any HIP call.
+ * Reference: lightningdit.py:76-88 (F.scaled_dot_product_attention). */
 int dmvae_attention_heads_stream_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
                                       int head_dim_padded, float scale, dmvae_stream_t stream);
+/* The decoder AttnBlock's attention at ANY token count (csrc/attention_wide.hip): ONE head of 512 channels over the h * w tokens of the mid block.  q, k, v
+ * [batch][seq][512] bf16, three pointers with token rows 512 elements apart (the block's three 1x1 conv outputs viewed [n, s, c]) -> out [batch][seq][512] bf16 =
+ * softmax(scale q k^T) v; lse f32 [batch][seq] = scale * max_k(q.k) + log(sum_k exp(scale (q.k - max))), natural log, or NULL.  A kernel of its own that streams
+ * 32-key K / V tiles through LDS with an online softmax and the rounding sites of csrc/attention_stream.hip: nothing of size seq x seq reaches HBM, reruns and
+ * batch splits are bit-identical.  Any seq >= 1, channels == 512, a finite scale > 0; everything else (a null q / k / v / out, batch < 1, a grid that does not
+ * fit) is rejected with -22 before any HIP call.  Reference: models/flux_ae.py:37-49 (AttnBlock.attention: one head, d = C). */
+int dmvae_attention_wide_stream_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int channels, float scale,
+                                     dmvae_stream_t stream);
 /* The whole attention of a LightningDiT block from the qkv Linear's output [batch][seq][3][heads][head_dim] bf16: per-head RMSNorm (bf16 result) * weight
  * and the 2-D rotary embedding (the arithmetic of dmvae_qknorm_rope_bf16; cos / sin tables [seq][head_dim] f32) are applied to q and k as they enter the
  * fused kernel -> out [batch][seq][heads*head_dim].  lightningdit.py:66-88 in one launch, no head-major q / k / v in HBM.  head_dim % 8 == 0, <= 96; seq <= 288. */
@@ -459,7 +468,8 @@ int dmvae_attention_bwd_qkv_stream_bf16(const void* qkv, const void* out, const 
                                         int head_dim, float scale, dmvae_stream_t stream);
 /* _bwd_heads_lse's operands and results at ANY token count, on the same two streaming passes (the backward of dmvae_attention_heads_stream_bf16): head_dim 64 or 72,
  * head_dim_padded = head_dim or head_dim rounded up to 32 (the padded columns of dq / dk are written as zeros).  lse REQUIRED, delta = batch * heads * seq floats of
- * caller-provided scratch, overwritten.  Fixed summation order: reruns and batch splits are bit-identical.  Everything else is rejected before any HIP call. */
+ * caller-provided scratch, overwritten.  Fixed summation order: reruns and batch splits are bit-identical.  Everything else is rejected before any HIP call.
+ * Reference: autograd of lightningdit.py:76-88 (train_dmd.py:565-575). */
 int dmvae_attention_bwd_heads_stream_bf16(const void* q, const void* k, const void* v, const void* out, const void* dout, const void* lse, void* dq, void* dk,
                                           void* dv, void* delta, int batch, int seq, int heads, int head_dim, int head_dim_padded, float scale,
                                           dmvae_stream_t stream);

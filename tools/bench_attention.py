@@ -16,7 +16,12 @@ either attention backward.
 `--heads-stream` / `--heads-stream-bwd` (either or both in one run; `--out FILE` writes their tables): LightningDiT's attention beyond 288 tokens on head-major
 operands -- `ops.attention_heads_stream` / `ops.attention_bwd_heads_stream` (the same two source files, instantiated at the staged head dims 64 and 96) against the
 composed route of `lightningdit_fast._attention` / `functional.DitBlockFn` built from this build's own ops (f32-score GEMM + row softmax + GEMM, P saved for the
-backward), at B x H = 16 x 16, N = 576 and 1024, D = 72 and 64; rounds interleaved in one process, median, minimum and spread."""
+backward), at B x H = 16 x 16, N = 576 and 1024, D = 72 and 64; rounds interleaved in one process, median, minimum and spread.
+
+`--wide` (`--out FILE` writes its table): the decoder AttnBlock's one head of 512 channels -- `ops.attention_wide_stream` (csrc/attention_wide.hip) against the
+composed forward of `functional.AttnBlockFn` (gemm_nt + softmax_rows + transpose_last2 + gemm_nt) at B = 32, S = 2304 (384 px), 4096 (512 px) and 1024 (the 256-px
+training shape, which stays on the composed route), rounds interleaved in one process; 4 S^2 512 FLOP per sample.  Then the allocation of one AttnBlock(512)
+forward + backward at S = 4096, B = 8, on either route: what the forward leaves allocated, and the peak of forward + backward."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -38,7 +43,7 @@ def timed(fn, n=50):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-SECTION_ONLY = any(f in sys.argv for f in ("--stream-only", "--stream-bwd", "--heads-stream", "--heads-stream-bwd"))
+SECTION_ONLY = any(f in sys.argv for f in ("--stream-only", "--stream-bwd", "--heads-stream", "--heads-stream-bwd", "--wide"))
 for B in (() if SECTION_ONLY else (16, 32, 64)):
     H, N, D, DP = 16, 256, 72, 96
     q = torch.zeros(B * H, N, DP, device="cuda", dtype=BF); k = torch.zeros_like(q)
@@ -264,8 +269,84 @@ def heads_stream_section(fwd, bwd, out_path):
             f.write(text + "\n")
 
 
+# ---- the decoder AttnBlock's attention: one head of 512 channels --------------------------------------------------------------------------------------------
+def wide_section(out_path):
+    from dmvae_amd import functional as Fn
+    from dmvae_amd.models.flux_ae import AttnBlock
+    B, C = 32, 512
+    scale = C ** -0.5
+    cases, lines = {}, []
+
+    def comp_fwd(q, k, v):      # functional.AttnBlockFn's composed forward
+        return ops.gemm_nt(ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), scale), ops.transpose_last2(v))
+    for S in (2304, 4096, 1024):
+        q, k, v = (torch.randn(B, S, C, device="cuda", generator=g).to(BF) for _ in range(3))
+        a, c = ops.attention_wide_stream(q, k, v, scale).float(), comp_fwd(q, k, v).float()
+        lines.append(f"S={S}: streaming vs composed out rel-L2 {((a - c).norm() / c.norm()).item():.2e}")
+        del a, c
+        cases[f"streaming + lse   S={S:4d}"] = (S, lambda q=q, k=k, v=v: ops.attention_wide_stream(q, k, v, scale, need_lse=True))
+        cases[f"streaming, no lse S={S:4d}"] = (S, lambda q=q, k=k, v=v: ops.attention_wide_stream(q, k, v, scale))
+        cases[f"composed          S={S:4d}"] = (S, lambda q=q, k=k, v=v: comp_fwd(q, k, v))
+    rounds, calls = 7, 10
+    times = {k_: [] for k_ in cases}
+    for _ in range(rounds):                 # interleaved rounds
+        for k_, (_, fn) in cases.items():
+            times[k_].append(timed(fn, n=calls))
+    lines += [f"decoder AttnBlock attention forward, one head of {C} channels, B = {B}, random data, {rounds} interleaved rounds of {calls} calls; TFLOP/s on 4 S^2 {C} FLOP "
+              f"per sample; composed = gemm_nt (f32 scores) + softmax_rows + transpose_last2 + gemm_nt, this build's own ops",
+              f"{'case':28s} {'median us':>10s} {'min us':>10s} {'max us':>10s} {'TF/s (median)':>14s}"]
+    med = {}
+    for k_, (S, _) in cases.items():
+        t = sorted(times[k_])
+        med[k_] = t[len(t) // 2]
+        lines.append(f"{k_:28s} {med[k_]:10.1f} {t[0]:10.1f} {t[-1]:10.1f} {4.0 * B * S * S * C / med[k_] * 1e-6:14.1f}")
+    for S in (2304, 4096, 1024):
+        lines.append(f"S={S}: composed / streaming + lse (median) = {med[f'composed          S={S:4d}'] / med[f'streaming + lse   S={S:4d}']:.2f}")
+    del cases, q, k, v
+    torch.cuda.empty_cache()
+    # one AttnBlock(512), forward + backward at 64 x 64 tokens: what the forward leaves allocated, and the peak of the whole, above the starting point
+    torch.manual_seed(0)
+    blk = AttnBlock(C).cuda()
+    Bm, side = 8, 64
+    x0 = torch.randn(Bm, side, side, C, device="cuda", generator=g).to(BF)
+    dy = torch.randn(Bm, side, side, C, device="cuda", generator=g).to(BF)
+
+    def block_alloc(route):
+        Fn.ATTN_WIDE_STREAM = route
+        try:
+            x = x0.clone().requires_grad_(True)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            y = blk.forward_nhwc(x)
+            torch.cuda.synchronize()
+            held, fwd_peak = torch.cuda.memory_allocated() - before, torch.cuda.max_memory_allocated() - before
+            y.backward(dy)
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - before
+        finally:
+            Fn.ATTN_WIDE_STREAM = None
+        blk.zero_grad(set_to_none=True)
+        return held / 2 ** 20, fwd_peak / 2 ** 20, peak / 2 ** 20
+    lines.append("")
+    lines.append(f"one AttnBlock({C}) at {side} x {side} = {side * side} tokens, B = {Bm}: MiB above the starting point (second call of each route; the first sizes the workspaces)")
+    lines.append(f"{'route':28s} {'held after fwd':>15s} {'peak of fwd':>12s} {'peak fwd+bwd':>13s}")
+    for name, route in (("streaming forward", True), ("composed forward", False)):
+        block_alloc(route)
+        held, fwd_peak, peak = block_alloc(route)
+        lines.append(f"{name:28s} {held:15.1f} {fwd_peak:12.1f} {peak:13.1f}")
+    text = "\n".join(lines)
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
-if "--heads-stream" in sys.argv or "--heads-stream-bwd" in sys.argv:
+if "--wide" in sys.argv:
+    wide_section(OUT)
+elif "--heads-stream" in sys.argv or "--heads-stream-bwd" in sys.argv:
     heads_stream_section("--heads-stream" in sys.argv, "--heads-stream-bwd" in sys.argv, OUT)
 elif "--stream-bwd" in sys.argv:
     stream_bwd_section(OUT)
