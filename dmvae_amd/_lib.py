@@ -127,6 +127,7 @@ SIGNATURES = {
     "dmvae_attention_heads_lse_bf16": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_attention_heads_stream_bf16": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_attention_wide_stream_bf16": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_float, c_void_p]),
+    "dmvae_attention_wide_bwd_stream_bf16": (c_int, [c_void_p] * 10 + [c_int] * 3 + [c_float, c_void_p]),
     "dmvae_attention_bwd_heads_stream_bf16": (c_int, [c_void_p] * 10 + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_attention_bwd_qkv_lse_bf16": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_float, c_void_p]),
     "dmvae_attention_bwd_qkv_stream_bf16": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_float, c_void_p]),

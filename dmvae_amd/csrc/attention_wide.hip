@@ -5,7 +5,8 @@
 // queries in registers beside 64-key tiles); at 512 channels the same structure needs the whole unified register file of a SIMD for one wave, hence a file of its own.
 //
 // Operands: q, k, v [B][S][512] bf16, three pointers, token rows 512 elements apart (the three 1x1 conv outputs of AttnBlockFn viewed [n, s, c]); out [B][S][512] bf16;
-// optional lse [B][S] f32 = scale * max + log(sum) of a query's scaled scores (natural log, the definition of attention_stream.hip).
+// optional lse [B][S] f32 = scale * max + log(sum) of a query's scaled scores (natural log, the definition of attention_stream.hip): what the streaming backward,
+// attention_wide_bwd.hip, rebuilds P from -- functional.AttnBlockFn asks for it whenever that backward will run; the out bits are the same with and without it.
 //
 // Structure: a workgroup = 4 waves, ONE PER SIMD (launch bound 256: a wave may take the unified 512-register file), owns 64 consecutive queries of one sample and walks
 // the ceil(S / 32) key tiles.  Two waves share 32 queries: both compute the same scores and the same softmax (the same instructions on the same data, so the same bits),

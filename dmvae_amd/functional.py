@@ -256,6 +256,20 @@ def _attn_wide_stream(s: int, c: int) -> bool:
     return bool(ATTN_WIDE_STREAM)
 
 
+ATTN_WIDE_BWD_STREAM = None      # None: the default below; True / False: tests force a route (tests/test_gpu_attention_wide_bwd.py)
+
+
+def _attn_wide_bwd_stream(s: int, c: int, fwd_streamed: bool) -> bool:
+    """AttnBlock's backward on the streaming d = 512 kernels (csrc/attention_wide_bwd.hip).  Only behind a streaming forward: a composed forward saved P and has no lse.
+    By default exactly when the forward streamed by ITS default rule; a forward route forced through ATTN_WIDE_STREAM is a test's A/B of the forward alone and keeps the
+    composed backward (tests/test_gpu_attention_wide.py pins that pair bit for bit).  True: whenever the forward streamed, forced or not.  False: never."""
+    if not fwd_streamed or not ops.attention_wide_supported(s, c) or parity.on():
+        return False
+    if ATTN_WIDE_BWD_STREAM is None:
+        return ATTN_WIDE_STREAM is None
+    return bool(ATTN_WIDE_BWD_STREAM)
+
+
 def _attn_pad(t: torch.Tensor, sp: int) -> torch.Tensor:
     """[n, s, c] -> [n, sp, c] with zero rows appended (the same tensor when sp == s)"""
     n, s, c = t.shape
@@ -277,7 +291,9 @@ def _attn_probs(q: torch.Tensor, k: torch.Tensor, scale: float, s: int) -> torch
 
 class AttnBlockFn(torch.autograd.Function):
     """x + proj_out(SDPA(q,k,v)) over (h w) tokens, single head, d = C (flux_ae.py:37-52).  Up to 1024 tokens the attention is composed from GEMMs with P [n, s, s]
-    saved for backward; above it (`_attn_wide_stream`) the forward is one streaming kernel that saves nothing s x s, and backward recomputes P on the composed ops.
+    saved for backward; above it (`_attn_wide_stream`) the forward is one streaming kernel that saves its row statistics lse [n, s] and nothing s x s, and backward
+    (`_attn_wide_bwd_stream`) is the two streaming kernels of csrc/attention_wide_bwd.hip, which rebuild P tile by tile in registers: nothing s x s reaches HBM in
+    either direction.  (A forward route forced by a test keeps a backward that recomputes P on the composed ops.)
     The composed GEMMs that reduce over tokens take multiples of 32 (gemm_nt: K % 32; gemm_tn: M % 8): another token count (18 x 18 latents give a 36 x 36 = 1296
     token grid) runs them on operands padded with zero rows to the next multiple -- with s % 32 == 0, every shape up to here, the calls are the unpadded ones."""
 
@@ -292,15 +308,21 @@ class AttnBlockFn(torch.autograd.Function):
         v = ops.conv2d_nhwc(hn, packed(vw), vb, ks=1).view(n, s, c)
         scale = float(c) ** -0.5
         ctx.stream = _attn_wide_stream(s, c)
-        if ctx.stream:       # above 1024 tokens: one streaming kernel (csrc/attention_wide.hip), no [n, s, s] tensor written or saved; backward recomputes P
-            o = ops.attention_wide_stream(q, k, v, scale)      # without lse: backward recomputes P, nothing reads the row statistics yet
+        ctx.bwd_stream = _attn_wide_bwd_stream(s, c, ctx.stream)
+        lse = None
+        if ctx.bwd_stream:   # above 1024 tokens: one streaming kernel (csrc/attention_wide.hip), no [n, s, s] tensor written or saved; the streaming backward reads lse
+            o, lse = ops.attention_wide_stream(q, k, v, scale, need_lse=True)      # the same out bits as the form without lse
+        elif ctx.stream:     # a forced forward route: backward recomputes P on the composed ops, nothing reads the row statistics
+            o = ops.attention_wide_stream(q, k, v, scale)
         else:
             p = _attn_probs(_attn_pad(q, sp), _attn_pad(k, sp), scale, s)         # [n, sp, sp] bf16
             o = ops.gemm_nt(p, ops.transpose_last2(_attn_pad(v, sp)))             # [n, sp, c]
             if sp != s:
                 o = o[:, :s].contiguous()
         y, sty = ops.conv2d_nhwc_gnstats(o.view(n, h, w, c), packed(pw), pb, residual=x, ks=1)
-        if ctx.stream:
+        if ctx.bwd_stream:
+            ctx.save_for_backward(x, st, hn, q, k, v, o, lse, nw, nb, qw, kw, vw, pw)
+        elif ctx.stream:
             ctx.save_for_backward(x, st, hn, q, k, v, o, nw, nb, qw, kw, vw, pw)
         else:
             ctx.save_for_backward(x, st, hn, q, k, v, p, o, nw, nb, qw, kw, vw, pw)
@@ -310,27 +332,32 @@ class AttnBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.stream:
+        if ctx.bwd_stream:
+            x, st, hn, q, k, v, o, lse, nw, nb, qw, kw, vw, pw = ctx.saved_tensors
+        elif ctx.stream:
             x, st, hn, q, k, v, o, nw, nb, qw, kw, vw, pw = ctx.saved_tensors
         else:
             x, st, hn, q, k, v, p, o, nw, nb, qw, kw, vw, pw = ctx.saved_tensors
         n, h, w, c = x.shape
         s = h * w
-        sp = (s + 31) // 32 * 32
-        q, k, v = _attn_pad(q, sp), _attn_pad(k, sp), _attn_pad(v, sp)
-        if ctx.stream:       # P from the two calls the composed forward makes: the [n, s, s] tensors exist only inside this backward
-            p = _attn_probs(q, k, ctx.scale, s)
         dy = _c(dy)
         qb, kb, vb, pb = ctx.bias_params
         dpw, dpb = ops.conv2d_nhwc_wgrad(dy, o.view(n, h, w, c), 1, dw_out=_dst(pw), db_out=_dst(pb))
-        do = _attn_pad(ops.conv2d_nhwc(dy, packed(pw, True), ks=1).view(n, s, c), sp)
-        dp = ops.gemm_nt(do, v, out_f32=True)                                  # dP[q][key] = do[q].v[key]
-        ds = ops.softmax_rows_bwd(dp, p, ctx.scale)                            # bf16, includes the scale
-        dv = ops.gemm_tn(p, do)                                                # [n, key, c]
-        dq = ops.gemm_nt(ds, ops.transpose_last2(k))                           # [n, q, c]
-        dk = ops.gemm_tn(ds, q)                                                # [n, key, c]
-        if sp != s:
-            dq, dk, dv = dq[:, :s].contiguous(), dk[:, :s].contiguous(), dv[:, :s].contiguous()
+        do = ops.conv2d_nhwc(dy, packed(pw, True), ks=1).view(n, s, c)
+        if ctx.bwd_stream:   # two streaming kernels (csrc/attention_wide_bwd.hip): P is rebuilt from lse in registers, no padding, nothing [n, s, s] in HBM
+            dq, dk, dv = ops.attention_wide_bwd_stream(q, k, v, o, do, lse, ctx.scale)
+        else:
+            sp = (s + 31) // 32 * 32
+            q, k, v, do = _attn_pad(q, sp), _attn_pad(k, sp), _attn_pad(v, sp), _attn_pad(do, sp)
+            if ctx.stream:   # P from the two calls the composed forward makes: the [n, s, s] tensors exist only inside this backward
+                p = _attn_probs(q, k, ctx.scale, s)
+            dp = ops.gemm_nt(do, v, out_f32=True)                              # dP[q][key] = do[q].v[key]
+            ds = ops.softmax_rows_bwd(dp, p, ctx.scale)                        # bf16, includes the scale
+            dv = ops.gemm_tn(p, do)                                            # [n, key, c]
+            dq = ops.gemm_nt(ds, ops.transpose_last2(k))                       # [n, q, c]
+            dk = ops.gemm_tn(ds, q)                                            # [n, key, c]
+            if sp != s:
+                dq, dk, dv = dq[:, :s].contiguous(), dk[:, :s].contiguous(), dv[:, :s].contiguous()
         dq4, dk4, dv4 = dq.view(n, h, w, c), dk.view(n, h, w, c), dv.view(n, h, w, c)
         dqw, dqb = ops.conv2d_nhwc_wgrad(dq4, hn, 1, dw_out=_dst(qw), db_out=_dst(qb))
         dkw, dkb = ops.conv2d_nhwc_wgrad(dk4, hn, 1, dw_out=_dst(kw), db_out=_dst(kb))

@@ -1146,6 +1146,24 @@ def attention_wide_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sca
     return (out, lse) if need_lse else out
 
 
+def attention_wide_bwd_stream(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, o: torch.Tensor, dout: torch.Tensor, lse: torch.Tensor, scale: float):
+    """Backward of `attention_wide_stream`: q, k, v, o (its result), dout [B, S, 512] bf16 contiguous and lse [B, S] f32 (its row statistics) -> (dq, dk, dv), each
+    [B, S, 512] bf16.  Any S >= 1, on the two streaming kernels of csrc/attention_wide_bwd.hip, which rebuild P tile by tile in registers: nothing of size S x S reaches
+    HBM (the only scratch is delta [B, S] f32, allocated here), reruns and batch splits are bit-identical.  o is checked and passed on; the kernels form delta from
+    their own P and dP and do not read it."""
+    q = _req(q, bf16, "q"); k = _req(k, bf16, "k"); v = _req(v, bf16, "v"); o = _req(o, bf16, "o"); dout = _req(dout, bf16, "dout")
+    b, s, c = q.shape
+    assert attention_wide_supported(s, c), f"attention_wide_bwd_stream: one head of 512 channels, S >= 1 (got S = {s}, C = {c})"
+    assert k.shape == q.shape and v.shape == q.shape and o.shape == q.shape and dout.shape == q.shape
+    assert lse.dtype == f32 and lse.is_contiguous() and lse.shape == (b, s)
+    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    delta = torch.empty(b, s, dtype=f32, device=q.device)      # the kernels' only scratch
+    check(_lib.lib().dmvae_attention_wide_bwd_stream_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(), lse.data_ptr(), dq.data_ptr(),
+                                                          dk.data_ptr(), dv.data_ptr(), delta.data_ptr(), b, s, c, float(scale), _stream()),
+          "attention_wide_bwd_stream_bf16")
+    return dq, dk, dv
+
+
 def attention_qknorm_rope(qkv: torch.Tensor, qw: torch.Tensor, kw: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads: int, eps: float,
                           scale: float) -> torch.Tensor:
     """qkv [B,N,3*H*D] bf16 -> softmax(scale rope(norm(q)) rope(norm(k))^T) v as [B,N,H*D] bf16: `qknorm_rope` + `attention_heads` in one kernel."""

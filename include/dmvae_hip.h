@@ -440,6 +440,16 @@ int dmvae_attention_heads_stream_bf16(const void* q, const void* k, const void* 
  * fit) is rejected with -22 before any HIP call.  Reference: models/flux_ae.py:37-49 (AttnBlock.attention: one head, d = C). */
 int dmvae_attention_wide_stream_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int channels, float scale,
                                      dmvae_stream_t stream);
+/* Backward of dmvae_attention_wide_stream_bf16 at ANY token count (csrc/attention_wide_bwd.hip): q, k, v, o (the forward's out), dout [batch][seq][512] bf16 and
+ * lse f32 [batch][seq] (the forward's row statistics, required) -> dq, dk, dv [batch][seq][512] bf16.  Two kernels on `stream` -- a query pass that writes dq and
+ * delta, a key pass that writes dk and dv -- which rebuild P = exp(scale s - lse) tile by tile in registers: nothing of size seq x seq reaches HBM, the only scratch
+ * is delta f32 [batch][seq] (required, its contents on entry do not matter): delta_q = sum_k P dP, formed in f32 by a first walk of the query pass from the kernel's
+ * own P and dP -- o is validated and not read (dout_q . o_q on the bf16 o is not accurate enough on ill-conditioned rows) -- and scale * dS enters the matrix cores
+ * as the sum of two bf16 values; otherwise the rounding sites of dmvae_attention_bwd_*_stream_bf16.  Every sum has a fixed order and everything is per sample: no
+ * float atomics, reruns and batch splits are bit-identical.  Any seq >= 1, channels == 512, a finite scale > 0;
+ * everything else (a null operand, batch < 1, a grid that does not fit) is rejected with -22 before any HIP call.  Reference: autograd of models/flux_ae.py:37-49. */
+int dmvae_attention_wide_bwd_stream_bf16(const void* q, const void* k, const void* v, const void* o, const void* dout, const void* lse, void* dq, void* dk, void* dv,
+                                         void* delta, int batch, int seq, int channels, float scale, dmvae_stream_t stream);
 /* The whole attention of a LightningDiT block from the qkv Linear's output [batch][seq][3][heads][head_dim] bf16: per-head RMSNorm (bf16 result) * weight
  * and the 2-D rotary embedding (the arithmetic of dmvae_qknorm_rope_bf16; cos / sin tables [seq][head_dim] f32) are applied to q and k as they enter the
  * fused kernel -> out [batch][seq][heads*head_dim].  lightningdit.py:66-88 in one launch, no head-major q / k / v in HBM.  head_dim % 8 == 0, <= 96; seq <= 288. */

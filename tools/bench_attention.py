@@ -21,7 +21,12 @@ backward), at B x H = 16 x 16, N = 576 and 1024, D = 72 and 64; rounds interleav
 `--wide` (`--out FILE` writes its table): the decoder AttnBlock's one head of 512 channels -- `ops.attention_wide_stream` (csrc/attention_wide.hip) against the
 composed forward of `functional.AttnBlockFn` (gemm_nt + softmax_rows + transpose_last2 + gemm_nt) at B = 32, S = 2304 (384 px), 4096 (512 px) and 1024 (the 256-px
 training shape, which stays on the composed route), rounds interleaved in one process; 4 S^2 512 FLOP per sample.  Then the allocation of one AttnBlock(512)
-forward + backward at S = 4096, B = 8, on either route: what the forward leaves allocated, and the peak of forward + backward."""
+forward + backward at S = 4096, B = 8, on either route: what the forward leaves allocated, and the peak of forward + backward.
+
+`--wide-bwd` (`--out FILE` writes its table): that attention's backward -- `ops.attention_wide_bwd_stream` (csrc/attention_wide_bwd.hip) against the backward
+`functional.AttnBlockFn` ran above 1024 tokens before it (P recomputed by gemm_nt + softmax_rows, then gemm_nt + softmax_rows_bwd + gemm_tn + gemm_nt + gemm_tn) at
+B = 32, S = 1024, 2304 and 4096, rounds interleaved in one process; 10 S^2 512 FLOP per sample (the five products of the minimal form; the kernels run eleven -- S and dP three times, the two dS products
+twice each as hi + lo, P^T dO once -- the recomputing route six).  Then the allocation table of `--wide` again with the streaming backward in it."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -43,7 +48,7 @@ def timed(fn, n=50):
 
 
 g = torch.Generator(device="cuda").manual_seed(0)
-SECTION_ONLY = any(f in sys.argv for f in ("--stream-only", "--stream-bwd", "--heads-stream", "--heads-stream-bwd", "--wide"))
+SECTION_ONLY = any(f in sys.argv for f in ("--stream-only", "--stream-bwd", "--heads-stream", "--heads-stream-bwd", "--wide", "--wide-bwd"))
 for B in (() if SECTION_ONLY else (16, 32, 64)):
     H, N, D, DP = 16, 256, 72, 96
     q = torch.zeros(B * H, N, DP, device="cuda", dtype=BF); k = torch.zeros_like(q)
@@ -343,8 +348,89 @@ def wide_section(out_path):
             f.write(text + "\n")
 
 
+# ---- its backward ----------------------------------------------------------------------------------------------------------------------------------------------
+def wide_bwd_section(out_path):
+    from dmvae_amd import functional as Fn
+    from dmvae_amd.models.flux_ae import AttnBlock
+    B, C = 32, 512
+    scale = C ** -0.5
+    cases, lines = {}, []
+
+    def comp_bwd(q, k, v, do):      # functional.AttnBlockFn's backward behind a streaming forward without the streaming backward: P recomputed, then the composed body
+        p = Fn._attn_probs(q, k, scale, q.shape[1])
+        ds = ops.softmax_rows_bwd(ops.gemm_nt(do, v, out_f32=True), p, scale)
+        return ops.gemm_nt(ds, ops.transpose_last2(k)), ops.gemm_tn(ds, q), ops.gemm_tn(p, do)
+    for S in (1024, 2304, 4096):
+        q, k, v, do = (torch.randn(B, S, C, device="cuda", generator=g).to(BF) for _ in range(4))
+        o, lse = ops.attention_wide_stream(q, k, v, scale, need_lse=True)
+        gs, gc = ops.attention_wide_bwd_stream(q, k, v, o, do, lse, scale), comp_bwd(q, k, v, do)
+        lines.append(f"S={S}: streaming vs composed " + "  ".join(f"{n_} rel-L2 {((x.float() - y.float()).norm() / y.float().norm()).item():.2e}"
+                                                                 for n_, x, y in zip(("dq", "dk", "dv"), gs, gc)))
+        del gs, gc
+        cases[f"bwd streaming          S={S:4d}"] = (S, lambda q=q, k=k, v=v, o=o, do=do, lse=lse: ops.attention_wide_bwd_stream(q, k, v, o, do, lse, scale))
+        cases[f"bwd composed recompute S={S:4d}"] = (S, lambda q=q, k=k, v=v, do=do: comp_bwd(q, k, v, do))
+    rounds, calls = 7, 10
+    times = {k_: [] for k_ in cases}
+    for _ in range(rounds):                 # interleaved rounds
+        for k_, (_, fn) in cases.items():
+            times[k_].append(timed(fn, n=calls))
+    lines += [f"decoder AttnBlock attention backward, one head of {C} channels, B = {B}, random data, {rounds} interleaved rounds of {calls} calls; TFLOP/s on 10 S^2 {C} "
+              f"FLOP per sample; composed recompute = gemm_nt (f32 scores) + softmax_rows, gemm_nt (f32 dP) + softmax_rows_bwd, gemm_tn, transpose_last2 + gemm_nt, "
+              f"gemm_tn, this build's own ops",
+              f"{'case':32s} {'median us':>10s} {'min us':>10s} {'max us':>10s} {'TF/s (median)':>14s}"]
+    med = {}
+    for k_, (S, _) in cases.items():
+        t = sorted(times[k_])
+        med[k_] = t[len(t) // 2]
+        lines.append(f"{k_:32s} {med[k_]:10.1f} {t[0]:10.1f} {t[-1]:10.1f} {10.0 * B * S * S * C / med[k_] * 1e-6:14.1f}")
+    for S in (1024, 2304, 4096):
+        lines.append(f"S={S}: composed recompute / streaming (median) = {med[f'bwd composed recompute S={S:4d}'] / med[f'bwd streaming          S={S:4d}']:.2f}")
+    del cases, q, k, v, do, o, lse
+    torch.cuda.empty_cache()
+    # one AttnBlock(512), forward + backward at 64 x 64 tokens: what the forward leaves allocated, and the peaks, above the starting point
+    torch.manual_seed(0)
+    blk = AttnBlock(C).cuda()
+    Bm, side = 8, 64
+    x0 = torch.randn(Bm, side, side, C, device="cuda", generator=g).to(BF)
+    dy = torch.randn(Bm, side, side, C, device="cuda", generator=g).to(BF)
+
+    def block_alloc(fwd, bwd):
+        Fn.ATTN_WIDE_STREAM, Fn.ATTN_WIDE_BWD_STREAM = fwd, bwd
+        try:
+            x = x0.clone().requires_grad_(True)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            before = torch.cuda.memory_allocated()
+            y = blk.forward_nhwc(x)
+            torch.cuda.synchronize()
+            held, fwd_peak = torch.cuda.memory_allocated() - before, torch.cuda.max_memory_allocated() - before
+            y.backward(dy)
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - before
+        finally:
+            Fn.ATTN_WIDE_STREAM, Fn.ATTN_WIDE_BWD_STREAM = None, None
+        blk.zero_grad(set_to_none=True)
+        return held / 2 ** 20, fwd_peak / 2 ** 20, peak / 2 ** 20
+    lines.append("")
+    lines.append(f"one AttnBlock({C}) at {side} x {side} = {side * side} tokens, B = {Bm}: MiB above the starting point (second call of each route; the first sizes the workspaces)")
+    lines.append(f"{'route':44s} {'held after fwd':>15s} {'peak of fwd':>12s} {'peak fwd+bwd':>13s}")
+    for name, fwd, bwd in (("streaming forward, streaming backward", None, None), ("streaming forward, composed recompute", None, False),
+                           ("composed forward and backward", False, None)):
+        block_alloc(fwd, bwd)
+        held, fwd_peak, peak = block_alloc(fwd, bwd)
+        lines.append(f"{name:44s} {held:15.1f} {fwd_peak:12.1f} {peak:13.1f}")
+    text = "\n".join(lines)
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text + "\n")
+
+
 OUT = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
-if "--wide" in sys.argv:
+if "--wide-bwd" in sys.argv:
+    wide_bwd_section(OUT)
+elif "--wide" in sys.argv:
     wide_section(OUT)
 elif "--heads-stream" in sys.argv or "--heads-stream-bwd" in sys.argv:
     heads_stream_section("--heads-stream" in sys.argv, "--heads-stream-bwd" in sys.argv, OUT)
