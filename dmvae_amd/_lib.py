@@ -222,6 +222,19 @@ SIGNATURES = {
     "dmvae_nchw_f32_to_nhwc_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dmvae_lpips_diff_f32": (c_int, [c_void_p] * 6 + [c_size_t, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "dmvae_layernorm_f32": (c_int, [c_void_p] * 4 + [c_int, c_int, c_float, c_void_p]),
+    # convolution along the token axis (csrc/conv_tokens.hip)
+    "dmvae_conv_tokens_pack": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
+    "dmvae_conv_tokens_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "dmvae_conv_tokens_dgrad": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "dmvae_conv_tokens_wgrad_workspace": (c_size_t, [c_int] * 4),
+    "dmvae_conv_tokens_wgrad": (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 4 + [c_void_p]),
+    # the passes around the DINOv2 discriminator's heads (csrc/dinodisc.hip), the frozen block's LayerScale backward (csrc/vit_bwd.hip)
+    "dmvae_dino_tap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dmvae_dino_untap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dmvae_dino_tail_fwd": (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_void_p]),
+    "dmvae_dino_tail_bwd_workspace": (c_size_t, [c_size_t, c_int]),
+    "dmvae_dino_tail_bwd": (c_int, [c_void_p] * 8 + [c_size_t, c_size_t, c_int, c_void_p]),
+    "dmvae_layerscale_bwd_dx": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
 }
 
 _lib = None

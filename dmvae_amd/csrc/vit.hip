@@ -9,18 +9,20 @@
 
 namespace dmvae_vit {
 
-// one wave per row; C % 256 == 0 (4 floats per lane per sweep), C <= 4096.
+// one wave per row; C = SWEEPS * 256 (4 floats per lane per sweep) + TAIL * 128 (a last half sweep of 2 floats per lane: ViT-S, C = 384 = 256 + 128), C <= 4096.
+// TAIL = false compiles to exactly the sweeps-only kernel: the widths that are multiples of 256 keep their bits.
 // RES: the LayerScale + residual add that precedes every LayerNorm but the first (x += ls * r, the previous branch's output r in bf16) in the same pass --
 // the f32 residual stream is read and written once instead of read-written by one kernel and read again by the next (bit-identical to the two kernels).
-template <int SWEEPS, bool RES = false>
+template <int SWEEPS, bool RES = false, bool TAIL = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, bf16* __restrict__ y, int rows, float eps,
                                                         const bf16* __restrict__ r = nullptr, const float* __restrict__ ls = nullptr) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
-  constexpr int C = SWEEPS * 256;
+  constexpr int C = SWEEPS * 256 + (TAIL ? 128 : 0), T0 = SWEEPS * 256;   // T0: first column of the half sweep
   float* xr = x + (size_t)row * C;
   f32x4 v[SWEEPS];
+  f32x2 vt = {0.f, 0.f};
   float s = 0.f;
 #pragma unroll
   for (int k = 0; k < SWEEPS; k++) {
@@ -34,12 +36,27 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, c
     }
     s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
   }
+  if constexpr (TAIL) {
+    vt = *reinterpret_cast<const f32x2*>(xr + T0 + lane * 2);
+    if constexpr (RES) {
+      const bf16x2 rv = *reinterpret_cast<const bf16x2*>(r + (size_t)row * C + T0 + lane * 2);
+      const f32x2 g = *reinterpret_cast<const f32x2*>(ls + T0 + lane * 2);
+#pragma unroll
+      for (int e = 0; e < 2; e++) vt[e] = fmaf(g[e], (float)rv[e], vt[e]);
+      *reinterpret_cast<f32x2*>(xr + T0 + lane * 2) = vt;
+    }
+    s += vt[0] + vt[1];
+  }
   const float mean = wave_sum(s) * (1.f / C);
   float ss = 0.f;
 #pragma unroll
   for (int k = 0; k < SWEEPS; k++)
 #pragma unroll
     for (int e = 0; e < 4; e++) { const float d = v[k][e] - mean; ss += d * d; }
+  if constexpr (TAIL) {
+#pragma unroll
+    for (int e = 0; e < 2; e++) { const float d = vt[e] - mean; ss += d * d; }
+  }
   const float rstd = rsqrtf(wave_sum(ss) * (1.f / C) + eps);
   bf16* yr = y + (size_t)row * C;
 #pragma unroll
@@ -50,6 +67,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* __restrict__ x, c
 #pragma unroll
     for (int e = 0; e < 4; e++) o[e] = (bf16)((v[k][e] - mean) * rstd * g[e] + b[e]);
     *reinterpret_cast<bf16x4*>(yr + k * 256 + lane * 4) = o;
+  }
+  if constexpr (TAIL) {
+    const f32x2 g = *reinterpret_cast<const f32x2*>(gamma + T0 + lane * 2);
+    const f32x2 b = *reinterpret_cast<const f32x2*>(beta + T0 + lane * 2);
+    bf16x2 o;
+#pragma unroll
+    for (int e = 0; e < 2; e++) o[e] = (bf16)((vt[e] - mean) * rstd * g[e] + b[e]);
+    *reinterpret_cast<bf16x2*>(yr + T0 + lane * 2) = o;
   }
 }
 
@@ -102,9 +127,14 @@ using namespace dmvae_vit;
 extern "C" int dmvae_layernorm_f32_bf16(const void* x, const void* gamma, const void* beta, void* y, int rows, int c, float eps,
                                         hipStream_t stream) {
   DMVAE_CHECK_ARG(x && gamma && beta && y && rows > 0, "layernorm_f32_bf16: bad argument");
-  DMVAE_CHECK_ARG(c == 256 || c == 512 || c == 768 || c == 1024 || c == 1280 || c == 1536,
-                  "layernorm_f32_bf16: width must be a multiple of 256 up to 1536 (got %d)", c);
+  DMVAE_CHECK_ARG(c == 256 || c == 384 || c == 512 || c == 768 || c == 1024 || c == 1280 || c == 1536,
+                  "layernorm_f32_bf16: width must be 384 or a multiple of 256 up to 1536 (got %d)", c);
   const dim3 grid((rows + 3) / 4), block(256);
+  if (c == 384) {
+    hipLaunchKernelGGL((layernorm_kernel<1, false, true>), grid, block, 0, stream, (float*)x, (const float*)gamma, (const float*)beta, (bf16*)y, rows, eps, nullptr, nullptr);
+    DMVAE_CHECK_LAUNCH();
+    return 0;
+  }
   switch (c / 256) {
     case 1: hipLaunchKernelGGL(layernorm_kernel<1>, grid, block, 0, stream, (float*)x, (const float*)gamma, (const float*)beta, (bf16*)y, rows, eps, nullptr, nullptr); break;
     case 2: hipLaunchKernelGGL(layernorm_kernel<2>, grid, block, 0, stream, (float*)x, (const float*)gamma, (const float*)beta, (bf16*)y, rows, eps, nullptr, nullptr); break;
@@ -120,9 +150,15 @@ extern "C" int dmvae_layernorm_f32_bf16(const void* x, const void* gamma, const 
 extern "C" int dmvae_scale_residual_layernorm(void* x, const void* r, const void* ls_gamma, const void* gamma, const void* beta, void* y, int rows, int c,
                                               float eps, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && r && ls_gamma && gamma && beta && y && rows > 0, "scale_residual_layernorm: bad argument");
-  DMVAE_CHECK_ARG(c == 256 || c == 512 || c == 768 || c == 1024 || c == 1280 || c == 1536,
-                  "scale_residual_layernorm: width must be a multiple of 256 up to 1536 (got %d)", c);
+  DMVAE_CHECK_ARG(c == 256 || c == 384 || c == 512 || c == 768 || c == 1024 || c == 1280 || c == 1536,
+                  "scale_residual_layernorm: width must be 384 or a multiple of 256 up to 1536 (got %d)", c);
   const dim3 grid((rows + 3) / 4), block(256);
+  if (c == 384) {
+    hipLaunchKernelGGL((layernorm_kernel<1, true, true>), grid, block, 0, stream, (float*)x, (const float*)gamma, (const float*)beta, (bf16*)y, rows, eps,
+                       (const bf16*)r, (const float*)ls_gamma);
+    DMVAE_CHECK_LAUNCH();
+    return 0;
+  }
 #define DMVAE_SRLN(S) hipLaunchKernelGGL((layernorm_kernel<S, true>), grid, block, 0, stream, (float*)x, (const float*)gamma, (const float*)beta, (bf16*)y, rows, eps, \
                                          (const bf16*)r, (const float*)ls_gamma)
   switch (c / 256) {

@@ -19,28 +19,36 @@ namespace dmvae_vit_bwd {
 
 constexpr int LN_MAX_BLOCKS = 256;
 
-// One wave per row, rows dealt round-robin to the grid's waves; C = SWEEPS * 256.
+// One wave per row, rows dealt round-robin to the grid's waves; C = SWEEPS * 256 + TAIL * 128 (the half sweep of 2 floats per lane: C = 384; TAIL = false is
+// exactly the sweeps-only kernel).
 // part: [gridDim.x][2][C] -- per-block sums of dy * x_hat (dgamma) and dy (dbeta).
-template <int SWEEPS>
+template <int SWEEPS, bool TAIL = false>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ gamma,
                                                             float* __restrict__ dx_io, float* __restrict__ part, int rows, float eps) {
-  constexpr int C = SWEEPS * 256;
+  constexpr int C = SWEEPS * 256 + (TAIL ? 128 : 0), T0 = SWEEPS * 256;
   __shared__ float red[4][2][C];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   f32x4 gm[SWEEPS], ag[SWEEPS], ab[SWEEPS];
+  f32x2 gmt = {0.f, 0.f}, agt = {0.f, 0.f}, abt = {0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < SWEEPS; k++) {
     gm[k] = *reinterpret_cast<const f32x4*>(gamma + k * 256 + lane * 4);
     ag[k] = f32x4{0, 0, 0, 0}; ab[k] = f32x4{0, 0, 0, 0};
   }
+  if constexpr (TAIL) gmt = *reinterpret_cast<const f32x2*>(gamma + T0 + lane * 2);
   for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
     const float* xr = x + (size_t)row * C;
     f32x4 v[SWEEPS];
+    f32x2 vt = {0.f, 0.f}, gt = {0.f, 0.f};
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < SWEEPS; k++) {
       v[k] = *reinterpret_cast<const f32x4*>(xr + k * 256 + lane * 4);
       s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+    }
+    if constexpr (TAIL) {
+      vt = *reinterpret_cast<const f32x2*>(xr + T0 + lane * 2);
+      s += vt[0] + vt[1];
     }
     const float mean = wave_sum(s) * (1.f / C);
     float ss = 0.f;
@@ -48,6 +56,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16* __restri
     for (int k = 0; k < SWEEPS; k++)
 #pragma unroll
       for (int e = 0; e < 4; e++) { v[k][e] -= mean; ss += v[k][e] * v[k][e]; }
+    if constexpr (TAIL) {
+#pragma unroll
+      for (int e = 0; e < 2; e++) { vt[e] -= mean; ss += vt[e] * vt[e]; }
+    }
     const float rstd = rsqrtf(wave_sum(ss) * (1.f / C) + eps);
     f32x4 g[SWEEPS];
     float s1 = 0.f, s2 = 0.f;
@@ -63,6 +75,17 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16* __restri
         ag[k][e] += dv * xh; ab[k][e] += dv;
       }
     }
+    if constexpr (TAIL) {
+      const bf16x2 d = *reinterpret_cast<const bf16x2*>(dy + (size_t)row * C + T0 + lane * 2);
+#pragma unroll
+      for (int e = 0; e < 2; e++) {
+        const float xh = vt[e] * rstd, dv = (float)d[e];
+        vt[e] = xh;
+        gt[e] = dv * gmt[e];
+        s1 += gt[e]; s2 += gt[e] * xh;
+        agt[e] += dv * xh; abt[e] += dv;
+      }
+    }
     const float m1 = wave_sum(s1) * (1.f / C), m2 = wave_sum(s2) * (1.f / C);
     float* dr = dx_io + (size_t)row * C;
 #pragma unroll
@@ -72,11 +95,21 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16* __restri
       for (int e = 0; e < 4; e++) o[e] += rstd * (g[k][e] - m1 - v[k][e] * m2);
       *reinterpret_cast<f32x4*>(dr + k * 256 + lane * 4) = o;
     }
+    if constexpr (TAIL) {
+      f32x2 o = *reinterpret_cast<const f32x2*>(dr + T0 + lane * 2);
+#pragma unroll
+      for (int e = 0; e < 2; e++) o[e] += rstd * (gt[e] - m1 - vt[e] * m2);
+      *reinterpret_cast<f32x2*>(dr + T0 + lane * 2) = o;
+    }
   }
 #pragma unroll
   for (int k = 0; k < SWEEPS; k++) {
     *reinterpret_cast<f32x4*>(&red[wave][0][k * 256 + lane * 4]) = ag[k];
     *reinterpret_cast<f32x4*>(&red[wave][1][k * 256 + lane * 4]) = ab[k];
+  }
+  if constexpr (TAIL) {
+    *reinterpret_cast<f32x2*>(&red[wave][0][T0 + lane * 2]) = agt;
+    *reinterpret_cast<f32x2*>(&red[wave][1][T0 + lane * 2]) = abt;
   }
   __syncthreads();
   for (int i = threadIdx.x; i < 2 * C; i += 256) {
@@ -141,6 +174,19 @@ __global__ __launch_bounds__(256) void layerscale_bwd_kernel(const float* __rest
   }
 }
 
+// dy = gamma * dt (bf16): the input-gradient half of layerscale_bwd_kernel, same product and rounding
+__global__ __launch_bounds__(256) void layerscale_bwd_dx_kernel(const float* __restrict__ dt, const float* __restrict__ gamma, bf16* __restrict__ dy, size_t n8, int c8) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % c8) * 8;
+    const f32x4 a = reinterpret_cast<const f32x4*>(dt)[2 * i], b = reinterpret_cast<const f32x4*>(dt)[2 * i + 1];
+    const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + c), g1 = *reinterpret_cast<const f32x4*>(gamma + c + 4);
+    bf16x8 o;
+#pragma unroll
+    for (int e = 0; e < 4; e++) { o[e] = (bf16)(g0[e] * a[e]); o[4 + e] = (bf16)(g1[e] * b[e]); }
+    reinterpret_cast<bf16x8*>(dy)[i] = o;
+  }
+}
+
 __device__ __forceinline__ float gelu_grad_f(float x) {
   return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
@@ -173,14 +219,17 @@ extern "C" size_t dmvae_vit_bwd_workspace(int c) { return (size_t)LN_MAX_BLOCKS 
 extern "C" int dmvae_layernorm_bwd_f32(const void* dy, const void* x, const void* gamma, void* dx_io, void* dgamma, void* dbeta, void* workspace,
                                        size_t workspace_bytes, int rows, int c, float eps, int accumulate, hipStream_t stream) {
   DMVAE_CHECK_ARG(dy && x && gamma && dx_io && workspace && rows > 0, "layernorm_bwd_f32: bad argument");
-  DMVAE_CHECK_ARG(c == 256 || c == 512 || c == 768 || c == 1024 || c == 1280 || c == 1536,
-                  "layernorm_bwd_f32: width must be a multiple of 256 up to 1536 (got %d)", c);
+  DMVAE_CHECK_ARG(c == 256 || c == 384 || c == 512 || c == 768 || c == 1024 || c == 1280 || c == 1536,
+                  "layernorm_bwd_f32: width must be 384 or a multiple of 256 up to 1536 (got %d)", c);
   DMVAE_CHECK_ARG(workspace_bytes >= dmvae_vit_bwd_workspace(c), "layernorm_bwd_f32: workspace too small");
   int nblk = (rows + 3) / 4; if (nblk > LN_MAX_BLOCKS) nblk = LN_MAX_BLOCKS;
   const dim3 grid(nblk), block(256);
 #define DMVAE_LNB(S) hipLaunchKernelGGL(layernorm_bwd_kernel<S>, grid, block, 0, stream, (const bf16*)dy, (const float*)x, (const float*)gamma, \
                                         (float*)dx_io, (float*)workspace, rows, eps)
-  switch (c / 256) {
+  if (c == 384) {
+    hipLaunchKernelGGL((layernorm_bwd_kernel<1, true>), grid, block, 0, stream, (const bf16*)dy, (const float*)x, (const float*)gamma, (float*)dx_io,
+                       (float*)workspace, rows, eps);
+  } else switch (c / 256) {
     case 1: DMVAE_LNB(1); break;
     case 2: DMVAE_LNB(2); break;
     case 3: DMVAE_LNB(3); break;
@@ -210,6 +259,15 @@ extern "C" int dmvae_layerscale_bwd(const void* dt, const void* y, const void* g
   DMVAE_CHECK_LAUNCH();
   hipLaunchKernelGGL(colsum_parts_kernel, dim3((c + 63) / 64), dim3(256), 0, stream, (const float*)workspace, (float*)dgamma, (float*)dgamma, nblk, 1, c,
                      accumulate);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_layerscale_bwd_dx(const void* dt, const void* gamma, void* dy, size_t rows, int c, hipStream_t stream) {
+  DMVAE_CHECK_ARG(dt && gamma && dy && c > 0 && c % 8 == 0, "layerscale_bwd_dx: width must be a multiple of 8 (got %d)", c);
+  if (rows == 0) return 0;
+  const size_t n8 = rows * (size_t)(c / 8);
+  hipLaunchKernelGGL(layerscale_bwd_dx_kernel, dim3(grid_for(n8, 256, 4096)), dim3(256), 0, stream, (const float*)dt, (const float*)gamma, (bf16*)dy, n8, c / 8);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -1205,6 +1205,121 @@ class VitBlockFn(torch.autograd.Function):
         return dt, dn1w, dn1b, dqkvw, dqkvb, dpw, dpb, dls1, dn2w, dn2b, df1w, df1b, df2w, df2b, dls2, None, None
 
 
+class VitBlockDxFn(torch.autograd.Function):
+    """`VitBlockFn` for a FROZEN block whose input needs a gradient (the DINOv2 discriminator's backbone in the generator's adversarial term, models/dinodisc.py:
+    123-125,181: requires_grad_(False) on the ViT, gradient wanted at the image): the same forward kernels and bits, and a backward that computes d t only -- no
+    weight-gradient GEMMs (`_lin_grads(need_w=False)`), no LayerNorm / LayerScale / bias gradients, attention backward from the saved row statistics -- and keeps
+    only what that needs (t, qkv, o, t_mid, h1).  Head dim 64."""
+
+    @staticmethod
+    def forward(ctx, t, n1w, n1b, qkvw, qkvb, pw, pb, ls1, n2w, n2b, f1w, f1b, f2w, f2b, ls2, heads, eps):
+        b, s, c = t.shape
+        hd = c // heads
+        hn1 = ops.layernorm_bf16(t, n1w, n1b, eps)
+        qkv = linear(hn1, qkvw, qkvb)
+        o, lse = ops.attention_qkv(qkv, heads, hd ** -0.5, need_lse=True)
+        o2 = linear(o, pw, pb)
+        t_mid = ops.scale_residual_(t.clone(), o2, ls1)
+        hn2 = ops.layernorm_bf16(t_mid, n2w, n2b, eps)
+        h1 = linear(hn2, f1w, f1b)
+        o3 = linear(ops.gelu(h1), f2w, f2b)
+        t_out = ops.scale_residual_(t_mid.clone(), o3, ls2)
+        ctx.save_for_backward(t, qkv, o, t_mid, h1, n1w, qkvw, pw, ls1, n2w, f1w, f2w, ls2)
+        ctx.others = (qkvb, pb, f1b, f2b, heads, eps)
+        ctx.lse = lse
+        return t_out
+
+    @staticmethod
+    def backward(ctx, dt_out):
+        t, qkv, o, t_mid, h1, n1w, qkvw, pw, ls1, n2w, f1w, f2w, ls2 = ctx.saved_tensors
+        qkvb, pb, f1b, f2b, heads, eps = ctx.others
+        b, s, c = t.shape
+        rows = b * s
+        dt = _c(dt_out).float().clone()                                # becomes d(t_mid), then d(t)
+        do3 = ops.layerscale_bwd_dx(dt, ls2)
+        dg, _, _ = _lin_grads(do3.view(rows, c), None, f2w, f2b, need_w=False)
+        dh1 = ops.gelu_bwd(dg.view_as(h1), h1)
+        dhn2, _, _ = _lin_grads(dh1.view(rows, -1), None, f1w, f1b, need_w=False)
+        ops.layernorm_bwd_(dt, dhn2.view(b, s, c), t_mid, n2w, eps, need_param_grads=False)
+        do2 = ops.layerscale_bwd_dx(dt, ls1)
+        do, _, _ = _lin_grads(do2.view(rows, c), None, pw, pb, need_w=False)
+        dqkv = ops.attention_bwd_qkv(qkv, o, do.view(b, s, c), heads, (c // heads) ** -0.5, lse=ctx.lse)
+        dhn1, _, _ = _lin_grads(dqkv.view(rows, 3 * c), None, qkvw, qkvb, need_w=False)
+        ops.layernorm_bwd_(dt, dhn1.view(b, s, c), t, n1w, eps, need_param_grads=False)
+        return (dt,) + (None,) * 16
+
+
+class DinoHeadFn(torch.autograd.Function):
+    """One head of the DINOv2 discriminator (models/dinodisc.py:134-141,182-190) on the token-major layout, from the un-normed f32 residual stream t [B, 1 + L, C]
+    to the f32 logits [B, L]:
+
+        act = bf16(t[:, 1:] + t[:, :1])                                   ops.dino_tap
+        h0  = conv_k1(act; W0 / s0, b0);  a = LeakyReLU(norm0(h0))        ops.conv_tokens (ks = 1), the GroupNorm kernels
+        c1  = conv_ks(a; W1 / s1, b1);    h = LeakyReLU(norm1(c1))        ops.conv_tokens, the GroupNorm kernels
+        logit = <(a + h) / sqrt 2, W2 / s2> + b2                          ops.dino_tail
+
+    W*: the f32 Conv1d weights (`weight_orig`), s*: the spectral norm's sigma as f32 [1] tensors (differentiable inputs: d s = -<dW~, W> / s^2 is returned, and
+    autograd takes it on to `weight_orig` through sigma = u . (W v)); the bf16 operand packs are W / s.  norm: `ngroups` "images" of `B / nimg` samples with
+    `groups` groups -- BatchNormLocal is (G, C): virtual batch groups as images, one channel per group; GroupNorm(32) is (B, 32).  Every activation and activation
+    gradient is bf16, every reduction f32 in a fixed order.  Only the gradients `needs_input_grad` asks for are computed: frozen heads (the generator's term) run
+    the two input-gradient convolutions and the norm backward without their parameter sums; a t that needs no gradient (the discriminator's turn) skips the first
+    conv's input gradient and the un-tap."""
+
+    @staticmethod
+    def forward(ctx, t, cfg, w0, s0, b0, g0, be0, w1, s1, b1, g1, be1, w2, s2, b2):
+        nimg, groups, eps = cfg
+        act = ops.dino_tap(_c(t))
+        b, l, c = act.shape
+        ks = w1.shape[-1]
+        wf0, wd0 = ops.conv_tokens_pack(_c(w0.detach()), s0.detach())
+        wf1, wd1 = ops.conv_tokens_pack(_c(w1.detach()), s1.detach())
+        w2t = (w2.detach().reshape(c) / s2.detach()).contiguous()
+        h0 = ops.conv_tokens(act, wf0, b0)
+        st0 = ops.groupnorm_stats(h0.view(nimg, -1, c), groups, eps)
+        a = ops.groupnorm_apply(h0.view(nimg, -1, c), st0, g0, be0, 2, groups=groups).view(b, l, c)
+        c1 = ops.conv_tokens(a, wf1, b1)
+        st1 = ops.groupnorm_stats(c1.view(nimg, -1, c), groups, eps)
+        h = ops.groupnorm_apply(c1.view(nimg, -1, c), st1, g1, be1, 2, groups=groups).view(b, l, c)
+        logit = ops.dino_tail(a, h, w2t, b2)
+        ctx.save_for_backward(act, h0, st0, a, c1, st1, h, wd0, wd1, w2t, w0, s0, g0, be0, w1, s1, g1, be1, w2, s2)
+        ctx.cfg = (nimg, groups, ks)
+        return logit
+
+    @staticmethod
+    def backward(ctx, dlogit):
+        act, h0, st0, a, c1, st1, h, wd0, wd1, w2t, w0, s0, g0, be0, w1, s1, g1, be1, w2, s2 = ctx.saved_tensors
+        nimg, groups, ks = ctx.cfg
+        b, l, c = act.shape
+        need = ctx.needs_input_grad
+        need_t = need[0]
+        nw0, nn0, nw1, nn1, nw2 = need[2] or need[3] or need[4], need[5] or need[6], need[7] or need[8] or need[9], need[10] or need[11], need[12] or need[13] or need[14]
+        v3 = lambda x: x.view(nimg, -1, c)
+
+        def sn_grads(dwt, w, s):      # W~ = W / s:  d W = dW~ / s,  d s = -<dW~, W> / s^2
+            inv = 1.0 / s
+            return dwt.view(w.shape) * inv, -(dwt.view(w.shape) * w).sum().reshape(s.shape) * inv * inv
+
+        dah, dw2t, db2 = ops.dino_tail_bwd(_c(dlogit).float(), a, h, w2t, need_dx=True, need_w=nw2)
+        dw2 = ds2 = None
+        if nw2:
+            dw2, ds2 = sn_grads(dw2t, w2, s2)
+        dc1, dg1, dbe1 = ops.groupnorm_bwd(v3(dah), v3(c1), st1, g1, be1, 2, groups=groups, need_param_grads=nn1)
+        dc1 = dc1.view(b, l, c)
+        dw1 = ds1 = db1 = None
+        if nw1:
+            dw1t, db1 = ops.conv_tokens_wgrad(dc1, a, ks)
+            dw1, ds1 = sn_grads(dw1t, w1, s1)
+        da = ops.conv_tokens_dgrad(dc1, wd1, dres=dah)                   # a feeds the conv and the skip: both gradients in one rounding
+        dh0, dg0, dbe0 = ops.groupnorm_bwd(v3(da), v3(h0), st0, g0, be0, 2, groups=groups, need_param_grads=nn0)
+        dh0 = dh0.view(b, l, c)
+        dw0 = ds0 = db0 = None
+        if nw0:
+            dw0t, db0 = ops.conv_tokens_wgrad(dh0, act, 1)
+            dw0, ds0 = sn_grads(dw0t, w0, s0)
+        dt = ops.dino_untap(ops.conv_tokens_dgrad(dh0, wd0)) if need_t else None
+        return dt, None, dw0, ds0, db0, dg0, dbe0, dw1, ds1, db1, dg1, dbe1, dw2, ds2, db2
+
+
 class LayerNormBf16Fn(torch.autograd.Function):
     """LayerNorm of the f32 residual stream with a bf16 result (the encoder's final norm feeding the bottleneck MLP)."""
 

@@ -118,7 +118,7 @@ class DinoV2ViT(nn.Module):
             else:
                 nh = self.blocks[0].attn.num_heads
                 why = (f"width {self.embed_dim} with {nh} heads at {self.pos_embed.shape[1]} tokens is outside the encoder kernels' range "
-                       "(width 256/512/768/1024/1280/1536, head dim 64)")
+                       "(width 256/384/512/768/1024/1280/1536, head dim 64)")
         else:
             why = "CPU tensor"
         from .._stock import require_opt_in

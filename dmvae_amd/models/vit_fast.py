@@ -36,13 +36,17 @@ def _w(p: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def frozen_forward_features(vit, x: torch.Tensor) -> torch.Tensor:
+def frozen_forward_features(vit, x: torch.Tensor, key_depths=None, pos_embed=None):
     """vit: a DinoV2ViT -- either a bf16 shadow (train.frozen_bf16_shadow: Linear / Conv2d weights already bf16) or the f32 module itself, whose
     Linear weights are then served as cached bf16 copies (`functional._bf`, refreshed when a parameter changes); x: [B,3,H,W] f32, already normalised.
-    Returns the final-norm tokens [B, 1+N, C] in bf16 (what the bottleneck MLP consumes)."""
+    Returns the final-norm tokens [B, 1+N, C] in bf16 (what the bottleneck MLP consumes).
+    key_depths (the DINOv2 discriminator's taps, models/dinodisc.py:181 with norm=False): returns instead the list of the UN-NORMED f32 residual stream [B, 1+N, C]
+    after each of those blocks (copies: the stream itself is updated in place), and stops after the last of them.  pos_embed: the position embedding to add when
+    it is not the module's own (interpolated to the input's grid, models/dinov2.py:179-211)."""
     from ..functional import linear
     t = patch_embed_gemm(vit, x).float()
-    t = torch.cat([vit.cls_token.expand(t.shape[0], -1, -1).float(), t], dim=1) + vit.pos_embed.float()
+    t = torch.cat([vit.cls_token.expand(t.shape[0], -1, -1).float(), t], dim=1) + (vit.pos_embed if pos_embed is None else pos_embed).float()
+    taps, last_tap = [], (max(key_depths) if key_depths is not None else -1)
     t = t.contiguous()                                   # f32 residual stream [B, S, C]
     b, s, c = t.shape
     hn = ops.layernorm_bf16(t, vit.blocks[0].norm1.weight, vit.blocks[0].norm1.bias, vit.blocks[0].norm1.eps)
@@ -68,22 +72,47 @@ def frozen_forward_features(vit, x: torch.Tensor) -> torch.Tensor:
         hn = ops.scale_residual_layernorm_(t, o.contiguous(), blk.ls1.gamma, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
         h = linear(hn, blk.mlp.fc1.weight, blk.mlp.fc1.bias, act=ops.ACT_GELU)   # GELU in the GEMM's epilogue (bit-identical to the two kernels)
         o = linear(h, blk.mlp.fc2.weight, blk.mlp.fc2.bias)
+        if i == last_tap:                                # the last tap: the stream is complete after the LayerScale + residual add, nothing reads a norm of it
+            taps.append(ops.scale_residual_(t, o.contiguous(), blk.ls2.gamma))
+            return taps
         nxt = vit.blocks[i + 1].norm1 if i + 1 < nblk else vit.norm
         hn = ops.scale_residual_layernorm_(t, o, blk.ls2.gamma, nxt.weight, nxt.bias, nxt.eps)
+        if key_depths is not None and i in key_depths:
+            taps.append(t.clone())
+    if key_depths is not None:
+        raise ValueError(f"key_depths {tuple(key_depths)}: the model has {nblk} blocks")
     return hn
 
 
 def hip_path_supported(vit, seq_len: int) -> bool:
-    """Shapes the encoder kernels cover: width 256 / 512 / 768 / 1024 / 1280 / 1536 (LayerNorm kernels; ViT-B = 768 and ViT-L = 1024 are the
-    reference's two sizes, models/vae.py:41-48) and head dim 64 (fused attention), at any token count: up to 288 tokens the attention kernel keeps a head's K / V
+    """Shapes the encoder kernels cover: width 256 / 384 / 512 / 768 / 1024 / 1280 / 1536 (LayerNorm kernels; ViT-B = 768 and ViT-L = 1024 are the
+    reference's two encoder sizes, models/vae.py:41-48; 384 = ViT-S, the DINOv2 discriminator's backbone, models/dinodisc.py:117) and head dim 64 (fused attention), at any token count: up to 288 tokens the attention kernel keeps a head's K / V
     resident in LDS, beyond that (patch 8, 384 px: models/vae.py:38-50) it streams them (csrc/attention_stream.hip).  `seq_len` stays in the signature for the
     callers; with gradients the attention backward above 288 tokens streams as well (csrc/attention_bwd_stream.hip): nothing S x S in HBM at any token count."""
     c = vit.embed_dim
     nh = vit.blocks[0].attn.num_heads
-    return c in (256, 512, 768, 1024, 1280, 1536) and c // nh == 64
+    return c in (256, 384, 512, 768, 1024, 1280, 1536) and c // nh == 64
 
 
 NOGRAD_FUSED = True      # trainable_forward_features under no_grad takes the frozen route's fused kernels (False: the block Functions' forward; tests compare)
+
+
+def frozen_taps_with_input_grad(vit, x: torch.Tensor, key_depths, pos_embed=None):
+    """The taps of `frozen_forward_features(key_depths=...)` with a gradient path back to the image x through a FROZEN backbone (the generator's adversarial term
+    on the DINOv2 discriminator): patch embedding as `LinearFn` (input gradient only: its weight does not require one), every block as `VitBlockDxFn`.
+    Same forward bits as the graph-free route's block Functions."""
+    from ..functional import VitBlockDxFn
+    t = patch_embed_gemm(vit, x)
+    t = torch.cat([vit.cls_token.expand(t.shape[0], -1, -1).float(), t.float()], dim=1) + (vit.pos_embed if pos_embed is None else pos_embed).float()
+    t = t.contiguous()
+    taps = []
+    for i, blk in enumerate(vit.blocks[:max(key_depths) + 1]):
+        t = VitBlockDxFn.apply(t, blk.norm1.weight, blk.norm1.bias, blk.attn.qkv.weight, blk.attn.qkv.bias, blk.attn.proj.weight, blk.attn.proj.bias,
+                               blk.ls1.gamma, blk.norm2.weight, blk.norm2.bias, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight,
+                               blk.mlp.fc2.bias, blk.ls2.gamma, blk.attn.num_heads, blk.norm1.eps)
+        if i in key_depths:
+            taps.append(t)
+    return taps
 
 
 def trainable_forward_features(vit, x: torch.Tensor) -> torch.Tensor:

@@ -2068,3 +2068,118 @@ def adamw_ema_step(p, g, m, v, ema, norm_out, lr, beta1, beta2, eps, wd, step, e
         return
     check(_lib.lib().dmvae_adamw_ema_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(ema), _ptr(norm_out), p.numel(), float(lr),
                                           float(beta1), float(beta2), float(eps), float(wd), int(step), float(ema_decay), _stream()), "adamw_ema_step")
+
+
+# ---- convolution along the token axis (csrc/conv_tokens.hip) ---------------------------------------------------------------
+def conv_tokens_pack(w: torch.Tensor, sigma: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Both bf16 operand packs of a Conv1d weight w [C, C, ks] (f32), divided by the device scalar `sigma` (the spectral norm's divisor) when given:
+    (w_fwd [C_out, ks, C_in], w_dgrad [C_in, ks reversed, C_out])."""
+    w = _req(w, f32, "w")
+    c, c_in, ks = w.shape
+    assert c == c_in, "conv_tokens: C -> C channels"
+    wf = torch.empty(c, ks, c, dtype=bf16, device=w.device)
+    wd = torch.empty(c, ks, c, dtype=bf16, device=w.device)
+    check(_lib.lib().dmvae_conv_tokens_pack(w.data_ptr(), _ptr(None if sigma is None else _req(sigma, f32, "sigma")), wf.data_ptr(), wd.data_ptr(), c, ks,
+                                            _stream()), "conv_tokens_pack")
+    return wf, wd
+
+
+def conv_tokens(x: torch.Tensor, w_fwd: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[b, l] = bias + sum_t x[b, l + t - ks // 2] @ W_t^T on token-major x [B, L, C] bf16 (zero padding per sample); w_fwd from `conv_tokens_pack`."""
+    x = _req(x, bf16, "x")
+    w_fwd = _req(w_fwd, bf16, "w_fwd")
+    b, l, c = x.shape
+    ks = w_fwd.shape[1]
+    assert w_fwd.shape == (c, ks, c)
+    y = torch.empty_like(x)
+    check(_lib.lib().dmvae_conv_tokens_fwd(x.data_ptr(), w_fwd.data_ptr(), _ptr(None if bias is None else _req(bias, f32, "bias")), y.data_ptr(), b, l, c, ks,
+                                           _stream()), "conv_tokens_fwd")
+    return y
+
+
+def conv_tokens_dgrad(dy: torch.Tensor, w_dgrad: torch.Tensor, dres: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Input gradient of `conv_tokens`: dy [B, L, C] bf16 -> dx [B, L, C] bf16 (+ dres, a second gradient of the same tensor, added before the rounding);
+    w_dgrad from `conv_tokens_pack`."""
+    dy = _req(dy, bf16, "dy")
+    w_dgrad = _req(w_dgrad, bf16, "w_dgrad")
+    b, l, c = dy.shape
+    ks = w_dgrad.shape[1]
+    assert w_dgrad.shape == (c, ks, c)
+    dx = torch.empty_like(dy)
+    if dres is not None:
+        assert _req(dres, bf16, "dres").shape == dy.shape
+    check(_lib.lib().dmvae_conv_tokens_dgrad(dy.data_ptr(), w_dgrad.data_ptr(), _ptr(dres), dx.data_ptr(), b, l, c, ks, _stream()), "conv_tokens_dgrad")
+    return dx
+
+
+def conv_tokens_wgrad(dy: torch.Tensor, x: torch.Tensor, ks: int, need_bias: bool = True):
+    """Weight and bias gradient of `conv_tokens`: (dw [C, C, ks] f32 in the Conv1d layout, dbias [C] f32 or None); fixed-order reductions."""
+    dy = _req(dy, bf16, "dy")
+    x = _req(x, bf16, "x")
+    assert dy.shape == x.shape
+    b, l, c = x.shape
+    L = _lib.lib()
+    nbytes = L.dmvae_conv_tokens_wgrad_workspace(b, l, c, ks)
+    if nbytes == 0:
+        raise _lib.DmvaeHipError(f"conv_tokens_wgrad: unsupported shape B {b} L {l} C {c} ks {ks}")
+    ws = workspace(nbytes, x.device, "conv_tokens")
+    dw = torch.empty(c, c, ks, dtype=f32, device=x.device)
+    db = torch.empty(c, dtype=f32, device=x.device) if need_bias else None
+    check(L.dmvae_conv_tokens_wgrad(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), _ptr(db), ws.data_ptr(), ws.numel(), b, l, c, ks, _stream()),
+          "conv_tokens_wgrad")
+    return dw, db
+
+
+# ---- the passes around the DINOv2 discriminator's heads (csrc/dinodisc.hip) -----------------------------------------------------
+def dino_tap(t: torch.Tensor) -> torch.Tensor:
+    """act [B, L, C] bf16 = t[:, 1:] + t[:, :1] of the f32 residual stream t [B, 1 + L, C]."""
+    t = _req(t, f32, "t")
+    b, s, c = t.shape
+    act = torch.empty(b, s - 1, c, dtype=bf16, device=t.device)
+    check(_lib.lib().dmvae_dino_tap(t.data_ptr(), act.data_ptr(), b, s - 1, c, _stream()), "dino_tap")
+    return act
+
+
+def dino_untap(dact: torch.Tensor) -> torch.Tensor:
+    """The adjoint of `dino_tap`: dt [B, 1 + L, C] f32 from dact [B, L, C] bf16."""
+    dact = _req(dact, bf16, "dact")
+    b, l, c = dact.shape
+    dt = torch.empty(b, l + 1, c, dtype=f32, device=dact.device)
+    check(_lib.lib().dmvae_dino_untap(dact.data_ptr(), dt.data_ptr(), b, l, c, _stream()), "dino_untap")
+    return dt
+
+
+def dino_tail(a: torch.Tensor, h: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """logit [B, L] f32 = <(a + h) / sqrt 2, w> + bias over a, h [B, L, C] bf16; w [C] f32, bias [1] f32."""
+    a, h = _req(a, bf16, "a"), _req(h, bf16, "h")
+    assert a.shape == h.shape
+    c = a.shape[-1]
+    logit = torch.empty(a.shape[:-1], dtype=f32, device=a.device)
+    check(_lib.lib().dmvae_dino_tail_fwd(a.data_ptr(), h.data_ptr(), _req(w, f32, "w").data_ptr(), _ptr(None if bias is None else _req(bias, f32, "bias")),
+                                         logit.data_ptr(), a.numel() // c, c, _stream()), "dino_tail_fwd")
+    return logit
+
+
+def dino_tail_bwd(dlogit: torch.Tensor, a: torch.Tensor, h: torch.Tensor, w: torch.Tensor, need_dx: bool = True, need_w: bool = True):
+    """-> (dah bf16 like a: the gradient of a and of h alike, dw [C] f32, dbias [1] f32); what is not needed is None."""
+    dlogit = _req(dlogit, f32, "dlogit")
+    a, h = _req(a, bf16, "a"), _req(h, bf16, "h")
+    c = a.shape[-1]
+    rows = a.numel() // c
+    L = _lib.lib()
+    dah = torch.empty_like(a) if need_dx else None
+    dw = torch.empty(c, dtype=f32, device=a.device) if need_w else None
+    db = torch.empty(1, dtype=f32, device=a.device) if need_w else None
+    ws = workspace(max(L.dmvae_dino_tail_bwd_workspace(rows, c), 1), a.device, "dino_tail") if need_w else None
+    check(L.dmvae_dino_tail_bwd(dlogit.data_ptr(), a.data_ptr(), h.data_ptr(), _req(w, f32, "w").data_ptr(), _ptr(dah), _ptr(dw), _ptr(db), _ptr(ws),
+                                0 if ws is None else ws.numel(), rows, c, _stream()), "dino_tail_bwd")
+    return dah, dw, db
+
+
+def layerscale_bwd_dx(dt: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:
+    """dy (bf16) = gamma * dt: `layerscale_bwd` without the parameter gradient (a frozen block)."""
+    dt = _req(dt, f32, "dt")
+    c = dt.shape[-1]
+    dy = torch.empty(dt.shape, dtype=bf16, device=dt.device)
+    check(_lib.lib().dmvae_layerscale_bwd_dx(dt.data_ptr(), _req(gamma, f32, "gamma").data_ptr(), dy.data_ptr(), dt.numel() // c, c, _stream()), "layerscale_bwd_dx")
+    return dy

@@ -396,7 +396,7 @@ int dmvae_silu_bwd(const void* x, const void* dy, void* dx, size_t n, dmvae_stre
 /* ---- frozen ViT encoder forward, elementwise part (models/vae.py:52-53; timm / dino_layers block algebra) ------------------- */
 
 /* y[rows][c] (bf16) = LayerNorm(x[rows][c] f32; gamma, beta f32, eps): nn.LayerNorm under autocast (f32) + the bf16 cast in front
- * of the following Linear.  c in {256, 512, ..., 1536}.  Reference: timm VisionTransformer blocks' norm1 / norm2 / norm through models/vae.py:47-53. */
+ * of the following Linear.  c in {256, 384, 512, 768, 1024, 1280, 1536} (384 = ViT-S, the DINOv2 discriminator's backbone).  Reference: timm VisionTransformer blocks' norm1 / norm2 / norm through models/vae.py:47-53. */
 int dmvae_layernorm_f32_bf16(const void* x, const void* gamma, const void* beta, void* y, int rows, int c, float eps,
                              dmvae_stream_t stream);
 /* The two calls below fused, for every LayerNorm that follows a LayerScale + residual add (all but a block's first): x += ls_gamma * r (in place, f32), then
@@ -870,6 +870,42 @@ int dmvae_qknorm_rope_fwd_f32(const void* qkv, const void* wq, const void* wk, c
 int dmvae_qknorm_rope_bwd_f32(const void* dq, const void* dk, const void* dv, const void* qkv, const void* wq, const void* wk, const void* cosb,
                               const void* sinb, const void* rstd, void* dqkv, void* gwq, void* gwk, int batch, int tokens, int heads, int d, int d_pad,
                               dmvae_stream_t stream);
+
+/* ---- convolution along the token axis of token-major activations (csrc/conv_tokens.hip) -------------------------------------- */
+
+/* Conv1d(C, C, ks, padding = ks / 2) on x [B][L][C] bf16: y[b][l][co] = bias[co] + sum_t sum_ci x[b][l + t - ks/2][ci] * W[co][ci][t], zero padding per sample,
+ * f32 accumulation, bf16 result.  C a multiple of 32 in 384..4096 (the weight gradient: of 64), ks odd <= 9, any L >= 1, B <= 65535, B*L*C < 2^31.
+ * Reference: the ResidualBlock conv of the DINOv2 discriminator's heads, models/dinodisc.py:73-105 (ks = 9: train_tokenizer.py:307-312), there on [B, C, L].
+ * pack:  w f32 [C][C][ks] (Conv1d layout), sigma f32[1] on the device or NULL (= 1: the spectral norm's divisor, models/dinodisc.py:76-77) ->
+ *        w_fwd bf16 [C_out][ks][C_in] and w_dgrad bf16 [C_in][ks, reversed][C_out], C*C*ks elements each.
+ * fwd:   bias f32 [C] or NULL.   dgrad: dx = the same convolution of dy on w_dgrad, + dres (bf16 [B][L][C] or NULL: the gradient arriving at x by a skip
+ *        connection, added in f32 before the one rounding).  Both: a sample's result does not depend on B; reruns identical.
+ * wgrad: dw f32 [C][C][ks] = sum_{b,l} dy[b][l][co] * x[b][l + t - ks/2][ci], dbias f32 [C] = sum_{b,l} dy (or NULL); split over tokens with a fixed-order
+ *        second stage (no atomics).  workspace: dmvae_conv_tokens_wgrad_workspace bytes (0 = unsupported shape). */
+int dmvae_conv_tokens_pack(const void* w, const void* sigma, void* w_fwd, void* w_dgrad, int c, int ks, dmvae_stream_t stream);
+int dmvae_conv_tokens_fwd(const void* x, const void* w_fwd, const void* bias, void* y, int b, int l, int c, int ks, dmvae_stream_t stream);
+int dmvae_conv_tokens_dgrad(const void* dy, const void* w_dgrad, const void* dres, void* dx, int b, int l, int c, int ks, dmvae_stream_t stream);
+size_t dmvae_conv_tokens_wgrad_workspace(int b, int l, int c, int ks);
+int dmvae_conv_tokens_wgrad(const void* dy, const void* x, void* dw, void* dbias, void* workspace, size_t workspace_bytes, int b, int l, int c, int ks,
+                            dmvae_stream_t stream);
+
+/* ---- the passes around the DINOv2 discriminator's heads (csrc/dinodisc.hip) -------------------------------------------------------- */
+
+/* tap:   act [B][L][C] bf16 = t[b][1 + l] + t[b][0] of the un-normed f32 residual stream t [B][1 + L][C] (patch tokens + class token).  C % 4 == 0.
+ * untap: its adjoint: dt [B][1 + L][C] f32 from dact bf16, the class row summed over the tokens in a fixed order.  C % 64 == 0.
+ * Reference: models/dinodisc.py:181-185. */
+int dmvae_dino_tap(const void* t, void* act, int b, int l, int c, dmvae_stream_t stream);
+int dmvae_dino_untap(const void* dact, void* dt, int b, int l, int c, dmvae_stream_t stream);
+/* logit[r] (f32) = <(a[r] + h[r]) / sqrt 2, w> + bias[0] over rows of a, h bf16 [rows][C], w f32 [C], bias f32[1] or NULL: the ResidualBlock's
+ * (fn(x) + x) / sqrt 2 and the closing C -> 1 conv of kernel size 1.  C a multiple of 128 up to 1024.
+ * bwd: dah bf16 [rows][C] = dlogit[r] * w / sqrt 2 (the gradient of a and of h alike; or NULL), dw f32 [C] and dbias f32[1] (dw NULL: neither; then a, h and
+ * the workspace may be NULL) by per-block sums and a fixed-order second stage.  Reference: models/dinodisc.py:13-20,138. */
+int dmvae_dino_tail_fwd(const void* a, const void* h, const void* w, const void* bias, void* logit, size_t rows, int c, dmvae_stream_t stream);
+size_t dmvae_dino_tail_bwd_workspace(size_t rows, int c);
+int dmvae_dino_tail_bwd(const void* dlogit, const void* a, const void* h, const void* w, void* dah, void* dw, void* dbias, void* workspace,
+                        size_t workspace_bytes, size_t rows, int c, dmvae_stream_t stream);
+/* dy (bf16) = gamma * dt: layerscale_bwd without the parameter sum (a frozen block: models/dinodisc.py:123-125).  c % 8 == 0. */
+int dmvae_layerscale_bwd_dx(const void* dt, const void* gamma, void* dy, size_t rows, int c, dmvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,13 +4,17 @@
     python run_on_mi355x.py /path/to/dmvae/train_tokenizer.py --local_bs 32 ...
     torchrun --nproc-per-node 8 run_on_mi355x.py /path/to/dmvae/train_dmd.py ...
     python run_on_mi355x.py --check            # print what is shadowed and exit
+    python run_on_mi355x.py --hip-dinodisc /path/to/dmvae/train_tokenizer.py --disc_type dino ...      (or DMVAE_HIP_DINODISC=1)
 
 The reference's drivers import their model code by module path (`from models.vae import VAE`, `from utils.lpips import LPIPS`,
 `from diffusion.lightningdit.lightningdit import LightningDiT_models`, `from diffusion.transport import create_transport`; train_tokenizer.py:10-17,
 train_dmd.py:10-17, train_diffusion.py:15-17, sample_50k.py:6-14).  `install_shadow()` registers this build's mirrors under exactly those module paths --
 same class names, constructor arguments, forward signatures and state_dict keys, HIP kernels underneath -- before the script runs.  Everything else the
 scripts import (utils.dist, utils.build_dataset, evaluation.*, models.dinodisc, models.init_param's callers ...) still resolves to the reference's own
-files: the shadow packages keep the reference's directories on their __path__."""
+files: the shadow packages keep the reference's directories on their __path__.
+
+`models.dinodisc` / `models.DinoDisc` (--disc_type dino) is an opt-in: by default it stays the reference's file; `--hip-dinodisc` in front of the script path,
+DMVAE_HIP_DINODISC=1 or `install_shadow(ref, dinodisc=True)` registers this build's `dmvae_amd.models.dinodisc` instead."""
 from __future__ import annotations
 
 import importlib
@@ -51,10 +55,14 @@ def _package(name: str, ref_dir: str | None) -> types.ModuleType:
     return mod
 
 
-def install_shadow(ref_dir: str | None = None) -> dict:
-    """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve)."""
+def install_shadow(ref_dir: str | None = None, dinodisc: bool = False) -> dict:
+    """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve).
+    dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them)."""
     out = {}
-    for path, target in SHADOWS.items():
+    shadows = dict(SHADOWS)
+    if dinodisc:
+        shadows["models.dinodisc"] = "dmvae_amd.models.dinodisc"           # DinoDisc                          (models/dinodisc.py)
+    for path, target in shadows.items():
         parts = path.split(".")
         for i in range(1, len(parts)):
             _package(".".join(parts[:i]), ref_dir)
@@ -67,7 +75,10 @@ def install_shadow(ref_dir: str | None = None) -> dict:
     models.VAE = out["models.vae"].VAE
     models.NLayerDiscriminator = out["models.patchgan"].NLayerDiscriminator
 
-    def _lazy(name):          # DinoDisc stays the reference's own (out of scope here): imported from its file on first use
+    if dinodisc:
+        models.DinoDisc = out["models.dinodisc"].DinoDisc
+
+    def _lazy(name):          # DinoDisc stays the reference's own unless opted in: imported from its file on first use
         if name == "DinoDisc":
             return importlib.import_module("models.dinodisc").DinoDisc
         raise AttributeError(f"module 'models' has no attribute {name!r}")
@@ -79,14 +90,20 @@ def main(argv) -> int:
     if not argv or argv[0] in ("-h", "--help"):
         print(__doc__)
         return 0
+    hip_dinodisc = os.environ.get("DMVAE_HIP_DINODISC", "0") not in ("", "0")
+    if argv[0] == "--hip-dinodisc":
+        hip_dinodisc, argv = True, argv[1:]
+        if not argv:
+            print(__doc__)
+            return 0
     if argv[0] == "--check":
         ref = argv[1] if len(argv) > 1 else None
-        for path, mod in install_shadow(ref).items():
+        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc).items():
             print(f"{path:40s} -> {mod.__name__}")
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref)
+    install_shadow(ref, dinodisc=hip_dinodisc)
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])
