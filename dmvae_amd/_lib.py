@@ -229,6 +229,8 @@ SIGNATURES = {
     "dmvae_conv_tokens_wgrad_workspace": (c_size_t, [c_int] * 4),
     "dmvae_conv_tokens_wgrad": (c_int, [c_void_p] * 5 + [c_size_t] + [c_int] * 4 + [c_void_p]),
     # the passes around the DINOv2 discriminator's heads (csrc/dinodisc.hip), the frozen block's LayerScale backward (csrc/vit_bwd.hip)
+    "dmvae_conv_tokens_fwd_bnact": (c_int, [c_void_p] * 7 + [c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "dmvae_dino_bnact_bwd": (c_int, [c_void_p] * 4 + [c_float, c_void_p, c_size_t, c_int, c_void_p]),
     "dmvae_dino_tap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dmvae_dino_untap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dmvae_dino_tail_fwd": (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_void_p]),

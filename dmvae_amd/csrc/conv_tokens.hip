@@ -42,8 +42,21 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ w, 
 
 // y[b][l][n] = bias[n] + sum_t sum_k x[b][l + t - ks/2][k] * w[n][t][k].  grid (ceil(L / 64), ceil(C / 128), B), 4 waves = 2 (tokens) x 2 (channels).
 // res (or NULL): a bf16 tensor of y's shape added in f32 before the one rounding (the input gradient's second summand where the conv's input also feeds a skip).
+// The epilogue is a template parameter.  EPI_PLAIN: y = bf16(acc + bias + res).  EPI_BNACT: an eval-mode BatchNorm + LeakyReLU(0.2) on the conv's result
+// (constant statistics: a per-channel affine map), y = bf16(leaky((acc + bias - mean) * rsqrt(var + eps) * gamma + beta)) in f32 with the one rounding; the four
+// per-channel f32 vectors are read as the bias is, a float4 per four channels.
+enum { EPI_PLAIN = 0, EPI_BNACT = 1 };
+struct BnAct {
+  const float* mean;
+  const float* var;
+  const float* gamma;
+  const float* beta;
+  float eps;
+};
+
+template <int EPI>
 __global__ __launch_bounds__(256) void conv_tokens_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w, const float* __restrict__ bias,
-                                                          const bf16* __restrict__ res, bf16* __restrict__ y, int L, int C, int ks) {
+                                                          const bf16* __restrict__ res, bf16* __restrict__ y, int L, int C, int ks, BnAct bn) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, kc = (lane >> 4) * 8;
   const int l0 = blockIdx.x * 64 + (wave & 1) * 32, n0 = blockIdx.y * 128 + (wave >> 1) * 64;
@@ -98,14 +111,24 @@ __global__ __launch_bounds__(256) void conv_tokens_kernel(const bf16* __restrict
       f32x4 b = {0.f, 0.f, 0.f, 0.f};
       if (bias) b = *reinterpret_cast<const f32x4*>(bias + n);
       const size_t off = ((size_t)blockIdx.z * L + l) * C + n;
-      if (res) {
-        const bf16x4 rv = *reinterpret_cast<const bf16x4*>(res + off);
-#pragma unroll
-        for (int j = 0; j < 4; j++) b[j] += (float)rv[j];
-      }
       bf16x4 o;
+      if constexpr (EPI == EPI_BNACT) {
+        const f32x4 mu = *reinterpret_cast<const f32x4*>(bn.mean + n), va = *reinterpret_cast<const f32x4*>(bn.var + n);
+        const f32x4 ga = *reinterpret_cast<const f32x4*>(bn.gamma + n), be = *reinterpret_cast<const f32x4*>(bn.beta + n);
 #pragma unroll
-      for (int j = 0; j < 4; j++) o[j] = (bf16)(acc[i][g][j] + b[j]);
+        for (int j = 0; j < 4; j++) {
+          const float v = (acc[i][g][j] + b[j] - mu[j]) * rsqrtf(va[j] + bn.eps) * ga[j] + be[j];
+          o[j] = (bf16)(v > 0.f ? v : 0.2f * v);
+        }
+      } else {
+        if (res) {
+          const bf16x4 rv = *reinterpret_cast<const bf16x4*>(res + off);
+#pragma unroll
+          for (int j = 0; j < 4; j++) b[j] += (float)rv[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) o[j] = (bf16)(acc[i][g][j] + b[j]);
+      }
       *reinterpret_cast<bf16x4*>(y + off) = o;
     }
   }
@@ -220,9 +243,15 @@ static int wgrad_splits(int b, int l) {
   return total < WG_SPLITS_MAX ? total : WG_SPLITS_MAX;
 }
 
-static int launch_conv(const void* x, const void* w, const void* bias, const void* res, void* y, int b, int l, int c, int ks, hipStream_t stream) {
+static int launch_conv(const void* x, const void* w, const void* bias, const void* res, void* y, int b, int l, int c, int ks, hipStream_t stream,
+                       const BnAct* bn = nullptr) {
   const dim3 grid((l + 63) / 64, (c + 127) / 128, b);
-  hipLaunchKernelGGL(conv_tokens_kernel, grid, dim3(256), 0, stream, (const bf16*)x, (const bf16*)w, (const float*)bias, (const bf16*)res, (bf16*)y, l, c, ks);
+  if (bn)
+    hipLaunchKernelGGL(conv_tokens_kernel<EPI_BNACT>, grid, dim3(256), 0, stream, (const bf16*)x, (const bf16*)w, (const float*)bias, (const bf16*)res, (bf16*)y, l,
+                       c, ks, *bn);
+  else
+    hipLaunchKernelGGL(conv_tokens_kernel<EPI_PLAIN>, grid, dim3(256), 0, stream, (const bf16*)x, (const bf16*)w, (const float*)bias, (const bf16*)res, (bf16*)y, l,
+                       c, ks, BnAct{nullptr, nullptr, nullptr, nullptr, 0.f});
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
@@ -245,6 +274,14 @@ extern "C" int dmvae_conv_tokens_fwd(const void* x, const void* w_fwd, const voi
   DMVAE_CHECK_ARG(x && w_fwd && y, "conv_tokens_fwd: bad argument");
   DMVAE_CHECK_ARG(shape_ok(b, l, c, ks), "conv_tokens_fwd: " CONV_TOKENS_SHAPE_MSG, b, l, c, ks);
   return launch_conv(x, w_fwd, bias, nullptr, y, b, l, c, ks, stream);
+}
+
+extern "C" int dmvae_conv_tokens_fwd_bnact(const void* x, const void* w_fwd, const void* bias, const void* running_mean, const void* running_var,
+                                           const void* gamma, const void* beta, float eps, void* y, int b, int l, int c, int ks, hipStream_t stream) {
+  DMVAE_CHECK_ARG(x && w_fwd && y && running_mean && running_var && gamma && beta, "conv_tokens_fwd_bnact: bad argument");
+  DMVAE_CHECK_ARG(shape_ok(b, l, c, ks), "conv_tokens_fwd_bnact: " CONV_TOKENS_SHAPE_MSG, b, l, c, ks);
+  const BnAct bn{(const float*)running_mean, (const float*)running_var, (const float*)gamma, (const float*)beta, eps};
+  return launch_conv(x, w_fwd, bias, nullptr, y, b, l, c, ks, stream, &bn);
 }
 
 extern "C" int dmvae_conv_tokens_dgrad(const void* dy, const void* w_dgrad, const void* dres, void* dx, int b, int l, int c, int ks, hipStream_t stream) {

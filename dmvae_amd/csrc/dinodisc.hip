@@ -6,7 +6,9 @@
 //                                                                          kernel size 1 (dinodisc.py:138) in one pass over the two bf16 operands; f32 logits
 //   tail bwd  da = dh = bf16(dlogit[r] * w / sqrt 2);  dw = sum_r dlogit[r] (a[r] + h[r]) / sqrt 2;  dbias = sum_r dlogit[r]      per-block partial sums + a
 //                                                                          fixed-order second stage (no atomics)
-// All four are HBM-bound single passes.
+//   bnact bwd g[r][c] = bf16(dy[r][c] * (y[r][c] > 0 ? 1 : 0.2) * gamma[c] * rsqrt(running_var[c] + eps))      the backward of an eval-mode BatchNorm + LeakyReLU(0.2)
+//                                                                          (constant statistics) from the stored bf16 output y: LeakyReLU keeps the sign
+// All five are HBM-bound single passes.
 #include "common.h"
 #include "dmvae_hip.h"
 
@@ -118,6 +120,28 @@ __global__ __launch_bounds__(256) void tail_bwd_final_kernel(const float* __rest
   else if (dbias) dbias[0] = s;
 }
 
+// bf16x8 pieces; C % 8 == 0, so a piece lies in one row
+__global__ __launch_bounds__(256) void bnact_bwd_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ y, const float* __restrict__ gamma,
+                                                        const float* __restrict__ var, float eps, bf16* __restrict__ g, size_t rows, int C) {
+  const int c8 = C / 8;
+  const size_t n = rows * c8;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % c8) * 8;
+    const bf16x8 dv = *reinterpret_cast<const bf16x8*>(dy + i * 8), yv = *reinterpret_cast<const bf16x8*>(y + i * 8);
+    bf16x8 o;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c + 4 * h), va = *reinterpret_cast<const f32x4*>(var + c + 4 * h);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int e = 4 * h + j;
+        o[e] = (bf16)((float)dv[e] * ((float)yv[e] > 0.f ? 1.0f : 0.2f) * ga[j] * rsqrtf(va[j] + eps));
+      }
+    }
+    *reinterpret_cast<bf16x8*>(g + i * 8) = o;
+  }
+}
+
 static int tail_blocks(size_t rows) {
   const size_t nb = (rows + 3) / 4;
   return (int)(nb < (size_t)TAIL_MAX_BLOCKS ? nb : (size_t)TAIL_MAX_BLOCKS);
@@ -168,5 +192,15 @@ extern "C" int dmvae_dino_tail_bwd(const void* dlogit, const void* a, const void
     hipLaunchKernelGGL(tail_bwd_final_kernel, dim3((c + 1 + 255) / 256), dim3(256), 0, stream, (const float*)workspace, (float*)dw, (float*)dbias, nblk, c);
     DMVAE_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+extern "C" int dmvae_dino_bnact_bwd(const void* dy, const void* y, const void* gamma, const void* running_var, float eps, void* g, size_t rows, int c,
+                                    hipStream_t stream) {
+  DMVAE_CHECK_ARG(dy && y && gamma && running_var && g && rows > 0 && c > 0 && c % 8 == 0 && rows * (size_t)c < ((size_t)1 << 31),
+                  "dino_bnact_bwd: rows >= 1, C a multiple of 8 and rows * C < 2^31 (got rows %zu C %d)", rows, c);
+  hipLaunchKernelGGL(bnact_bwd_kernel, dim3(grid_for(rows * (size_t)(c / 8), 256, 4096)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)y, (const float*)gamma,
+                     (const float*)running_var, eps, (bf16*)g, rows, c);
+  DMVAE_CHECK_LAUNCH();
   return 0;
 }

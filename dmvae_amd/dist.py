@@ -79,6 +79,13 @@ def is_master() -> bool:
     return _rank == 0
 
 
+def new_local_machine_group():
+    """utils/dist.py:99-103: this rank's subgroup of `torch.distributed.new_subgroups()` (the ranks of one machine) when initialised, else None."""
+    if tdist.is_available() and tdist.is_initialized():
+        return tdist.new_subgroups()[0]
+    return None
+
+
 def barrier() -> None:
     if _initialized:
         tdist.barrier()

@@ -1249,6 +1249,39 @@ class VitBlockDxFn(torch.autograd.Function):
         return (dt,) + (None,) * 16
 
 
+def _dino_norm_fwd(x, gamma, beta, nimg, groups, eps, stats_of=None):
+    """LeakyReLU(0.2)(norm(x)) of a DinoDisc head on x [B, L, C] bf16 -> (y, stats, sync).  stats_of None: the statistics of `nimg` "images" with `groups` groups
+    (BatchNormLocal, GroupNorm), sync None.  Else SyncBatchNorm: stats_of(x) -> (stats [1, C, 2], batch_stats, global count, group), sync = the last three."""
+    b, l, c = x.shape
+    sync = None
+    if stats_of is None:
+        st = ops.groupnorm_stats(x.view(nimg, -1, c), groups, eps)
+    else:
+        assert nimg == 1 and groups == c
+        st, *sync = stats_of(x)
+    return ops.groupnorm_apply(x.view(nimg, -1, c), st, gamma, beta, 2, groups=groups).view(b, l, c), st, sync
+
+
+def _dino_norm_bwd(dy, x, st, gamma, beta, nimg, groups, need_p, sync=None):
+    """Backward of `_dino_norm_fwd` -> (dx [nimg, -1, C], dgamma, dbeta).  SyncBatchNorm (`sync`) as BatchNormActFn.backward: the two per-channel sums, all-reduced
+    over the group, then the elementwise pass with 1 / global count; constant statistics: zero sums."""
+    c = x.shape[-1]
+    v3 = lambda v: v.view(nimg, -1, c)
+    if sync is None:
+        return ops.groupnorm_bwd(v3(dy), v3(x), st, gamma, beta, 2, groups=groups, need_param_grads=need_p)
+    batch_stats, count, group = sync
+    dg = db = None
+    if batch_stats or need_p:
+        sums, dg, db = ops.groupnorm_bwd_reduce(v3(dy), v3(x), st, gamma, beta, 2, groups=groups, need_param_grads=need_p)
+    if batch_stats:
+        if group is not None:
+            import torch.distributed as tdist
+            tdist.all_reduce(sums, group=group)
+    else:
+        sums = torch.zeros(1, c, 2, dtype=f32, device=x.device)
+    return ops.groupnorm_bwd_apply(v3(dy), v3(x), st, sums, gamma, beta, 2, groups=groups, inv_count=1.0 / count), dg, db
+
+
 class DinoHeadFn(torch.autograd.Function):
     """One head of the DINOv2 discriminator (models/dinodisc.py:134-141,182-190) on the token-major layout, from the un-normed f32 residual stream t [B, 1 + L, C]
     to the f32 logits [B, L]:
@@ -1263,11 +1296,18 @@ class DinoHeadFn(torch.autograd.Function):
     `groups` groups -- BatchNormLocal is (G, C): virtual batch groups as images, one channel per group; GroupNorm(32) is (B, 32).  Every activation and activation
     gradient is bf16, every reduction f32 in a fixed order.  Only the gradients `needs_input_grad` asks for are computed: frozen heads (the generator's term) run
     the two input-gradient convolutions and the norm backward without their parameter sums; a t that needs no gradient (the discriminator's turn) skips the first
-    conv's input gradient and the un-tap."""
+    conv's input gradient and the un-tap.
+
+    SyncBatchNorm (norm_type 'sbn' / 'lbn' / 'hbn') is (1, C) with a fourth entry in `cfg`: one callable per norm, `stats_of(x) -> (stats [1, C, 2], batch_stats,
+    global count, group)` -- `models.patchgan._bn_stats` bound to the norm's module, which takes this rank's statistics, combines them over the process group and
+    updates the running estimates (train mode), or hands out the running estimates as constants (eval mode with trainable heads).  The backward is then
+    `BatchNormActFn`'s: `groupnorm_bwd_reduce`, the all-reduce of the two per-channel sums over the group, `groupnorm_bwd_apply` with 1 / global count (constant
+    statistics: zero sums)."""
 
     @staticmethod
     def forward(ctx, t, cfg, w0, s0, b0, g0, be0, w1, s1, b1, g1, be1, w2, s2, b2):
-        nimg, groups, eps = cfg
+        nimg, groups, eps = cfg[:3]
+        stats_of = cfg[3] if len(cfg) > 3 else (None, None)
         act = ops.dino_tap(_c(t))
         b, l, c = act.shape
         ks = w1.shape[-1]
@@ -1275,14 +1315,13 @@ class DinoHeadFn(torch.autograd.Function):
         wf1, wd1 = ops.conv_tokens_pack(_c(w1.detach()), s1.detach())
         w2t = (w2.detach().reshape(c) / s2.detach()).contiguous()
         h0 = ops.conv_tokens(act, wf0, b0)
-        st0 = ops.groupnorm_stats(h0.view(nimg, -1, c), groups, eps)
-        a = ops.groupnorm_apply(h0.view(nimg, -1, c), st0, g0, be0, 2, groups=groups).view(b, l, c)
+        a, st0, sync0 = _dino_norm_fwd(h0, g0, be0, nimg, groups, eps, stats_of[0])
         c1 = ops.conv_tokens(a, wf1, b1)
-        st1 = ops.groupnorm_stats(c1.view(nimg, -1, c), groups, eps)
-        h = ops.groupnorm_apply(c1.view(nimg, -1, c), st1, g1, be1, 2, groups=groups).view(b, l, c)
+        h, st1, sync1 = _dino_norm_fwd(c1, g1, be1, nimg, groups, eps, stats_of[1])
         logit = ops.dino_tail(a, h, w2t, b2)
         ctx.save_for_backward(act, h0, st0, a, c1, st1, h, wd0, wd1, w2t, w0, s0, g0, be0, w1, s1, g1, be1, w2, s2)
         ctx.cfg = (nimg, groups, ks)
+        ctx.sync = (sync0, sync1)
         return logit
 
     @staticmethod
@@ -1293,24 +1332,24 @@ class DinoHeadFn(torch.autograd.Function):
         need = ctx.needs_input_grad
         need_t = need[0]
         nw0, nn0, nw1, nn1, nw2 = need[2] or need[3] or need[4], need[5] or need[6], need[7] or need[8] or need[9], need[10] or need[11], need[12] or need[13] or need[14]
-        v3 = lambda x: x.view(nimg, -1, c)
 
         def sn_grads(dwt, w, s):      # W~ = W / s:  d W = dW~ / s,  d s = -<dW~, W> / s^2
             inv = 1.0 / s
             return dwt.view(w.shape) * inv, -(dwt.view(w.shape) * w).sum().reshape(s.shape) * inv * inv
 
+        sync0, sync1 = ctx.sync
         dah, dw2t, db2 = ops.dino_tail_bwd(_c(dlogit).float(), a, h, w2t, need_dx=True, need_w=nw2)
         dw2 = ds2 = None
         if nw2:
             dw2, ds2 = sn_grads(dw2t, w2, s2)
-        dc1, dg1, dbe1 = ops.groupnorm_bwd(v3(dah), v3(c1), st1, g1, be1, 2, groups=groups, need_param_grads=nn1)
+        dc1, dg1, dbe1 = _dino_norm_bwd(dah, c1, st1, g1, be1, nimg, groups, nn1, sync1)
         dc1 = dc1.view(b, l, c)
         dw1 = ds1 = db1 = None
         if nw1:
             dw1t, db1 = ops.conv_tokens_wgrad(dc1, a, ks)
             dw1, ds1 = sn_grads(dw1t, w1, s1)
         da = ops.conv_tokens_dgrad(dc1, wd1, dres=dah)                   # a feeds the conv and the skip: both gradients in one rounding
-        dh0, dg0, dbe0 = ops.groupnorm_bwd(v3(da), v3(h0), st0, g0, be0, 2, groups=groups, need_param_grads=nn0)
+        dh0, dg0, dbe0 = _dino_norm_bwd(da, h0, st0, g0, be0, nimg, groups, nn0, sync0)
         dh0 = dh0.view(b, l, c)
         dw0 = ds0 = db0 = None
         if nw0:
@@ -1318,6 +1357,44 @@ class DinoHeadFn(torch.autograd.Function):
             dw0, ds0 = sn_grads(dw0t, w0, s0)
         dt = ops.dino_untap(ops.conv_tokens_dgrad(dh0, wd0)) if need_t else None
         return dt, None, dw0, ds0, db0, dg0, dbe0, dw1, ds1, db1, dg1, dbe1, dw2, ds2, db2
+
+
+class DinoHeadEvalFn(torch.autograd.Function):
+    """`DinoHeadFn` for SyncBatchNorm heads in eval mode with frozen parameters -- the generator's adversarial term (train_tokenizer.py:190-193): the running
+    estimates are constants, so norm + LeakyReLU is a per-channel affine map in each convolution's epilogue and its backward one elementwise pass over the stored
+    output:
+
+        act = tap(t);  a = conv_k1(act) + epilogue;  h = conv_ks(a) + epilogue;  logit = tail(a, h)
+        dah = tail_bwd;  dc1 = bnact_bwd(dah, h);  da = dgrad_ks(dc1) + dah;  dh0 = bnact_bwd(da, a);  dt = untap(dgrad_k1(dh0))
+
+    bn0 / bn1: (running_mean, running_var, gamma, beta) f32 [C].  Only dt is computed (and only when asked); a head parameter that asks for a gradient is an error:
+    such a head goes through `DinoHeadFn` with constant statistics."""
+
+    @staticmethod
+    def forward(ctx, t, eps, w0, s0, b0, bn0, w1, s1, b1, bn1, w2, s2, b2):
+        if any(ctx.needs_input_grad[1:]):
+            raise NotImplementedError("DinoHeadEvalFn computes the input gradient only; heads that train take DinoHeadFn")
+        act = ops.dino_tap(_c(t))
+        c = act.shape[-1]
+        wf0, wd0 = ops.conv_tokens_pack(_c(w0.detach()), s0)
+        wf1, wd1 = ops.conv_tokens_pack(_c(w1.detach()), s1)
+        w2t = (w2.detach().reshape(c) / s2).contiguous()
+        a = ops.conv_tokens(act, wf0, b0, bn=(*bn0, eps))
+        h = ops.conv_tokens(a, wf1, b1, bn=(*bn1, eps))
+        logit = ops.dino_tail(a, h, w2t, b2)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(a, h, wd0, wd1, w2t, bn0[1], bn0[2], bn1[1], bn1[2])
+            ctx.eps = eps
+        return logit
+
+    @staticmethod
+    def backward(ctx, dlogit):
+        a, h, wd0, wd1, w2t, rv0, g0, rv1, g1 = ctx.saved_tensors
+        dah, _, _ = ops.dino_tail_bwd(_c(dlogit).float(), a, h, w2t, need_dx=True, need_w=False)
+        dc1 = ops.dino_bnact_bwd(dah, h, g1, rv1, ctx.eps)
+        da = ops.conv_tokens_dgrad(dc1, wd1, dres=dah)
+        dh0 = ops.dino_bnact_bwd(da, a, g0, rv0, ctx.eps)
+        return (ops.dino_untap(ops.conv_tokens_dgrad(dh0, wd0)),) + (None,) * 12
 
 
 class LayerNormBf16Fn(torch.autograd.Function):

@@ -9,10 +9,19 @@ A frozen DINOv2 ViT (patch 14, position embedding for 518 px interpolated to the
 and the heads' logits are concatenated: [B, len(key_depths) * L].
 
 Routes.  The HIP route runs when the input is a GPU tensor under autocast(bfloat16), the fp32 parity mode is off, the backbone's width is one the LayerNorm
-kernels take with head dim 64 and at most 512 channels (the heads' norm kernels: ViT-S, the scripts' backbone, is; ViT-B / L are not) and `norm_type` is 'bn' or 'gn': backbone on the frozen encoder route (graph-free `vit_fast.frozen_forward_features`
+kernels take with head dim 64 and at most 512 channels (the heads' norm kernels: ViT-S, the scripts' backbone, is; ViT-B / L are not): backbone on the frozen encoder route (graph-free `vit_fast.frozen_forward_features`
 with taps when the image needs no gradient -- the discriminator's turn --, `VitBlockDxFn` per block when it does -- the generator's term), each head as one
 `functional.DinoHeadFn` (csrc/conv_tokens.hip, the GroupNorm kernels, csrc/dinodisc.hip).  Anything else goes through `_stock.require_opt_in` to
 `forward_stock`, the plain-PyTorch statement of the module below, which is also its definition on the CPU.
+
+Norms.  Both trainers build the module with `norm_type=args.disc_norm`, default "sbn", and `use_specnorm=args.disc_specnorm`, default False
+(train_tokenizer.py:48-49,307-314, train_dmd.py:50-51,389-396): `nn.SyncBatchNorm(C, eps)` per block (models/dinodisc.py:62-65; 'lbn' / 'hbn': over the local
+machine's process group, `dist.new_local_machine_group`), the holder of weight, bias, running_mean, running_var and num_batches_tracked under the reference's
+keys.  On the HIP route it is the GroupNorm kernels with one "image" of B * L rows and one channel per group, the statistics through
+`models.patchgan._bn_stats` -- PatchGAN's BatchNorm rule: combined over the ranks, running estimates updated with momentum 0.1 and the unbiased variance, the
+backward's two per-channel sums all-reduced -- in train mode, and `functional.DinoHeadEvalFn` in eval mode with frozen heads (the generator's term): the running
+estimates folded into the convolutions' epilogues.  The mode is chosen by `norm.training or not norm.track_running_stats`, as `_bn_stats` does.  'bn'
+(BatchNormLocal, the module's own default) and 'gn' are selected by no script unless it is told to.
 
 What differs from the reference, on purpose:
   * Spectral norm is computed in f32.  Under autocast the reference's `torch.mv` / `torch.dot` inside the legacy SpectralNorm hook run in bf16; the captured
@@ -23,7 +32,9 @@ What differs from the reference, on purpose:
   * `init_params` of the reference writes its xavier values into the recomputed `weight` attribute, which the next forward overwrites: it has no effect, and
     `weight_orig` keeps Conv1d's default initialisation there and here (biases zero, norm affine ones / zeros).  Seeded-construction RNG parity is not attempted.
   * `grad_ckpt=True` gives the same numbers; on the HIP route the head Function already keeps only what its backward reads, so nothing is recomputed.
-  * `norm_type` 'sbn' / 'lbn' / 'hbn' (SyncBatchNorm variants, models/dinodisc.py:62-65; no script passes them) raise NotImplementedError.
+  * `norm_type` 'sbn' / 'lbn' / 'hbn' (the SyncBatchNorm variants, models/dinodisc.py:62-65) sit behind a module-level switch that is off by default: with it off
+    the constructor raises NotImplementedError.  `enable_syncbn_heads()` turns it on; `run_on_mi355x.install_shadow(ref, dinodisc=True)`, `--hip-dinodisc` and
+    DMVAE_HIP_DINODISC=1 do so, since the scripts pass 'sbn'.
 """
 import math
 import random
@@ -35,6 +46,16 @@ import torch.nn.functional as F
 from torch import nn
 
 from .vit import DinoV2ViT
+
+_SYNCBN_HEADS = False
+
+
+def enable_syncbn_heads(on: bool = True) -> bool:
+    """Turn the SyncBatchNorm head variants (`norm_type` 'sbn' / 'lbn' / 'hbn') on or off for constructors that follow; returns the previous setting."""
+    global _SYNCBN_HEADS
+    was, _SYNCBN_HEADS = _SYNCBN_HEADS, bool(on)
+    return was
+
 
 _ARCH = {"vit_small": dict(embed_dim=384, depth=12, num_heads=6), "vit_base": dict(embed_dim=768, depth=12, num_heads=12),
          "vit_large": dict(embed_dim=1024, depth=24, num_heads=16)}
@@ -174,7 +195,11 @@ def make_block(channels, kernel_size, norm_type, norm_eps, use_specnorm):
     elif norm_type == "gn":
         norm = nn.GroupNorm(32, channels, eps=norm_eps, affine=True)
     elif norm_type in ("sbn", "lbn", "hbn"):
-        raise NotImplementedError(f"norm_type {norm_type!r}: the SyncBatchNorm head variants of models/dinodisc.py:62-65 are not built (no script passes them)")
+        if not _SYNCBN_HEADS:
+            raise NotImplementedError(f"norm_type {norm_type!r}: the SyncBatchNorm head variants of models/dinodisc.py:62-65 are behind a switch that is off; "
+                                      "dmvae_amd.models.dinodisc.enable_syncbn_heads() turns it on (run_on_mi355x.py --hip-dinodisc does)")
+        from .. import dist
+        norm = nn.SyncBatchNorm(channels, eps=norm_eps, process_group=None if norm_type == "sbn" else dist.new_local_machine_group())
     else:
         raise NotImplementedError
     conv = (SpectralConv1d if use_specnorm else PlainConv1d)(channels, channels, kernel_size, padding=kernel_size // 2)
@@ -264,7 +289,9 @@ class DinoDisc(nn.Module):
             from .._stock import require_opt_in
             require_opt_in("DinoDisc.forward", why)
             return self.forward_stock(x, grad_ckpt)
-        from ..functional import DinoHeadFn
+        from functools import partial
+        from ..functional import DinoHeadEvalFn, DinoHeadFn
+        from .patchgan import _bn_stats
         from .vit_fast import frozen_forward_features, frozen_taps_with_input_grad
         vit = self.dino[0]
         x = self.preprocess(x)
@@ -279,7 +306,18 @@ class DinoDisc(nn.Module):
             c0, n0 = head[0][0], head[0][1]
             c1, n1 = head[1].fn[0], head[1].fn[1]
             c2 = head[2]
-            cfg = (n0.groups_for(b), t.shape[-1], n0.eps) if self.norm_type == "bn" else (b, 32, n0.eps)
+            if isinstance(n0, nn.SyncBatchNorm):
+                if not (n0.training or not n0.track_running_stats) and not (torch.is_grad_enabled() and any(p.requires_grad for p in head.parameters())):
+                    bn0, bn1 = ((n.running_mean, n.running_var, n.weight.detach(), n.bias.detach()) for n in (n0, n1))
+                    out.append(DinoHeadEvalFn.apply(t, n0.eps, c0.weight_orig.detach(), c0.sigma().detach(), c0.bias.detach(), bn0, c1.weight_orig.detach(),
+                                                    c1.sigma().detach(), c1.bias.detach(), bn1, c2.weight_orig.detach(), c2.sigma().detach(),
+                                                    c2.bias.detach()).view(b, -1))
+                    continue
+                cfg = (1, t.shape[-1], n0.eps, (partial(_bn_stats, n0), partial(_bn_stats, n1)))
+            elif self.norm_type == "bn":
+                cfg = (n0.groups_for(b), t.shape[-1], n0.eps)
+            else:
+                cfg = (b, 32, n0.eps)
             out.append(DinoHeadFn.apply(t, cfg, c0.weight_orig, c0.sigma(), c0.bias, n0.weight, n0.bias, c1.weight_orig, c1.sigma(), c1.bias, n1.weight, n1.bias,
                                         c2.weight_orig, c2.sigma(), c2.bias).view(b, -1))
         return torch.cat(out, dim=1)

@@ -2084,14 +2084,24 @@ def conv_tokens_pack(w: torch.Tensor, sigma: Optional[torch.Tensor] = None) -> T
     return wf, wd
 
 
-def conv_tokens(x: torch.Tensor, w_fwd: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y[b, l] = bias + sum_t x[b, l + t - ks // 2] @ W_t^T on token-major x [B, L, C] bf16 (zero padding per sample); w_fwd from `conv_tokens_pack`."""
+def conv_tokens(x: torch.Tensor, w_fwd: torch.Tensor, bias: Optional[torch.Tensor] = None, bn=None) -> torch.Tensor:
+    """y[b, l] = bias + sum_t x[b, l + t - ks // 2] @ W_t^T on token-major x [B, L, C] bf16 (zero padding per sample); w_fwd from `conv_tokens_pack`.
+    bn = (running_mean, running_var, gamma, beta, eps), four f32 [C] tensors: an eval-mode BatchNorm + LeakyReLU(0.2) in the epilogue,
+    y = leaky((conv - running_mean) * rsqrt(running_var + eps) * gamma + beta), one rounding."""
     x = _req(x, bf16, "x")
     w_fwd = _req(w_fwd, bf16, "w_fwd")
     b, l, c = x.shape
     ks = w_fwd.shape[1]
     assert w_fwd.shape == (c, ks, c)
     y = torch.empty_like(x)
+    if bn is not None:
+        rm, rv, gamma, beta, eps = bn
+        for name, v in (("running_mean", rm), ("running_var", rv), ("gamma", gamma), ("beta", beta)):
+            assert _req(v, f32, name).numel() == c, name
+        check(_lib.lib().dmvae_conv_tokens_fwd_bnact(x.data_ptr(), w_fwd.data_ptr(), _ptr(None if bias is None else _req(bias, f32, "bias")), rm.data_ptr(),
+                                                     rv.data_ptr(), gamma.data_ptr(), beta.data_ptr(), float(eps), y.data_ptr(), b, l, c, ks, _stream()),
+              "conv_tokens_fwd_bnact")
+        return y
     check(_lib.lib().dmvae_conv_tokens_fwd(x.data_ptr(), w_fwd.data_ptr(), _ptr(None if bias is None else _req(bias, f32, "bias")), y.data_ptr(), b, l, c, ks,
                                            _stream()), "conv_tokens_fwd")
     return y
@@ -2174,6 +2184,18 @@ def dino_tail_bwd(dlogit: torch.Tensor, a: torch.Tensor, h: torch.Tensor, w: tor
     check(L.dmvae_dino_tail_bwd(dlogit.data_ptr(), a.data_ptr(), h.data_ptr(), _req(w, f32, "w").data_ptr(), _ptr(dah), _ptr(dw), _ptr(db), _ptr(ws),
                                 0 if ws is None else ws.numel(), rows, c, _stream()), "dino_tail_bwd")
     return dah, dw, db
+
+
+def dino_bnact_bwd(dy: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, running_var: torch.Tensor, eps: float) -> torch.Tensor:
+    """g = dy * (y > 0 ? 1 : 0.2) * gamma * rsqrt(running_var + eps), bf16 like dy: the backward of `conv_tokens(..., bn=...)`'s epilogue from its stored output y."""
+    dy, y = _req(dy, bf16, "dy"), _req(y, bf16, "y")
+    assert dy.shape == y.shape
+    c = y.shape[-1]
+    assert _req(gamma, f32, "gamma").numel() == c and _req(running_var, f32, "running_var").numel() == c
+    g = torch.empty_like(dy)
+    check(_lib.lib().dmvae_dino_bnact_bwd(dy.data_ptr(), y.data_ptr(), gamma.data_ptr(), running_var.data_ptr(), float(eps), g.data_ptr(), y.numel() // c, c,
+                                          _stream()), "dino_bnact_bwd")
+    return g
 
 
 def layerscale_bwd_dx(dt: torch.Tensor, gamma: torch.Tensor) -> torch.Tensor:

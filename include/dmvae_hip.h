@@ -888,6 +888,13 @@ int dmvae_conv_tokens_dgrad(const void* dy, const void* w_dgrad, const void* dre
 size_t dmvae_conv_tokens_wgrad_workspace(int b, int l, int c, int ks);
 int dmvae_conv_tokens_wgrad(const void* dy, const void* x, void* dw, void* dbias, void* workspace, size_t workspace_bytes, int b, int l, int c, int ks,
                             dmvae_stream_t stream);
+/* fwd with an eval-mode SyncBatchNorm + LeakyReLU(0.2) in the epilogue (constant statistics: a per-channel affine map):
+ * y = bf16(leaky((acc + bias[n] - running_mean[n]) * rsqrt(running_var[n] + eps) * gamma[n] + beta[n])), f32 with the one rounding; the four vectors f32 [C]
+ * on the device (bias may be NULL).  The same kernel as fwd with another epilogue: shapes, determinism and batch independence as there.
+ * Reference: the heads' conv -> norm -> LeakyReLU block, models/dinodisc.py:59-76, with norm_type 'sbn' (models/dinodisc.py:62-65; the scripts' default,
+ * train_tokenizer.py:48-49) under disc.eval() in the generator's term, train_tokenizer.py:190-193. */
+int dmvae_conv_tokens_fwd_bnact(const void* x, const void* w_fwd, const void* bias, const void* running_mean, const void* running_var, const void* gamma,
+                                const void* beta, float eps, void* y, int b, int l, int c, int ks, dmvae_stream_t stream);
 
 /* ---- the passes around the DINOv2 discriminator's heads (csrc/dinodisc.hip) -------------------------------------------------------- */
 
@@ -904,6 +911,12 @@ int dmvae_dino_tail_fwd(const void* a, const void* h, const void* w, const void*
 size_t dmvae_dino_tail_bwd_workspace(size_t rows, int c);
 int dmvae_dino_tail_bwd(const void* dlogit, const void* a, const void* h, const void* w, void* dah, void* dw, void* dbias, void* workspace,
                         size_t workspace_bytes, size_t rows, int c, dmvae_stream_t stream);
+/* g[r][c] (bf16) = dy[r][c] * (y[r][c] > 0 ? 1 : 0.2) * gamma[c] * rsqrt(running_var[c] + eps): the backward of dmvae_conv_tokens_fwd_bnact's epilogue to the
+ * conv's result, from its stored bf16 output y (LeakyReLU keeps the sign; y = +-0 takes the slope, as ATen's backward does at 0); the operand of
+ * dmvae_conv_tokens_dgrad.  dy, y, g bf16 [rows][C], gamma, running_var f32 [C]; C % 8 == 0, rows * C < 2^31.
+ * Reference: autograd of models/dinodisc.py:59-76 with norm_type 'sbn' (models/dinodisc.py:62-65) in eval mode, train_tokenizer.py:190-193. */
+int dmvae_dino_bnact_bwd(const void* dy, const void* y, const void* gamma, const void* running_var, float eps, void* g, size_t rows, int c,
+                         dmvae_stream_t stream);
 /* dy (bf16) = gamma * dt: layerscale_bwd without the parameter sum (a frozen block: models/dinodisc.py:123-125).  c % 8 == 0. */
 int dmvae_layerscale_bwd_dx(const void* dt, const void* gamma, void* dy, size_t rows, int c, dmvae_stream_t stream);
 

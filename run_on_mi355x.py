@@ -14,7 +14,8 @@ scripts import (utils.dist, utils.build_dataset, evaluation.*, models.dinodisc, 
 files: the shadow packages keep the reference's directories on their __path__.
 
 `models.dinodisc` / `models.DinoDisc` (--disc_type dino) is an opt-in: by default it stays the reference's file; `--hip-dinodisc` in front of the script path,
-DMVAE_HIP_DINODISC=1 or `install_shadow(ref, dinodisc=True)` registers this build's `dmvae_amd.models.dinodisc` instead."""
+DMVAE_HIP_DINODISC=1 or `install_shadow(ref, dinodisc=True)` registers this build's `dmvae_amd.models.dinodisc` instead and turns its SyncBatchNorm head
+variants on (`enable_syncbn_heads`): the scripts' default is `--disc_norm sbn`."""
 from __future__ import annotations
 
 import importlib
@@ -77,6 +78,7 @@ def install_shadow(ref_dir: str | None = None, dinodisc: bool = False) -> dict:
 
     if dinodisc:
         models.DinoDisc = out["models.dinodisc"].DinoDisc
+        out["models.dinodisc"].enable_syncbn_heads()                       # the scripts pass norm_type "sbn" (train_tokenizer.py:48-49, train_dmd.py:50-51)
 
     def _lazy(name):          # DinoDisc stays the reference's own unless opted in: imported from its file on first use
         if name == "DinoDisc":
