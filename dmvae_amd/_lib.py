@@ -182,6 +182,13 @@ SIGNATURES = {
     "dmvae_grad_norm": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_float, c_int, c_void_p]),
     "dmvae_adamw_ema_step": (c_int, [c_void_p] * 6 + [c_size_t] + [c_float] * 5 + [c_int, c_float, c_void_p]),
     "dmvae_adamw_ema_step_shadow": (c_int, [c_void_p] * 7 + [c_size_t] + [c_float] * 5 + [c_int, c_float, c_void_p]),
+    # multi-tensor tail: (table, n_tensors, chunks, n_chunks, ...); dmvae_mt_tensor = six 8-byte words {p, g, m, v, ema, numel}, dmvae_mt_chunk = two {tensor, first}
+    "dmvae_mt_chunk_elems": (c_size_t, []),
+    "dmvae_mt_grad_norm_workspace": (c_size_t, [c_size_t]),
+    "dmvae_mt_grad_norm": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_float, c_void_p]),
+    "dmvae_mt_scale_grads": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dmvae_mt_adamw_ema_step": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p] + [c_float] * 5 + [c_int, c_float, c_void_p]),
+    "dmvae_mt_ema": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_float, c_void_p]),
     "dmvae_groupnorm_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "dmvae_groupnorm_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "dmvae_groupnorm_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

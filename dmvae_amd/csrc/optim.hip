@@ -3,6 +3,7 @@
 // update_ema's per-tensor Python loop (train_tokenizer.py:140-150,382,415-419,437).  HBM-bound:
 // reads p,g,m,v,ema and writes p,m,v,ema once (36 B/param) + one 4 B/param norm pass.
 #include "common.h"
+#include "optim_common.h"
 #include "dmvae_hip.h"
 
 namespace dmvae_optim {
@@ -36,18 +37,6 @@ __global__ void norm_final_kernel(const float* __restrict__ part, float* __restr
     norm_out[1] = c < 1.f ? c : 1.f;
     norm_out[2] = (float)a;
   }
-}
-
-// One element's update: torch.optim.AdamW's arithmetic (decoupled decay, bias corrections, IEEE sqrt and division) + the EMA; shared by the vector body and the tail.
-__device__ __forceinline__ void adamw_one(float& pi, const float g, float& mi, float& vi, float* ema_i, const float coef, const float lr, const float b1, const float b2,
-                                          const float eps, const float wd, const float step, const float bc2_sqrt, const float decay) {
-  const float gi = g * coef;
-  pi = pi * (1.f - lr * wd);
-  mi = b1 * mi + (1.f - b1) * gi;
-  vi = b2 * vi + (1.f - b2) * gi * gi;
-  const float denom = sqrtf(vi) / bc2_sqrt + eps;
-  pi -= step * mi / denom;
-  if (ema_i) *ema_i = *ema_i * decay + pi * (1.f - decay);
 }
 
 // 16 B per lane and stream (the scalar form moved 4 B per lane: 4.8 TB/s over the student's 20 GB per step); the same per-element arithmetic, so the same bits.
@@ -88,6 +77,12 @@ __global__ __launch_bounds__(256) void adamw_ema_kernel(float* __restrict__ p, c
   }
 }
 
+int norm_final_launch(const float* part, float* norm_out3, int nb, float max_norm, int use_prev, hipStream_t stream) {
+  hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(64), 0, stream, part, norm_out3, nb, max_norm, use_prev);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace dmvae_optim
 using namespace dmvae_optim;
 
@@ -98,9 +93,7 @@ extern "C" int dmvae_grad_norm(const void* grads, void* norm_out3, void* workspa
   size_t nb = (n / 4 + 255) / 256; if (nb > 2048) nb = 2048; if (nb < 1) nb = 1;
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3((unsigned)nb), dim3(256), 0, stream, (const float*)grads, (float*)workspace, n);
   DMVAE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(64), 0, stream, (const float*)workspace, (float*)norm_out3, (int)nb, max_norm, accumulate_prev);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return norm_final_launch((const float*)workspace, (float*)norm_out3, (int)nb, max_norm, accumulate_prev, stream);
 }
 
 static int adamw_launch(void* params, const void* grads, void* exp_avg, void* exp_avg_sq, void* ema, void* shadow, const void* norm_out3, size_t n,

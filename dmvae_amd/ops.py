@@ -2070,6 +2070,108 @@ def adamw_ema_step(p, g, m, v, ema, norm_out, lr, beta1, beta2, eps, wd, step, e
                                           float(beta1), float(beta2), float(eps), float(wd), int(step), float(ema_decay), _stream()), "adamw_ema_step")
 
 
+# ---- the same tail over lists of separately allocated tensors (csrc/optim_mt.hip) ------------------------------------------------
+_MT_TABLES = _TableCache()      # (pointers and sizes, device) -> record table; (sizes, device) -> chunk list: both are read by launched kernels
+
+
+def mt_chunk_elems() -> int:
+    return int(_lib.lib().dmvae_mt_chunk_elems())
+
+
+def _mt_upload(rows, device) -> torch.Tensor:
+    """int64 rows -> device, from pinned memory without blocking the host (the caching host allocator keeps the staging block until the copy has run)."""
+    host = torch.tensor(rows, dtype=torch.int64).reshape(-1)
+    if host.numel() == 0:
+        host = torch.zeros(2, dtype=torch.int64)       # an address to hand over; no kernel reads it
+    TABLE_BUILDS[0] += 1
+    return host.pin_memory().to(device, non_blocking=True)
+
+
+def _mt_tables(columns, what: str):
+    """columns: five lists (p, g, m, v, ema) of equal length, or None for a column the entry point does not read (ema: a list may hold None).  Every tensor: GPU,
+    f32, contiguous, and of its record's size.  -> (record table, n_tensors, chunk list, n_chunks), both cached: parameter and state pointers are stable, and a
+    gradient freed by zero_grad(set_to_none=True) usually comes back at the same address from the caching allocator."""
+    lead = next(c for c in columns if c is not None)
+    n = len(lead)
+    dev = lead[0].device
+    sizes = tuple(t.numel() for t in lead)
+    ptrs = []
+    for col in columns:
+        if col is None:
+            ptrs.append((0,) * n)
+            continue
+        if len(col) != n:
+            raise ValueError(f"{what}: the tensor lists differ in length")
+        row = []
+        for t, size in zip(col, sizes):
+            if t is None:
+                row.append(0)
+                continue
+            if not t.is_cuda:
+                raise _lib.DmvaeHipError(f"{what}: expected GPU tensors; dmvae_amd has no CPU path")
+            if t.dtype != f32 or not t.is_contiguous() or t.numel() != size or t.device != dev:
+                raise ValueError(f"{what}: every tensor must be f32, contiguous, on one device and of its record's size")
+            row.append(t.data_ptr())
+        ptrs.append(tuple(row))
+    key = (tuple(ptrs), sizes, dev)
+    table = _MT_TABLES.lookup(key)
+    if table is None:
+        table = _mt_upload([[ptrs[0][i], ptrs[1][i], ptrs[2][i], ptrs[3][i], ptrs[4][i], sizes[i]] for i in range(n)], dev)
+        _MT_TABLES.store(key, table)
+    ckey = (sizes, dev)
+    hit = _MT_TABLES.lookup(ckey)
+    if hit is None:
+        c = mt_chunk_elems()
+        rows = [(i, first) for i, size in enumerate(sizes) for first in range(0, size, c)]
+        hit = (_mt_upload(rows, dev), len(rows))
+        _MT_TABLES.store(ckey, hit)
+    return table, n, hit[0], hit[1]
+
+
+def mt_grad_norm(grads: Sequence[torch.Tensor], max_norm: float, norm_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """norm_out3 = [||g||_2 over all tensors, min(1, max_norm / (norm + 1e-6)), sum of squares], a device tensor (no host sync), as `grad_norm` writes it."""
+    grads = list(grads)
+    out = norm_out if norm_out is not None else torch.zeros(3, dtype=f32, device=grads[0].device if grads else None)
+    if not grads:
+        return out
+    table, n, chunks, nc = _mt_tables((None, grads, None, None, None), "mt_grad_norm")
+    L = _lib.lib()
+    ws = workspace(L.dmvae_mt_grad_norm_workspace(nc), out.device, slot="opt")
+    check(L.dmvae_mt_grad_norm(table.data_ptr(), n, chunks.data_ptr(), nc, _req(out, f32, "norm_out").data_ptr(), ws.data_ptr(), ws.numel(), float(max_norm),
+                               _stream()), "mt_grad_norm")
+    return out
+
+
+def mt_scale_grads(grads: Sequence[torch.Tensor], norm_out3: torch.Tensor) -> None:
+    """g *= norm_out3[1] in place on every tensor, one launch."""
+    grads = list(grads)
+    if not grads:
+        return
+    table, n, chunks, nc = _mt_tables((None, grads, None, None, None), "mt_scale_grads")
+    check(_lib.lib().dmvae_mt_scale_grads(table.data_ptr(), n, chunks.data_ptr(), nc, _req(norm_out3, f32, "norm_out3").data_ptr(), _stream()), "mt_scale_grads")
+
+
+def mt_adamw_ema_step(params, grads, exp_avgs, exp_avg_sqs, emas, norm_out3, lr, beta1, beta2, eps, wd, step, ema_decay=0.0) -> None:
+    """`adamw_ema_step` on every (p, g, m, v[, ema]) of the lists in one launch; emas: None, or a list that may hold None; norm_out3: None = no clip coefficient."""
+    params = list(params)
+    if not params:
+        if int(step) < 1:
+            raise _lib.DmvaeHipError("mt_adamw_ema_step: step counts from 1")
+        return
+    table, n, chunks, nc = _mt_tables((params, list(grads), list(exp_avgs), list(exp_avg_sqs), None if emas is None else list(emas)), "mt_adamw_ema_step")
+    check(_lib.lib().dmvae_mt_adamw_ema_step(table.data_ptr(), n, chunks.data_ptr(), nc, _ptr(norm_out3), float(lr), float(beta1), float(beta2), float(eps),
+                                             float(wd), int(step), float(ema_decay), _stream()), "mt_adamw_ema_step")
+
+
+def mt_ema(emas, params, decay: float) -> None:
+    """ema = ema * decay + p * (1 - decay) on every pair, one launch (update_ema's loop, train_tokenizer.py:140-150)."""
+    emas, params = list(emas), list(params)
+    if not emas:
+        return
+    table, n, chunks, nc = _mt_tables((params, None, None, None, emas), "mt_ema")
+    check(_lib.lib().dmvae_mt_ema(table.data_ptr(), n, chunks.data_ptr(), nc, float(decay), _stream()), "mt_ema")
+
+
 # ---- convolution along the token axis (csrc/conv_tokens.hip) ---------------------------------------------------------------
 def conv_tokens_pack(w: torch.Tensor, sigma: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Both bf16 operand packs of a Conv1d weight w [C, C, ks] (f32), divided by the device scalar `sigma` (the spectral norm's divisor) when given:

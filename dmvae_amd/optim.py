@@ -3,7 +3,10 @@
 
 `FlatParams.flatten` re-homes the given parameters (and their .grad) as views into flat buffers, in the order given
 (use backward-completion order so FlatGradSync's buckets fill front to back).  state_dict()/load_state_dict() of the
-owning module keep working: the views are ordinary nn.Parameters."""
+owning module keep working: the views are ordinary nn.Parameters.
+
+For the reference's OWN loop, whose parameters cannot be re-homed (zero_grad(set_to_none=True), stock DDP, deepcopy), the same tail as drop-in objects over
+ordinary parameters: `AdamW`, `clip_grad_norm_`, `update_ema` (multi-tensor kernels, csrc/optim_mt.hip)."""
 from __future__ import annotations
 
 from typing import List, Sequence
@@ -12,6 +15,7 @@ import os
 
 import torch
 
+from . import _stock
 from . import functional as Fn
 from . import ops
 
@@ -297,3 +301,208 @@ class FlatAdamWEMA:
     def scheduler_state_dict(self) -> dict:
         """What torch's LambdaLR.state_dict() carries that matters on resume: the number of completed scheduler steps."""
         return {"last_epoch": self.t, "base_lrs": [self.lr], "_last_lr": [self.current_lr()]}
+
+
+# ---- drop-in tail for the reference's own loop (train_tokenizer.py:140-150,382,415-419,437; train_dmd.py:473-475,540-574; train_diffusion.py:209,293-297) ----
+_bump = torch.autograd.graph.increment_version      # the kernels write through raw pointers: `_version` has to move by hand, as under the stock in-place ops
+
+
+def _why_not(t: torch.Tensor, what: str):
+    """None if the multi-tensor kernels take `t` (GPU, f32, dense, contiguous), else the reason."""
+    if not t.is_cuda:
+        return f"{what} on {t.device.type}"
+    if t.dtype != torch.float32:
+        return f"{what} of dtype {t.dtype}"
+    if t.layout != torch.strided or not t.is_contiguous():
+        return f"{what} that is not dense and contiguous"
+    return None
+
+
+def _refuse_flat_owned(p) -> None:
+    if hasattr(p, "_dmvae_epoch"):
+        raise ValueError("optim.AdamW: this parameter is owned by a FlatParams buffer (FlatAdamWEMA updates it and its packed operands); "
+                         "two owners would race on them")
+
+
+class AdamW(torch.optim.AdamW):
+    """torch.optim.AdamW with its step as ONE HIP launch per param group over the parameters as they are (no flat buffer).  `param_groups`, `state` (the parent's
+    `step` tensor, `exp_avg`, `exp_avg_sq`), state_dict() / load_state_dict() and the LR schedulers are the parent's own: an entry saved by either class loads
+    into the other.  A step the kernels do not cover (CPU, another dtype, non-contiguous tensors, amsgrad / maximize / capturable / differentiable, a tensor lr,
+    a GradScaler's grad_scale) raises unless DMVAE_ALLOW_STOCK=1, and then runs the parent's step for the whole call."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False, foreach=None,
+                 capturable=False, differentiable=False, fused=None):
+        self._ema, self._ema_decay = {}, 0.0
+        self._steps = {}             # parameter -> step count on the host, for groups whose `step` tensors live on the device (fused=True)
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=foreach,
+                         capturable=capturable, differentiable=differentiable, fused=fused)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        for p in self.param_groups[-1]["params"]:
+            _refuse_flat_owned(p)
+
+    def attach_ema(self, pairs, decay: float = 0.9999) -> None:
+        """pairs: (ema tensor, parameter) -- from then on the step's launch also moves each EMA tensor towards its updated parameter
+        (ema = ema * decay + p * (1 - decay)): update_ema folded into the step, for callers who can drop their own call."""
+        mine = {id(p) for g in self.param_groups for p in g["params"]}
+        ema = {}
+        for e, p in pairs:
+            why = _why_not(e, "an EMA tensor")
+            if id(p) not in mine or why is not None or e.numel() != p.numel():
+                raise ValueError(f"optim.AdamW.attach_ema: {why or 'the pair is not (ema tensor, parameter of this optimiser) of one size'}")
+            ema[p] = e
+        self._ema, self._ema_decay = ema, float(decay)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._steps = {}
+
+    def _why_stock(self):
+        if getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
+            return "a GradScaler's grad_scale / found_inf"
+        for group in self.param_groups:
+            for flag in ("amsgrad", "maximize", "capturable", "differentiable"):
+                if group[flag]:
+                    return f"{flag}=True"
+            if not isinstance(group["lr"], (int, float)):
+                return "lr is not a Python float"
+            if not all(isinstance(b, (int, float)) for b in group["betas"]):
+                return "betas are not Python floats"
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                why = _why_not(p, "a parameter") or (None if p.grad.layout == torch.strided else "a sparse gradient") or _why_not(p.grad, "a gradient")
+                if why is not None:
+                    return why
+        return None
+
+    def _step_of(self, p, t: torch.Tensor) -> int:
+        if not t.is_cuda:
+            return int(t.item())
+        if p not in self._steps:
+            self._steps[p] = int(t.item())        # once per parameter after construction / load_state_dict; counted on the host from then on
+        return self._steps[p]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            for p in group["params"]:
+                _refuse_flat_owned(p)
+        why = self._why_stock()
+        if why is not None:
+            _stock.require_opt_in("optim.AdamW.step", why)
+            parent = _TORCH_ADAMW.step
+            if getattr(parent, "hooked", False):      # this call already runs inside the step hooks
+                parent = parent.__wrapped__
+            parent(self)
+            self._steps = {}
+            return loss
+        for group in self.param_groups:
+            params, grads, ms, vs, steps = [], [], [], [], []
+            self._init_group(group, params, grads, ms, vs, [], steps)
+            if not params:
+                continue
+            for ts in (ms, vs):
+                for t in ts:
+                    bad = _why_not(t, "optimiser state")
+                    if bad is not None:
+                        raise ValueError(f"optim.AdamW.step: {bad}")
+            beta1, beta2 = group["betas"]
+            counts = [self._step_of(p, t) + 1 for p, t in zip(params, steps)]
+            for count in sorted(set(counts)):         # one launch per step count: parameters that sat out a step lag behind the others
+                idx = [i for i, c in enumerate(counts) if c == count] if len(set(counts)) > 1 else range(len(params))
+                sel = lambda xs: [xs[i] for i in idx]
+                ps = sel(params)
+                emas = [self._ema.get(p) for p in ps] if self._ema else None
+                ops.mt_adamw_ema_step(ps, sel(grads), sel(ms), sel(vs), emas, None, group["lr"], beta1, beta2, group["eps"], group["weight_decay"],
+                                      count, self._ema_decay)
+                _bump(ps + sel(ms) + sel(vs) + [e for e in (emas or ()) if e is not None])
+            for on_device in (False, True):           # the parent keeps `step` on the host unless fused / capturable put it on the device
+                ts = [t for t in steps if t.is_cuda == on_device]
+                if ts:
+                    torch._foreach_add_(ts, 1)
+            for p, t, c in zip(params, steps, counts):
+                if t.is_cuda:
+                    self._steps[p] = c
+        return loss
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ (train_tokenizer.py:415) as two HIP launches over the gradients as they are: the norm in a fixed summation order, then
+    g *= min(1, max_norm / (norm + 1e-6)) in place.  Returns the 0-dim norm on the device (no host sync; the scripts call .item() on it).  Anything the kernels do
+    not cover (another norm_type, error_if_nonfinite, CPU / non-f32 / non-contiguous gradients) raises unless DMVAE_ALLOW_STOCK=1, then runs torch's own."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    parameters = list(parameters)
+    grads = [p.grad for p in parameters if p.grad is not None]
+    why = None
+    if float(norm_type) != 2.0:
+        why = f"norm_type {norm_type}"
+    elif error_if_nonfinite:
+        why = "error_if_nonfinite=True"
+    else:
+        for g in grads:
+            why = (None if g.layout == torch.strided else "a sparse gradient") or _why_not(g, "a gradient")
+            if why is not None:
+                break
+    if why is not None:
+        _stock.require_opt_in("optim.clip_grad_norm_", why)
+        return _TORCH_CLIP(parameters, max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite, foreach=foreach)
+    if not grads:
+        return torch.tensor(0.0)
+    norm3 = ops.mt_grad_norm(grads, float(max_norm), norm_out=torch.empty(3, dtype=torch.float32, device=grads[0].device))
+    ops.mt_scale_grads(grads, norm3)
+    _bump(grads)
+    return norm3[0]
+
+
+# torch's own, bound before a launcher may replace the attributes (run_on_mi355x.py --hip-optim)
+_TORCH_CLIP = torch.nn.utils.clip_grad_norm_
+_TORCH_ADAMW = AdamW.__mro__[1]
+
+
+@torch.no_grad()
+def update_ema(ema_model, model, decay=0.9999) -> None:
+    """The scripts' update_ema (train_tokenizer.py:140-150): every parameter of `model`, paired by name, ema = ema * decay + p * (1 - decay) -- in one launch."""
+    ema_params = dict(ema_model.named_parameters())
+    emas, params = [], []
+    for name, p in model.named_parameters():
+        e = ema_params[name]
+        why = _why_not(e, "an EMA parameter") or _why_not(p, "a parameter")
+        if why is None and e.numel() != p.numel():
+            why = f"EMA parameter {name} of another size"
+        if why is not None:
+            _stock.require_opt_in("optim.update_ema", why)
+            for name2, p2 in model.named_parameters():
+                ema_params[name2].mul_(decay).add_(p2.data, alpha=1 - decay)
+            return
+        emas.append(e)
+        params.append(p)
+    ops.mt_ema(emas, params, float(decay))
+    _bump(emas)
+
+
+# attribute of torch the reference's scripts call -> this module's object (train_tokenizer.py:382-383,415,424; train_dmd.py:473-475,545,573; train_diffusion.py:209,293)
+TORCH_PATCHES = {"torch.optim.AdamW": "AdamW", "torch.nn.utils.clip_grad_norm_": "clip_grad_norm_"}
+
+
+def requested() -> bool:
+    """DMVAE_HIP_OPTIM=1 in the environment: run_on_mi355x.py then installs the drop-in tail as under --hip-optim."""
+    return os.environ.get("DMVAE_HIP_OPTIM", "0") not in ("", "0")
+
+
+def install() -> dict:
+    """Make torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ this module's for the process (opt-in: nothing calls this unasked); returns {attribute path: object}."""
+    import importlib
+    out = {}
+    for path, name in TORCH_PATCHES.items():
+        owner, attr = path.rsplit(".", 1)
+        setattr(importlib.import_module(owner), attr, globals()[name])
+        out[path] = globals()[name]
+    return out

@@ -712,6 +712,44 @@ int dmvae_adamw_ema_step_shadow(void* params, const void* grads, void* exp_avg, 
                                 const void* norm_out3, size_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, int step, float ema_decay, dmvae_stream_t stream);
 
+/* ---- the same tail over a table of separately allocated tensors (the reference's own loop: no flat buffers) ---- */
+
+/* One record per tensor, in device memory: f32 tensors of `numel` elements each, dense, 4-byte aligned or better (a record whose pointers are all 16-byte
+ * aligned takes the vector path).  An entry point reads only the pointers it names; ema may be NULL; numel == 0 is legal. */
+typedef struct dmvae_mt_tensor {
+  void* p;
+  void* g;
+  void* m;
+  void* v;
+  void* ema;
+  size_t numel;
+} dmvae_mt_tensor;
+/* Chunk `first / dmvae_mt_chunk_elems()` of tensor `tensor`: elements [first, min(first + chunk length, numel)).  The list, in device memory, holds every chunk
+ * of every non-empty tensor once, tensor by tensor; the grad-norm partial sums are written in this order. */
+typedef struct dmvae_mt_chunk {
+  size_t tensor;
+  size_t first;
+} dmvae_mt_chunk;
+/* Chunk length in elements (a multiple of 4).  Every dmvae_mt_* entry: n_tensors == 0 returns 0 and launches nothing; a NULL table or chunk list, a workspace
+ * too small or step < 1 return -22.  Reference: the loop these serve, train_tokenizer.py:140-150,382,415-419. */
+size_t dmvae_mt_chunk_elems(void);
+/* Bytes of workspace dmvae_mt_grad_norm needs for n_chunks chunks (one f32 partial sum per chunk). */
+size_t dmvae_mt_grad_norm_workspace(size_t n_chunks);
+/* norm_out3 as dmvae_grad_norm writes it, over the g of every record: per-chunk f32 sums of g^2 in chunk order, then the f64 sum of the partials; the order is
+ * fixed, so two calls give the same bits.  Reference: clip_grad_norm_, train_tokenizer.py:382,415 (train_dmd.py:545,573; train_diffusion.py:293). */
+int dmvae_mt_grad_norm(const dmvae_mt_tensor* table, size_t n_tensors, const dmvae_mt_chunk* chunks, size_t n_chunks, void* norm_out3, void* workspace,
+                       size_t workspace_bytes, float max_norm, dmvae_stream_t stream);
+/* g *= norm_out3[1] in place over the table: clip_grad_norm_ scales the gradients themselves.  Reference: clip_grad_norm_, train_tokenizer.py:415. */
+int dmvae_mt_scale_grads(const dmvae_mt_tensor* table, size_t n_tensors, const dmvae_mt_chunk* chunks, size_t n_chunks, const void* norm_out3,
+                         dmvae_stream_t stream);
+/* dmvae_adamw_ema_step's arithmetic, element for element, on every record (the EMA where the record has one); the hyper-parameters and `step` hold for the whole
+ * table: one call per param group.  Reference: torch.optim.AdamW.step + update_ema, train_tokenizer.py:140-150,382,415-419. */
+int dmvae_mt_adamw_ema_step(const dmvae_mt_tensor* table, size_t n_tensors, const dmvae_mt_chunk* chunks, size_t n_chunks, const void* norm_out3, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, int step, float ema_decay, dmvae_stream_t stream);
+/* ema = ema*decay + p*(1-decay) over the (ema, p) of every record; decay = 0 gives p bit for bit for finite ema (train_diffusion.py:231).
+ * Reference: update_ema, train_tokenizer.py:140-150,437. */
+int dmvae_mt_ema(const dmvae_mt_tensor* table, size_t n_tensors, const dmvae_mt_chunk* chunks, size_t n_chunks, float decay, dmvae_stream_t stream);
+
 /* ---- downstream consumers: SDE sampler state update, image -> uint8 (sample_50k.py:142-164), the dopri5 ODE sampler ---- */
 
 /* One Euler-Maruyama step of diffusion/transport/integrators.py:27-35 on the whole state with the drift of transport.py:254-257 and

@@ -5,6 +5,7 @@
     torchrun --nproc-per-node 8 run_on_mi355x.py /path/to/dmvae/train_dmd.py ...
     python run_on_mi355x.py --check            # print what is shadowed and exit
     python run_on_mi355x.py --hip-dinodisc /path/to/dmvae/train_tokenizer.py --disc_type dino ...      (or DMVAE_HIP_DINODISC=1)
+    python run_on_mi355x.py --hip-optim /path/to/dmvae/train_tokenizer.py ...                          (or DMVAE_HIP_OPTIM=1)
 
 The reference's drivers import their model code by module path (`from models.vae import VAE`, `from utils.lpips import LPIPS`,
 `from diffusion.lightningdit.lightningdit import LightningDiT_models`, `from diffusion.transport import create_transport`; train_tokenizer.py:10-17,
@@ -15,7 +16,12 @@ files: the shadow packages keep the reference's directories on their __path__.
 
 `models.dinodisc` / `models.DinoDisc` (--disc_type dino) is an opt-in: by default it stays the reference's file; `--hip-dinodisc` in front of the script path,
 DMVAE_HIP_DINODISC=1 or `install_shadow(ref, dinodisc=True)` registers this build's `dmvae_amd.models.dinodisc` instead and turns its SyncBatchNorm head
-variants on (`enable_syncbn_heads`): the scripts' default is `--disc_norm sbn`."""
+variants on (`enable_syncbn_heads`): the scripts' default is `--disc_norm sbn`.
+
+The optimiser tail is an opt-in too: `--hip-optim` in front of the script path (in either order with `--hip-dinodisc`), DMVAE_HIP_OPTIM=1 or
+`install_shadow(ref, optim=True)` makes `torch.optim.AdamW` and `torch.nn.utils.clip_grad_norm_` this build's `dmvae_amd.optim.AdamW` / `clip_grad_norm_` for the
+process (train_tokenizer.py:382-383,415,424): multi-tensor HIP kernels over the scripts' own parameters.  Without it nothing in `torch` is touched.  The scripts'
+`update_ema` is defined in the scripts themselves and cannot be replaced from outside; `from dmvae_amd.optim import update_ema` is the one-line edit."""
 from __future__ import annotations
 
 import importlib
@@ -56,9 +62,15 @@ def _package(name: str, ref_dir: str | None) -> types.ModuleType:
     return mod
 
 
-def install_shadow(ref_dir: str | None = None, dinodisc: bool = False) -> dict:
+def install_optim() -> dict:
+    """Replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ for this process (dmvae_amd.optim.install); returns {attribute path: object}."""
+    return importlib.import_module("dmvae_amd.optim").install()
+
+
+def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False) -> dict:
     """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve).
-    dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them)."""
+    dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them).
+    optim: also replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (`install_optim`; not part of the returned dict)."""
     out = {}
     shadows = dict(SHADOWS)
     if dinodisc:
@@ -85,6 +97,8 @@ def install_shadow(ref_dir: str | None = None, dinodisc: bool = False) -> dict:
             return importlib.import_module("models.dinodisc").DinoDisc
         raise AttributeError(f"module 'models' has no attribute {name!r}")
     models.__getattr__ = _lazy
+    if optim:
+        install_optim()
     return out
 
 
@@ -93,19 +107,27 @@ def main(argv) -> int:
         print(__doc__)
         return 0
     hip_dinodisc = os.environ.get("DMVAE_HIP_DINODISC", "0") not in ("", "0")
-    if argv[0] == "--hip-dinodisc":
-        hip_dinodisc, argv = True, argv[1:]
-        if not argv:
-            print(__doc__)
-            return 0
+    hip_optim = importlib.import_module("dmvae_amd.optim").requested()      # DMVAE_HIP_OPTIM=1
+    while argv and argv[0] in ("--hip-dinodisc", "--hip-optim"):
+        if argv[0] == "--hip-dinodisc":
+            hip_dinodisc = True
+        else:
+            hip_optim = True
+        argv = argv[1:]
+    if not argv:
+        print(__doc__)
+        return 0
     if argv[0] == "--check":
         ref = argv[1] if len(argv) > 1 else None
         for path, mod in install_shadow(ref, dinodisc=hip_dinodisc).items():
             print(f"{path:40s} -> {mod.__name__}")
+        if hip_optim:
+            for path, obj in install_optim().items():
+                print(f"{path:40s} -> {obj.__module__}.{obj.__qualname__}")
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref, dinodisc=hip_dinodisc)
+    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim)
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])
