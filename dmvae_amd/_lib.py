@@ -37,6 +37,11 @@ class OdeTerms(Structure):
     _fields_ = [("k", c_void_p * 7), ("c", c_float * 7), ("nk", c_int32), ("k_bf16", c_int32)]
 
 
+class ModelTerms(Structure):
+    """dmvae_model_terms (include/dmvae_hip.h): the prologue scalars of a noise / score model, passed by value into the sampler's _m kernels."""
+    _fields_ = [("kind", c_int32), ("c0", c_float), ("dv", c_float), ("nsig", c_float)]
+
+
 ABI_VERSION = 9     # 9: nine retired entry points removed (the two-kernel split-K, the NULL-lse attention aliases, ...); 8: dmvae_reparam_kl_*, dmvae_linear_bf16_sk*, the f32 transformer steps of csrc/parity_dit.hip; 7: dmvae_linear_wgrad_grouped_plan / _xcd, dmvae_conv_k4c1_*; 6: dmvae_dit_stack_* / dmvae_dit_boundary_bwd / batched rows Linears / batched weight transposes; 5: dmvae_groupnorm_*_short; include/dmvae_hip.h: dmvae_abi_version (3: struct dmvae_pack_entry, dmvae_pack_weights_batched, dmvae_linear_bf16*; 4: dmvae_norm_conv_out_bwd*)
 
 # name -> (restype, argtypes); every symbol include/dmvae_hip.h declares
@@ -106,6 +111,11 @@ SIGNATURES = {
     "dmvae_sde_heun_predict": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t] + [c_float] * 4 + [c_void_p]),
     "dmvae_sde_heun_correct": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t] + [c_float] * 4 + [c_void_p]),
     "dmvae_sde_last_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int] + [c_float] * 5 + [c_void_p]),
+    "dmvae_sde_euler_step_m": (c_int, [c_void_p, c_void_p, c_int, POINTER(ModelTerms), c_void_p, c_void_p, c_void_p, c_size_t] + [c_float] * 6 + [c_void_p]),
+    "dmvae_sde_heun_predict_m": (c_int, [c_void_p, c_void_p, c_int, POINTER(ModelTerms), c_void_p, c_void_p, c_size_t] + [c_float] * 4 + [c_void_p]),
+    "dmvae_sde_heun_correct_m": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, POINTER(ModelTerms), c_void_p, c_size_t] + [c_float] * 4 + [c_void_p]),
+    "dmvae_sde_last_step_m": (c_int, [c_void_p, c_void_p, c_int, POINTER(ModelTerms), c_void_p, c_size_t, c_int] + [c_float] * 3 + [c_void_p]),
+    "dmvae_model_velocity": (c_int, [c_void_p, c_void_p, c_int, POINTER(ModelTerms), c_void_p, c_size_t, c_void_p]),
     "dmvae_autoguidance_combine": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_size_t, c_int, c_float, c_void_p, c_float, c_float, c_void_p]),
     "dmvae_batchnorm_running_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_float, c_float, c_float, c_void_p]),
     "dmvae_diffaug_fwd": (c_int, [c_void_p] * 4 + [c_int] * 9 + [c_void_p]),

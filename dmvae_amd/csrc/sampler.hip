@@ -17,12 +17,50 @@
 // correct --, and the "Tweedie" / "Euler" last steps (transport.py:279-288) one pass with a mode argument; autoguidance (lightningdit.py:450-465) is one pass
 // over the two models' outputs (dmvae_autoguidance_combine), its interval gate read from t on the device like the guidance kernel's.
 // Every kernel but the Euler-Maruyama one takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail.
+// A noise- or score-predicting model (transport.py:171-181) adds a prologue to every model-consuming pass -- the `_m` entry points, which share the bodies of
+// the velocity ones through a template parameter --: v = (c0 * x) + dv * (m / nsig) or (c0 * x) + dv * m, its three t-only coefficients host scalars in
+// struct dmvae_model_terms, passed by value.  dmvae_model_velocity writes v alone (the ODE samplers' drift).
 #include <initializer_list>
 
 #include "common.h"
 #include "dmvae_hip.h"
 
 namespace dmvae_sampler {
+
+// sde_drift at (y, v): v + diff * ((rar * v - y) / var)   (transport.py:253-256 over get_score_from_velocity, path.py:74-89)
+__device__ __forceinline__ float sde_drift_one(float v, float y, float rar, float var, float diff) {
+#pragma clang fp contract(off)
+  const float score = (rar * v - y) / var;
+  return v + diff * score;
+}
+
+// Transport.get_score of a noise / score model (transport.py:202-216): m / -sigma_t, or m itself
+__device__ __forceinline__ float model_score_one(const dmvae_model_terms& P, float m) {
+  return P.kind == DMVAE_MODEL_NOISE ? m / P.nsig : m;
+}
+
+// Transport.get_drift of a noise / score model at the state y (transport.py:171-181): (-drift_mean) + drift_var * score, with -drift_mean = c0 * y
+__device__ __forceinline__ float model_velocity_one(const dmvae_model_terms& P, float m, float y) {
+#pragma clang fp contract(off)
+  const float a = P.c0 * y;
+  const float b = P.dv * model_score_one(P, m);
+  return a + b;
+}
+
+// The model's output as the velocity: itself (M false: a velocity model), or through the prologue
+template <bool M>
+__device__ __forceinline__ float velocity_of(const dmvae_model_terms& P, float m, float y) {
+  if constexpr (M) return model_velocity_one(P, m, y);
+  else return m;
+}
+
+// One element of the Euler-Maruyama step: mean = x + sde_drift * dt, x' = mean + sqrt(2 diffusion) * (w sqrt(dt))
+__device__ __forceinline__ void euler_one(float x, float v, float w, float rar, float var, float diff, float dt, float sq2d, float sqdt, float& mean, float& xo) {
+#pragma clang fp contract(off)
+  const float drift = sde_drift_one(v, x, rar, var, diff);
+  mean = x + drift * dt;
+  xo = mean + sq2d * (w * sqdt);
+}
 
 template <typename TV>
 __global__ __launch_bounds__(256) void sde_euler_kernel(const float* __restrict__ x, const TV* __restrict__ v, const float* __restrict__ w,
@@ -45,13 +83,7 @@ __global__ __launch_bounds__(256) void sde_euler_kernel(const float* __restrict_
     if (w) { const float4 t = reinterpret_cast<const float4*>(w)[i]; wv[0] = t.x; wv[1] = t.y; wv[2] = t.z; wv[3] = t.w; }
     float mo[4], xo[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const float score = (rar * vv[j] - xs[j]) / var;       // get_score_from_velocity
-      const float drift = vv[j] + diff * score;               // sde_drift
-      const float mean = xs[j] + drift * dt;
-      mo[j] = mean;
-      xo[j] = mean + sq2d * (wv[j] * sqdt);                   // mean_x + sqrt(2 diffusion) * (w sqrt(dt))
-    }
+    for (int j = 0; j < 4; j++) euler_one(xs[j], vv[j], wv[j], rar, var, diff, dt, sq2d, sqdt, mo[j], xo[j]);
     if (mean_out) reinterpret_cast<float4*>(mean_out)[i] = make_float4(mo[0], mo[1], mo[2], mo[3]);
     if (x_out) reinterpret_cast<float4*>(x_out)[i] = w ? make_float4(xo[0], xo[1], xo[2], xo[3]) : make_float4(mo[0], mo[1], mo[2], mo[3]);
   }
@@ -350,24 +382,17 @@ __global__ __launch_bounds__(256) void sde_heun_perturb_kernel(const float* __re
   for (size_t e = 4 * nq + tid; e < n; e += stride) heun_perturb_at<1>(x, w, xhat, e, sq2d, sqdt);
 }
 
-// sde_drift at (y, v): v + diff * ((rar * v - y) / var)   (transport.py:253-256 over get_score_from_velocity, path.py:74-89)
-__device__ __forceinline__ float sde_drift_one(float v, float y, float rar, float var, float diff) {
-#pragma clang fp contract(off)
-  const float score = (rar * v - y) / var;
-  return v + diff * score;
-}
-
-// K1 = sde_drift(xhat, v1);  xp = xhat + dt * K1
-template <int W>
+// K1 = sde_drift(xhat, v1);  xp = xhat + dt * K1.  M: v1 is a noise / score model's output, converted at xhat first
+template <int W, bool M = false>
 __device__ __forceinline__ void heun_predict_at(const float* __restrict__ xhat, const void* v, int v_bf16, float* __restrict__ k1, float* __restrict__ xp, size_t e,
-                                                float rar, float var, float diff, float dt) {
+                                                float rar, float var, float diff, float dt, const dmvae_model_terms& P = {}) {
 #pragma clang fp contract(off)
   float y[W], vv[W], k[W], o[W];
   load_w<W>(xhat, false, e, y);
   load_w<W>(v, v_bf16, e, vv);
 #pragma unroll
   for (int j = 0; j < W; j++) {
-    k[j] = sde_drift_one(vv[j], y[j], rar, var, diff);
+    k[j] = sde_drift_one(velocity_of<M>(P, vv[j], y[j]), y[j], rar, var, diff);
     o[j] = y[j] + dt * k[j];
   }
   store_w<W>(k1, e, k);
@@ -381,10 +406,17 @@ __global__ __launch_bounds__(256) void sde_heun_predict_kernel(const float* __re
   for (size_t e = 4 * nq + tid; e < n; e += stride) heun_predict_at<1>(xhat, v, v_bf16, k1, xp, e, rar, var, diff, dt);
 }
 
+__global__ __launch_bounds__(256) void sde_heun_predict_m_kernel(const float* __restrict__ xhat, const void* m, int m_bf16, dmvae_model_terms P, float* __restrict__ k1,
+                                                                 float* __restrict__ xp, size_t n, size_t nq, float rar, float var, float diff, float dt) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) heun_predict_at<4, true>(xhat, m, m_bf16, k1, xp, 4 * i, rar, var, diff, dt, P);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_predict_at<1, true>(xhat, m, m_bf16, k1, xp, e, rar, var, diff, dt, P);
+}
+
 // K2 = sde_drift(xp, v2) with the coefficients at t + dt;  x = xhat + (0.5 dt) * (K1 + K2)
-template <int W>
+template <int W, bool M = false>
 __device__ __forceinline__ void heun_correct_at(const float* __restrict__ xhat, const float* __restrict__ xp, const float* __restrict__ k1, const void* v, int v_bf16,
-                                                float* __restrict__ out, size_t e, float rar, float var, float diff, float hdt) {
+                                                float* __restrict__ out, size_t e, float rar, float var, float diff, float hdt, const dmvae_model_terms& P = {}) {
 #pragma clang fp contract(off)
   float y[W], p[W], k[W], vv[W], o[W];
   load_w<W>(xhat, false, e, y);
@@ -393,7 +425,7 @@ __device__ __forceinline__ void heun_correct_at(const float* __restrict__ xhat, 
   load_w<W>(v, v_bf16, e, vv);
 #pragma unroll
   for (int j = 0; j < W; j++) {
-    const float k2 = sde_drift_one(vv[j], p[j], rar, var, diff);
+    const float k2 = sde_drift_one(velocity_of<M>(P, vv[j], p[j]), p[j], rar, var, diff);
     o[j] = y[j] + hdt * (k[j] + k2);
   }
   store_w<W>(out, e, o);
@@ -406,10 +438,20 @@ __global__ __launch_bounds__(256) void sde_heun_correct_kernel(const float* __re
   for (size_t e = 4 * nq + tid; e < n; e += stride) heun_correct_at<1>(xhat, xp, k1, v, v_bf16, out, e, rar, var, diff, hdt);
 }
 
+__global__ __launch_bounds__(256) void sde_heun_correct_m_kernel(const float* __restrict__ xhat, const float* __restrict__ xp, const float* __restrict__ k1, const void* m,
+                                                                 int m_bf16, dmvae_model_terms P, float* __restrict__ out, size_t n, size_t nq, float rar, float var,
+                                                                 float diff, float hdt) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) heun_correct_at<4, true>(xhat, xp, k1, m, m_bf16, out, 4 * i, rar, var, diff, hdt, P);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_correct_at<1, true>(xhat, xp, k1, m, m_bf16, out, e, rar, var, diff, hdt, P);
+}
+
 // Tweedie: x / a + c * ((rar * v - x) / var).  Euler: x + (v * h), the product rounded to bf16 when v is bf16 (`bf16 tensor * python float` stays bf16).
-template <int W>
+// M (a noise / score model's output m): Tweedie takes Transport.get_score -- m / nsig (f32) or m itself, and then c * m is a 0-d f32 tensor times a tensor of m's
+// type: a bf16 m makes it a bf16 product (c cast to bf16, the f32 product rounded to bf16) before it meets x / a --; Euler takes the converted velocity, which is f32 whatever m is.
+template <int W, bool M = false>
 __device__ __forceinline__ void last_step_at(const float* __restrict__ x, const void* v, int v_bf16, float* __restrict__ out, size_t e, int mode, float a, float c,
-                                             float rar, float var, float h) {
+                                             float rar, float var, float h, const dmvae_model_terms& P = {}) {
 #pragma clang fp contract(off)
   float y[W], vv[W], o[W];
   load_w<W>(x, false, e, y);
@@ -417,11 +459,20 @@ __device__ __forceinline__ void last_step_at(const float* __restrict__ x, const 
 #pragma unroll
   for (int j = 0; j < W; j++) {
     if (mode == DMVAE_LAST_STEP_TWEEDIE) {
-      const float score = (rar * vv[j] - y[j]) / var;
-      o[j] = y[j] / a + c * score;
+      if constexpr (M) {
+        const bool both_bf16 = v_bf16 && P.kind == DMVAE_MODEL_SCORE;      // a bf16 product: the 0-d factor is cast to the result type first
+        float p = (both_bf16 ? (float)(bf16)c : c) * model_score_one(P, vv[j]);
+        if (both_bf16) p = (float)(bf16)p;
+        o[j] = y[j] / a + p;
+      } else {
+        const float score = (rar * vv[j] - y[j]) / var;
+        o[j] = y[j] / a + c * score;
+      }
     } else {
-      float p = vv[j] * h;
-      if (v_bf16) p = (float)(bf16)p;
+      float p = velocity_of<M>(P, vv[j], y[j]) * h;
+      if constexpr (!M) {
+        if (v_bf16) p = (float)(bf16)p;
+      }
       o[j] = y[j] + p;
     }
   }
@@ -433,6 +484,57 @@ __global__ __launch_bounds__(256) void sde_last_step_kernel(const float* __restr
   const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
   for (size_t i = tid; i < nq; i += stride) last_step_at<4>(x, v, v_bf16, out, 4 * i, mode, a, c, rar, var, h);
   for (size_t e = 4 * nq + tid; e < n; e += stride) last_step_at<1>(x, v, v_bf16, out, e, mode, a, c, rar, var, h);
+}
+
+__global__ __launch_bounds__(256) void sde_last_step_m_kernel(const float* __restrict__ x, const void* m, int m_bf16, dmvae_model_terms P, float* __restrict__ out, size_t n,
+                                                              size_t nq, int mode, float a, float c, float h) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) last_step_at<4, true>(x, m, m_bf16, out, 4 * i, mode, a, c, 0.f, 1.f, h, P);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) last_step_at<1, true>(x, m, m_bf16, out, e, mode, a, c, 0.f, 1.f, h, P);
+}
+
+// The Euler-Maruyama step of a noise / score model: the prologue at x, then euler_one; w NULL: x_out = mean (the "Mean" last step).  Any n.
+template <int W>
+__device__ __forceinline__ void euler_m_at(const float* __restrict__ x, const void* m, int m_bf16, const dmvae_model_terms& P, const float* __restrict__ w,
+                                           float* __restrict__ x_out, float* __restrict__ mean_out, size_t e, float rar, float var, float diff, float dt, float sq2d,
+                                           float sqdt) {
+  float y[W], mv[W], wv[W], mo[W], xo[W];
+  load_w<W>(x, false, e, y);
+  load_w<W>(m, m_bf16, e, mv);
+  if (w) load_w<W>(w, false, e, wv);
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    if (!w) wv[j] = 0.f;
+    euler_one(y[j], model_velocity_one(P, mv[j], y[j]), wv[j], rar, var, diff, dt, sq2d, sqdt, mo[j], xo[j]);
+  }
+  if (mean_out) store_w<W>(mean_out, e, mo);
+  if (x_out) store_w<W>(x_out, e, w ? xo : mo);
+}
+
+__global__ __launch_bounds__(256) void sde_euler_m_kernel(const float* __restrict__ x, const void* m, int m_bf16, dmvae_model_terms P, const float* __restrict__ w,
+                                                          float* __restrict__ x_out, float* __restrict__ mean_out, size_t n, size_t nq, float rar, float var, float diff,
+                                                          float dt, float sq2d, float sqdt) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) euler_m_at<4>(x, m, m_bf16, P, w, x_out, mean_out, 4 * i, rar, var, diff, dt, sq2d, sqdt);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) euler_m_at<1>(x, m, m_bf16, P, w, x_out, mean_out, e, rar, var, diff, dt, sq2d, sqdt);
+}
+
+// v alone, f32: the drift of the probability-flow ODE (Transport.get_drift) for a noise / score model
+template <int W>
+__device__ __forceinline__ void model_velocity_at(const float* __restrict__ x, const void* m, int m_bf16, const dmvae_model_terms& P, float* __restrict__ out, size_t e) {
+  float y[W], mv[W], o[W];
+  load_w<W>(x, false, e, y);
+  load_w<W>(m, m_bf16, e, mv);
+#pragma unroll
+  for (int j = 0; j < W; j++) o[j] = model_velocity_one(P, mv[j], y[j]);
+  store_w<W>(out, e, o);
+}
+
+__global__ __launch_bounds__(256) void model_velocity_kernel(const float* __restrict__ x, const void* m, int m_bf16, dmvae_model_terms P, float* __restrict__ out, size_t n,
+                                                             size_t nq) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) model_velocity_at<4>(x, m, m_bf16, P, out, 4 * i);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) model_velocity_at<1>(x, m, m_bf16, P, out, e);
 }
 
 // ---- autoguidance (LightningDiT.forward_with_autoguidance, lightningdit.py:450-465) ------------------------------------------------------------------------
@@ -502,6 +604,8 @@ inline bool terms_ok(const dmvae_ode_terms* T) {
     if (!T->k[j]) return false;
   return true;
 }
+
+inline bool model_terms_ok(const dmvae_model_terms* P) { return P && (P->kind == DMVAE_MODEL_NOISE || P->kind == DMVAE_MODEL_SCORE); }
 
 }  // namespace dmvae_sampler
 
@@ -668,6 +772,65 @@ extern "C" int dmvae_autoguidance_combine(const void* eps, int c_eps, const void
   else
     hipLaunchKernelGGL(autoguidance_combine_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)eps, (const float*)ag, (float*)dst, half, nq, per, per_eps,
                        per_ag, scale, (const float*)t, lo, hi);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_euler_step_m(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, const void* w, void* x_out, void* mean_out, size_t n,
+                                      float rar, float var, float diff, float dt, float sqrt_2diff, float sqrt_dt, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(x && m && (x_out || mean_out) && n > 0, "sde_euler_step_m: bad argument (x, m, x_out or mean_out non-NULL, n > 0)");
+  DMVAE_CHECK_ARG(model_terms_ok(terms), "sde_euler_step_m: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
+  const size_t nq = aligned(m, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, w, x_out, mean_out}) : 0;
+  hipLaunchKernelGGL(sde_euler_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, m, m_is_bf16 != 0, *terms, (const float*)w, (float*)x_out,
+                     (float*)mean_out, n, nq, rar, var, diff, dt, sqrt_2diff, sqrt_dt);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_heun_predict_m(const void* xhat, const void* m1, int m_is_bf16, const dmvae_model_terms* terms, void* k1, void* xp, size_t n, float rar, float var,
+                                        float diff, float dt, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(xhat && m1 && k1 && xp && n > 0, "sde_heun_predict_m: bad argument (xhat, m1, k1, xp non-NULL, n > 0)");
+  DMVAE_CHECK_ARG(model_terms_ok(terms), "sde_heun_predict_m: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
+  const size_t nq = aligned(m1, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, k1, xp}) : 0;
+  hipLaunchKernelGGL(sde_heun_predict_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, m1, m_is_bf16 != 0, *terms, (float*)k1, (float*)xp, n,
+                     nq, rar, var, diff, dt);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_heun_correct_m(const void* xhat, const void* xp, const void* k1, const void* m2, int m_is_bf16, const dmvae_model_terms* terms2, void* x_out,
+                                        size_t n, float rar2, float var2, float diff2, float half_dt, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(xhat && xp && k1 && m2 && x_out && n > 0, "sde_heun_correct_m: bad argument (xhat, xp, k1, m2, x_out non-NULL, n > 0)");
+  DMVAE_CHECK_ARG(model_terms_ok(terms2), "sde_heun_correct_m: terms2->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
+  const size_t nq = aligned(m2, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, xp, k1, x_out}) : 0;
+  hipLaunchKernelGGL(sde_heun_correct_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, (const float*)xp, (const float*)k1, m2,
+                     m_is_bf16 != 0, *terms2, (float*)x_out, n, nq, rar2, var2, diff2, half_dt);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_sde_last_step_m(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, void* out, size_t n, int mode, float a, float c, float h,
+                                     hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(x && m && out && n > 0, "sde_last_step_m: bad argument (x, m, out non-NULL, n > 0)");
+  DMVAE_CHECK_ARG(model_terms_ok(terms), "sde_last_step_m: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
+  DMVAE_CHECK_ARG(mode == DMVAE_LAST_STEP_TWEEDIE || mode == DMVAE_LAST_STEP_EULER, "sde_last_step_m: mode must be DMVAE_LAST_STEP_TWEEDIE or _EULER, got %d", mode);
+  const size_t nq = aligned(m, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, out}) : 0;
+  hipLaunchKernelGGL(sde_last_step_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, m, m_is_bf16 != 0, *terms, (float*)out, n, nq, mode, a, c,
+                     h);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_model_velocity(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, void* out, size_t n, hipStream_t stream) {
+  using namespace dmvae_sampler;
+  DMVAE_CHECK_ARG(x && m && out && n > 0, "model_velocity: bad argument (x, m, out non-NULL, n > 0)");
+  DMVAE_CHECK_ARG(model_terms_ok(terms), "model_velocity: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
+  const size_t nq = aligned(m, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, out}) : 0;
+  hipLaunchKernelGGL(model_velocity_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, m, m_is_bf16 != 0, *terms, (float*)out, n, nq);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

@@ -1883,6 +1883,86 @@ def sde_last_step(x: torch.Tensor, v: torch.Tensor, mode: int, *, a: float = 1.0
     return out
 
 
+MODEL_NOISE, MODEL_SCORE = 1, 2      # DMVAE_MODEL_* of include/dmvae_hip.h
+
+
+def _model_terms(terms, name: str) -> "_lib.ModelTerms":
+    """(kind, c0, dv, nsig) -> struct dmvae_model_terms: the prologue of a noise / score model, v = c0 * x + dv * (m / nsig) or c0 * x + dv * m."""
+    try:
+        kind, c0, dv, nsig = terms
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: terms must be (kind, c0, dv, nsig), got {terms!r}") from None
+    if kind not in (MODEL_NOISE, MODEL_SCORE):
+        raise ValueError(f"{name}: terms[0] must be MODEL_NOISE or MODEL_SCORE, got {kind!r}")
+    return _lib.ModelTerms(int(kind), float(c0), float(dv), float(nsig))
+
+
+def sde_euler_step_m(x: torch.Tensor, m: torch.Tensor, terms, w: Optional[torch.Tensor], rar: float, var: float, diff: float, dt: float, sqrt_2diff: float,
+                     sqrt_dt: float, need_mean: bool = False):
+    """`sde_euler_step` for a noise / score model's output m (bf16 or f32): the velocity v = c0 * x + dv * (m / nsig) (MODEL_NOISE) or c0 * x + dv * m
+    (MODEL_SCORE) -- transport.py:171-181 with `terms` = (kind, c0, dv, nsig) formed by the host -- in f32, then the step -> (x_new, mean_x or None).
+    w = None: x_new = x + drift * dt.  x, w f32; one shape; any number of elements."""
+    pt = _model_terms(terms, "sde_euler_step_m")
+    _req_v(m, _req(x, f32, "x"), "m")
+    if w is not None:
+        _same(_req(w, f32, "w"), x, "w")
+    out = torch.empty_like(x)
+    mean = torch.empty_like(x) if need_mean else None
+    check(_lib.lib().dmvae_sde_euler_step_m(x.data_ptr(), m.data_ptr(), int(m.dtype == bf16), ctypes.byref(pt), _ptr(w), out.data_ptr(), _ptr(mean), x.numel(),
+                                            float(rar), float(var), float(diff), float(dt), float(sqrt_2diff), float(sqrt_dt), _stream()), "sde_euler_step_m")
+    return out, mean
+
+
+def sde_heun_predict_m(xhat: torch.Tensor, m1: torch.Tensor, terms, rar: float, var: float, diff: float, dt: float):
+    """`sde_heun_predict` for a noise / score model's output m1, converted to the velocity at xhat with `terms` (at t) first -> (k1, xp), both f32."""
+    pt = _model_terms(terms, "sde_heun_predict_m")
+    _req_v(m1, _req(xhat, f32, "xhat"), "m1")
+    k1, xp = torch.empty_like(xhat), torch.empty_like(xhat)
+    check(_lib.lib().dmvae_sde_heun_predict_m(xhat.data_ptr(), m1.data_ptr(), int(m1.dtype == bf16), ctypes.byref(pt), k1.data_ptr(), xp.data_ptr(), xhat.numel(),
+                                              float(rar), float(var), float(diff), float(dt), _stream()), "sde_heun_predict_m")
+    return k1, xp
+
+
+def sde_heun_correct_m(xhat: torch.Tensor, xp: torch.Tensor, k1: torch.Tensor, m2: torch.Tensor, terms2, rar2: float, var2: float, diff2: float,
+                       half_dt: float) -> torch.Tensor:
+    """`sde_heun_correct` for a noise / score model's output m2, converted to the velocity at xp with `terms2` (at t + dt) first."""
+    pt = _model_terms(terms2, "sde_heun_correct_m")
+    _req(xhat, f32, "xhat")
+    for name, t in (("xp", xp), ("k1", k1)):
+        _same(_req(t, f32, name), xhat, name)
+    _req_v(m2, xhat, "m2")
+    out = torch.empty_like(xhat)
+    check(_lib.lib().dmvae_sde_heun_correct_m(xhat.data_ptr(), xp.data_ptr(), k1.data_ptr(), m2.data_ptr(), int(m2.dtype == bf16), ctypes.byref(pt), out.data_ptr(),
+                                              xhat.numel(), float(rar2), float(var2), float(diff2), float(half_dt), _stream()), "sde_heun_correct_m")
+    return out
+
+
+def sde_last_step_m(x: torch.Tensor, m: torch.Tensor, terms, mode: int, *, a: float = 1.0, c: float = 0.0, h: float = 0.0) -> torch.Tensor:
+    """`sde_last_step` for a noise / score model's output m.  LAST_STEP_TWEEDIE: x / a + c * s with the model's own score s (`Transport.get_score`: m / nsig for
+    MODEL_NOISE, m for MODEL_SCORE -- then a bf16 m makes c * m a bf16 product, c cast to bf16 first, as a 0-d f32 tensor times a bf16 tensor is).  LAST_STEP_EULER: x + v * h with the
+    converted f32 velocity v."""
+    if mode not in (LAST_STEP_TWEEDIE, LAST_STEP_EULER):
+        raise ValueError(f"sde_last_step_m: mode must be LAST_STEP_TWEEDIE or LAST_STEP_EULER, got {mode!r}")
+    pt = _model_terms(terms, "sde_last_step_m")
+    _req_v(m, _req(x, f32, "x"), "m")
+    out = torch.empty_like(x)
+    check(_lib.lib().dmvae_sde_last_step_m(x.data_ptr(), m.data_ptr(), int(m.dtype == bf16), ctypes.byref(pt), out.data_ptr(), x.numel(), int(mode), float(a), float(c),
+                                           float(h), _stream()), "sde_last_step_m")
+    return out
+
+
+def model_velocity(x: torch.Tensor, m: torch.Tensor, terms, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The probability-flow ODE's drift of a noise / score model (`Transport.get_drift`, transport.py:171-181) in one launch: out (f32, x's shape; given or new)
+    = c0 * x + dv * (m / nsig) or c0 * x + dv * m.  x f32; m bf16 or f32; contiguous, one shape, one device."""
+    pt = _model_terms(terms, "model_velocity")
+    _req_v(m, _req(x, f32, "x"), "m")
+    if out is None:
+        out = torch.empty_like(x)
+    _same(_req(out, f32, "out"), x, "out")
+    check(_lib.lib().dmvae_model_velocity(x.data_ptr(), m.data_ptr(), int(m.dtype == bf16), ctypes.byref(pt), out.data_ptr(), x.numel(), _stream()), "model_velocity")
+    return out
+
+
 def autoguidance_combine(eps: torch.Tensor, ag: torch.Tensor, k: int, scale: float, t: torch.Tensor, interval=(-1e4, -1e4),
                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Autoguidance on two model outputs in one launch (LightningDiT.forward_with_autoguidance, lightningdit.py:450-465): eps [n, C, H, W] is this model's

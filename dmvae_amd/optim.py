@@ -12,6 +12,7 @@ from __future__ import annotations
 from typing import List, Sequence
 
 import os
+import weakref
 
 import torch
 
@@ -113,7 +114,7 @@ class FlatParams:
         conditional block, a Function returning None) would keep the previous step's gradient and AdamW / grad_norm would consume it silently.  No such
         parameter exists in the VAE or the DiT routes; DMVAE_CHECK_DIRECT_GRADS=1 (or `check_direct_writes`) verifies it per step, and a trainer that cannot
         guarantee it sets `self.zero_all = True` to fall back to zeroing the whole buffer."""
-        opt = getattr(self, "_opt", None)
+        opt = getattr(self, "_opt", lambda: None)()
         if opt is not None:
             opt.wait()            # an overlapped optimiser step still reads the gradient buffer
         if _CHECK_DIRECT and getattr(self, "direct", False):
@@ -180,7 +181,7 @@ class FlatAdamWEMA:
         self.norm = torch.zeros(3, dtype=torch.float32, device=fp.flat.device)   # [norm, clip coef, sumsq] stays on device
         self.t = 0
         self.side, self._done, self._then = None, None, None
-        fp._opt = self
+        fp._opt = weakref.ref(self)      # weak: a strong reference closes a cycle with `self.fp`, and a dropped trainer's buffers then wait for the cyclic collector
 
     _SIDE = {}      # device index -> THE side stream of this process: every overlapped optimiser shares it
 

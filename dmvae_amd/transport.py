@@ -1,5 +1,6 @@
-"""Host mirror of the reference's `diffusion/transport` package for the configuration its scripts run (Linear path, velocity prediction):
-`create_transport` (__init__.py:3-64), `Transport` (transport.py:39-221), `ICPlan` (path.py:18-136), `Sampler` (transport.py:223-458) and the
+"""Host mirror of the reference's `diffusion/transport` package: the Linear path with velocity prediction (the configuration its scripts run), noise /
+score prediction (`--prediction noise|score`) and, behind `enable_all_paths()`, the GVP and VP paths (`--path_type GVP|VP`):
+`create_transport` (__init__.py:3-64), `Transport` (transport.py:39-221), `ICPlan` / `VPCPlan` / `GVPCPlan` (path.py:18-192), `Sampler` (transport.py:223-458) and the
 `sde` / `ode` integrators (integrators.py:8-118) -- same names, arguments, defaults, random-number consumption and error behaviour.
 
 What runs where: a sampler step is one model forward (LightningDiT on the HIP kernels, models/lightningdit_fast.py) plus the state update;
@@ -14,7 +15,18 @@ integrates the tuple state (x, logp) as one flat f32 buffer with torchdiffeq's m
 kernel (`ops.ode_hutchinson_pack`) that writes the stage value.  The per-step noise is drawn on the CPU generator and moved to the state's
 device exactly as the reference does (`th.randn(x.size()).to(x)`, integrators.py:28,38), so a seeded run consumes the same stream.
 
-Not built: the GVP / VP plans (path.py:138-191; never selected by the reference's scripts: `path_type` is "Linear" everywhere), dopri5 and tuple states
+Model types: everything downstream of the model is the same once its output is a velocity.  A noise / score model adds a prologue to each model-consuming
+pass (the `_m` entry points of csrc/sampler.hip): v = (-drift_mean) + drift_var * score (transport.py:171-181), its three t-only coefficients host scalars
+(`model_terms`).  Host-scalar rule: every coefficient of a kernel route is formed on the CPU in f32 from the host's copy of t by the path's own methods, never
+read back from the device and never formed there.  The ODE routes take the converted drift from one kernel per evaluation (`ops.model_velocity`, written
+straight into dopri5's stage slot); the likelihood sampler of a noise / score model stays composed (it needs the VJP through the conversion).
+
+Paths: the GVP and VP plans are opt-in (`enable_all_paths()`; off, `Transport` refuses them as it always did -- `run_on_mi355x.py` turns the switch on when it
+runs a script, whose own `--path_type` is then the selection).  Nothing downstream of the model depends on the path beyond the t-only scalars the plans' own
+methods give on the CPU, so a velocity model on GVP / VP runs on the same kernels as on the Linear path and a noise / score model on the same `_m` kernels.
+Their transcendental coefficients (sin / cos / tan, exp / sqrt of t) are exactly why the host-scalar rule holds: the device's are not the CPU's.
+
+Not built: dopri5 and tuple states
 on CPU or non-f32 states and the other adaptive ODE solvers unless `torchdiffeq` (an unpinned third-party dependency) is importable."""
 from __future__ import annotations
 
@@ -132,6 +144,71 @@ class ICPlan:
         return t, xt, self.compute_ut(t, x0, x1, xt)
 
 
+class VPCPlan(ICPlan):
+    """Variance-preserving path (path.py:139-171): alpha_t = exp(log_mean_coeff(t)), sigma_t = sqrt(1 - alpha_t^2), with its own `compute_drift`."""
+
+    def __init__(self, sigma_min=0.1, sigma_max=20.0):
+        self.sigma_min = sigma_min
+        self.sigma_max = sigma_max
+
+    def log_mean_coeff(self, t):
+        return -0.25 * ((1 - t) ** 2) * (self.sigma_max - self.sigma_min) - 0.5 * (1 - t) * self.sigma_min
+
+    def d_log_mean_coeff(self, t):
+        return 0.5 * (1 - t) * (self.sigma_max - self.sigma_min) + 0.5 * self.sigma_min
+
+    def compute_alpha_t(self, t):
+        alpha_t = th.exp(self.log_mean_coeff(t))
+        return alpha_t, alpha_t * self.d_log_mean_coeff(t)
+
+    def compute_sigma_t(self, t):
+        p_sigma_t = 2 * self.log_mean_coeff(t)
+        sigma_t = th.sqrt(1 - th.exp(p_sigma_t))
+        return sigma_t, th.exp(p_sigma_t) * (2 * self.d_log_mean_coeff(t)) / (-2 * sigma_t)
+
+    def compute_d_alpha_alpha_ratio_t(self, t):
+        return self.d_log_mean_coeff(t)
+
+    def compute_drift(self, x, t):
+        t = expand_t_like_x(t, x)
+        beta_t = self.sigma_min + (1 - t) * (self.sigma_max - self.sigma_min)
+        return -0.5 * beta_t * x, beta_t / 2
+
+
+class GVPCPlan(ICPlan):
+    """Trigonometric (generalised VP) path (path.py:174-192): alpha_t = sin(pi t / 2), sigma_t = cos(pi t / 2)."""
+
+    def compute_alpha_t(self, t):
+        return th.sin(t * np.pi / 2), np.pi / 2 * th.cos(t * np.pi / 2)
+
+    def compute_sigma_t(self, t):
+        return th.cos(t * np.pi / 2), -np.pi / 2 * th.sin(t * np.pi / 2)
+
+    def compute_d_alpha_alpha_ratio_t(self, t):
+        return np.pi / (2 * th.tan(t * np.pi / 2))
+
+
+_ALL_PATHS = False
+
+
+def enable_all_paths(on: bool = True) -> bool:
+    """Let `Transport` build the GVP and VP plans (off by default: only the Linear path, as the reference's scripts select it) -> the previous setting."""
+    global _ALL_PATHS
+    prev, _ALL_PATHS = _ALL_PATHS, bool(on)
+    return prev
+
+
+def model_terms(ps, model_type, te):
+    """The prologue scalars (kind, c0, dv, nsig) of a noise / score model at the CPU f32 time te [1, 1], from the path's own methods on the CPU:
+    v = c0 * x + dv * (m / nsig) (NOISE) or c0 * x + dv * m (SCORE) is the reference's (-drift_mean) + drift_var * score (transport.py:171-181).  drift_mean is
+    -(ratio * x) (Linear, GVP) or (-0.5 * beta_t) * x (VP), so at x = 1 its negation is c0 itself (a product with 1 and a negation are exact)."""
+    assert not te.is_cuda and te.dtype == th.float32
+    drift_mean, dv = ps.compute_drift(th.ones(1, 1), te.view(1))
+    nsig = -ps.compute_sigma_t(te)[0]
+    kind = {ModelType.NOISE: ops.MODEL_NOISE, ModelType.SCORE: ops.MODEL_SCORE}[model_type]
+    return kind, float(-drift_mean), float(dv), float(nsig)
+
+
 _RAND_RING = {}
 
 
@@ -159,14 +236,15 @@ def cpu_rand_like_batch(x1):
 
 
 class Transport:
-    """transport.py:39-221 for the Linear path."""
+    """transport.py:39-221."""
 
     def __init__(self, *, model_type, path_type, loss_type, train_eps, sample_eps, time_dist_shift=1.0):
-        if path_type != PathType.LINEAR:
-            raise NotImplementedError("only the Linear path (path.ICPlan) is built; the reference's scripts never select GVP / VP")
+        if path_type != PathType.LINEAR and not _ALL_PATHS:
+            raise NotImplementedError("only the Linear path (path.ICPlan) is built by default; the reference's scripts never select GVP / VP -- "
+                                      "dmvae_amd.transport.enable_all_paths() turns the GVP / VP plans on")
         self.loss_type = loss_type
         self.model_type = model_type
-        self.path_sampler = ICPlan()
+        self.path_sampler = {PathType.LINEAR: ICPlan, PathType.GVP: GVPCPlan, PathType.VP: VPCPlan}[path_type]()
         self.train_eps = train_eps
         self.sample_eps = sample_eps
         self.time_dist_shift = time_dist_shift
@@ -176,10 +254,12 @@ class Transport:
         return -n / 2.0 * np.log(2 * np.pi) - th.sum(z.flatten(1) ** 2, dim=1) / 2.0
 
     def check_interval(self, train_eps, sample_eps, *, diffusion_form="SBDM", sde=False, reverse=False, eval=False, last_step_size=0.0):
-        """transport.py:75-102 (ICPlan branch)."""
+        """transport.py:75-102."""
         t0, t1 = 0, 1
         eps = train_eps if not eval else sample_eps
-        if self.model_type != ModelType.VELOCITY or sde:
+        if type(self.path_sampler) is VPCPlan:
+            t1 = 1 - eps if (not sde or last_step_size == 0) else 1 - last_step_size
+        elif self.model_type != ModelType.VELOCITY or sde:
             t0 = eps if (diffusion_form == "SBDM" and sde) or self.model_type != ModelType.VELOCITY else 0
             t1 = 1 - eps if (not sde or last_step_size == 0) else 1 - last_step_size
         if reverse:
@@ -196,7 +276,8 @@ class Transport:
         return t, x0, x1
 
     def training_losses(self, model, x1, model_kwargs=None):
-        """transport.py:119-164: flow-matching loss per sample, `terms = {"pred", "loss"}`."""
+        """transport.py:119-164: flow-matching loss per sample, `terms = {"pred", "loss"}` -- the velocity MSE for every model type, as in the reference (its
+        per-model-type weights are commented out, transport.py:142-162; `loss_type` is kept and unused)."""
         if model_kwargs is None:
             model_kwargs = {}
         t, x0, x1 = self.sample(x1)
@@ -275,9 +356,10 @@ def _time_vector(n, t, like=None, device=None):
 class sde:
     """integrators.py:8-77.  `sampler_type` "Euler" (Euler-Maruyama) or "Heun".
 
-    With `fused` (set by `Sampler.sample_sde` for the Linear path with a velocity model) a step calls the model for the velocity and does the whole
+    With `fused` (set by `Sampler.sample_sde`) a step calls the model and does the whole
     update on csrc/sampler.hip -- Euler-Maruyama in `ops.sde_euler_step`, Heun in `ops.sde_heun_perturb` / `sde_heun_predict` / `sde_heun_correct` around its
-    two evaluations --; otherwise it evaluates the caller's `drift` / `diffusion` callables like the reference."""
+    two evaluations; for a noise / score model their `_m` forms, which convert the model's output to the velocity first (`model_terms`) --; otherwise it
+    evaluates the caller's `drift` / `diffusion` callables like the reference."""
 
     def __init__(self, drift, diffusion, *, t0, t1, num_steps, sampler_type, fused=None):
         assert t0 < t1, "SDE sampler has to be in forward time"
@@ -287,7 +369,7 @@ class sde:
         self.drift = drift
         self.diffusion = diffusion
         self.sampler_type = sampler_type
-        self.fused = fused                     # (path_sampler, diffusion_form, diffusion_norm) or None
+        self.fused = fused                     # (path_sampler, diffusion_form, diffusion_norm[, model_type = VELOCITY]) or None
 
     def _noise(self, x):
         """`th.randn(x.size()).to(x)` (integrators.py:28,38): drawn on the CPU generator like the reference.  For a device state the draw lands in one of
@@ -311,18 +393,30 @@ class sde:
 
     def _coeffs(self, ti):
         """The scalars of one fused step, computed in f32 the way the reference's broadcast graph computes them."""
-        ps, form, norm = self.fused
+        ps, form, norm = self.fused[:3]
         te = ti.view(1, 1)
         rar, var = ps._score_coeffs(te)
         diff = ps.compute_diffusion(te, te.view(1), form=form, norm=norm)
         diff = diff if th.is_tensor(diff) else th.tensor(float(diff), dtype=th.float32)
         return float(rar), float(var), float(diff), float(th.sqrt(2 * diff))
 
+    def _terms(self, ti):
+        """The prologue scalars of a noise / score model at the CPU f32 time ti (`model_terms`); None for a velocity model."""
+        mt = self.fused[3] if len(self.fused) > 3 else ModelType.VELOCITY
+        return None if mt == ModelType.VELOCITY else model_terms(self.fused[0], mt, ti.view(1, 1))
+
     def _fused_ok(self, x):
         return FUSED_STATE_UPDATE and self.fused is not None and x.is_cuda and x.dtype == th.float32
 
     def _euler_maruyama_step(self, x, mean_x, t, model, **model_kwargs):
         w_cur = self._noise(x)
+        terms = self._terms(t) if self._fused_ok(x) else None
+        if terms is not None:
+            m = model(x, _time_vector(x.size(0), t, x), **model_kwargs)
+            assert m.shape == x.shape, "Output shape from ODE solver must match input shape"
+            rar, var, diff, sq2d = self._coeffs(t)
+            return ops.sde_euler_step_m(x.contiguous(), m.contiguous(), terms, w_cur, rar, var, diff, float(self.dt), sq2d, float(th.sqrt(self.dt)),
+                                        need_mean=True)
         if self._fused_ok(x) and x.numel() % 4 == 0:
             tv = _time_vector(x.size(0), t, x)
             v = model(x, tv, **model_kwargs)
@@ -344,13 +438,18 @@ class sde:
             n, t2 = x.size(0), t + self.dt
             rar, var, diff, sq2d = self._coeffs(t)
             rar2, var2, diff2, _ = self._coeffs(t2)
+            terms, terms2 = self._terms(t), self._terms(t2)
             xhat = ops.sde_heun_perturb(x.contiguous(), w_cur, sq2d, float(th.sqrt(self.dt)))
             v1 = model(xhat, _time_vector(n, t, x), **model_kwargs)
             assert v1.shape == x.shape, "Output shape from ODE solver must match input shape"
-            k1, xp = ops.sde_heun_predict(xhat, v1.contiguous(), rar, var, diff, float(self.dt))      # v1 is consumed here: a graphed model reuses its output buffer
+            # v1 is consumed here: a graphed model reuses its output buffer
+            k1, xp = (ops.sde_heun_predict(xhat, v1.contiguous(), rar, var, diff, float(self.dt)) if terms is None else
+                      ops.sde_heun_predict_m(xhat, v1.contiguous(), terms, rar, var, diff, float(self.dt)))
             v2 = model(xp, _time_vector(n, t2, x), **model_kwargs)
             assert v2.shape == x.shape, "Output shape from ODE solver must match input shape"
-            return ops.sde_heun_correct(xhat, xp, k1, v2.contiguous(), rar2, var2, diff2, float(0.5 * self.dt)), xhat
+            if terms2 is None:
+                return ops.sde_heun_correct(xhat, xp, k1, v2.contiguous(), rar2, var2, diff2, float(0.5 * self.dt)), xhat
+            return ops.sde_heun_correct_m(xhat, xp, k1, v2.contiguous(), terms2, rar2, var2, diff2, float(0.5 * self.dt)), xhat
         dw = w_cur * th.sqrt(self.dt)
         t_cur = _time_vector(x.size(0), t, x)
         diffusion = self.diffusion(x, t_cur)
@@ -458,9 +557,9 @@ class _Dopri5:
     torchdiffeq's _mixed_norm -- the max over the parts of each part's RMS -- in the initial step and in the error ratio (one error-ratio launch pair per part,
     8 bytes read back per part and attempted step); the combine and dense-output kernels run on the whole buffer."""
 
-    def __init__(self, fn, y0, *, atol, rtol, fused, round_bf16, parts=None, batch=None, fn_into=None):
+    def __init__(self, fn, y0, *, atol, rtol, fused, round_bf16, parts=None, batch=None, fn_into=None, fn_into_t=None):
         self.fn, self.atol, self.rtol, self.fused, self.amp = fn, float(atol), float(rtol), fused, round_bf16
-        self.parts, self.fn_into = parts, fn_into
+        self.parts, self.fn_into, self.fn_into_t = parts, fn_into, fn_into_t      # fn_into_t(t32, tv, y, out): fn_into that also gets the host's f32 time
         self.batch = y0.size(0) if batch is None else batch
         self.nfe = 0
         self.k = [th.empty_like(y0) for _ in range(7)]      # f32, like torchdiffeq's k buffer: a bf16 model output is copied exactly
@@ -473,7 +572,9 @@ class _Dopri5:
     def f(self, t32, y, slot):
         """k[slot] = drift(t, y); t goes to the model as th.full (== th.ones(B).to(x) * t without a blocking host copy)."""
         tv = th.full((self.batch,), float(t32), device=y.device, dtype=y.dtype)
-        if self.fn_into is not None:
+        if self.fn_into_t is not None:
+            self.fn_into_t(t32, tv, y, self.k[slot])
+        elif self.fn_into is not None:
             self.fn_into(tv, y, self.k[slot])
         else:
             r = self.fn(tv, y)
@@ -606,9 +707,10 @@ class ode:
     integrated here, and anything else is delegated to torchdiffeq when it can be imported.  After a dopri5 call `nfe`, `n_accepted` and
     `n_rejected` hold its model evaluations and steps."""
 
-    def __init__(self, drift, *, t0, t1, sampler_type, num_steps, atol, rtol, time_dist_shift=1.0, max_num_steps=2 ** 31 - 1):
+    def __init__(self, drift, *, t0, t1, sampler_type, num_steps, atol, rtol, time_dist_shift=1.0, max_num_steps=2 ** 31 - 1, model_terms=None):
         assert t0 < t1, "ODE sampler has to be in forward time"
         self.drift = drift
+        self.model_terms = model_terms      # te (CPU f32 [1, 1]) -> (kind, c0, dv, nsig) when `drift` is Transport.get_drift of a noise / score model, else None
         t = th.linspace(t0, t1, num_steps)
         self.t = 1 - time_dist_shift * (1 - t) / (1 + (time_dist_shift - 1) * (1 - t))
         self.atol, self.rtol = atol, rtol
@@ -616,10 +718,20 @@ class ode:
         self.max_num_steps = max_num_steps      # dopri5: attempted steps allowed per output interval (torchdiffeq's max_num_steps)
         self.nfe = self.n_accepted = self.n_rejected = 0      # dopri5's counters of the last call
 
+    def _velocity_into(self, t32, tv, state, out, model, model_kwargs):
+        """out = the drift of a noise / score model at (state, t): one forward and one kernel, its scalars from the host's f32 time t32.  The model's keywords
+        come as a dict: the drivers pass the labels as `y`."""
+        m = model(state, tv, **model_kwargs)
+        assert m.shape == state.shape, "Output shape from ODE solver must match input shape"
+        return ops.model_velocity(state, m.contiguous(), self.model_terms(th.tensor(float(t32), dtype=th.float32).view(1, 1)), out=out)
+
     def _dopri5(self, x, model, **model_kwargs):
         """dopri5 on a CUDA f32 state; the output is stacked [num_steps, ...] like odeint's."""
+        into = None
+        if FUSED_STATE_UPDATE and self.model_terms is not None:      # k[slot] straight from the conversion kernel
+            into = lambda t32, tv, y, out: self._velocity_into(t32, tv, y, out, model, model_kwargs)
         solver = _Dopri5(lambda t, y: self.drift(y, t, model, **model_kwargs), x, atol=self.atol, rtol=self.rtol, fused=FUSED_STATE_UPDATE,
-                         round_bf16=th.is_autocast_enabled())
+                         round_bf16=th.is_autocast_enabled(), fn_into_t=into)
         try:
             with th.no_grad():
                 return solver.solve(x.contiguous(), self.t.double().tolist(), self.max_num_steps)
@@ -670,7 +782,7 @@ class ode:
             return self._dopri5_tuple(x, model, **model_kwargs)
         device = x[0].device if isinstance(x, tuple) else x.device
 
-        def fn(t, x):
+        def fn(t, x, tc=None):      # tc: the CPU twin of the device time t (the kernel route's scalars come from it)
             n = x[0].size(0) if isinstance(x, tuple) else x.size(0)
             return self.drift(x, _time_vector(n, t, device=device), model, **model_kwargs)
 
@@ -690,27 +802,33 @@ class ode:
             batch = x[0].size(0)
             x, _, unflat, fn_into = self._flat(x, model, **model_kwargs)      # elementwise methods: they run on the flat buffer as they stand
 
-            def fn(t, y):
+            def fn(t, y, tc=None):
                 out = th.empty_like(y)
                 fn_into(_time_vector(batch, t, device=device), y, out)
                 return out
+        elif FUSED_STATE_UPDATE and self.model_terms is not None and x.is_cuda and x.dtype == th.float32:
+            def fn(t, x, tc):       # a noise / score model: one forward and the conversion kernel; the model's time vector is filled from the host's number too
+                return self._velocity_into(tc, _time_vector(x.size(0), float(tc), device=device), x.contiguous(), None, model, model_kwargs)
         out = [x]
+        tc = self.t                 # the grid on the CPU: the kernel route takes its scalars AND the model's time vector from this twin (no device read; the device's
+                                    # own stage times, where a division by a Python number may be a multiplication by its reciprocal, are not used on that route)
         with th.no_grad():
             for i in range(t.numel() - 1):
                 t0, dt = t[i], t[i + 1] - t[i]
-                k1 = fn(t0, x)
+                c0, cdt = tc[i], tc[i + 1] - tc[i]
+                k1 = fn(t0, x, c0)
                 if self.sampler_type == "euler":
                     x = x + dt * k1
                 elif self.sampler_type == "midpoint":
-                    x = x + dt * fn(t0 + 0.5 * dt, x + 0.5 * dt * k1)
+                    x = x + dt * fn(t0 + 0.5 * dt, x + 0.5 * dt * k1, c0 + 0.5 * cdt)
                 elif self.sampler_type == "heun3":
-                    k2 = fn(t0 + dt / 3, x + dt * k1 / 3)
-                    k3 = fn(t0 + dt * 2 / 3, x + dt * k2 * (2 / 3))
+                    k2 = fn(t0 + dt / 3, x + dt * k1 / 3, c0 + cdt / 3)
+                    k3 = fn(t0 + dt * 2 / 3, x + dt * k2 * (2 / 3), c0 + cdt * 2 / 3)
                     x = x + dt * (0.25 * k1 + 0.75 * k3)
                 else:                                                    # rk4, 3/8 rule
-                    k2 = fn(t0 + dt / 3, x + dt * k1 / 3)
-                    k3 = fn(t0 + dt * 2 / 3, x + dt * (k2 - k1 / 3))
-                    k4 = fn(t0 + dt, x + dt * (k1 - k2 + k3))
+                    k2 = fn(t0 + dt / 3, x + dt * k1 / 3, c0 + cdt / 3)
+                    k3 = fn(t0 + dt * 2 / 3, x + dt * (k2 - k1 / 3), c0 + cdt * 2 / 3)
+                    k4 = fn(t0 + dt, x + dt * (k1 - k2 + k3), c0 + cdt)
                     x = x + dt * (k1 + 3 * (k2 + k3) + k4) * 0.125
                 out.append(x)
         return th.stack(out) if unflat is None else unflat(th.stack(out))
@@ -744,8 +862,15 @@ class Sampler:
         if last_step is None:
             return lambda x, t, model, **kw: x
         on_kernel = lambda x: FUSED_STATE_UPDATE and fused is not None and x.is_cuda and x.dtype == th.float32
+        mt = fused[3] if fused is not None and len(fused) > 3 else ModelType.VELOCITY
+        terms = None if mt == ModelType.VELOCITY else (lambda: model_terms(ps, mt, te))      # a noise / score model: the `_m` kernels take the model's output itself; formed on the kernel route only
         if last_step == "Mean":
             def mean_step(x, t, model, **kw):
+                if on_kernel(x) and terms is not None:
+                    rar, var = ps._score_coeffs(te)
+                    diff = float(ps.compute_diffusion(te, te.view(1), form=fused[1], norm=fused[2]))
+                    return ops.sde_euler_step_m(x.contiguous(), model(x, t, **kw).contiguous(), terms(), None, float(rar), float(var), diff, float(last_step_size),
+                                                0.0, 0.0)[0]
                 if on_kernel(x) and x.numel() % 4 == 0:
                     v = self.drift(x, t, model, **kw)
                     rar, var = ps._score_coeffs(te)
@@ -757,6 +882,10 @@ class Sampler:
             alpha, sigma = ps.compute_alpha_t, ps.compute_sigma_t
 
             def tweedie_step(x, t, model, **kw):
+                if on_kernel(x) and terms is not None:          # Transport.get_score: the model's own score, not the one converted from the velocity
+                    a = alpha(te)[0]
+                    return ops.sde_last_step_m(x.contiguous(), model(x, t, **kw).contiguous(), terms(), ops.LAST_STEP_TWEEDIE, a=float(a),
+                                               c=float((sigma(te)[0] ** 2) / a))
                 if on_kernel(x):
                     v = self.drift(x, t, model, **kw)
                     rar, var = ps._score_coeffs(te)
@@ -767,6 +896,8 @@ class Sampler:
             return tweedie_step
         if last_step == "Euler":
             def euler_step(x, t, model, **kw):
+                if on_kernel(x) and terms is not None:
+                    return ops.sde_last_step_m(x.contiguous(), model(x, t, **kw).contiguous(), terms(), ops.LAST_STEP_EULER, h=float(last_step_size))
                 if on_kernel(x):
                     return ops.sde_last_step(x.contiguous(), self.drift(x, t, model, **kw).contiguous(), ops.LAST_STEP_EULER, h=float(last_step_size))
                 return x + self.drift(x, t, model, **kw) * last_step_size
@@ -780,7 +911,7 @@ class Sampler:
         sde_drift, sde_diffusion = self._sde_diffusion_and_drift(diffusion_form=diffusion_form, diffusion_norm=diffusion_norm)
         t0, t1 = self.transport.check_interval(self.transport.train_eps, self.transport.sample_eps, diffusion_form=diffusion_form, sde=True, eval=True,
                                                reverse=False, last_step_size=last_step_size)
-        fused = (self.transport.path_sampler, diffusion_form, diffusion_norm) if self.transport.model_type == ModelType.VELOCITY else None
+        fused = (self.transport.path_sampler, diffusion_form, diffusion_norm, self.transport.model_type)
         _sde = sde(sde_drift, sde_diffusion, t0=t0, t1=t1, num_steps=num_steps, sampler_type=sampling_method, fused=fused)
         last_step_fn = self._last_step(sde_drift, last_step=last_step, last_step_size=last_step_size, t1=t1, fused=fused)
 
@@ -801,8 +932,11 @@ class Sampler:
             drift = self.drift
         t0, t1 = self.transport.check_interval(self.transport.train_eps, self.transport.sample_eps, sde=False, eval=True, reverse=reverse,
                                                last_step_size=0.0)
+        terms = None          # a noise / score model in forward time: the drift's conversion is one kernel per evaluation (ode._velocity_into)
+        if self.transport.model_type != ModelType.VELOCITY and not reverse:
+            terms = lambda te: model_terms(self.transport.path_sampler, self.transport.model_type, te)
         return ode(drift=drift, t0=t0, t1=t1, sampler_type=sampling_method, num_steps=num_steps, atol=atol, rtol=rtol,
-                   time_dist_shift=self.transport.time_dist_shift).sample
+                   time_dist_shift=self.transport.time_dist_shift, model_terms=terms).sample
 
     def sample_ode_likelihood(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3):
         """transport.py:402-459 -> `_sample_fn(x, model, **model_kwargs)` returning (logp [B], z): the probability-flow ODE from the data (model time 1) to the
@@ -811,7 +945,8 @@ class Sampler:
         The reference evaluates the model twice per drift call (once inside autograd.grad, once more for the drift itself); here the drift is the output of
         the forward whose graph gives the VJP (the same values: the second call repeats the first).  On a CUDA f32 state the (x, logp) tuple is one flat
         buffer (`ode._dopri5_tuple`) and each evaluation's stage value comes from one kernel (`ops.ode_hutchinson_pack`).  After a call `_sample_fn.ode` holds
-        the solver's `nfe`, `n_accepted` and `n_rejected`."""
+        the solver's `nfe`, `n_accepted` and `n_rejected`.  For a noise / score model the drift stays the tensor-op composition of `Transport.get_drift`:
+        autograd needs the VJP through the conversion."""
         drift_fn = self.drift
 
         def _vjp(x, t, model, **kw):

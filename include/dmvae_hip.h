@@ -831,6 +831,34 @@ int dmvae_sde_heun_correct(const void* xhat, const void* xp, const void* k1, con
 #define DMVAE_LAST_STEP_EULER 1
 int dmvae_sde_last_step(const void* x, const void* v, int v_is_bf16, void* out, size_t n, int mode, float a, float c, float rar, float var, float h,
                         dmvae_stream_t stream);
+/* Noise- and score-predicting models (ModelType.NOISE / SCORE, diffusion/transport/transport.py:171-181,202-216): the model's output m is converted to the
+ * velocity inside every pass that consumes it, at the state y the model was evaluated at,
+ *   DMVAE_MODEL_NOISE:  v = (c0 * y) + dv * (m / nsig)        DMVAE_MODEL_SCORE:  v = (c0 * y) + dv * m
+ * which is the reference's (-drift_mean) + drift_var * score with drift_mean = -(ratio * y): c0 = d_alpha / alpha, dv = drift_var and nsig = -sigma_t at the
+ * pass's time, formed by the host in f32 from the path's own methods (like every other coefficient here) and passed BY VALUE into the kernels.  m is bf16
+ * (m_is_bf16 != 0) or f32 and is widened first (it meets f32 [B, 1, 1, 1] coefficients in the reference's graph); v is f32.  No FMA contraction, IEEE divide.
+ * The _m entry points are the velocity ones above with this prologue (the same device bodies); every array [n], any n.  kind must be _NOISE or _SCORE. */
+#define DMVAE_MODEL_NOISE 1
+#define DMVAE_MODEL_SCORE 2
+typedef struct {
+  int32_t kind;
+  float c0, dv, nsig;
+} dmvae_model_terms;
+/* dmvae_sde_euler_step on m; w = NULL: x_out = mean (the "Mean" last step). */
+int dmvae_sde_euler_step_m(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, const void* w, void* x_out, void* mean_out, size_t n,
+                           float rar, float var, float diff, float dt, float sqrt_2diff, float sqrt_dt, dmvae_stream_t stream);
+/* dmvae_sde_heun_predict / _correct on m1 (converted at xhat, terms at t) and m2 (converted at xp, terms2 at t + dt). */
+int dmvae_sde_heun_predict_m(const void* xhat, const void* m1, int m_is_bf16, const dmvae_model_terms* terms, void* k1, void* xp, size_t n, float rar, float var,
+                             float diff, float dt, dmvae_stream_t stream);
+int dmvae_sde_heun_correct_m(const void* xhat, const void* xp, const void* k1, const void* m2, int m_is_bf16, const dmvae_model_terms* terms2, void* x_out, size_t n,
+                             float rar2, float var2, float diff2, float half_dt, dmvae_stream_t stream);
+/* The last steps on m.  DMVAE_LAST_STEP_TWEEDIE: out = x / a + c * s with Transport.get_score's s = m / nsig (NOISE, f32) or m (SCORE) -- not the score
+ * converted from the velocity; for SCORE with a bf16 m the product is a bf16 one, as a 0-d f32 tensor times a bf16 tensor is: bf16(f32(bf16(c)) * m), before it meets x / a.
+ * DMVAE_LAST_STEP_EULER: out = x + v * h with the f32 v above. */
+int dmvae_sde_last_step_m(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, void* out, size_t n, int mode, float a, float c, float h,
+                          dmvae_stream_t stream);
+/* out = v alone, f32: the probability-flow ODE's drift (Transport.get_drift) for the ODE samplers, written where the solver wants it. */
+int dmvae_model_velocity(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, void* out, size_t n, dmvae_stream_t stream);
 /* Autoguidance on two model outputs (LightningDiT.forward_with_autoguidance, diffusion/lightningdit/lightningdit.py:450-465), one launch: eps [n, c_eps, hw] is
  * this model's output and ag [n, c_ag, hw] the additional model's, both bf16 (is_bf16 != 0) or both f32; dst [2n, k, hw] of the same type, neither eps nor ag,
  * receives in BOTH halves the first k channels (k = in_channels; 0 < k <= c_eps, c_ag) of

@@ -21,7 +21,10 @@ variants on (`enable_syncbn_heads`): the scripts' default is `--disc_norm sbn`.
 The optimiser tail is an opt-in too: `--hip-optim` in front of the script path (in either order with `--hip-dinodisc`), DMVAE_HIP_OPTIM=1 or
 `install_shadow(ref, optim=True)` makes `torch.optim.AdamW` and `torch.nn.utils.clip_grad_norm_` this build's `dmvae_amd.optim.AdamW` / `clip_grad_norm_` for the
 process (train_tokenizer.py:382-383,415,424): multi-tensor HIP kernels over the scripts' own parameters.  Without it nothing in `torch` is touched.  The scripts'
-`update_ema` is defined in the scripts themselves and cannot be replaced from outside; `from dmvae_amd.optim import update_ema` is the one-line edit."""
+`update_ema` is defined in the scripts themselves and cannot be replaced from outside; `from dmvae_amd.optim import update_ema` is the one-line edit.
+
+The GVP / VP paths of `diffusion.transport` are off in the mirror by default (`dmvae_amd.transport.enable_all_paths`).  Running a script turns them on -- the
+script's own `--path_type` is the selection --; `--check` and a bare `install_shadow(ref)` leave the switch alone (`install_shadow(ref, all_paths=True)` asks)."""
 from __future__ import annotations
 
 import importlib
@@ -67,10 +70,11 @@ def install_optim() -> dict:
     return importlib.import_module("dmvae_amd.optim").install()
 
 
-def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False) -> dict:
+def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False, all_paths: bool = False) -> dict:
     """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve).
     dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them).
-    optim: also replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (`install_optim`; not part of the returned dict)."""
+    optim: also replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (`install_optim`; not part of the returned dict).
+    all_paths: also let the transport mirror build the GVP / VP plans (`dmvae_amd.transport.enable_all_paths`; default: left as it is)."""
     out = {}
     shadows = dict(SHADOWS)
     if dinodisc:
@@ -99,6 +103,8 @@ def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bo
     models.__getattr__ = _lazy
     if optim:
         install_optim()
+    if all_paths:
+        out["diffusion.transport"].enable_all_paths()
     return out
 
 
@@ -127,7 +133,7 @@ def main(argv) -> int:
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim)
+    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True)      # the script's --path_type selects
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])
