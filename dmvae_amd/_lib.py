@@ -254,6 +254,9 @@ SIGNATURES = {
     "dmvae_dino_tail_bwd_workspace": (c_size_t, [c_size_t, c_int]),
     "dmvae_dino_tail_bwd": (c_int, [c_void_p] * 8 + [c_size_t, c_size_t, c_int, c_void_p]),
     "dmvae_layerscale_bwd_dx": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    # FID: f64 feature statistics, bicubic resize + uint8 quantisation (csrc/fid.hip)
+    "dmvae_fid_accumulate": (c_int, [c_void_p, c_int, c_size_t, c_int, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "dmvae_fid_resize_u8": (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

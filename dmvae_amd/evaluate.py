@@ -1,4 +1,4 @@
-"""The tokenizer's `eval()` (train_tokenizer.py:324-367, train_dmd.py:419-461) without the FID: reconstruction PSNR and the latent statistics
+"""The tokenizer's `eval()` (train_tokenizer.py:324-367, train_dmd.py:419-461): the FID through the object passed as `fid`, reconstruction PSNR and the latent statistics
 `latent_mean` / `latent_scale` that the later stages normalise the latents with (`(z - latent_mean) * latent_scale`: train_dmd.py:525-526,
 train_diffusion.py:279-286, sample_50k.py:143-148; readme.md:31 quotes 0.0685 / 0.1763 for the released tokenizer).  `latent_stats(result)` turns the
 result into the keyword arguments of `train.DMDTrainer`, `train.DiffusionTrainer` and `sample.SamplePipeline`.
@@ -8,8 +8,10 @@ What is computed, exactly as the reference does (it is NOT the mean / std over t
 divided by the number of batches; PSNR per image on [0, 1]-scaled images (evaluation/metrics.py:6-13), summed over every rank's images and divided by
 `num_samples` -- the DATASET's size, as the reference divides, whatever the loaders delivered.  The model's `encode` / `decode` run the HIP path under
 autocast(bf16) like the reference's (`train_tokenizer.py:342`); the reductions are a handful of small device ops per batch, every 10 000 steps.
-FID needs torchmetrics' Inception weights, which neither the reference repo nor this image holds: `fid` takes any object with the
-reference's `update(images01, real: bool)` / `compute()` protocol (evaluation/fid.py:51-65) and is skipped when None."""
+`fid` takes any object with the reference's `update(images01, real: bool)` / `compute()` protocol (evaluation/fid.py:51-65) and is skipped when None.
+`dmvae_amd.fid.FID` is this package's: the 299-px resize, the quantisation and the f64 feature statistics on HIP kernels, the Frechet distance on the host.  The
+Inception network inside it is the caller's -- a module, or torchmetrics' through `FID(2048)` -- since neither the reference repo nor this package holds its
+weights (SURVEY.md 2.1 #11)."""
 from __future__ import annotations
 
 from typing import Iterable, Optional

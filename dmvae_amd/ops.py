@@ -2002,6 +2002,43 @@ def image_to_u8(y: torch.Tensor, channels: int, round_bf16: bool = False) -> tor
     return out
 
 
+# ---- FID (csrc/fid.hip) ---------------------------------------------------------------------------
+_FID_DTYPES = {f32: 0, bf16: 1, torch.float64: 2}
+
+
+def fid_accumulate(features: torch.Tensor, sum: torch.Tensor, cov_sum: torch.Tensor) -> None:
+    """In place: sum [F] += features.sum(0), cov_sum [F, F] += features^T features, f64 states, features [N, F] f32 / bf16 / f64 with unit stride along F (any
+    row pitch >= F: a column slice of a wider buffer is taken as it is).  Deterministic and exactly symmetric (include/dmvae_hip.h: dmvae_fid_accumulate)."""
+    if not features.is_cuda:
+        raise _lib.DmvaeHipError("features: expected a GPU tensor; dmvae_amd has no CPU path")
+    if features.dtype not in _FID_DTYPES:
+        raise TypeError(f"features: expected float32, bfloat16 or float64, got {features.dtype}")
+    if features.dim() != 2:
+        raise ValueError(f"features: expected [N, F], got {tuple(features.shape)}")
+    n, f = features.shape
+    if features.stride(1) != 1 or (n > 1 and features.stride(0) < f):
+        features = features.contiguous()
+    ld = features.stride(0) if n > 1 else f
+    _req(sum, torch.float64, "sum")
+    _req(cov_sum, torch.float64, "cov_sum")
+    if tuple(sum.shape) != (f,) or tuple(cov_sum.shape) != (f, f) or sum.device != features.device or cov_sum.device != features.device:
+        raise ValueError(f"fid_accumulate: states must be [{f}] and [{f}, {f}] on {features.device}, got {tuple(sum.shape)} and {tuple(cov_sum.shape)}")
+    check(_lib.lib().dmvae_fid_accumulate(features.data_ptr(), _FID_DTYPES[features.dtype], n, f, ld, sum.data_ptr(), cov_sum.data_ptr(), _stream()),
+          "fid_accumulate")
+
+
+def fid_resize_u8(images: torch.Tensor, size: int) -> torch.Tensor:
+    """images [B, C, H, W] f32 or bf16 in [0, 1] -> uint8 [B, C, size, size]: bicubic resize (skipped when H == W == size), * 255, clamp, truncation
+    (evaluation/fid.py:61-64 in one pass; include/dmvae_hip.h: dmvae_fid_resize_u8)."""
+    images = _req(images, bf16 if images.dtype == bf16 else f32, "images")
+    if images.dim() != 4 or images.numel() == 0:
+        raise ValueError(f"images: expected a non-empty [B, C, H, W], got {tuple(images.shape)}")
+    b, c, h, w_ = images.shape
+    out = torch.empty(b, c, int(size), int(size), dtype=torch.uint8, device=images.device)
+    check(_lib.lib().dmvae_fid_resize_u8(images.data_ptr(), int(images.dtype == bf16), b * c, h, w_, int(size), out.data_ptr(), _stream()), "fid_resize_u8")
+    return out
+
+
 # ---- losses ---------------------------------------------------------------------------------------
 def _loss_ws(device) -> torch.Tensor:
     return workspace(_lib.lib().dmvae_loss_workspace(), device, slot="loss")

@@ -1,5 +1,7 @@
 """The sampling loop of the reference's sample_50k.py (`sample`, :62-164) as a reusable pipeline: class labels split over ranks, noise -> SDE / ODE sampler
-on LightningDiT -> tokens -> `vae.decode` -> uint8 -> `"{index:06d}.png"`.  FID / Inception (torch_fidelity, :171-209) are evaluation and not built.
+on LightningDiT -> tokens -> `vae.decode` -> uint8 -> `"{index:06d}.png"`.  torch_fidelity's FID / Inception Score over the written folder
+(:171-209) are evaluation and not built here; `dmvae_amd.fid.FID` (resize, quantisation and f64 statistics on HIP kernels around an extractor the caller brings)
+is not fed from this loop.
 
 Device work per batch: `num_sampling_steps` DiT forwards on the HIP kernels + one fused state update each (transport.py), then the flux decoder forward and
 ONE conversion kernel to channels-last uint8 (`VAE.decode_uint8`), so the host receives 196 KB per image instead of the f32 NCHW tensor.  PNG encoding

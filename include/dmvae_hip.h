@@ -986,6 +986,23 @@ int dmvae_dino_bnact_bwd(const void* dy, const void* y, const void* gamma, const
 /* dy (bf16) = gamma * dt: layerscale_bwd without the parameter sum (a frozen block: models/dinodisc.py:123-125).  c % 8 == 0. */
 int dmvae_layerscale_bwd_dx(const void* dt, const void* gamma, void* dy, size_t rows, int c, dmvae_stream_t stream);
 
+/* ---- FID: the f64 feature statistics and the resize to the extractor's input (csrc/fid.hip) ---------------------------------------- */
+
+/* sum [f] += sum_n x[n][:], cov_sum [f][f] += x^T x, both f64, for features x [n][f] with row pitch ld (elements): x_dtype 0 f32, 1 bf16, 2 f64, every
+ * element converted to f64 exactly, products and sums in f64 (v_mfma_f64_16x16x4_f64).  One owner per element of the state, n walked in ascending order, no
+ * atomics and no split over n: the result depends on (x, previous state) only and repeats bit for bit; the grid depends on f alone.  The state is read from
+ * the upper triangle of cov_sum (diagonal included) and the owner stores the mirrored element too: cov_sum is exactly symmetric afterwards.  Rows past n and
+ * columns past f are never read.  f % 16 == 0, 16 <= f <= 4096, n >= 1, ld >= f; anything else returns -22 before any launch.
+ * Reference: torchmetrics' FrechetInceptionDistance.update under evaluation/fid.py:51-65 (`features.sum(dim=0)`, `features.t().mm(features)` on
+ * `features.double()`), whose states evaluation/fid.py:67-95 saves and loads. */
+int dmvae_fid_accumulate(const void* x, int x_dtype, size_t n, int f, size_t ld, void* sum, void* cov_sum, dmvae_stream_t stream);
+/* out [planes][s][s] uint8 from img [planes][h][w] f32 or bf16 (is_bf16 != 0), planes = B * C: F.interpolate(mode="bicubic") (align_corners False, no
+ * antialias: scale (float)h / (float)s in f32, source coordinate scale * (o + 0.5f) - 0.5f in f32, taps floor - 1 .. floor + 2 clamped to the edge, Keys'
+ * weights with A = -0.75, f32 accumulation, rows first), (x * 255).clamp(0, 255) and the truncation to uint8 in one pass.  A bf16 image is rounded where the
+ * three ops round: the interpolated value once, the product with 255 once.  h == s and w == s skips the interpolation and keeps the quantisation.  Any
+ * h, w, s >= 1; anything else returns -22 before any launch.  Reference: evaluation/fid.py:61-64. */
+int dmvae_fid_resize_u8(const void* img, int is_bf16, size_t planes, int h, int w, int s, void* out, dmvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@
     python run_on_mi355x.py --check            # print what is shadowed and exit
     python run_on_mi355x.py --hip-dinodisc /path/to/dmvae/train_tokenizer.py --disc_type dino ...      (or DMVAE_HIP_DINODISC=1)
     python run_on_mi355x.py --hip-optim /path/to/dmvae/train_tokenizer.py ...                          (or DMVAE_HIP_OPTIM=1)
+    python run_on_mi355x.py --hip-fid /path/to/dmvae/train_tokenizer.py ...                            (or DMVAE_HIP_FID=1)
 
 The reference's drivers import their model code by module path (`from models.vae import VAE`, `from utils.lpips import LPIPS`,
 `from diffusion.lightningdit.lightningdit import LightningDiT_models`, `from diffusion.transport import create_transport`; train_tokenizer.py:10-17,
@@ -22,6 +23,10 @@ The optimiser tail is an opt-in too: `--hip-optim` in front of the script path (
 `install_shadow(ref, optim=True)` makes `torch.optim.AdamW` and `torch.nn.utils.clip_grad_norm_` this build's `dmvae_amd.optim.AdamW` / `clip_grad_norm_` for the
 process (train_tokenizer.py:382-383,415,424): multi-tensor HIP kernels over the scripts' own parameters.  Without it nothing in `torch` is touched.  The scripts'
 `update_ema` is defined in the scripts themselves and cannot be replaced from outside; `from dmvae_amd.optim import update_ema` is the one-line edit.
+
+`evaluation.fid` (`from evaluation.fid import FID`, train_tokenizer.py:20, train_dmd.py:20) is an opt-in as well: `--hip-fid` in front of the script path (in any
+order with the other two), DMVAE_HIP_FID=1 or `install_shadow(ref, fid=True)` registers `dmvae_amd.fid` under that path: the resize and the f64 feature
+statistics on this build's kernels.  `FID()` as the scripts call it (feature=2048) still needs torchmetrics for the Inception network itself.
 
 The GVP / VP paths of `diffusion.transport` are off in the mirror by default (`dmvae_amd.transport.enable_all_paths`).  Running a script turns them on -- the
 script's own `--path_type` is the selection --; `--check` and a bare `install_shadow(ref)` leave the switch alone (`install_shadow(ref, all_paths=True)` asks)."""
@@ -70,15 +75,18 @@ def install_optim() -> dict:
     return importlib.import_module("dmvae_amd.optim").install()
 
 
-def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False, all_paths: bool = False) -> dict:
+def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False, all_paths: bool = False, fid: bool = False) -> dict:
     """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve).
     dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them).
     optim: also replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (`install_optim`; not part of the returned dict).
-    all_paths: also let the transport mirror build the GVP / VP plans (`dmvae_amd.transport.enable_all_paths`; default: left as it is)."""
+    all_paths: also let the transport mirror build the GVP / VP plans (`dmvae_amd.transport.enable_all_paths`; default: left as it is).
+    fid: also shadow evaluation.fid with this build's `dmvae_amd.fid` (default: the reference's own file serves it)."""
     out = {}
     shadows = dict(SHADOWS)
     if dinodisc:
         shadows["models.dinodisc"] = "dmvae_amd.models.dinodisc"           # DinoDisc                          (models/dinodisc.py)
+    if fid:
+        shadows["evaluation.fid"] = "dmvae_amd.fid"                        # FID                               (evaluation/fid.py)
     for path, target in shadows.items():
         parts = path.split(".")
         for i in range(1, len(parts)):
@@ -114,9 +122,12 @@ def main(argv) -> int:
         return 0
     hip_dinodisc = os.environ.get("DMVAE_HIP_DINODISC", "0") not in ("", "0")
     hip_optim = importlib.import_module("dmvae_amd.optim").requested()      # DMVAE_HIP_OPTIM=1
-    while argv and argv[0] in ("--hip-dinodisc", "--hip-optim"):
+    hip_fid = os.environ.get("DMVAE_HIP_FID", "0") not in ("", "0")
+    while argv and argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid"):
         if argv[0] == "--hip-dinodisc":
             hip_dinodisc = True
+        elif argv[0] == "--hip-fid":
+            hip_fid = True
         else:
             hip_optim = True
         argv = argv[1:]
@@ -125,7 +136,7 @@ def main(argv) -> int:
         return 0
     if argv[0] == "--check":
         ref = argv[1] if len(argv) > 1 else None
-        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc).items():
+        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid).items():
             print(f"{path:40s} -> {mod.__name__}")
         if hip_optim:
             for path, obj in install_optim().items():
@@ -133,7 +144,7 @@ def main(argv) -> int:
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True)      # the script's --path_type selects
+    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid)      # the script's --path_type selects
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])
