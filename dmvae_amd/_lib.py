@@ -42,6 +42,10 @@ class ModelTerms(Structure):
     _fields_ = [("kind", c_int32), ("c0", c_float), ("dv", c_float), ("nsig", c_float)]
 
 
+IMAGE_RECORD_WORDS = 12                     # DMVAE_IMAGE_RECORD_WORDS (include/dmvae_hip.h): int64 words of one image's record of dmvae_image_preprocess
+IMAGE_OUT_U8_NHWC, IMAGE_OUT_F32_NCHW = 0, 1
+
+
 ABI_VERSION = 9     # 9: nine retired entry points removed (the two-kernel split-K, the NULL-lse attention aliases, ...); 8: dmvae_reparam_kl_*, dmvae_linear_bf16_sk*, the f32 transformer steps of csrc/parity_dit.hip; 7: dmvae_linear_wgrad_grouped_plan / _xcd, dmvae_conv_k4c1_*; 6: dmvae_dit_stack_* / dmvae_dit_boundary_bwd / batched rows Linears / batched weight transposes; 5: dmvae_groupnorm_*_short; include/dmvae_hip.h: dmvae_abi_version (3: struct dmvae_pack_entry, dmvae_pack_weights_batched, dmvae_linear_bf16*; 4: dmvae_norm_conv_out_bwd*)
 
 # name -> (restype, argtypes); every symbol include/dmvae_hip.h declares
@@ -257,6 +261,10 @@ SIGNATURES = {
     # FID: f64 feature statistics, bicubic resize + uint8 quantisation (csrc/fid.hip)
     "dmvae_fid_accumulate": (c_int, [c_void_p, c_int, c_size_t, c_int, c_size_t, c_void_p, c_void_p, c_void_p]),
     "dmvae_fid_resize_u8": (c_int, [c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_void_p, c_void_p]),
+    # input pipeline: PIL-exact Lanczos tables (host) and resize + crop + flip + float conversion (csrc/data.hip)
+    "dmvae_lanczos_kmax": (c_int, [c_int, c_int]),
+    "dmvae_lanczos_table": (c_int, [c_int] * 5 + [c_void_p] * 3),
+    "dmvae_image_preprocess": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

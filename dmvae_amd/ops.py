@@ -2039,6 +2039,64 @@ def fid_resize_u8(images: torch.Tensor, size: int) -> torch.Tensor:
     return out
 
 
+# ---- input pipeline (csrc/data.hip) ---------------------------------------------------------------
+def lanczos_kmax(n_in: int, n_out: int) -> int:
+    """Taps allotted per output index for a LANCZOS resize of one axis from n_in to n_out samples (PIL's ksize).  Host only."""
+    k = _lib.lib().dmvae_lanczos_kmax(int(n_in), int(n_out))
+    if k < 0:
+        raise ValueError(f"lanczos_kmax: n_in >= 1 and n_out >= 1 required, got {n_in} -> {n_out}")
+    return k
+
+
+def lanczos_table(n_in: int, n_out: int, first: int = 0, count: Optional[int] = None, kmax: Optional[int] = None):
+    """PIL's 8-bit LANCZOS coefficients of the output indices first .. first + count - 1 of an axis resized from n_in to n_out samples -> int32 CPU tensors
+    (lo [count], n [count], k [count, kmax]).  Built on the host by the library (libm sin, as PIL; include/dmvae_hip.h: dmvae_lanczos_table); no GPU."""
+    n_in, n_out, first = int(n_in), int(n_out), int(first)
+    count = n_out - first if count is None else int(count)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"lanczos_table: n_in >= 1 and n_out >= 1 required, got {n_in} -> {n_out}")
+    if count < 1 or first < 0 or first + count > n_out:
+        raise ValueError(f"lanczos_table: window [{first}, {first} + {count}) outside [0, {n_out})")
+    kmax = lanczos_kmax(n_in, n_out) if kmax is None else int(kmax)
+    lo = torch.empty(count, dtype=torch.int32)
+    n = torch.empty(count, dtype=torch.int32)
+    k = torch.empty(count, max(kmax, 0), dtype=torch.int32)
+    check(_lib.lib().dmvae_lanczos_table(n_in, n_out, first, count, kmax, lo.data_ptr(), n.data_ptr(), k.data_ptr()), "lanczos_table")
+    return lo, n, k
+
+
+def image_preprocess(pack: torch.Tensor, table: torch.Tensor, taps: torch.Tensor, size: int, out: str = "f32",
+                     into: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pack: uint8 1-D (decoded HWC RGB images back to back, any offsets); table [B, 12] int64 records and taps int32 1-D, both on the pack's device
+    (include/dmvae_hip.h: dmvae_image_preprocess; dmvae_amd/data.py builds them) -> crop(resize(flip(image))) of every image, PIL's bytes:
+    out "u8" [B, size, size, 3] uint8, "f32" [B, 3, size, size] float32 = ToTensor then x + x - 1.  `into`: a contiguous tensor of that shape and dtype to
+    write to (default: a new one).  The records are on the device and are NOT checked here: `DeviceInputPipeline.tables` validates sizes, crop corners and
+    offsets on the host before it uploads them, and is the supported way to build them."""
+    pack = _req(pack, torch.uint8, "pack")
+    table = _req(table, torch.int64, "table")
+    taps = _req(taps, torch.int32, "taps")
+    if out not in ("f32", "u8"):
+        raise ValueError(f"out: expected 'f32' or 'u8', got {out!r}")
+    if pack.dim() != 1 or taps.dim() != 1 or table.dim() != 2 or table.shape[1] != _lib.IMAGE_RECORD_WORDS or table.shape[0] < 1:
+        raise ValueError(f"image_preprocess: expected pack [bytes], table [B, {_lib.IMAGE_RECORD_WORDS}], taps [n], got {tuple(pack.shape)}, "
+                         f"{tuple(table.shape)}, {tuple(taps.shape)}")
+    if table.device != pack.device or taps.device != pack.device:
+        raise ValueError(f"image_preprocess: table and taps must be on {pack.device}, got {table.device} and {taps.device}")
+    b, s = table.shape[0], int(size)
+    if s < 1:
+        raise ValueError(f"size: expected >= 1, got {size}")
+    shape, dtype = ((b, 3, s, s), f32) if out == "f32" else ((b, s, s, 3), torch.uint8)
+    if into is None:
+        res = torch.empty(shape, dtype=dtype, device=pack.device)
+    else:
+        res = _req(into, dtype, "into")
+        if tuple(res.shape) != shape or res.device != pack.device:
+            raise ValueError(f"into: expected {shape} on {pack.device}, got {tuple(res.shape)} on {res.device}")
+    check(_lib.lib().dmvae_image_preprocess(pack.data_ptr(), table.data_ptr(), taps.data_ptr() if taps.numel() else None, b, s, res.data_ptr(),
+                                            _lib.IMAGE_OUT_F32_NCHW if out == "f32" else _lib.IMAGE_OUT_U8_NHWC, _stream()), "image_preprocess")
+    return res
+
+
 # ---- losses ---------------------------------------------------------------------------------------
 def _loss_ws(device) -> torch.Tensor:
     return workspace(_lib.lib().dmvae_loss_workspace(), device, slot="loss")

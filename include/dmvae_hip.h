@@ -1003,6 +1003,37 @@ int dmvae_fid_accumulate(const void* x, int x_dtype, size_t n, int f, size_t ld,
  * h, w, s >= 1; anything else returns -22 before any launch.  Reference: evaluation/fid.py:61-64. */
 int dmvae_fid_resize_u8(const void* img, int is_bf16, size_t planes, int h, int w, int s, void* out, dmvae_stream_t stream);
 
+/* ---- input pipeline: PIL-exact Lanczos resize, crop, flip and float conversion of decoded uint8 images (csrc/data.hip) ---------------------- */
+
+#define DMVAE_IMAGE_OUT_U8_NHWC 0  /* [B][S][S][3] uint8 */
+#define DMVAE_IMAGE_OUT_F32_NCHW 1 /* [B][3][S][S] f32 = (u / 255) * 2 - 1 as ToTensor and x + x - 1 round it */
+/* int64 words of one image's record in dmvae_image_preprocess's table: 0 byte offset of the image in the pack, 1 H, 2 W (the decoded size), 3 H', 4 W' (the
+ * resized size: carried for the caller's bookkeeping, the kernel does not read words 3 and 4 -- the tables already embody them), 5 top, 6 left (the crop's corner in the resized image), 7 flip (0 / 1), 8 / 9 the offsets (in int32 elements of `taps`) of its x- and y-tap
+ * tables, -1 for a pass that is skipped (W' == W, H' == H), 10 / 11 the kmax (row pitch of k) of the x and y tables. */
+#define DMVAE_IMAGE_RECORD_WORDS 12
+
+/* The kmax (taps allotted per output index) dmvae_lanczos_table needs for a resize of one axis from `in` to `out` samples: PIL's ksize,
+ * 2 * ceil(3 * max(in / out, 1)) + 1.  No GPU.  -22 for in < 1 or out < 1.  Reference: the LANCZOS Resize of utils/build_dataset.py:57,61. */
+int dmvae_lanczos_kmax(int in, int out);
+/* PIL's 8-bit LANCZOS coefficients (libImaging/Resample.c: precompute_coeffs + normalize_coeffs_8bpc) of the output indices first .. first + count - 1 of an
+ * axis resized from `in` to `out` samples, on the HOST (plain C++, libm sin, no GPU): lo[i] the first source index, n[i] the tap count, k[i * kmax + j] the
+ * 22-bit fixed-point coefficient of source index lo[i] + j (zero for j >= n[i]).  scale = in / out, fs = max(scale, 1), support = 3 fs, center =
+ * (i + 0.5) scale, lo = max((int)(center - support + 0.5), 0), n = min((int)(center + support + 0.5), in) - lo, w_j = lanczos3((j + lo - center + 0.5) *
+ * (1 / fs)) summed left to right in double and divided by the sum, k_j = (int)(w * 2^22 +- 0.5).  Only the `count` entries are built (the crop window).
+ * -22 on NULL pointers, in < 1, out < 1, count < 1, first < 0, first + count > out, kmax < dmvae_lanczos_kmax(in, out).
+ * Reference: utils/build_dataset.py:57,61 (transforms.Resize(mid_reso, interpolation=LANCZOS) on a PIL image). */
+int dmvae_lanczos_table(int in, int out, int first, int count, int kmax, int32_t* lo, int32_t* n, int32_t* k);
+/* out = crop(resize(flip(image))) for each of the B images of a ragged pack, as transforms.RandomHorizontalFlip, Resize(mid, LANCZOS), RandomCrop /
+ * CenterCrop (and, for DMVAE_IMAGE_OUT_F32_NCHW, ToTensor and x + x - 1) compute it on PIL images, byte for byte: each pass is
+ * clamp((2^21 + sum_j k_j * pixel_j) >> 22, 0, 255) in int32, horizontal first, the horizontal result rounded to uint8 before the vertical pass, a pass whose
+ * in == out skipped.  pack: uint8, image b is [H][W][3] RGB at its record's byte offset (any offset, no alignment, no padding needed: no byte outside
+ * [offset, offset + 3 H W) is read).  table: device, [B][DMVAE_IMAGE_RECORD_WORDS] int64.  taps: device int32; an axis' table (built with first = left or
+ * top, count = S) is lo[S], n[S], k[S][kmax] at its offset; may be NULL when every pass of every image is skipped.  The records are trusted: the caller
+ * guarantees S <= H', S <= W', 0 <= top <= H' - S, 0 <= left <= W' - S and tables that match.  One launch, no workspace, no atomics; the result depends on
+ * the record alone, not on an image's place in the pack.  1 <= B <= 65535, 1 <= S <= 16384; anything else returns -22 before any launch.
+ * Reference: utils/build_dataset.py:55-66. */
+int dmvae_image_preprocess(const uint8_t* pack, const int64_t* table, const int32_t* taps, int B, int S, void* out, int out_kind, dmvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
