@@ -9,6 +9,8 @@
 //   gated_residual   : x += bf16( gate[b] * y )
 //
 // All HBM-bound single passes with 8- or 16-byte accesses.  GEMMs go through the library, attention through the batched GEMM + softmax kernels.
+// Tests: tests/test_gpu_dit_forms.py launches every instantiation below (both channel-per-lane forms at each SW, both RMSNorm backward routes, the generic and the
+// 16-lane QK kernels, the grid-stride loops past their caps) against tests/dit_kernels_spec.py; tests/test_gpu_dit.py runs the model widths 128 .. 2048.
 #include "common.h"
 #include <cstdlib>
 #include <type_traits>
