@@ -164,6 +164,16 @@ SIGNATURES = {
     "dmvae_qknorm_rope_bwd_nblk": (c_int, [c_int] * 5),
     "dmvae_qknorm_rope_bwd_partial": (c_int, [c_void_p] * 10 + [c_size_t] + [c_int] * 5 + [c_float, c_void_p]),
     "dmvae_qknorm_rope_bwd_dx": (c_int, [c_void_p] * 9 + [c_int] * 5 + [c_float, c_void_p]),
+    # LightningDiT block variants (csrc/dit_variants.hip)
+    "dmvae_layernorm_modulate_bf16": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_float, c_void_p]),
+    "dmvae_gated_residual_layernorm_modulate": (c_int, [c_void_p] * 4 + [c_int] * 2 + [c_void_p] * 2 + [c_int] * 6 + [c_float, c_void_p]),
+    "dmvae_layernorm_modulate_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "dmvae_layernorm_modulate_bwd": (c_int, [c_void_p] * 6 + [c_size_t] + [c_int] * 6 + [c_float, c_void_p]),
+    "dmvae_head_split_bf16": (c_int, [c_void_p] * 8 + [c_int] * 7 + [c_float, c_void_p]),
+    "dmvae_head_split_bwd_nblk": (c_int, [c_int] * 3),
+    "dmvae_head_split_bwd": (c_int, [c_void_p] * 12 + [c_size_t] + [c_int] * 7 + [c_float, c_int, c_void_p]),
+    "dmvae_gelu_tanh_fwd": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dmvae_gelu_tanh_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dmvae_dit_stack_bps": (c_int, [c_int]),
     "dmvae_dit_stack_part_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dmvae_dit_stack_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),

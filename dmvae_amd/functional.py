@@ -1488,6 +1488,128 @@ class DitBlockFn(torch.autograd.Function):
         return (dt, dmod.to(mod.dtype), dn1w, dqkvw, dqkvb, dqnw, dknw, dpw, dpb, dn2w, dw12, db12, dw3, db3, None, None, None, None)
 
 
+def dit_mod_offsets(c: int, wo_shift: bool):
+    """Element offsets of (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp) inside a block's adaLN row (lightningdit.py:243-248); -1: the chunk
+    does not exist (`wo_shift`: four chunks scale_msa | gate_msa | scale_mlp | gate_mlp, stride 4C)."""
+    return (-1, 0, c, -1, 2 * c, 3 * c) if wo_shift else (0, c, 2 * c, 3 * c, 4 * c, 5 * c)
+
+
+class DitBlockVarFn(torch.autograd.Function):
+    """`DitBlockFn` for the block VARIANTS (lightningdit.py:183-252 with the constructor's switches away from their defaults), one node per block on the f32 residual
+    stream.  Absent parameters are None and pick the branch: n1w / n2w None -> affine-free LayerNorm (csrc/dit_variants.hip) instead of RMSNorm; qnw / knw None -> no
+    QK-norm; cos / sin None -> no RoPE; `swiglu` False -> fc1, tanh-GELU, fc2 (f1 = fc1, f2 = fc2; else f1 = w12, f2 = w3); `wo_shift` -> the 4-chunk adaLN row.
+    With no parameter needing a gradient (frozen weights: the likelihood sampler's input-VJP) the backward computes d h and d mod only."""
+
+    @staticmethod
+    def forward(ctx, h, mod, n1w, qkvw, qkvb, qnw, knw, pw, pb, n2w, f1w, f1b, f2w, f2b, cos, sin, heads, eps, wo_shift, swiglu):
+        b, n, c = h.shape
+        d = c // heads
+        mod = _c(mod)
+        sh1, sc1, g1, sh2, sc2, g2 = dit_mod_offsets(c, wo_shift)
+        a1 = ops.rmsnorm_modulate(h, n1w, mod, sh1, sc1, eps) if n1w is not None else ops.layernorm_modulate(h, mod, sh1, sc1, eps)
+        qkv = linear(a1, qkvw, qkvb)
+        if qnw is not None and cos is not None:
+            q, k, v = ops.qknorm_rope(qkv, qnw, knw, cos, sin, heads, eps)
+        else:
+            q, k, v = ops.head_split(qkv, heads, qnw, knw, cos, sin, eps)
+        fused = ops.attention_heads_supported(n, d)
+        lse = p = None
+        if fused:
+            if n > ops.ATTENTION_RESIDENT_MAX:      # the streaming kernels: the backward rebuilds the probabilities from the forward's row statistics
+                o, lse = ops.attention_heads(q, k, v, b, d ** -0.5, need_lse=True)
+            else:
+                o = ops.attention_heads(q, k, v, b, d ** -0.5)
+        else:
+            p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), d ** -0.5)
+            o = ops.gemm_nt(p, ops.transpose_last2(v)).view(b, heads, n, d).permute(0, 2, 1, 3).reshape(b, n, c)
+        o2 = linear(o, pw, pb)
+        if n2w is not None:
+            h_mid, a2 = ops.gated_residual_out(h, o2, mod, g1, n2w, mod, sh2, sc2, eps)
+        else:
+            h_mid, a2 = ops.gated_residual_layernorm_out(h, o2, mod, g1, mod, sh2, sc2, eps)
+        if swiglu:
+            x1, g = linear_swiglu(a2, f1w, f1b)
+        else:
+            x1 = _c(linear(a2, f1w, f1b))
+            g = ops.gelu_tanh(x1)
+        o3 = linear(g, f2w, f2b)
+        h_out, _ = ops.gated_residual_out(h_mid, o3, mod, g2)
+        ctx.save_for_backward(h, mod, a1, qkv, q, k, v, p, o, o2, h_mid, a2, x1, g, o3, n1w, qkvw, qnw, knw, pw, n2w, f1w, f2w, cos, sin)
+        ctx.others = (qkvb, pb, f1b, f2b, heads, eps, wo_shift, swiglu, fused, lse)
+        return h_out
+
+    @staticmethod
+    def backward(ctx, dh_out):
+        import torch.nn.functional as F
+        h, mod, a1, qkv, q, k, v, p, o, o2, h_mid, a2, x1, g, o3, n1w, qkvw, qnw, knw, pw, n2w, f1w, f2w, cos, sin = ctx.saved_tensors
+        qkvb, pb, f1b, f2b, heads, eps, wo_shift, swiglu, fused, lse = ctx.others
+        b, n, c = h.shape
+        d, rows = c // heads, b * n
+        dp_ = q.shape[-1]
+        sh1, sc1, g1, sh2, sc2, g2 = dit_mod_offsets(c, wo_shift)
+        need_w = any(ctx.needs_input_grad[2:14])
+        dt = dh_out.float().clone()                                 # becomes d(h_mid), then d(h)
+        dmod = torch.zeros(b, mod.shape[1], dtype=f32, device=h.device)
+
+        def norm_bwd(da, x, w, sh, sc):
+            if w is None:
+                ops.layernorm_modulate_bwd_(dt, da, x, mod, dmod, sh, sc, eps)
+                return None
+            dw = ops.rmsnorm_modulate_bwd_(dt, da, x, w, mod, dmod, sh, sc, eps, dw_out=_dst(w) if need_w else None)
+            return dw if need_w else None
+        # MLP branch
+        do3 = ops.gated_residual_bwd(dt, o3, mod, dmod, g2)
+        dg, df2w, df2b = _lin_grads(do3.view(rows, c), g.view(rows, -1), f2w, f2b, need_w=need_w)
+        dx1 = ops.swiglu_bwd(dg.view_as(g), x1) if swiglu else ops.gelu_tanh_bwd(_c(dg).view_as(x1), x1)
+        da2, df1w, df1b = _lin_grads(dx1.view(rows, -1), a2.view(rows, c), f1w, f1b, need_w=need_w)
+        dn2w = norm_bwd(da2.view(b, n, c), h_mid, n2w, sh2, sc2)
+        # attention branch
+        do2 = ops.gated_residual_bwd(dt, o2, mod, dmod, g1)
+        do, dpw, dpb = _lin_grads(do2.view(rows, c), o.view(rows, c), pw, pb, need_w=need_w)
+        if fused:
+            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=lse)
+        else:
+            do_h = do.view(b, n, heads, d).permute(0, 2, 1, 3).reshape(b * heads, n, d)
+            pad = dp_ - d                                                   # head dim padded to the GEMM kernel's 32-wide K step
+            do_p, v_p = (F.pad(do_h, (0, pad)), F.pad(v, (0, pad))) if pad else (do_h.contiguous(), v)
+            ds = ops.softmax_rows_bwd(ops.gemm_nt(do_p, v_p, out_f32=True), p, d ** -0.5)
+            dv = ops.gemm_tn(p, do_h.contiguous())                          # [B*H, key, D]
+            dq = ops.gemm_nt(ds, ops.transpose_last2(k))                    # [B*H, N, Dp]
+            dk = ops.gemm_tn(ds, q)
+        if qnw is not None and cos is not None:     # the default's head split (a `wo_shift` / LayerNorm / GELU variant around it): its own backward
+            dqkv, dqnw, dknw = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, heads, eps, dqw_out=_dst(qnw) if need_w else None,
+                                                   dkw_out=_dst(knw) if need_w else None)
+            if not need_w:
+                dqnw = dknw = None
+        else:
+            dqkv, dqnw, dknw = ops.head_split_bwd(dq, dk, dv, qkv, heads, qnw, knw, cos, sin, eps, need_w=need_w, dqw_out=_dst(qnw) if need_w else None,
+                                                  dkw_out=_dst(knw) if need_w else None)
+        da1, dqkvw, dqkvb = _lin_grads(dqkv.view(rows, 3 * c), a1.view(rows, c), qkvw, qkvb, need_w=need_w)
+        dn1w = norm_bwd(da1.view(b, n, c), h, n1w, sh1, sc1)
+        return (dt, dmod.to(mod.dtype), dn1w, dqkvw, dqkvb, dqnw, dknw, dpw, dpb, dn2w, df1w, df1b, df2w, df2b) + (None,) * 6
+
+
+class LayernormModulateFn(torch.autograd.Function):
+    """bf16( LayerNorm(h; no affine) * bf16(1 + scale) + shift ) with gradients to h and the adaLN chunks: `RmsnormModulateFn`'s twin for use_rmsnorm=False
+    (FinalLayer, lightningdit.py:260-273)."""
+
+    @staticmethod
+    def forward(ctx, h, mod, shift_off, scale_off, eps):
+        mod = _c(mod)
+        ctx.save_for_backward(h, mod)
+        ctx.cfg = (shift_off, scale_off, eps)
+        return ops.layernorm_modulate(h, mod, shift_off, scale_off, eps)
+
+    @staticmethod
+    def backward(ctx, da):
+        h, mod = ctx.saved_tensors
+        shift_off, scale_off, eps = ctx.cfg
+        dt = torch.zeros_like(h)
+        dmod = torch.zeros(mod.shape, dtype=f32, device=h.device)
+        ops.layernorm_modulate_bwd_(dt, _c(da).to(bf16), h, mod, dmod, shift_off, scale_off, eps)
+        return dt, dmod.to(mod.dtype), None, None, None
+
+
 # gradient tensors this build's backward Functions created and handed to autograd for the f32 residual stream: the next Function down the chain may update such a
 # tensor in place instead of cloning it (nobody else holds it: autograd's input buffer passes a single incoming gradient through as it is).  A strong reference is
 # kept until the tensor is taken, so its address cannot be reused by another tensor in between; cleared at the start of every training forward.

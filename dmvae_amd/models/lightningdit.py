@@ -9,6 +9,8 @@ Two routes through `forward`:
     residual on HIP kernels (csrc/dit.hip), GEMMs through the library, attention on the conv kernel's batched-GEMM path;
   * gradients needed (the student's own training turn, train_dmd.py:565-575) on such a GPU shape -> `lightningdit_fast.forward_train`: one autograd
     Function per block (`functional.DitBlockFn`) over the same kernels and their backward counterparts;
+  * the constructor's block switches away from their defaults (LayerNorm, `wo_shift`, GELU-MLP, no RoPE, no QK-norm) take the same two routes on the kernels of
+    csrc/dit_variants.hip (`lightningdit_fast.variant_supported`); only use_qknorm=True with use_rmsnorm=False is refused;
   * otherwise (CPU, no autocast, unusual shapes) -> the stock PyTorch modules below, which also define the parameters.
 SURVEY.md 8(f) rank 3."""
 from __future__ import annotations
@@ -300,8 +302,7 @@ class LightningDiT(nn.Module):
                     # passes then skip every parameter-gradient computation (functional.DitStackFn._input_grad, LinearFn / RmsnormModulateFn dx-only)
                     return lightningdit_fast.forward_train(self, x, t, y)
                 return lightningdit_fast.forward_inference(self, x, t, y)
-            why = ("call outside autocast(bfloat16) or a configuration the DiT kernels do not cover (RoPE + RMSNorm + SwiGLU blocks, width <= 2048, "
-                   "even head dim <= 128, tokens a multiple of 32)")
+            why = lightningdit_fast.refused_reason(self)
         else:
             why = "CPU tensor"
         from .._stock import require_opt_in

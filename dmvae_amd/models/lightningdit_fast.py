@@ -6,7 +6,12 @@ csrc/dit.hip); per block: 1 fused (gated residual +) RMSNorm+modulate, qkv GEMM,
 alike: the staged head dim pads to 96; beyond 288 tokens QK-norm + RoPE as their own kernel and the streaming-softmax kernel of csrc/attention_stream.hip -- nothing N x N in
 HBM at any token count; other head dims beyond 288 tokens: composed batched QK^T GEMM / f32 softmax / PV GEMM), proj GEMM, 1 gated residual, RMSNorm+modulate, w12 GEMM, SwiGLU gate, w3 GEMM,
 gated residual -- every token-level Linear on this build's GEMM kernel (`functional.linear`: csrc/gemm_pp.hip).
-The per-sample pieces (timestep / label embedding, adaLN Linear: one row per sample) stay stock PyTorch under autocast."""
+The per-sample pieces (timestep / label embedding, adaLN Linear: one row per sample) stay stock PyTorch under autocast.
+
+Block VARIANTS (the constructor's use_rmsnorm / wo_shift / use_swiglu / use_rope / use_qknorm away from their defaults; `variant_supported`) take the same two
+routes with per-block choices: affine-free LayerNorm + modulate instead of RMSNorm, the 4-chunk adaLN row, the head split for {no norm, RMS} x {no RoPE, RoPE}
+in front of `ops.attention_heads`, fc1 / tanh-GELU / fc2 instead of the SwiGLU pair (csrc/dit_variants.hip); training through `functional.DitBlockVarFn`.  The
+default block issues the launches it always did."""
 import os
 from typing import Optional
 
@@ -29,10 +34,46 @@ def structurally_supported(model) -> bool:
                 and c % 8 == 0 and c <= 2048 and hd % 2 == 0 and hd <= 128 and tokens % 32 == 0 and blk.mlp.w3.in_features % 8 == 0)
 
 
+def variant_supported(model) -> bool:
+    """A NON-default configuration of the constructor's five switches that the variant kernels (csrc/dit_variants.hip) cover, at the shape limits of
+    `structurally_supported`: RMSNorm or affine-free LayerNorm, 6- or 4-chunk adaLN (`wo_shift`), SwiGLU or fc1 / tanh-GELU / fc2, with or without RoPE, RMS
+    QK-norm or none.  Out: use_qknorm with use_rmsnorm=False (an affine nn.LayerNorm(head_dim) on q and k).  Kept apart from `structurally_supported`, which also
+    gates the fp32 parity mode, `DitStackFn`, the one-token route and the batched-adaLN path -- all of which assume the default block.  Per-sample like the
+    default route: a 2B-sample call equals two B-sample calls bit for bit."""
+    from .lightningdit import RMSNorm, SwiGLUFFN, _Mlp
+    if structurally_supported(model):
+        return False
+    blk = model.blocks[0]
+    c, hd = model.hidden_size, model.hidden_size // model.num_heads
+    tokens = model.x_embedder.num_patches
+    norm_ok = isinstance(blk.norm1, RMSNorm) or (isinstance(blk.norm1, torch.nn.LayerNorm) and not blk.norm1.elementwise_affine)
+    qk_ok = isinstance(blk.attn.q_norm, (RMSNorm, torch.nn.Identity))
+    if isinstance(blk.mlp, SwiGLUFFN):
+        inner = blk.mlp.w3.in_features
+    elif isinstance(blk.mlp, _Mlp):
+        inner = blk.mlp.fc1.out_features
+    else:
+        return False
+    return bool(norm_ok and qk_ok and (model.feat_rope is not None) == bool(model.use_rope)
+                and c % 8 == 0 and c <= 2048 and hd % 2 == 0 and hd <= 128 and tokens % 32 == 0 and inner % 8 == 0)
+
+
+def refused_reason(model) -> str:
+    """What `LightningDiT.forward` names when it refuses a call: the configurations and shapes still outside the kernels."""
+    blk = model.blocks[0]
+    if isinstance(blk.attn.q_norm, torch.nn.LayerNorm):
+        return ("use_qknorm=True with use_rmsnorm=False (an affine nn.LayerNorm(head_dim) on q and k): the one combination of the constructor's switches the DiT "
+                "kernels do not cover")
+    return ("call outside autocast(bfloat16), the fp32 parity mode with a non-default block, or a shape the DiT kernels do not cover (width % 8 == 0 and <= 2048, "
+            "even head dim <= 128, tokens a multiple of 32, MLP inner width % 8 == 0)")
+
+
 def supported(model, x: torch.Tensor) -> bool:
     if not (x.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == _BF):
         return False
-    return structurally_supported(model) and x.shape[-1] * x.shape[-2] == model.x_embedder.num_patches * model.patch_size ** 2
+    if x.shape[-1] * x.shape[-2] != model.x_embedder.num_patches * model.patch_size ** 2:
+        return False
+    return structurally_supported(model) or (variant_supported(model) and not _parity_on())
 
 
 def _bf(p):
@@ -58,9 +99,16 @@ def _attention(qkv, blk, rope, heads):
     b, n, c3 = qkv.shape
     c = c3 // 3
     d = c // heads
-    if _FUSED_ATTN and _FUSED_QKNORM and n <= ops.ATTENTION_RESIDENT_MAX and ops.attention_heads_supported(n, d):      # the QK-norm variant is resident-only
-        return ops.attention_qknorm_rope(qkv, blk.attn.q_norm.weight, blk.attn.k_norm.weight, rope.freqs_cos, rope.freqs_sin, heads, blk.attn.q_norm.eps, d ** -0.5)
-    q, k, v = ops.qknorm_rope(qkv, blk.attn.q_norm.weight, blk.attn.k_norm.weight, rope.freqs_cos, rope.freqs_sin, heads, blk.attn.q_norm.eps)
+    qn, kn = blk.attn.q_norm, blk.attn.k_norm
+    if isinstance(qn, torch.nn.Identity) or rope is None:
+        # a variant (no QK-norm and / or no RoPE): its own head split (csrc/dit_variants.hip), then the attention kernels on the head-major operands
+        nw = (None, None) if isinstance(qn, torch.nn.Identity) else (qn.weight, kn.weight)
+        tabs = (None, None) if rope is None else (rope.freqs_cos, rope.freqs_sin)
+        q, k, v = ops.head_split(qkv, heads, nw[0], nw[1], tabs[0], tabs[1], getattr(qn, "eps", 1e-6))
+    elif _FUSED_ATTN and _FUSED_QKNORM and n <= ops.ATTENTION_RESIDENT_MAX and ops.attention_heads_supported(n, d):      # the QK-norm variant is resident-only
+        return ops.attention_qknorm_rope(qkv, qn.weight, kn.weight, rope.freqs_cos, rope.freqs_sin, heads, qn.eps, d ** -0.5)
+    else:
+        q, k, v = ops.qknorm_rope(qkv, qn.weight, kn.weight, rope.freqs_cos, rope.freqs_sin, heads, qn.eps)
     if _FUSED_ATTN and ops.attention_heads_supported(n, d):
         return ops.attention_heads(q, k, v, b, d ** -0.5)
     p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), d ** -0.5)            # [B*H, N, N] bf16
@@ -78,6 +126,18 @@ def _t_embed(model, t: torch.Tensor, train: bool = False) -> torch.Tensor:
     if train:
         return LinearFn.apply(SiluFn.apply(LinearFn.apply(emb, l0.weight, l0.bias)), l2.weight, l2.bias)
     return linear(linear(emb.to(_BF), l0.weight, l0.bias, ops.ACT_SILU), l2.weight, l2.bias)
+
+
+def _norm_modulate(norm, h, mod, shift_off, scale_off, pend=None):
+    """norm + adaLN modulate of the residual stream h -> the next Linear's bf16 input, by the norm's kind: RMSNorm with weight (csrc/dit.hip) or affine-free
+    LayerNorm (csrc/dit_variants.hip).  pend = (y, its adaLN row, its gate offset): the gated residual not yet added to h, folded into the same pass (h in place)."""
+    if getattr(norm, "weight", None) is not None:
+        if pend is None:
+            return ops.rmsnorm_modulate(h, norm.weight, mod, shift_off, scale_off, norm.eps)
+        return ops.gated_residual_rmsnorm_modulate_(h, pend[0], pend[1], pend[2], norm.weight, mod, shift_off, scale_off, norm.eps)
+    if pend is None:
+        return ops.layernorm_modulate(h, mod, shift_off, scale_off, norm.eps)
+    return ops.gated_residual_layernorm_modulate_(h, pend[0], pend[1], pend[2], mod, shift_off, scale_off, norm.eps)
 
 
 @torch.no_grad()
@@ -111,23 +171,24 @@ def forward_inference(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) 
         wb = [ww if ww.dtype == _BF else _bf(ww) for ww in (l.weight for l in lins)]
         bb = [bv if bv.dtype == _BF else _bf(bv) for bv in (l.bias for l in lins)]
         mods = ops.linear_rows_batched(scb, wb, bb)                               # [L, B, 6C]
-    pend = None                                                                   # (y, mod) of the previous block's MLP branch, not yet added to h
+    pend = None                                                                   # (y, mod, gate offset) of the previous block's MLP branch, not yet added to h
+    from .lightningdit import SwiGLUFFN
+    from ..functional import dit_mod_offsets
+    sh1, sc1, g1, sh2, sc2, g2 = dit_mod_offsets(c, bool(model.blocks) and model.blocks[0].wo_shift)      # the default block: 0, C, 2C, 3C, 4C, 5C
     for i, blk in enumerate(model.blocks):
         mod = mods[i] if mods is not None else adaln(blk.adaLN_modulation[1])
-        if pend is None:
-            a = ops.rmsnorm_modulate(h, blk.norm1.weight, mod, 0, c, blk.norm1.eps)
-        else:
-            a = ops.gated_residual_rmsnorm_modulate_(h, pend[0], pend[1], 5 * c, blk.norm1.weight, mod, 0, c, blk.norm1.eps)
+        a = _norm_modulate(blk.norm1, h, mod, sh1, sc1, pend)
         qkv = linear(a, blk.attn.qkv.weight, blk.attn.qkv.bias)
         o = linear(_attention(qkv, blk, model.feat_rope, heads), blk.attn.proj.weight, blk.attn.proj.bias)
-        a = ops.gated_residual_rmsnorm_modulate_(h, o, mod, 2 * c, blk.norm2.weight, mod, 3 * c, 4 * c, blk.norm2.eps)
-        g = linear(a, blk.mlp.w12.weight, blk.mlp.w12.bias, ops.ACT_SWIGLU)        # silu(x1) * x2 in the GEMM's epilogue: x12 never reaches HBM
-        pend = (linear(g, blk.mlp.w3.weight, blk.mlp.w3.bias), mod)
-    mod = adaln(fl.adaLN_modulation[1])                                           # [B, 2C]: shift | scale
-    if pend is None:
-        a = ops.rmsnorm_modulate(h, fl.norm_final.weight, mod, 0, c, fl.norm_final.eps)
-    else:
-        a = ops.gated_residual_rmsnorm_modulate_(h, pend[0], pend[1], 5 * c, fl.norm_final.weight, mod, 0, c, fl.norm_final.eps)
+        a = _norm_modulate(blk.norm2, h, mod, sh2, sc2, (o, mod, g1))
+        if isinstance(blk.mlp, SwiGLUFFN):
+            g = linear(a, blk.mlp.w12.weight, blk.mlp.w12.bias, ops.ACT_SWIGLU)    # silu(x1) * x2 in the GEMM's epilogue: x12 never reaches HBM
+            pend = (linear(g, blk.mlp.w3.weight, blk.mlp.w3.bias), mod, g2)
+        else:                                                                      # fc1 -> tanh-GELU (its own pass, csrc/dit_variants.hip) -> fc2
+            g = ops.gelu_tanh(linear(a, blk.mlp.fc1.weight, blk.mlp.fc1.bias).contiguous())
+            pend = (linear(g, blk.mlp.fc2.weight, blk.mlp.fc2.bias), mod, g2)
+    mod = adaln(fl.adaLN_modulation[1])                                           # [B, 2C]: shift | scale (the final layer always has its shift)
+    a = _norm_modulate(fl.norm_final, h, mod, 0, c, pend)
     out = model.unpatchify(linear(a, fl.linear.weight, fl.linear.bias))
     if model.learn_sigma:
         out, _ = out.chunk(2, dim=1)
@@ -339,6 +400,8 @@ def forward_train(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) -> t
     cvec = _t_embed(model, t, train=True).float() + model.y_embedder(y, model.training)      # the embedding lookup (and its index-add backward) is not a GEMM
     sc = F.silu(cvec)                                                             # adaLN_modulation[0] of every block: the same f32 values, computed once
     rope = model.feat_rope
+    if not structurally_supported(model):
+        return _forward_train_variant(model, h, sc)
     stack = STACK_FN and Fn.dit_stack_supported(b, h.shape[1], c, heads)
     if stack:
         # One node per SEGMENT of blocks.  A single process takes all blocks as one segment; under data parallelism the gradients of a node reach autograd -- and
@@ -362,6 +425,34 @@ def forward_train(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) -> t
                              blk.mlp.w3.bias, rope.freqs_cos, rope.freqs_sin, heads, blk.norm1.eps)
     fl = model.final_layer
     a = RmsnormModulateFn.apply(h, fl.norm_final.weight, LinearFn.apply(sc, fl.adaLN_modulation[1].weight, fl.adaLN_modulation[1].bias), 0, c, fl.norm_final.eps)
+    out = model.unpatchify(LinearFn.apply(a, fl.linear.weight, fl.linear.bias))
+    if model.learn_sigma:
+        out, _ = out.chunk(2, dim=1)
+    return out
+
+
+def _forward_train_variant(model, h: torch.Tensor, sc: torch.Tensor) -> torch.Tensor:
+    """The blocks and the final layer of `forward_train` for a variant model (`variant_supported`): one `functional.DitBlockVarFn` per block behind its `LinearFn`
+    adaLN modulation, the final norm by its kind.  `DitStackFn`, the grouped weight gradients and the stream-K scoping stay with the default block."""
+    from ..functional import DitBlockVarFn, LayernormModulateFn, LinearFn, RmsnormModulateFn
+    from .lightningdit import SwiGLUFFN
+    c, heads = model.hidden_size, model.num_heads
+    rope = model.feat_rope
+    cos, sin = (None, None) if rope is None else (rope.freqs_cos, rope.freqs_sin)
+    w = lambda m: getattr(m, "weight", None)
+    for blk in model.blocks:
+        lin = blk.adaLN_modulation[1]
+        mod = LinearFn.apply(sc, lin.weight, lin.bias)                            # [B, 6C] or [B, 4C] bf16
+        swiglu = isinstance(blk.mlp, SwiGLUFFN)
+        f1, f2 = (blk.mlp.w12, blk.mlp.w3) if swiglu else (blk.mlp.fc1, blk.mlp.fc2)
+        h = DitBlockVarFn.apply(h, mod, w(blk.norm1), blk.attn.qkv.weight, blk.attn.qkv.bias, w(blk.attn.q_norm), w(blk.attn.k_norm), blk.attn.proj.weight,
+                                blk.attn.proj.bias, w(blk.norm2), f1.weight, f1.bias, f2.weight, f2.bias, cos, sin, heads, blk.norm1.eps, bool(blk.wo_shift), swiglu)
+    fl = model.final_layer
+    mod = LinearFn.apply(sc, fl.adaLN_modulation[1].weight, fl.adaLN_modulation[1].bias)
+    if w(fl.norm_final) is not None:
+        a = RmsnormModulateFn.apply(h, fl.norm_final.weight, mod, 0, c, fl.norm_final.eps)
+    else:
+        a = LayernormModulateFn.apply(h, mod, 0, c, fl.norm_final.eps)
     out = model.unpatchify(LinearFn.apply(a, fl.linear.weight, fl.linear.bias))
     if model.learn_sigma:
         out, _ = out.chunk(2, dim=1)

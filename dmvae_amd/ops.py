@@ -1418,6 +1418,109 @@ def qknorm_rope_bwd(dq, dk, dv, qkv, qw, kw, cos, sin, heads: int, eps: float = 
     return dqkv, dqw, dkw
 
 
+# ---- LightningDiT block variants (csrc/dit_variants.hip) -----------------------------------------------------------------------------
+def layernorm_modulate(x: torch.Tensor, mod: torch.Tensor, shift_off: int, scale_off: int, eps: float = 1e-6) -> torch.Tensor:
+    """bf16( LayerNorm(x [B,N,C] f32; no affine) * bf16(1 + scale[b]) + shift[b] ); mod [B, k*C] bf16 holds the adaLN chunks at the given element offsets
+    (shift_off < 0: no shift)."""
+    x = _req(x, f32, "x")
+    mod = _req(mod, bf16, "mod")
+    b, n, c = x.shape
+    y = torch.empty(b, n, c, dtype=bf16, device=x.device)
+    check(_lib.lib().dmvae_layernorm_modulate_bf16(x.data_ptr(), mod.data_ptr(), y.data_ptr(), b * n, n, c, mod.shape[1], int(shift_off), int(scale_off),
+                                                   float(eps), _stream()), "layernorm_modulate_bf16")
+    return y
+
+
+def _gated_residual_layernorm(x, xo, r, gate_mod, gate_off, mod, shift_off, scale_off, eps):
+    r = _req(r, bf16, "r"); gate_mod = _req(gate_mod, bf16, "gate_mod"); mod = _req(mod, bf16, "mod")
+    b, n, c = x.shape
+    y = torch.empty(b, n, c, dtype=bf16, device=x.device)
+    check(_lib.lib().dmvae_gated_residual_layernorm_modulate(x.data_ptr(), xo.data_ptr(), r.data_ptr(), gate_mod.data_ptr(), gate_mod.shape[1], int(gate_off),
+                                                             mod.data_ptr(), y.data_ptr(), b * n, n, c, mod.shape[1], int(shift_off), int(scale_off), float(eps),
+                                                             _stream()), "gated_residual_layernorm_modulate")
+    return y
+
+
+def gated_residual_layernorm_modulate_(x: torch.Tensor, r: torch.Tensor, gate_mod: torch.Tensor, gate_off: int, mod: torch.Tensor, shift_off: int,
+                                       scale_off: int, eps: float = 1e-6) -> torch.Tensor:
+    """x [B,N,C] (f32, in place) += bf16(gate_mod[b, gate_off:gate_off+C] * r); returns layernorm_modulate(x, mod, shift_off, scale_off) -- one pass."""
+    x = _req(x, f32, "x")
+    return _gated_residual_layernorm(x, x, r, gate_mod, gate_off, mod, shift_off, scale_off, eps)
+
+
+def gated_residual_layernorm_out(x: torch.Tensor, r: torch.Tensor, gate_mod: torch.Tensor, gate_off: int, mod: torch.Tensor, shift_off: int, scale_off: int,
+                                 eps: float = 1e-6):
+    """-> (x_new = x + bf16(gate * r) as a NEW tensor, layernorm_modulate(x_new, mod, ...)): the out-of-place form for the training route."""
+    x = _req(x, f32, "x")
+    xo = torch.empty_like(x)
+    return xo, _gated_residual_layernorm(x, xo, r, gate_mod, gate_off, mod, shift_off, scale_off, eps)
+
+
+def layernorm_modulate_bwd_(dx_io: torch.Tensor, da: torch.Tensor, x: torch.Tensor, mod: torch.Tensor, dmod: torch.Tensor, shift_off: int, scale_off: int,
+                            eps: float = 1e-6) -> None:
+    """dx_io (f32, in place) += backward of layernorm_modulate at x; fills the shift / scale chunks of dmod (f32)."""
+    dx_io = _req(dx_io, f32, "dx_io"); da = _req(da, bf16, "da"); x = _req(x, f32, "x"); mod = _req(mod, bf16, "mod"); dmod = _req(dmod, f32, "dmod")
+    b, n, c = x.shape
+    L = _lib.lib()
+    ws = workspace(L.dmvae_layernorm_modulate_bwd_workspace(b, n, c), x.device)
+    check(L.dmvae_layernorm_modulate_bwd(da.data_ptr(), x.data_ptr(), mod.data_ptr(), dx_io.data_ptr(), dmod.data_ptr(), ws.data_ptr(), ws.numel(), b, n, c,
+                                         mod.shape[1], int(shift_off), int(scale_off), float(eps), _stream()), "layernorm_modulate_bwd")
+
+
+def head_split(qkv: torch.Tensor, heads: int, qw: Optional[torch.Tensor] = None, kw: Optional[torch.Tensor] = None, cos: Optional[torch.Tensor] = None,
+               sin: Optional[torch.Tensor] = None, eps: float = 1e-6):
+    """qkv [B,N,3*H*D] bf16 -> (q, k [B*H, N, Dp] with Dp = D rounded up to 32 and zero padding, v [B*H, N, D]).  qw / kw given: per-head RMSNorm * weight;
+    cos / sin given: 2-D RoPE; neither: a relayout.  The operand layout of `attention_heads` / `attention_bwd_heads` / the composed route."""
+    qkv = _req(qkv, bf16, "qkv")
+    assert (qw is None) == (kw is None) and (cos is None) == (sin is None)
+    b, n, c3 = qkv.shape
+    d = c3 // 3 // heads
+    dp = (d + 31) // 32 * 32
+    q = torch.empty(b * heads, n, dp, dtype=bf16, device=qkv.device)
+    k = torch.empty_like(q)
+    v = torch.empty(b * heads, n, d, dtype=bf16, device=qkv.device)
+    opt = lambda t, name: None if t is None else _req(t, f32, name)
+    check(_lib.lib().dmvae_head_split_bf16(qkv.data_ptr(), _ptr(opt(qw, "qw")), _ptr(opt(kw, "kw")), _ptr(opt(cos, "cos")), _ptr(opt(sin, "sin")), q.data_ptr(),
+                                           k.data_ptr(), v.data_ptr(), b, n, heads, d, dp, int(qw is not None), int(cos is not None), float(eps), _stream()),
+          "head_split_bf16")
+    return q, k, v
+
+
+def head_split_bwd(dq, dk, dv, qkv, heads: int, qw=None, kw=None, cos=None, sin=None, eps: float = 1e-6, need_w: bool = True, dqw_out=None, dkw_out=None):
+    """-> (dqkv [B,N,3*H*D] bf16, dq_weight [D], dk_weight [D]); the weight gradients are None without a norm or with need_w False."""
+    dq = _req(dq, bf16, "dq"); dk = _req(dk, bf16, "dk"); dv = _req(dv, bf16, "dv"); qkv = _req(qkv, bf16, "qkv")
+    b, n, c3 = qkv.shape
+    d = c3 // 3 // heads
+    dp = dq.shape[-1]
+    L = _lib.lib()
+    dqkv = torch.empty_like(qkv)
+    dqw = dkw = ws = None
+    if qw is not None and need_w:
+        ws = workspace(L.dmvae_head_split_bwd_nblk(b, n, heads) * 2 * d * 4, qkv.device)
+        dqw = dqw_out if dqw_out is not None else torch.empty(d, dtype=f32, device=qkv.device)
+        dkw = dkw_out if dkw_out is not None else torch.empty(d, dtype=f32, device=qkv.device)
+    opt = lambda t, name: None if t is None else _req(t, f32, name)
+    check(L.dmvae_head_split_bwd(dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), qkv.data_ptr(), _ptr(opt(qw, "qw")), _ptr(opt(kw, "kw")), _ptr(opt(cos, "cos")),
+                                 _ptr(opt(sin, "sin")), dqkv.data_ptr(), _ptr(dqw), _ptr(dkw), _ptr(ws), 0 if ws is None else ws.numel(), b, n, heads, d, dp,
+                                 int(qw is not None), int(cos is not None), float(eps), 0, _stream()), "head_split_bwd")
+    return dqkv, dqw, dkw
+
+
+def gelu_tanh(x: torch.Tensor) -> torch.Tensor:
+    """nn.GELU(approximate="tanh") on a bf16 tensor, f32 inside."""
+    x = _req(x, bf16, "x")
+    y = torch.empty_like(x)
+    check(_lib.lib().dmvae_gelu_tanh_fwd(x.data_ptr(), y.data_ptr(), x.numel(), _stream()), "gelu_tanh_fwd")
+    return y
+
+
+def gelu_tanh_bwd(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    dy = _req(dy, bf16, "dy"); x = _req(x, bf16, "x")
+    dx = torch.empty_like(x)
+    check(_lib.lib().dmvae_gelu_tanh_bwd(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(), _stream()), "gelu_tanh_bwd")
+    return dx
+
+
 # ---- whole-stack LightningDiT backward + batched per-sample Linears (csrc/dit_stack.hip, linear_rows.hip) ---------------------------
 class _TableCache(dict):
     """key -> device table(s) that LAUNCHED KERNELS READ (pointer tables of the batched / grouped entry points).  Dropping an entry frees device memory a kernel in

@@ -331,7 +331,7 @@ def _batchable(model) -> bool:
     drop-outs (eval mode)."""
     from .models.lightningdit import LightningDiT
     from .models import lightningdit_fast
-    return isinstance(model, LightningDiT) and not model.training and lightningdit_fast.structurally_supported(model)
+    return isinstance(model, LightningDiT) and not model.training and (lightningdit_fast.structurally_supported(model) or lightningdit_fast.variant_supported(model))
 
 
 class DMDTrainer(_AdversarialBranch):

@@ -556,6 +556,39 @@ int dmvae_qknorm_rope_bwd_dx(const void* dq, const void* dk, const void* dv, con
                              const void* cos_table, const void* sin_table, void* dqkv, int batch, int seq, int heads, int head_dim, int head_dim_padded,
                              float eps, dmvae_stream_t stream);
 
+/* ---- LightningDiT block variants (csrc/dit_variants.hip; diffusion/lightningdit/lightningdit.py:183-252 with use_rmsnorm / wo_shift / use_swiglu / use_rope /
+ * use_qknorm away from their defaults).  Conventions of the block above: residual stream f32, mod bf16 [B][mod_stride], shift_off < 0: no shift.
+ * layernorm_modulate: y = bf16( (x - mean) * rsqrt(var + eps) * bf16(1 + scale[b]) + shift[b] ) -- nn.LayerNorm(c, elementwise_affine=False) + modulate; the
+ *   variance is the mean squared deviation from the row held in registers (two-pass).  c % 4 == 0, c <= 2048, offsets % 4 == 0 inside the row.
+ * gated_residual_layernorm_modulate: x_out = x_in + bf16(gate[b] * r) (x_out == x_in: in place), then y = layernorm_modulate(x_out) in the same pass -- the bits
+ *   of dmvae_gated_residual_out (y == NULL) followed by dmvae_layernorm_modulate_bf16.
+ * layernorm_modulate_bwd: dx_io (f32) += LayerNorm backward of g = da * bf16(1 + scale): rs * (g - mean(g) - xh * mean(g * xh)); dmod[scale] = sum_n da * xh,
+ *   dmod[shift] = sum_n da (skipped when shift_off < 0); two-stage reduction in a fixed order.  workspace: dmvae_layernorm_modulate_bwd_workspace bytes.
+ * head_split: qkv [B][N][3][H][D] bf16 -> q, k [B*H][N][Dp] (columns [D, Dp) zero), v [B*H][N][D].  norm_kind 0: none, 1: per-head RMSNorm (bf16 result) * weight;
+ *   rope 0 / 1: t * cos + rotate_half(t) * sin with the [N][D] tables; one rounding to bf16.  Weights / tables may be NULL where their switch is off.
+ *   (norm_kind 1, rope 1) computes what dmvae_qknorm_rope_bf16 computes.  D even, Dp even, <= 128.
+ * head_split_bwd: (dq, dk [B*H][N][Dp], dv [B*H][N][D]) -> dqkv; dq_weight / dk_weight [D] f32 (norm_kind 1; both NULL: not wanted, workspace unused;
+ *   accumulate != 0 adds).  workspace: dmvae_head_split_bwd_nblk(batch, seq, heads) * 2 * D floats.
+ * gelu_tanh: y = bf16( 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) ), nn.GELU(approximate="tanh"), evaluated in f32 as x * sigmoid(2u); bwd takes the
+ *   pre-activation x.  Any n (16-byte vectors where the pointers allow, the tail element by element). */
+int dmvae_layernorm_modulate_bf16(const void* x, const void* mod, void* y, int rows, int rows_per_sample, int c, int mod_stride, int shift_off, int scale_off,
+                                  float eps, dmvae_stream_t stream);
+int dmvae_gated_residual_layernorm_modulate(const void* x_in, void* x_out, const void* r, const void* gate_mod, int gate_stride, int gate_off, const void* mod,
+                                            void* y, int rows, int rows_per_sample, int c, int mod_stride, int shift_off, int scale_off, float eps,
+                                            dmvae_stream_t stream);
+size_t dmvae_layernorm_modulate_bwd_workspace(int batch, int seq, int c);
+int dmvae_layernorm_modulate_bwd(const void* da, const void* x, const void* mod, void* dx_io, void* dmod, void* workspace, size_t workspace_bytes, int batch,
+                                 int seq, int c, int mod_stride, int shift_off, int scale_off, float eps, dmvae_stream_t stream);
+int dmvae_head_split_bf16(const void* qkv, const void* q_weight, const void* k_weight, const void* cos_table, const void* sin_table, void* q_out, void* k_out,
+                          void* v_out, int batch, int seq, int heads, int head_dim, int head_dim_padded, int norm_kind, int rope, float eps,
+                          dmvae_stream_t stream);
+int dmvae_head_split_bwd_nblk(int batch, int seq, int heads);
+int dmvae_head_split_bwd(const void* dq, const void* dk, const void* dv, const void* qkv, const void* q_weight, const void* k_weight, const void* cos_table,
+                         const void* sin_table, void* dqkv, void* dq_weight, void* dk_weight, void* workspace, size_t workspace_bytes, int batch, int seq,
+                         int heads, int head_dim, int head_dim_padded, int norm_kind, int rope, float eps, int accumulate, dmvae_stream_t stream);
+int dmvae_gelu_tanh_fwd(const void* x, void* y, size_t n, dmvae_stream_t stream);
+int dmvae_gelu_tanh_bwd(const void* dy, const void* x, void* dx, size_t n, dmvae_stream_t stream);
+
 /* Whole-stack backward of LightningDiT's blocks (diffusion/lightningdit/lightningdit.py:236-250 x depth; the student's flow-matching step, train_dmd.py:565-575,
  * train_diffusion.py:290-297) -- csrc/dit_stack.hip, driven by dmvae_amd/functional.py::DitStackFn.
  * dmvae_dit_boundary_bwd: one pass over the f32 residual-stream gradient dx_io [B][seq][c] at a sub-layer boundary.  Norm half (da != NULL): dx_io += backward of
