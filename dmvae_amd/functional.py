@@ -1143,6 +1143,39 @@ def _attention_bwd(qkv: torch.Tensor, do: torch.Tensor, heads: int, scale: float
     return out.reshape(b, s, c3).contiguous()
 
 
+def _heads_attention(q, k, v, b: int, scale: float, fused: Optional[bool] = None):
+    """softmax(scale q k^T) v of the head-major operands q, k [B*H, N, Dp], v [B*H, N, D] (`ops.qknorm_rope` / `ops.head_split`) -> (o [B, N, H*D], p, lse), the one
+    place that chooses the route: the resident fused kernel up to `ops.ATTENTION_RESIDENT_MAX` tokens (p = lse = None: its backward recomputes the probabilities in
+    registers), the streaming kernels beyond (lse: the row statistics their backward rebuilds the probabilities from), and for the head dims outside
+    `ops.attention_heads_supported` -- or with fused=False -- the composition QK^T GEMM / f32 softmax / PV GEMM, whose bf16 probabilities p are kept."""
+    bh, n, d = v.shape
+    if fused is None:
+        fused = ops.attention_heads_supported(n, d)
+    if not fused:
+        p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), scale)            # [B*H, N, N] bf16
+        o = ops.gemm_nt(p, ops.transpose_last2(v))                              # [B*H, N, D]
+        return o.view(b, bh // b, n, d).permute(0, 2, 1, 3).reshape(b, n, bh // b * d), p, None
+    if n > ops.ATTENTION_RESIDENT_MAX:
+        o, lse = ops.attention_heads(q, k, v, b, scale, need_lse=True)
+        return o, None, lse
+    return ops.attention_heads(q, k, v, b, scale), None, None
+
+
+def _heads_attention_bwd(q, k, v, o, do, p, lse, scale: float):
+    """(dq, dk [B*H, N, Dp], dv [B*H, N, D]) of `_heads_attention` from its operands, its results and d(o) [B, N, H*D]: the fused backward kernels (p None), else the
+    composition on the saved p -- `softmax_rows_bwd` and four GEMMs, the head dim zero-padded to the GEMM kernel's 32-wide K step (72 -> 96)."""
+    b, n, _ = do.shape
+    bh, _, d = v.shape
+    if p is None:
+        return ops.attention_bwd_heads(q, k, v, o, do, b, scale, lse=lse)
+    do_h = do.view(b, n, bh // b, d).permute(0, 2, 1, 3).reshape(bh, n, d)
+    pad = q.shape[-1] - d
+    do_p, v_p = (torch.nn.functional.pad(do_h, (0, pad)), torch.nn.functional.pad(v, (0, pad))) if pad else (do_h.contiguous(), v)
+    ds = ops.softmax_rows_bwd(ops.gemm_nt(do_p, v_p, out_f32=True), p, scale)
+    dv = ops.gemm_tn(p, do_h.contiguous())                                      # [B*H, key, D]
+    return ops.gemm_nt(ds, ops.transpose_last2(k)), ops.gemm_tn(ds, q), dv      # dq [B*H, N, Dp], dk
+
+
 class VitBlockFn(torch.autograd.Function):
     """One pre-norm transformer block on the f32 residual stream t [B,S,C]:
         t += ls1 * proj(MHA(LN1(t)));  t += ls2 * fc2(GELU(fc1(LN2(t))))
@@ -1416,92 +1449,23 @@ class LayerNormBf16Fn(torch.autograd.Function):
 
 
 # ---- LightningDiT block with gradients (the student's training turn, train_dmd.py:565-575) -------------------------------------------
-class DitBlockFn(torch.autograd.Function):
-    """LightningDiTBlock.forward (lightningdit.py:236-250) on the f32 residual stream h [B,N,C] with the adaLN chunks `mod` [B,6C] (bf16, computed by
-    stock autograd outside): forward = the inference path's kernels (csrc/dit.hip), backward = their backward kernels, the GEMM-composed
-    attention backward and `_lin_grads` for the four Linear layers.  Returns the new residual stream; gradients flow to h, mod and all block
-    parameters."""
-
-    @staticmethod
-    def forward(ctx, h, mod, n1w, qkvw, qkvb, qnw, knw, pw, pb, n2w, w12w, w12b, w3w, w3b, cos, sin, heads, eps):
-        import torch.nn.functional as F
-        b, n, c = h.shape
-        d = c // heads
-        mod = _c(mod)
-        a1 = ops.rmsnorm_modulate(h, n1w, mod, 0, c, eps)
-        qkv = linear(a1, qkvw, qkvb)
-        q, k, v = ops.qknorm_rope(qkv, qnw, knw, cos, sin, heads, eps)
-        fused = ops.attention_heads_supported(n, d)
-        lse = None
-        if fused:       # the inference kernel; its backward recomputes the probabilities in registers (csrc/attention_bwd.hip); no P is saved
-            p = None
-            if n > ops.ATTENTION_RESIDENT_MAX:      # the streaming kernels: the backward rebuilds the probabilities from the forward's row statistics
-                o, lse = ops.attention_heads(q, k, v, b, d ** -0.5, need_lse=True)
-            else:
-                o = ops.attention_heads(q, k, v, b, d ** -0.5)
-        else:
-            p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), d ** -0.5)
-            o = ops.gemm_nt(p, ops.transpose_last2(v)).view(b, heads, n, d).permute(0, 2, 1, 3).reshape(b, n, c)
-        o2 = linear(o, pw, pb)
-        h_mid, a2 = ops.gated_residual_out(h, o2, mod, 2 * c, n2w, mod, 3 * c, 4 * c, eps)       # h itself is saved for the backward pass
-        x12, g = linear_swiglu(a2, w12w, w12b)
-        o3 = linear(g, w3w, w3b)
-        h_out, _ = ops.gated_residual_out(h_mid, o3, mod, 5 * c)
-        ctx.save_for_backward(h, mod, a1, qkv, q, k, v, p, o, o2, h_mid, a2, x12, g, o3, n1w, qkvw, qnw, knw, pw, n2w, w12w, w3w, cos, sin)
-        ctx.others = (qkvb, pb, w12b, w3b, heads, eps)
-        ctx.fused_attn = fused
-        ctx.lse = lse
-        return h_out
-
-    @staticmethod
-    def backward(ctx, dh_out):
-        import torch.nn.functional as F
-        h, mod, a1, qkv, q, k, v, p, o, o2, h_mid, a2, x12, g, o3, n1w, qkvw, qnw, knw, pw, n2w, w12w, w3w, cos, sin = ctx.saved_tensors
-        qkvb, pb, w12b, w3b, heads, eps = ctx.others
-        b, n, c = h.shape
-        d, rows = c // heads, b * n
-        dp_ = q.shape[-1]
-        dt = dh_out.float().clone()                                 # becomes d(h_mid), then d(h)
-        dmod = torch.zeros(b, mod.shape[1], dtype=f32, device=h.device)
-        # MLP branch
-        do3 = ops.gated_residual_bwd(dt, o3, mod, dmod, 5 * c)
-        dg, dw3, db3 = _lin_grads(do3.view(rows, c), g.view(rows, -1), w3w, w3b)
-        dx12 = ops.swiglu_bwd(dg.view_as(g), x12)
-        da2, dw12, db12 = _lin_grads(dx12.view(rows, -1), a2.view(rows, c), w12w, w12b)
-        dn2w = ops.rmsnorm_modulate_bwd_(dt, da2.view(b, n, c), h_mid, n2w, mod, dmod, 3 * c, 4 * c, eps, dw_out=_dst(n2w))
-        # attention branch
-        do2 = ops.gated_residual_bwd(dt, o2, mod, dmod, 2 * c)
-        do, dpw, dpb = _lin_grads(do2.view(rows, c), o.view(rows, c), pw, pb)
-        if ctx.fused_attn:
-            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=ctx.lse)
-        else:
-            do_h = do.view(b, n, heads, d).permute(0, 2, 1, 3).reshape(b * heads, n, d)
-            pad = dp_ - d                                                   # head dim padded to the GEMM kernel's 32-wide K step (72 -> 96)
-            do_p, v_p = (F.pad(do_h, (0, pad)), F.pad(v, (0, pad))) if pad else (do_h.contiguous(), v)
-            ds = ops.softmax_rows_bwd(ops.gemm_nt(do_p, v_p, out_f32=True), p, d ** -0.5)
-            dv = ops.gemm_tn(p, do_h.contiguous())                          # [B*H, key, D]
-            dq = ops.gemm_nt(ds, ops.transpose_last2(k))                    # [B*H, N, Dp]
-            dk = ops.gemm_tn(ds, q)
-        dqkv, dqnw, dknw = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, heads, eps, dqw_out=_dst(qnw), dkw_out=_dst(knw))
-        da1, dqkvw, dqkvb = _lin_grads(dqkv.view(rows, 3 * c), a1.view(rows, c), qkvw, qkvb)
-        dn1w = ops.rmsnorm_modulate_bwd_(dt, da1.view(b, n, c), h, n1w, mod, dmod, 0, c, eps, dw_out=_dst(n1w))
-        return (dt, dmod.to(mod.dtype), dn1w, dqkvw, dqkvb, dqnw, dknw, dpw, dpb, dn2w, dw12, db12, dw3, db3, None, None, None, None)
-
-
 def dit_mod_offsets(c: int, wo_shift: bool):
     """Element offsets of (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp) inside a block's adaLN row (lightningdit.py:243-248); -1: the chunk
     does not exist (`wo_shift`: four chunks scale_msa | gate_msa | scale_mlp | gate_mlp, stride 4C)."""
     return (-1, 0, c, -1, 2 * c, 3 * c) if wo_shift else (0, c, 2 * c, 3 * c, 4 * c, 5 * c)
 
 
-class DitBlockVarFn(torch.autograd.Function):
-    """`DitBlockFn` for the block VARIANTS (lightningdit.py:183-252 with the constructor's switches away from their defaults), one node per block on the f32 residual
-    stream.  Absent parameters are None and pick the branch: n1w / n2w None -> affine-free LayerNorm (csrc/dit_variants.hip) instead of RMSNorm; qnw / knw None -> no
-    QK-norm; cos / sin None -> no RoPE; `swiglu` False -> fc1, tanh-GELU, fc2 (f1 = fc1, f2 = fc2; else f1 = w12, f2 = w3); `wo_shift` -> the 4-chunk adaLN row.
-    With no parameter needing a gradient (frozen weights: the likelihood sampler's input-VJP) the backward computes d h and d mod only."""
+class DitBlockFn(torch.autograd.Function):
+    """LightningDiTBlock.forward (lightningdit.py:183-252) on the f32 residual stream h [B,N,C] with the adaLN chunks `mod` [B,6C] (bf16, a `LinearFn` outside):
+    forward = the inference path's kernels (csrc/dit.hip, csrc/dit_variants.hip), backward = their backward kernels, `_heads_attention_bwd` and `_lin_grads` for the
+    four Linear layers.  Returns the new residual stream; gradients flow to h, mod and all block parameters.  Absent parameters are None and pick the branch of a
+    block VARIANT: n1w / n2w None -> affine-free LayerNorm instead of RMSNorm; qnw / knw None -> no QK-norm; cos / sin None -> no RoPE (`ops.head_split` unless both
+    are there: the default's `ops.qknorm_rope`); `swiglu` False -> fc1, tanh-GELU, fc2 (f1 = fc1, f2 = fc2; else f1 = w12, f2 = w3); `wo_shift` -> the 4-chunk adaLN
+    row [B,4C].  The two trailing arguments may be left out (the default block's 18).  With no parameter needing a gradient (frozen weights: the likelihood
+    sampler's input-VJP) the backward computes d h and d mod only."""
 
     @staticmethod
-    def forward(ctx, h, mod, n1w, qkvw, qkvb, qnw, knw, pw, pb, n2w, f1w, f1b, f2w, f2b, cos, sin, heads, eps, wo_shift, swiglu):
+    def forward(ctx, h, mod, n1w, qkvw, qkvb, qnw, knw, pw, pb, n2w, f1w, f1b, f2w, f2b, cos, sin, heads, eps, wo_shift=False, swiglu=True):
         b, n, c = h.shape
         d = c // heads
         mod = _c(mod)
@@ -1512,19 +1476,10 @@ class DitBlockVarFn(torch.autograd.Function):
             q, k, v = ops.qknorm_rope(qkv, qnw, knw, cos, sin, heads, eps)
         else:
             q, k, v = ops.head_split(qkv, heads, qnw, knw, cos, sin, eps)
-        fused = ops.attention_heads_supported(n, d)
-        lse = p = None
-        if fused:
-            if n > ops.ATTENTION_RESIDENT_MAX:      # the streaming kernels: the backward rebuilds the probabilities from the forward's row statistics
-                o, lse = ops.attention_heads(q, k, v, b, d ** -0.5, need_lse=True)
-            else:
-                o = ops.attention_heads(q, k, v, b, d ** -0.5)
-        else:
-            p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), d ** -0.5)
-            o = ops.gemm_nt(p, ops.transpose_last2(v)).view(b, heads, n, d).permute(0, 2, 1, 3).reshape(b, n, c)
+        o, p, lse = _heads_attention(q, k, v, b, d ** -0.5)
         o2 = linear(o, pw, pb)
         if n2w is not None:
-            h_mid, a2 = ops.gated_residual_out(h, o2, mod, g1, n2w, mod, sh2, sc2, eps)
+            h_mid, a2 = ops.gated_residual_out(h, o2, mod, g1, n2w, mod, sh2, sc2, eps)       # h itself is saved for the backward pass
         else:
             h_mid, a2 = ops.gated_residual_layernorm_out(h, o2, mod, g1, mod, sh2, sc2, eps)
         if swiglu:
@@ -1535,19 +1490,18 @@ class DitBlockVarFn(torch.autograd.Function):
         o3 = linear(g, f2w, f2b)
         h_out, _ = ops.gated_residual_out(h_mid, o3, mod, g2)
         ctx.save_for_backward(h, mod, a1, qkv, q, k, v, p, o, o2, h_mid, a2, x1, g, o3, n1w, qkvw, qnw, knw, pw, n2w, f1w, f2w, cos, sin)
-        ctx.others = (qkvb, pb, f1b, f2b, heads, eps, wo_shift, swiglu, fused, lse)
+        ctx.others = (qkvb, pb, f1b, f2b, heads, eps, wo_shift, swiglu, lse)
         return h_out
 
     @staticmethod
     def backward(ctx, dh_out):
-        import torch.nn.functional as F
         h, mod, a1, qkv, q, k, v, p, o, o2, h_mid, a2, x1, g, o3, n1w, qkvw, qnw, knw, pw, n2w, f1w, f2w, cos, sin = ctx.saved_tensors
-        qkvb, pb, f1b, f2b, heads, eps, wo_shift, swiglu, fused, lse = ctx.others
+        qkvb, pb, f1b, f2b, heads, eps, wo_shift, swiglu, lse = ctx.others
         b, n, c = h.shape
         d, rows = c // heads, b * n
-        dp_ = q.shape[-1]
         sh1, sc1, g1, sh2, sc2, g2 = dit_mod_offsets(c, wo_shift)
         need_w = any(ctx.needs_input_grad[2:14])
+        dst = _dst if need_w else (lambda w: None)
         dt = dh_out.float().clone()                                 # becomes d(h_mid), then d(h)
         dmod = torch.zeros(b, mod.shape[1], dtype=f32, device=h.device)
 
@@ -1555,7 +1509,7 @@ class DitBlockVarFn(torch.autograd.Function):
             if w is None:
                 ops.layernorm_modulate_bwd_(dt, da, x, mod, dmod, sh, sc, eps)
                 return None
-            dw = ops.rmsnorm_modulate_bwd_(dt, da, x, w, mod, dmod, sh, sc, eps, dw_out=_dst(w) if need_w else None)
+            dw = ops.rmsnorm_modulate_bwd_(dt, da, x, w, mod, dmod, sh, sc, eps, dw_out=dst(w))
             return dw if need_w else None
         # MLP branch
         do3 = ops.gated_residual_bwd(dt, o3, mod, dmod, g2)
@@ -1566,27 +1520,17 @@ class DitBlockVarFn(torch.autograd.Function):
         # attention branch
         do2 = ops.gated_residual_bwd(dt, o2, mod, dmod, g1)
         do, dpw, dpb = _lin_grads(do2.view(rows, c), o.view(rows, c), pw, pb, need_w=need_w)
-        if fused:
-            dq, dk, dv = ops.attention_bwd_heads(q, k, v, o, do.view(b, n, c), b, d ** -0.5, lse=lse)
-        else:
-            do_h = do.view(b, n, heads, d).permute(0, 2, 1, 3).reshape(b * heads, n, d)
-            pad = dp_ - d                                                   # head dim padded to the GEMM kernel's 32-wide K step
-            do_p, v_p = (F.pad(do_h, (0, pad)), F.pad(v, (0, pad))) if pad else (do_h.contiguous(), v)
-            ds = ops.softmax_rows_bwd(ops.gemm_nt(do_p, v_p, out_f32=True), p, d ** -0.5)
-            dv = ops.gemm_tn(p, do_h.contiguous())                          # [B*H, key, D]
-            dq = ops.gemm_nt(ds, ops.transpose_last2(k))                    # [B*H, N, Dp]
-            dk = ops.gemm_tn(ds, q)
-        if qnw is not None and cos is not None:     # the default's head split (a `wo_shift` / LayerNorm / GELU variant around it): its own backward
-            dqkv, dqnw, dknw = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, heads, eps, dqw_out=_dst(qnw) if need_w else None,
-                                                   dkw_out=_dst(knw) if need_w else None)
+        dq, dk, dv = _heads_attention_bwd(q, k, v, o, do.view(b, n, c), p, lse, d ** -0.5)
+        if qnw is not None and cos is not None:
+            dqkv, dqnw, dknw = ops.qknorm_rope_bwd(dq, dk, dv, qkv, qnw, knw, cos, sin, heads, eps, dqw_out=dst(qnw), dkw_out=dst(knw))
             if not need_w:
                 dqnw = dknw = None
         else:
-            dqkv, dqnw, dknw = ops.head_split_bwd(dq, dk, dv, qkv, heads, qnw, knw, cos, sin, eps, need_w=need_w, dqw_out=_dst(qnw) if need_w else None,
-                                                  dkw_out=_dst(knw) if need_w else None)
+            dqkv, dqnw, dknw = ops.head_split_bwd(dq, dk, dv, qkv, heads, qnw, knw, cos, sin, eps, need_w=need_w, dqw_out=dst(qnw), dkw_out=dst(knw))
         da1, dqkvw, dqkvb = _lin_grads(dqkv.view(rows, 3 * c), a1.view(rows, c), qkvw, qkvb, need_w=need_w)
         dn1w = norm_bwd(da1.view(b, n, c), h, n1w, sh1, sc1)
-        return (dt, dmod.to(mod.dtype), dn1w, dqkvw, dqkvb, dqnw, dknw, dpw, dpb, dn2w, df1w, df1b, df2w, df2b) + (None,) * 6
+        # one gradient per argument actually passed: 18 for the default call, 20 with wo_shift and swiglu
+        return (dt, dmod.to(mod.dtype), dn1w, dqkvw, dqkvb, dqnw, dknw, dpw, dpb, dn2w, df1w, df1b, df2w, df2b) + (None,) * (len(ctx.needs_input_grad) - 14)
 
 
 class LayernormModulateFn(torch.autograd.Function):

@@ -8,9 +8,11 @@ Two routes through `forward`:
     the kernels cover -> `lightningdit_fast.forward_inference`: RMSNorm + adaLN modulate, QK-norm + RoPE, SwiGLU gate and the gated
     residual on HIP kernels (csrc/dit.hip), GEMMs through the library, attention on the conv kernel's batched-GEMM path;
   * gradients needed (the student's own training turn, train_dmd.py:565-575) on such a GPU shape -> `lightningdit_fast.forward_train`: one autograd
-    Function per block (`functional.DitBlockFn`) over the same kernels and their backward counterparts;
-  * the constructor's block switches away from their defaults (LayerNorm, `wo_shift`, GELU-MLP, no RoPE, no QK-norm) take the same two routes on the kernels of
-    csrc/dit_variants.hip (`lightningdit_fast.variant_supported`); only use_qknorm=True with use_rmsnorm=False is refused;
+    Function per block (`functional.DitBlockFn`; the default configuration as `functional.DitStackFn` segments) over the same kernels and their backward
+    counterparts;
+  * the constructor's block switches away from their defaults (LayerNorm, `wo_shift`, GELU-MLP, no RoPE, no QK-norm) take the same two routes -- the same
+    `forward_inference` and the same `DitBlockFn`, which pick each branch by the block -- on the kernels of csrc/dit_variants.hip
+    (`lightningdit_fast.variant_supported`); only use_qknorm=True with use_rmsnorm=False is refused;
   * otherwise (CPU, no autocast, unusual shapes) -> the stock PyTorch modules below, which also define the parameters.
 SURVEY.md 8(f) rank 3."""
 from __future__ import annotations

@@ -10,8 +10,8 @@ The per-sample pieces (timestep / label embedding, adaLN Linear: one row per sam
 
 Block VARIANTS (the constructor's use_rmsnorm / wo_shift / use_swiglu / use_rope / use_qknorm away from their defaults; `variant_supported`) take the same two
 routes with per-block choices: affine-free LayerNorm + modulate instead of RMSNorm, the 4-chunk adaLN row, the head split for {no norm, RMS} x {no RoPE, RoPE}
-in front of `ops.attention_heads`, fc1 / tanh-GELU / fc2 instead of the SwiGLU pair (csrc/dit_variants.hip); training through `functional.DitBlockVarFn`.  The
-default block issues the launches it always did."""
+in front of `ops.attention_heads`, fc1 / tanh-GELU / fc2 instead of the SwiGLU pair (csrc/dit_variants.hip); training through the same `functional.DitBlockFn` as
+the default block, whose absent parameters are None.  The default block issues the launches it always did."""
 import os
 from typing import Optional
 
@@ -19,43 +19,50 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
+from .lightningdit import RMSNorm, SwiGLUFFN, _Mlp
 
 _BF = torch.bfloat16
+
+
+def _mlp(blk):
+    """(is SwiGLU, first Linear, second Linear) of a block's MLP: w12 / w3 of `SwiGLUFFN`, fc1 / fc2 of the tanh-GELU `_Mlp`; None for any other module.  The inner
+    width is the second Linear's in_features."""
+    if isinstance(blk.mlp, SwiGLUFFN):
+        return True, blk.mlp.w12, blk.mlp.w3
+    if isinstance(blk.mlp, _Mlp):
+        return False, blk.mlp.fc1, blk.mlp.fc2
+    return None
+
+
+def _shapes_supported(model) -> bool:
+    """The shape limits of the DiT kernels, the same for the default block and the variants (`refused_reason` spells them out): width % 8 == 0 and <= 2048, even
+    head dim <= 128, tokens a multiple of 32, MLP inner width % 8 == 0."""
+    mlp = _mlp(model.blocks[0])
+    c, hd = model.hidden_size, model.hidden_size // model.num_heads
+    return bool(mlp is not None and c % 8 == 0 and c <= 2048 and hd % 2 == 0 and hd <= 128 and model.x_embedder.num_patches % 32 == 0
+                and mlp[2].in_features % 8 == 0)
 
 
 def structurally_supported(model) -> bool:
     """The configuration the DiT kernels cover (what `supported` checks besides the call's tensor and autocast state).  On this route every op is per sample
     -- per token row, per (sample, head) -- so a 2B-sample call equals two B-sample calls bit for bit (train.DMDTrainer's batched cond / uncond evaluation)."""
-    from .lightningdit import RMSNorm, SwiGLUFFN
     blk = model.blocks[0]
-    c, hd = model.hidden_size, model.hidden_size // model.num_heads
-    tokens = model.x_embedder.num_patches
     return bool(model.use_rope and model.use_rmsnorm and isinstance(blk.attn.q_norm, RMSNorm) and isinstance(blk.mlp, SwiGLUFFN) and not blk.wo_shift
-                and c % 8 == 0 and c <= 2048 and hd % 2 == 0 and hd <= 128 and tokens % 32 == 0 and blk.mlp.w3.in_features % 8 == 0)
+                and _shapes_supported(model))
 
 
 def variant_supported(model) -> bool:
     """A NON-default configuration of the constructor's five switches that the variant kernels (csrc/dit_variants.hip) cover, at the shape limits of
     `structurally_supported`: RMSNorm or affine-free LayerNorm, 6- or 4-chunk adaLN (`wo_shift`), SwiGLU or fc1 / tanh-GELU / fc2, with or without RoPE, RMS
-    QK-norm or none.  Out: use_qknorm with use_rmsnorm=False (an affine nn.LayerNorm(head_dim) on q and k).  Kept apart from `structurally_supported`, which also
-    gates the fp32 parity mode, `DitStackFn`, the one-token route and the batched-adaLN path -- all of which assume the default block.  Per-sample like the
-    default route: a 2B-sample call equals two B-sample calls bit for bit."""
-    from .lightningdit import RMSNorm, SwiGLUFFN, _Mlp
+    QK-norm or none.  Out: use_qknorm with use_rmsnorm=False (an affine nn.LayerNorm(head_dim) on q and k).  False for the default configuration: that is
+    `structurally_supported`, which alone gates the fp32 parity mode, `DitStackFn`, the one-token route and the batched-adaLN path -- all of which assume the
+    default block.  Per-sample like the default route: a 2B-sample call equals two B-sample calls bit for bit."""
     if structurally_supported(model):
         return False
     blk = model.blocks[0]
-    c, hd = model.hidden_size, model.hidden_size // model.num_heads
-    tokens = model.x_embedder.num_patches
     norm_ok = isinstance(blk.norm1, RMSNorm) or (isinstance(blk.norm1, torch.nn.LayerNorm) and not blk.norm1.elementwise_affine)
     qk_ok = isinstance(blk.attn.q_norm, (RMSNorm, torch.nn.Identity))
-    if isinstance(blk.mlp, SwiGLUFFN):
-        inner = blk.mlp.w3.in_features
-    elif isinstance(blk.mlp, _Mlp):
-        inner = blk.mlp.fc1.out_features
-    else:
-        return False
-    return bool(norm_ok and qk_ok and (model.feat_rope is not None) == bool(model.use_rope)
-                and c % 8 == 0 and c <= 2048 and hd % 2 == 0 and hd <= 128 and tokens % 32 == 0 and inner % 8 == 0)
+    return bool(norm_ok and qk_ok and (model.feat_rope is not None) == bool(model.use_rope) and _shapes_supported(model))
 
 
 def refused_reason(model) -> str:
@@ -111,9 +118,8 @@ def _attention(qkv, blk, rope, heads):
         q, k, v = ops.qknorm_rope(qkv, qn.weight, kn.weight, rope.freqs_cos, rope.freqs_sin, heads, qn.eps)
     if _FUSED_ATTN and ops.attention_heads_supported(n, d):
         return ops.attention_heads(q, k, v, b, d ** -0.5)
-    p = ops.softmax_rows(ops.gemm_nt(q, k, out_f32=True), d ** -0.5)            # [B*H, N, N] bf16
-    o = ops.gemm_nt(p, ops.transpose_last2(v))                                  # [B*H, N, D]
-    return o.view(b, heads, n, d).permute(0, 2, 1, 3).reshape(b, n, c)
+    from ..functional import _heads_attention
+    return _heads_attention(q, k, v, b, d ** -0.5, fused=False)[0]               # composed: QK^T GEMM, f32 softmax, PV GEMM
 
 
 def _t_embed(model, t: torch.Tensor, train: bool = False) -> torch.Tensor:
@@ -172,7 +178,6 @@ def forward_inference(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) 
         bb = [bv if bv.dtype == _BF else _bf(bv) for bv in (l.bias for l in lins)]
         mods = ops.linear_rows_batched(scb, wb, bb)                               # [L, B, 6C]
     pend = None                                                                   # (y, mod, gate offset) of the previous block's MLP branch, not yet added to h
-    from .lightningdit import SwiGLUFFN
     from ..functional import dit_mod_offsets
     sh1, sc1, g1, sh2, sc2, g2 = dit_mod_offsets(c, bool(model.blocks) and model.blocks[0].wo_shift)      # the default block: 0, C, 2C, 3C, 4C, 5C
     for i, blk in enumerate(model.blocks):
@@ -181,12 +186,12 @@ def forward_inference(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) 
         qkv = linear(a, blk.attn.qkv.weight, blk.attn.qkv.bias)
         o = linear(_attention(qkv, blk, model.feat_rope, heads), blk.attn.proj.weight, blk.attn.proj.bias)
         a = _norm_modulate(blk.norm2, h, mod, sh2, sc2, (o, mod, g1))
-        if isinstance(blk.mlp, SwiGLUFFN):
-            g = linear(a, blk.mlp.w12.weight, blk.mlp.w12.bias, ops.ACT_SWIGLU)    # silu(x1) * x2 in the GEMM's epilogue: x12 never reaches HBM
-            pend = (linear(g, blk.mlp.w3.weight, blk.mlp.w3.bias), mod, g2)
+        swiglu, f1, f2 = _mlp(blk)
+        if swiglu:
+            g = linear(a, f1.weight, f1.bias, ops.ACT_SWIGLU)                      # silu(x1) * x2 in the GEMM's epilogue: x12 never reaches HBM
         else:                                                                      # fc1 -> tanh-GELU (its own pass, csrc/dit_variants.hip) -> fc2
-            g = ops.gelu_tanh(linear(a, blk.mlp.fc1.weight, blk.mlp.fc1.bias).contiguous())
-            pend = (linear(g, blk.mlp.fc2.weight, blk.mlp.fc2.bias), mod, g2)
+            g = ops.gelu_tanh(linear(a, f1.weight, f1.bias).contiguous())
+        pend = (linear(g, f2.weight, f2.bias), mod, g2)
     mod = adaln(fl.adaLN_modulation[1])                                           # [B, 2C]: shift | scale (the final layer always has its shift)
     a = _norm_modulate(fl.norm_final, h, mod, 0, c, pend)
     out = model.unpatchify(linear(a, fl.linear.weight, fl.linear.bias))
@@ -333,7 +338,6 @@ STACK_FN = True      # forward_train: all blocks as one functional.DitStackFn no
 def tokens1_supported(model, x: torch.Tensor) -> bool:
     """The one-token configuration of the 2-D toy (toy_example_2d/dmd.py:436-454: LightningDiT-Mini/1 with input_size = 1): RoPE + RMSNorm + SwiGLU blocks, any
     SwiGLU width (682 there), width a multiple of 8, under autocast(bf16) on the GPU."""
-    from .lightningdit import RMSNorm, SwiGLUFFN
     if not (x.is_cuda and torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == _BF):
         return False
     blk = model.blocks[0]
@@ -377,8 +381,19 @@ def forward_tokens1(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) ->
         w12, b12, w3 = _swiglu_operands(blk)
         g = SwigluFn.apply(LinearFn.apply(a2, w12, b12))
         h = GatedResidualFn.apply(h, LinearFn.apply(g, w3, blk.mlp.w3.bias), mod, 5 * c)
-    fl = model.final_layer
-    a = RmsnormModulateFn.apply(h, fl.norm_final.weight, LinearFn.apply(sc, fl.adaLN_modulation[1].weight, fl.adaLN_modulation[1].bias), 0, c, fl.norm_final.eps)
+    return _final_layer_train(model, h, sc)
+
+
+def _final_layer_train(model, h: torch.Tensor, sc: torch.Tensor) -> torch.Tensor:
+    """FinalLayer (lightningdit.py:260-273) with gradients on the residual stream h and sc = SiLU(conditioning): the adaLN Linear, the norm + modulate by the norm's
+    kind (`RmsnormModulateFn`, or `LayernormModulateFn` for use_rmsnorm=False), the output Linear; then unpatchify and the `learn_sigma` split."""
+    from ..functional import LayernormModulateFn, LinearFn, RmsnormModulateFn
+    fl, c = model.final_layer, model.hidden_size
+    mod = LinearFn.apply(sc, fl.adaLN_modulation[1].weight, fl.adaLN_modulation[1].bias)      # [B, 2C]: shift | scale (the final layer always has its shift)
+    if getattr(fl.norm_final, "weight", None) is not None:
+        a = RmsnormModulateFn.apply(h, fl.norm_final.weight, mod, 0, c, fl.norm_final.eps)
+    else:
+        a = LayernormModulateFn.apply(h, mod, 0, c, fl.norm_final.eps)
     out = model.unpatchify(LinearFn.apply(a, fl.linear.weight, fl.linear.bias))
     if model.learn_sigma:
         out, _ = out.chunk(2, dim=1)
@@ -387,10 +402,11 @@ def forward_tokens1(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) ->
 
 def forward_train(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """`forward` with gradients (the student's flow-matching turn, train_dmd.py:565-575) under the caller's autocast(bf16): timestep / label embedders
-    and the per-sample adaLN Linears through stock autograd, the patch embedding and the output Linear as `functional.LinearFn`, every block as one `functional.DitBlockFn`,
-    the final norm as `RmsnormModulateFn`.  Label dropout as in the module (`y_embedder(y, model.training)`)."""
+    and the per-sample adaLN Linears through stock autograd, the patch embedding and the output Linear as `functional.LinearFn`, the blocks of the default
+    configuration as `functional.DitStackFn` segments, else every block -- default or variant -- as one `functional.DitBlockFn` whose arguments are read off the
+    block (an absent parameter is None), the final layer as `_final_layer_train`.  Label dropout as in the module (`y_embedder(y, model.training)`)."""
     from .. import functional as Fn
-    from ..functional import DitBlockFn, DitStackFn, LinearFn, RmsnormModulateFn
+    from ..functional import DitBlockFn, DitStackFn, LinearFn
     Fn._OWNED_GRADS.clear()
     b, cin, hh, ww = x.shape
     ps, c, heads = model.patch_size, model.hidden_size, model.num_heads
@@ -400,9 +416,9 @@ def forward_train(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) -> t
     cvec = _t_embed(model, t, train=True).float() + model.y_embedder(y, model.training)      # the embedding lookup (and its index-add backward) is not a GEMM
     sc = F.silu(cvec)                                                             # adaLN_modulation[0] of every block: the same f32 values, computed once
     rope = model.feat_rope
-    if not structurally_supported(model):
-        return _forward_train_variant(model, h, sc)
-    stack = STACK_FN and Fn.dit_stack_supported(b, h.shape[1], c, heads)
+    cos, sin = (None, None) if rope is None else (rope.freqs_cos, rope.freqs_sin)
+    # `DitStackFn`, its grouped weight gradients and its stream-K scoping assume the default block
+    stack = STACK_FN and structurally_supported(model) and Fn.dit_stack_supported(b, h.shape[1], c, heads)
     if stack:
         # One node per SEGMENT of blocks.  A single process takes all blocks as one segment; under data parallelism the gradients of a node reach autograd -- and
         # FlatGradSync's post-accumulate hooks, which start a bucket's all-reduce -- only when the node returns, so the stack is cut into STACK_SEGMENTS_DP nodes:
@@ -416,44 +432,12 @@ def forward_train(model, x: torch.Tensor, t: torch.Tensor, y: torch.Tensor) -> t
                 params += [blk.norm1.weight, blk.attn.qkv.weight, blk.attn.qkv.bias, blk.attn.q_norm.weight, blk.attn.k_norm.weight, blk.attn.proj.weight,
                            blk.attn.proj.bias, blk.norm2.weight, blk.mlp.w12.weight, blk.mlp.w12.bias, blk.mlp.w3.weight, blk.mlp.w3.bias,
                            blk.adaLN_modulation[1].weight, blk.adaLN_modulation[1].bias]
-            h = DitStackFn.apply(h, sc, rope.freqs_cos, rope.freqs_sin, heads, model.blocks[0].norm1.eps, *params)
+            h = DitStackFn.apply(h, sc, cos, sin, heads, model.blocks[0].norm1.eps, *params)
+    wt = lambda m: getattr(m, "weight", None)                                     # None: affine-free LayerNorm, no QK-norm (nn.Identity)
     for blk in (() if stack else model.blocks):
         lin = blk.adaLN_modulation[1]
-        mod = LinearFn.apply(sc, lin.weight, lin.bias)                            # [B, 6C] bf16; one row per sample: csrc/linear_rows.hip forward and input gradient
-        h = DitBlockFn.apply(h, mod, blk.norm1.weight, blk.attn.qkv.weight, blk.attn.qkv.bias, blk.attn.q_norm.weight, blk.attn.k_norm.weight,
-                             blk.attn.proj.weight, blk.attn.proj.bias, blk.norm2.weight, blk.mlp.w12.weight, blk.mlp.w12.bias, blk.mlp.w3.weight,
-                             blk.mlp.w3.bias, rope.freqs_cos, rope.freqs_sin, heads, blk.norm1.eps)
-    fl = model.final_layer
-    a = RmsnormModulateFn.apply(h, fl.norm_final.weight, LinearFn.apply(sc, fl.adaLN_modulation[1].weight, fl.adaLN_modulation[1].bias), 0, c, fl.norm_final.eps)
-    out = model.unpatchify(LinearFn.apply(a, fl.linear.weight, fl.linear.bias))
-    if model.learn_sigma:
-        out, _ = out.chunk(2, dim=1)
-    return out
-
-
-def _forward_train_variant(model, h: torch.Tensor, sc: torch.Tensor) -> torch.Tensor:
-    """The blocks and the final layer of `forward_train` for a variant model (`variant_supported`): one `functional.DitBlockVarFn` per block behind its `LinearFn`
-    adaLN modulation, the final norm by its kind.  `DitStackFn`, the grouped weight gradients and the stream-K scoping stay with the default block."""
-    from ..functional import DitBlockVarFn, LayernormModulateFn, LinearFn, RmsnormModulateFn
-    from .lightningdit import SwiGLUFFN
-    c, heads = model.hidden_size, model.num_heads
-    rope = model.feat_rope
-    cos, sin = (None, None) if rope is None else (rope.freqs_cos, rope.freqs_sin)
-    w = lambda m: getattr(m, "weight", None)
-    for blk in model.blocks:
-        lin = blk.adaLN_modulation[1]
-        mod = LinearFn.apply(sc, lin.weight, lin.bias)                            # [B, 6C] or [B, 4C] bf16
-        swiglu = isinstance(blk.mlp, SwiGLUFFN)
-        f1, f2 = (blk.mlp.w12, blk.mlp.w3) if swiglu else (blk.mlp.fc1, blk.mlp.fc2)
-        h = DitBlockVarFn.apply(h, mod, w(blk.norm1), blk.attn.qkv.weight, blk.attn.qkv.bias, w(blk.attn.q_norm), w(blk.attn.k_norm), blk.attn.proj.weight,
-                                blk.attn.proj.bias, w(blk.norm2), f1.weight, f1.bias, f2.weight, f2.bias, cos, sin, heads, blk.norm1.eps, bool(blk.wo_shift), swiglu)
-    fl = model.final_layer
-    mod = LinearFn.apply(sc, fl.adaLN_modulation[1].weight, fl.adaLN_modulation[1].bias)
-    if w(fl.norm_final) is not None:
-        a = RmsnormModulateFn.apply(h, fl.norm_final.weight, mod, 0, c, fl.norm_final.eps)
-    else:
-        a = LayernormModulateFn.apply(h, mod, 0, c, fl.norm_final.eps)
-    out = model.unpatchify(LinearFn.apply(a, fl.linear.weight, fl.linear.bias))
-    if model.learn_sigma:
-        out, _ = out.chunk(2, dim=1)
-    return out
+        mod = LinearFn.apply(sc, lin.weight, lin.bias)                            # [B, 6C] or [B, 4C] bf16; one row per sample: csrc/linear_rows.hip forward and input gradient
+        swiglu, f1, f2 = _mlp(blk)
+        h = DitBlockFn.apply(h, mod, wt(blk.norm1), blk.attn.qkv.weight, blk.attn.qkv.bias, wt(blk.attn.q_norm), wt(blk.attn.k_norm), blk.attn.proj.weight,
+                             blk.attn.proj.bias, wt(blk.norm2), f1.weight, f1.bias, f2.weight, f2.bias, cos, sin, heads, blk.norm1.eps, bool(blk.wo_shift), swiglu)
+    return _final_layer_train(model, h, sc)

@@ -36,6 +36,20 @@ SEEDS = {"dit_var_plain": 81, "dit_var_noqk": 82, "dit_var_woshift": 83, "dit_va
 # the one combination that stays outside the kernels: an affine nn.LayerNorm(head_dim) on q and k
 CFG_LAYERNORM_QK = dict(_BASE, hidden_size=192, num_heads=3, use_qknorm=True, use_rmsnorm=False)
 
+# The frozen-against-trainable cases of test_gpu_dit_variants.py: (hidden, heads, grid side) per attention regime of `functional.DitBlockFn`, times three
+# configurations.  Two things about these models follow from the predicates, not from a choice (test_dit_variants_cpu.py asserts both):
+#  * the token count is a square that is a multiple of 32 (64, 256, 576, ...), so the smallest model above the resident kernels' 288 tokens has 24 x 24 = 576
+#    -- a 320-token LightningDiT cannot be built;
+#  * at the constructor's mlp_ratio = 4 the SwiGLU widths of hidden 128 and 64 are 341 and 170, no multiples of 8: mlp_ratio = 3 gives 256 and 128.
+FROZEN_SHAPES = {"resident": (128, 2, 8), "streaming": (128, 2, 24), "composed": (64, 2, 8)}      # composed: head dim 32, outside the fused kernels
+FROZEN_CONFIGS = {"default": {}, "noqk": dict(use_qknorm=False), "plain": dict(use_rmsnorm=False, use_qknorm=False, use_swiglu=False, wo_shift=True)}
+MLP_RATIO = 3.0
+
+
+def frozen_case_cfg(shape):
+    hidden, heads, side = FROZEN_SHAPES[shape]
+    return dict(input_size=side, patch_size=1, in_channels=16, hidden_size=hidden, depth=2, num_heads=heads, mlp_ratio=MLP_RATIO, num_classes=10)
+
 
 def flags(kw):
     """the five switches of a configuration with the constructor's defaults filled in"""

@@ -89,6 +89,33 @@ def test_predicates_route_variants_and_keep_the_default_guards():
     assert not fast.variant_supported(LightningDiT(**dict(V._BASE, input_size=5), hidden_size=192, num_heads=3, use_rope=False))      # 25 tokens
 
 
+def test_one_block_function_and_one_train_loop():
+    """The variant copies are gone, not aliased: `DitBlockFn` and `forward_train` serve every configuration."""
+    from dmvae_amd import functional
+    from dmvae_amd.models import lightningdit_fast as fast
+    assert hasattr(functional, "DitBlockFn") and not hasattr(functional, "DitBlockVarFn")
+    assert hasattr(fast, "forward_train") and not hasattr(fast, "_forward_train_variant")
+
+
+def test_frozen_bit_identity_models_sit_in_the_attention_regime_they_are_named_for():
+    """The shapes and configurations of test_gpu_dit_variants.py's frozen / trainable cases, by the predicates alone: each shape's attention regime, and that the
+    kernels take every model (the default through `structurally_supported`, the two variants through `variant_supported`).  With the constructor's mlp_ratio of 4
+    the SwiGLU widths of hidden 128 and 64 (341, 170) are no multiples of 8 and both predicates refuse: hence `MLP_RATIO`."""
+    from dmvae_amd import ops
+    from dmvae_amd.models import lightningdit_fast as fast
+    from dmvae_amd.models.lightningdit import LightningDiT
+    want = {"resident": (True, True), "streaming": (True, False), "composed": (False, True)}      # (fused attention, within the resident kernels' tokens)
+    assert set(V.FROZEN_SHAPES) == set(want)
+    for name, (hidden, heads, side) in V.FROZEN_SHAPES.items():
+        n, d = side * side, hidden // heads
+        assert (ops.attention_heads_supported(n, d), n <= ops.ATTENTION_RESIDENT_MAX) == want[name], name
+        for cname, sw in V.FROZEN_CONFIGS.items():
+            m = LightningDiT(**V.frozen_case_cfg(name), **sw).eval()
+            assert (fast.structurally_supported(m), fast.variant_supported(m)) == ((True, False) if cname == "default" else (False, True)), (name, cname)
+            four = LightningDiT(**dict(V.frozen_case_cfg(name), mlp_ratio=4.0), **sw)
+            assert sw.get("use_swiglu", True) == (not (fast.structurally_supported(four) or fast.variant_supported(four))), (name, cname)
+
+
 def test_forward_on_the_cpu_still_raises_without_the_opt_in(monkeypatch):
     from dmvae_amd._lib import DmvaeHipError
     from dmvae_amd.models.lightningdit import LightningDiT

@@ -216,7 +216,8 @@ def _twin(tag):
 
 
 def _count_new_ops(mp, counts):
-    """Wraps the ops that only a variant reaches: the entry points of csrc/dit_variants.hip, and the RMSNorm kernels' no-shift form."""
+    """Wraps the ops that only a variant reaches: the entry points of csrc/dit_variants.hip, and the RMSNorm kernels' no-shift form.  Also the default block's own
+    head split (`qknorm_rope`, `qknorm_rope_bwd`: the per-block training route of every configuration with QK-norm and RoPE)."""
     from dmvae_amd import ops
 
     def wrap(name, key, is_hit=lambda a, kw: True):
@@ -237,6 +238,8 @@ def _count_new_ops(mp, counts):
     wrap("gated_residual_rmsnorm_modulate_", "no_shift", lambda a, kw: a[6] < 0)
     wrap("gated_residual_out", "no_shift", lambda a, kw: len(a) > 4 and a[4] is not None and a[6] < 0)
     wrap("rmsnorm_modulate_bwd_", "no_shift_bwd", lambda a, kw: a[6] < 0)
+    wrap("qknorm_rope", "qknorm_rope")
+    wrap("qknorm_rope_bwd", "qknorm_rope_bwd")
 
 
 def _expected_new_ops(tag, grad):
@@ -402,6 +405,88 @@ def test_plain_variant_above_288_tokens_streams_its_attention(monkeypatch):
             continue
         assert p.grad is not None, n_
         assert _rl2(p.grad, pb[n_].grad) < 4e-2, (n_, _rl2(p.grad, pb[n_].grad))
+
+
+# ---- one block Function (`functional.DitBlockFn`) for the default and the variant blocks ---------------------------------------------------
+def _frozen_case(shape, config):
+    """A depth-2 model of dit_variants_spec.FROZEN_SHAPES x FROZEN_CONFIGS with deterministic non-zero weights, and B = 2 inputs."""
+    from dmvae_amd.models import lightningdit_fast as LF
+    from dmvae_amd.models.lightningdit import LightningDiT
+    from oracle.detweights import det_fill_
+    cfg = V.frozen_case_cfg(shape)
+    m = det_fill_(LightningDiT(**cfg, **V.FROZEN_CONFIGS[config]).eval(), 91, skip=("pos_embed",)).to(DEV)
+    assert LF.structurally_supported(m) if config == "default" else LF.variant_supported(m)
+    side = cfg["input_size"]
+    gen = torch.Generator().manual_seed(17)
+    x = torch.randn(2, 16, side, side, generator=gen).to(DEV)
+    t, y = torch.rand(2, generator=gen).to(DEV), torch.tensor([3, 7], device=DEV)
+    dy = torch.randn(2, 16, side, side, generator=gen).to(DEV)
+    return m, x, t, y, dy
+
+
+def _fwd_bwd(m, x, t, y, dy, before_backward=lambda: None):
+    m.zero_grad(set_to_none=True)
+    xa = x.clone().requires_grad_(True)
+    with torch.autocast("cuda", dtype=BF):
+        out = m(xa, t, y)
+    before_backward()
+    (out.float() * dy).sum().backward()
+    return out.detach(), xa.grad
+
+
+def test_default_block_reaches_no_variant_kernel(monkeypatch):
+    """The default model on the per-block route (`STACK_FN` False: `DitBlockFn`, the Function the variants share) and on the stack route: no entry point of
+    csrc/dit_variants.hip and no no-shift launch, forward or backward; per block its own `qknorm_rope` / `qknorm_rope_bwd`, never `head_split`."""
+    from dmvae_amd.models import lightningdit_fast as LF
+    m, x, t, y, dy = _frozen_case("resident", "default")
+    for stack in (False, True):
+        counts = {}
+        with monkeypatch.context() as mp:
+            mp.setattr(LF, "STACK_FN", stack)
+            _count_new_ops(mp, counts)
+            out, dx = _fwd_bwd(m, x, t, y, dy)
+        assert out.float().abs().max() > 0 and dx.abs().max() > 0
+        own = {k: counts.pop(k, 0) for k in ("qknorm_rope", "qknorm_rope_bwd")}
+        assert not any(counts.values()), (stack, counts)
+        if not stack:
+            assert own["qknorm_rope"] == len(m.blocks) and own["qknorm_rope_bwd"] == len(m.blocks), own
+
+
+@pytest.mark.parametrize("config", list(V.FROZEN_CONFIGS))
+@pytest.mark.parametrize("shape", list(V.FROZEN_SHAPES))
+def test_frozen_and_trainable_runs_give_the_same_input_gradient_bits(shape, config, monkeypatch):
+    """`DitBlockFn` with no parameter needing a gradient (`need_w` False: dx-only Linear backward, no norm-weight sums) against the same model trainable: the same
+    output and the same d x bit for bit, no parameter gradient -- in each attention regime (resident, streaming with lse, composed with the saved P) and for the
+    default block (per-block route), the default without QK-norm, and LayerNorm + GELU-MLP + `wo_shift` without QK-norm."""
+    from dmvae_amd.models import lightningdit_fast as LF
+    monkeypatch.setattr(LF, "STACK_FN", False)
+    m, x, t, y, dy = _frozen_case(shape, config)
+    out, dx = _fwd_bwd(m, x, t, y, dy)
+    assert out.float().abs().max() > 0 and dx.abs().max() > 0
+    assert all(p.grad is not None for n, p in m.named_parameters() if n != "pos_embed")
+    m.requires_grad_(False)
+    out_f, dx_f = _fwd_bwd(m, x, t, y, dy)
+    assert torch.equal(out_f, out) and torch.equal(dx_f, dx)
+    assert all(p.grad is None for p in m.parameters())
+
+
+def test_frozen_default_block_does_no_weight_gradient_work(monkeypatch):
+    """The frozen default model on the per-block route: its backward reaches none of the weight-gradient entry points (before the default block shared the variants'
+    Function it computed every weight gradient and dropped it)."""
+    from dmvae_amd import ops
+    from dmvae_amd.models import lightningdit_fast as LF
+    monkeypatch.setattr(LF, "STACK_FN", False)
+    m, x, t, y, dy = _frozen_case("resident", "default")
+    m.requires_grad_(False)
+    calls = []
+
+    def watch():
+        for name in ("conv2d_nhwc_wgrad", "linear_wgrad_grouped", "linear_rows_wgrad"):
+            fn = getattr(ops, name)
+            monkeypatch.setattr(ops, name, lambda *a, _fn=fn, _name=name, **kw: (calls.append(_name), _fn(*a, **kw))[1])
+    out, dx = _fwd_bwd(m, x, t, y, dy, before_backward=watch)
+    assert dx.abs().max() > 0 and not calls, calls
+    assert all(p.grad is None for p in m.parameters())
 
 
 # ---- riders: what sits above `forward` works for a variant with no code of its own ----------------------------------------------------------

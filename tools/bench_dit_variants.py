@@ -6,7 +6,7 @@
   noqk  : the default block without QK-norm,
 
 at B = 16 under autocast(bf16), two cases each: the inference forward (frozen weights, no gradient: lightningdit_fast.forward_inference) and forward + backward
-(trainable weights: lightningdit_fast.forward_train, functional.DitBlockVarFn), each against the SAME model's `forward_stock` (ATen / library kernels) under the
+(trainable weights: lightningdit_fast.forward_train, one functional.DitBlockFn per block), each against the SAME model's `forward_stock` (ATen / library kernels) under the
 same autocast.  The yardstick is the stock route on the same box in the same process, not an earlier run of this code.  The two routes alternate within every
 round after one untimed round; a round times `--iters` calls between two device events.  Prints one JSON line per configuration: milliseconds per call (median
 over the rounds, and every round), the spread of each series ((max - min) / median), the ratio HIP / stock, whether the gap exceeds both spreads, the rel-L2
