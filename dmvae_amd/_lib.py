@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_longlong, c_size_t, c_uint, c_ulonglong, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_longlong, c_size_t, c_uint, c_ulonglong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DMVAE_LIB") or os.path.join(_HERE, "libdmvae_hip.so")      # DMVAE_LIB: another build of the same ABI (kernel A/B runs on one box)
@@ -275,6 +275,9 @@ SIGNATURES = {
     "dmvae_lanczos_kmax": (c_int, [c_int, c_int]),
     "dmvae_lanczos_table": (c_int, [c_int] * 5 + [c_void_p] * 3),
     "dmvae_image_preprocess": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    # SSIM: f64 windowed moments, one partial per (plane, tile), fixed-order sums (csrc/ssim.hip)
+    "dmvae_ssim_workspace": (c_size_t, [c_size_t, c_int, c_int, c_int]),
+    "dmvae_ssim": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,79 @@
+"""The reference's reconstruction metrics (evaluation/metrics.py) under its own names: `PSNR`, `SSIM`, `LPIPS`.
+
+`SSIM(pred, gt, data_range=1.0)` has the reference's signature and return pair -- (per-image values [T], their mean) for images in [-1, 1] -- without
+torchmetrics: the 11 x 11 Gaussian window moments, the SSIM map and its mean are one HIP kernel in f64 (csrc/ssim.hip through `ops.ssim`), deterministic.
+torchmetrics runs the same algorithm in the inputs' dtype; in f32 its `E[x^2] - mu^2` loses 3e-5 ... 7e-5 of the per-image value (1e-4 ... 4e-4 with the
+newer versions' variance clamp) on near-identical flat images, exactly where a good tokenizer lives (tests/test_ssim_cpu.py prints the figures), so the
+two agree to f32's error, not to f64's.  `ssim01` is the same for images already in [0, 1] and returns the f64 values.  bf16 images are widened to f32
+first: the value is that of `SSIM(pred.float(), gt.float())`.
+
+CPU tensors take a plain-torch f64 composition behind `DMVAE_ALLOW_STOCK=1`, like every other module (dmvae_amd/_stock.py).
+
+`LPIPS` is not built (see its message)."""
+from __future__ import annotations
+
+from typing import Tuple
+
+import torch
+
+from . import _stock, ops
+from .evaluate import psnr as PSNR
+
+__all__ = ["PSNR", "SSIM", "LPIPS", "ssim01"]
+
+_WIN, _SIGMA, _K1, _K2 = 11, 1.5, 0.01, 0.03
+
+
+def _stock_ssim01(p: torch.Tensor, t: torch.Tensor, data_range: float) -> torch.Tensor:
+    """The CPU route: the valid 11 x 11 filter over the raw images in f64 (what torchmetrics' pad / filter / crop leaves), per-image mean."""
+    p, t = p.double(), t.double()
+    c = p.shape[1]
+    d = torch.arange(_WIN, dtype=torch.float64) - _WIN // 2
+    g = torch.exp(-(d / _SIGMA) ** 2 / 2)
+    g = g / g.sum()
+    kernel = torch.outer(g, g).expand(c, 1, _WIN, _WIN)
+    c1, c2 = (_K1 * data_range) ** 2, (_K2 * data_range) ** 2
+    mp, mt, epp, ett, ept = (torch.nn.functional.conv2d(x, kernel, groups=c) for x in (p, t, p * p, t * t, p * t))
+    sp, st, spt = epp - mp * mp, ett - mt * mt, ept - mp * mt
+    m = ((2 * mp * mt + c1) * (2 * spt + c2)) / ((mp * mp + mt * mt + c1) * (sp + st + c2))
+    return m.flatten(1).mean(-1)
+
+
+def _ssim(a: torch.Tensor, b: torch.Tensor, data_range: float, from_pm1: bool, what: str) -> torch.Tensor:
+    if a.dim() != 4 or a.shape != b.shape or a.numel() == 0:
+        raise ValueError(f"{what}: expected two non-empty [T, C, H, W] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape[-1] < _WIN or a.shape[-2] < _WIN:
+        raise ValueError(f"{what}: H and W must be at least {_WIN} (the window has no output below that; torchmetrics returns NaN), got {tuple(a.shape)}")
+    data_range = float(data_range)
+    if not (data_range > 0 and data_range != float("inf")):
+        raise ValueError(f"{what}: data_range must be finite and positive, got {data_range}")
+    if a.dtype != b.dtype or a.dtype not in (torch.float32, torch.bfloat16):
+        a, b = a.float(), b.float()
+    if a.is_cuda:
+        return ops.ssim(a.contiguous(), b.contiguous(), data_range=data_range, from_pm1=from_pm1)
+    _stock.require_opt_in(what, "CPU images")
+    a, b = a.float(), b.float()
+    if from_pm1:
+        a, b = a.add(1).mul(0.5), b.add(1).mul(0.5)
+    return _stock_ssim01(a, b, data_range)
+
+
+@torch.no_grad()
+def ssim01(img1: torch.Tensor, img2: torch.Tensor, data_range: float = 1.0) -> torch.Tensor:
+    """[T, C, H, W] images already scaled to [0, 1] -> per-image SSIM, f64 [T]."""
+    return _ssim(img1, img2, data_range, False, "metrics.ssim01")
+
+
+@torch.no_grad()
+def SSIM(pred: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """evaluation/metrics.py:16-23: [T, C, H, W] images in [-1, 1] -> (per-image SSIM [T], their mean), f32 as the reference returns for f32 inputs; the
+    values are computed in f64 and rounded once, the mean is taken over the f64 values."""
+    v = _ssim(pred, gt, data_range, True, "metrics.SSIM")
+    return v.float(), v.mean().float()
+
+
+def LPIPS(img1, img2, net_type="alex"):
+    """evaluation/metrics.py:26-29 builds torchmetrics' LearnedPerceptualImagePatchSimilarity, whose AlexNet backbone and linear heads are weights neither this
+    package nor the reference repo holds; `dmvae_amd.losses` / utils/lpips.py is the TRAINING loss's VGG16 LPIPS, a different network with different numbers."""
+    raise NotImplementedError("metrics.LPIPS is not built: the reference's evaluation LPIPS is torchmetrics' AlexNet network, whose weights are not part of this "
+                              "package or of the reference repo, and utils/lpips.py is the training loss's VGG16 -- not a substitute for it")

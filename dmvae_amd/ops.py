@@ -2142,6 +2142,26 @@ def fid_resize_u8(images: torch.Tensor, size: int) -> torch.Tensor:
     return out
 
 
+# ---- SSIM (csrc/ssim.hip) --------------------------------------------------------------------------
+def ssim(a: torch.Tensor, b: torch.Tensor, *, data_range: float = 1.0, from_pm1: bool = False) -> torch.Tensor:
+    """Per-image SSIM of a against b, both [B, C, H, W] f32 or bf16 (one dtype), H, W >= 11 -> f64 [B]: torchmetrics' defaults (11 x 11 Gaussian window,
+    sigma 1.5, k1 0.01, k2 0.03) with the window moments in f64; `from_pm1` maps both inputs from [-1, 1] with (x + 1) * 0.5 in f32 first
+    (evaluation/metrics.py:18-19).  Deterministic; an image's value does not depend on its batch (include/dmvae_hip.h: dmvae_ssim)."""
+    a = _req(a, bf16 if a.dtype == bf16 else f32, "a")
+    b = _req(b, a.dtype, "b")
+    if a.dim() != 4 or a.numel() == 0:
+        raise ValueError(f"a: expected a non-empty [B, C, H, W], got {tuple(a.shape)}")
+    if b.shape != a.shape or b.device != a.device:
+        raise ValueError(f"b: expected {tuple(a.shape)} on {a.device}, got {tuple(b.shape)} on {b.device}")
+    n, c, h, w_ = a.shape
+    lib = _lib.lib()
+    ws = torch.empty(max(lib.dmvae_ssim_workspace(n, c, h, w_) // 8, 1), dtype=torch.float64, device=a.device)
+    out = torch.empty(n, dtype=torch.float64, device=a.device)
+    check(lib.dmvae_ssim(a.data_ptr(), b.data_ptr(), int(a.dtype == bf16), n, c, h, w_, int(bool(from_pm1)), float(data_range), ws.data_ptr(), out.data_ptr(),
+                         _stream()), "ssim")
+    return out
+
+
 # ---- input pipeline (csrc/data.hip) ---------------------------------------------------------------
 def lanczos_kmax(n_in: int, n_out: int) -> int:
     """Taps allotted per output index for a LANCZOS resize of one axis from n_in to n_out samples (PIL's ksize).  Host only."""

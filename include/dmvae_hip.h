@@ -1067,6 +1067,25 @@ int dmvae_lanczos_table(int in, int out, int first, int count, int kmax, int32_t
  * Reference: utils/build_dataset.py:55-66. */
 int dmvae_image_preprocess(const uint8_t* pack, const int64_t* table, const int32_t* taps, int B, int S, void* out, int out_kind, dmvae_stream_t stream);
 
+/* ---- SSIM: the structural similarity of two image batches with the window moments in f64 (csrc/ssim.hip) -------------------------------------- */
+
+/* Bytes of dmvae_ssim's workspace: one f64 partial sum per (image, channel, 32 x 16 output tile), batch * channels * ceil((w - 10) / 32) *
+ * ceil((h - 10) / 16) * 8; 0 for channels < 1, h < 11 or w < 11.  No GPU.  Reference: evaluation/metrics.py:16-23. */
+size_t dmvae_ssim_workspace(size_t batch, int channels, int h, int w);
+/* out [batch] f64 = per-image SSIM of a against b, both contiguous [batch][channels][h][w] f32 or bf16 (is_bf16 != 0, the same dtype for both), as
+ * torchmetrics' StructuralSimilarityIndexMeasure(data_range, reduction='none') defines it at its defaults: 11 x 11 Gaussian window g g^T, g[i] =
+ * exp(-((i - 5) / 1.5)^2 / 2) / sum g, k1 = 0.01, k2 = 0.03, c1 = (k1 data_range)^2, c2 = (k2 data_range)^2; per pixel ((2 mp mt + c1)(2 spt + c2)) /
+ * ((mp^2 + mt^2 + c1)(sp + st + c2)) from the window means mp, mt and sp = E[p^2] - mp^2, st = E[t^2] - mt^2, spt = E[p t] - mp mt; mean over the
+ * channels * (h - 10) * (w - 10) pixels whose window lies inside the image (torchmetrics' reflect padding by 5 and crop by 5 keep exactly those).  Elements
+ * are widened to f32, mapped with (x + 1.0f) * 0.5f in f32 when from_pm1 != 0 (inputs in [-1, 1], as evaluation/metrics.py:18-19 maps them), then widened to
+ * f64: the window weights, products, both filter passes, the moments, the SSIM value and every sum are f64.  No variance clamp (it changes nothing in f64).
+ * Two launches, no atomics: the result repeats bit for bit, and an image's value does not depend on the batch around it.  Nothing outside the two images is
+ * read; workspace (dmvae_ssim_workspace bytes) and out are written for `batch` images only.  -22 before any HIP call for a NULL pointer, h < 11 or w < 11,
+ * channels < 1, batch < 1, a data_range that is not finite and positive, or more than 2^31 - 1 (plane, tile) pairs.
+ * Reference: evaluation/metrics.py:16-23. */
+int dmvae_ssim(const void* a, const void* b, int is_bf16, size_t batch, int channels, int h, int w, int from_pm1, double data_range, void* workspace,
+               void* out, dmvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
     python run_on_mi355x.py --hip-dinodisc /path/to/dmvae/train_tokenizer.py --disc_type dino ...      (or DMVAE_HIP_DINODISC=1)
     python run_on_mi355x.py --hip-optim /path/to/dmvae/train_tokenizer.py ...                          (or DMVAE_HIP_OPTIM=1)
     python run_on_mi355x.py --hip-fid /path/to/dmvae/train_tokenizer.py ...                            (or DMVAE_HIP_FID=1)
+    python run_on_mi355x.py --hip-metrics /path/to/dmvae/script.py ...                                 (or DMVAE_HIP_METRICS=1)
 
 The reference's drivers import their model code by module path (`from models.vae import VAE`, `from utils.lpips import LPIPS`,
 `from diffusion.lightningdit.lightningdit import LightningDiT_models`, `from diffusion.transport import create_transport`; train_tokenizer.py:10-17,
@@ -27,6 +28,10 @@ process (train_tokenizer.py:382-383,415,424): multi-tensor HIP kernels over the 
 `evaluation.fid` (`from evaluation.fid import FID`, train_tokenizer.py:20, train_dmd.py:20) is an opt-in as well: `--hip-fid` in front of the script path (in any
 order with the other two), DMVAE_HIP_FID=1 or `install_shadow(ref, fid=True)` registers `dmvae_amd.fid` under that path: the resize and the f64 feature
 statistics on this build's kernels.  `FID()` as the scripts call it (feature=2048) still needs torchmetrics for the Inception network itself.
+
+`evaluation.metrics` (`PSNR`, `SSIM`, `LPIPS`) is an opt-in too: `--hip-metrics`, DMVAE_HIP_METRICS=1 or `install_shadow(ref, metrics=True)` registers
+`dmvae_amd.metrics` under that path: `SSIM` on this build's f64 kernel with no torchmetrics import, `PSNR` unchanged, `LPIPS` a NotImplementedError (its AlexNet
+weights are not here).  Without the opt-in the reference's file keeps serving it.
 
 The GVP / VP paths of `diffusion.transport` are off in the mirror by default (`dmvae_amd.transport.enable_all_paths`).  Running a script turns them on -- the
 script's own `--path_type` is the selection --; `--check` and a bare `install_shadow(ref)` leave the switch alone (`install_shadow(ref, all_paths=True)` asks)."""
@@ -75,18 +80,22 @@ def install_optim() -> dict:
     return importlib.import_module("dmvae_amd.optim").install()
 
 
-def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False, all_paths: bool = False, fid: bool = False) -> dict:
+def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False, all_paths: bool = False, fid: bool = False,
+                   metrics: bool = False) -> dict:
     """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve).
     dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them).
     optim: also replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (`install_optim`; not part of the returned dict).
     all_paths: also let the transport mirror build the GVP / VP plans (`dmvae_amd.transport.enable_all_paths`; default: left as it is).
-    fid: also shadow evaluation.fid with this build's `dmvae_amd.fid` (default: the reference's own file serves it)."""
+    fid: also shadow evaluation.fid with this build's `dmvae_amd.fid` (default: the reference's own file serves it).
+    metrics: also shadow evaluation.metrics with this build's `dmvae_amd.metrics` (default: the reference's own file serves it)."""
     out = {}
     shadows = dict(SHADOWS)
     if dinodisc:
         shadows["models.dinodisc"] = "dmvae_amd.models.dinodisc"           # DinoDisc                          (models/dinodisc.py)
     if fid:
         shadows["evaluation.fid"] = "dmvae_amd.fid"                        # FID                               (evaluation/fid.py)
+    if metrics:
+        shadows["evaluation.metrics"] = "dmvae_amd.metrics"                # PSNR, SSIM, LPIPS                 (evaluation/metrics.py)
     for path, target in shadows.items():
         parts = path.split(".")
         for i in range(1, len(parts)):
@@ -123,11 +132,14 @@ def main(argv) -> int:
     hip_dinodisc = os.environ.get("DMVAE_HIP_DINODISC", "0") not in ("", "0")
     hip_optim = importlib.import_module("dmvae_amd.optim").requested()      # DMVAE_HIP_OPTIM=1
     hip_fid = os.environ.get("DMVAE_HIP_FID", "0") not in ("", "0")
-    while argv and argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid"):
+    hip_metrics = os.environ.get("DMVAE_HIP_METRICS", "0") not in ("", "0")
+    while argv and argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid", "--hip-metrics"):
         if argv[0] == "--hip-dinodisc":
             hip_dinodisc = True
         elif argv[0] == "--hip-fid":
             hip_fid = True
+        elif argv[0] == "--hip-metrics":
+            hip_metrics = True
         else:
             hip_optim = True
         argv = argv[1:]
@@ -136,7 +148,7 @@ def main(argv) -> int:
         return 0
     if argv[0] == "--check":
         ref = argv[1] if len(argv) > 1 else None
-        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid).items():
+        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid, metrics=hip_metrics).items():
             print(f"{path:40s} -> {mod.__name__}")
         if hip_optim:
             for path, obj in install_optim().items():
@@ -144,7 +156,7 @@ def main(argv) -> int:
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid)      # the script's --path_type selects
+    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid, metrics=hip_metrics)      # the script's --path_type selects
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])
