@@ -278,6 +278,10 @@ SIGNATURES = {
     # SSIM: f64 windowed moments, one partial per (plane, tile), fixed-order sums (csrc/ssim.hip)
     "dmvae_ssim_workspace": (c_size_t, [c_size_t, c_int, c_int, c_int]),
     "dmvae_ssim": (c_int, [c_void_p, c_void_p, c_int, c_size_t, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    # sampler evaluation: torch-fidelity's TF1 bilinear resize and the Inception Score, f64, fixed-order sums (csrc/fidelity.hip)
+    "dmvae_resize_tf1_bilinear": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "dmvae_inception_score_workspace": (c_size_t, [c_size_t, c_int, c_size_t]),
+    "dmvae_inception_score": (c_int, [c_void_p, c_int, c_size_t, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

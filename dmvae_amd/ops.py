@@ -2162,6 +2162,60 @@ def ssim(a: torch.Tensor, b: torch.Tensor, *, data_range: float = 1.0, from_pm1:
     return out
 
 
+# ---- sampler evaluation (csrc/fidelity.hip) ----------------------------------------------------------
+def resize_tf1_bilinear(images_u8: torch.Tensor, size: int, nhwc: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """images_u8 uint8 [B, H, W, C] (nhwc) or [B, C, H, W] -> f32 [B, C, size, size] = (resize - 128) / 128: torch-fidelity's TF1-style bilinear rule
+    (align_corners=False: source coordinate o * (in / out), no half-pixel offset) and its extractor's normalisation, every operation in f32, equal bit for bit
+    to the index-select form (include/dmvae_hip.h: dmvae_resize_tf1_bilinear).  `out`: a contiguous f32 [B, C, size, size] on the images' device to write into."""
+    images_u8 = _req(images_u8, torch.uint8, "images_u8")
+    if images_u8.dim() != 4 or images_u8.numel() == 0:
+        raise ValueError(f"images_u8: expected a non-empty [B, H, W, C] or [B, C, H, W], got {tuple(images_u8.shape)}")
+    b, h, w_, c = images_u8.shape if nhwc else (images_u8.shape[0], images_u8.shape[2], images_u8.shape[3], images_u8.shape[1])
+    size = int(size)
+    if size < 1:
+        raise ValueError(f"size: expected size >= 1, got {size}")
+    if out is None:
+        out = torch.empty(b, c, size, size, dtype=f32, device=images_u8.device)
+    _req(out, f32, "out")
+    if tuple(out.shape) != (b, c, size, size) or out.device != images_u8.device:
+        raise ValueError(f"resize_tf1_bilinear: out must be {(b, c, size, size)} on {images_u8.device}, got {tuple(out.shape)} on {out.device}")
+    check(_lib.lib().dmvae_resize_tf1_bilinear(images_u8.data_ptr(), b, c, h, w_, int(bool(nhwc)), size, out.data_ptr(), _stream()), "resize_tf1_bilinear")
+    return out
+
+
+def inception_score(logits: torch.Tensor, order: Optional[torch.Tensor] = None, splits: int = 10) -> torch.Tensor:
+    """logits [n, classes] f32 / bf16 / f64 with unit stride along the classes (any row pitch >= classes: a view of a wider buffer is taken as it is) -> f64
+    [splits]: the Inception Score of each split of the row sequence logits[order[0]], logits[order[1]], ... (order: int64 [n] on the logits' device, every row
+    index in [0, n); None: the rows as they lie), everything in f64 (include/dmvae_hip.h: dmvae_inception_score).  Deterministic; a table gives the bits that
+    physically reordered rows give.  The table's range is checked on the device first (one reduction, one synchronisation): the kernels trust it."""
+    if not logits.is_cuda:
+        raise _lib.DmvaeHipError("logits: expected a GPU tensor; dmvae_amd has no CPU path")
+    if logits.dtype not in _FID_DTYPES:
+        raise TypeError(f"logits: expected float32, bfloat16 or float64, got {logits.dtype}")
+    if logits.dim() != 2 or logits.numel() == 0:
+        raise ValueError(f"logits: expected a non-empty [n, classes], got {tuple(logits.shape)}")
+    n, classes = logits.shape
+    if logits.stride(1) != 1 or (n > 1 and logits.stride(0) < classes):
+        logits = logits.contiguous()
+    ld = logits.stride(0) if n > 1 else classes
+    splits = int(splits)
+    if not 1 <= splits <= n:
+        raise ValueError(f"splits: expected 1 <= splits <= n = {n}, got {splits}")
+    if order is not None:
+        _req(order, torch.int64, "order")
+        if tuple(order.shape) != (n,) or order.device != logits.device:
+            raise ValueError(f"order: expected [{n}] on {logits.device}, got {tuple(order.shape)} on {order.device}")
+        lo, hi = torch.stack(torch.aminmax(order)).tolist()
+        if lo < 0 or hi >= n:
+            raise ValueError(f"order: every entry must be a row index in [0, {n}), got a range of [{lo}, {hi}]")
+    lib = _lib.lib()
+    ws = torch.empty(max(lib.dmvae_inception_score_workspace(n, classes, splits) // 8, 1), dtype=torch.float64, device=logits.device)
+    scores = torch.empty(splits, dtype=torch.float64, device=logits.device)
+    check(lib.dmvae_inception_score(logits.data_ptr(), _FID_DTYPES[logits.dtype], n, classes, ld, _ptr(order), splits, ws.data_ptr(), scores.data_ptr(),
+                                    _stream()), "inception_score")
+    return scores
+
+
 # ---- input pipeline (csrc/data.hip) ---------------------------------------------------------------
 def lanczos_kmax(n_in: int, n_out: int) -> int:
     """Taps allotted per output index for a LANCZOS resize of one axis from n_in to n_out samples (PIL's ksize).  Host only."""

@@ -1,7 +1,9 @@
 """The sampling loop of the reference's sample_50k.py (`sample`, :62-164) as a reusable pipeline: class labels split over ranks, noise -> SDE / ODE sampler
 on LightningDiT -> tokens -> `vae.decode` -> uint8 -> `"{index:06d}.png"`.  torch_fidelity's FID / Inception Score over the written folder
-(:171-209) are evaluation and not built here; `dmvae_amd.fid.FID` (resize, quantisation and f64 statistics on HIP kernels around an extractor the caller brings)
-is not fed from this loop.
+(:171-209) are `dmvae_amd.fidelity.FidelityMetrics` (its resize, the f64 feature statistics and the Inception Score on HIP kernels around an extractor the
+caller brings -- the Inception network is not built here): `run(..., metrics=m)` feeds it each batch's uint8 tensor straight from device memory, so the PNG
+folder is optional (`write_png=False`), and `m.update_folder(dir)` scores a folder written earlier.  `dmvae_amd.fid.FID` (torchmetrics' protocol: float
+images, bicubic resize, re-quantisation) is the tokenizer trainers' metric and is not fed from this loop.
 
 Device work per batch: `num_sampling_steps` DiT forwards on the HIP kernels + one fused state update each (transport.py), then the flux decoder forward and
 ONE conversion kernel to channels-last uint8 (`VAE.decode_uint8`), so the host receives 196 KB per image instead of the f32 NCHW tensor.  PNG encoding
@@ -191,13 +193,18 @@ class SamplePipeline:
             return self.vae.decode_uint8(tok), tok
 
     def run(self, sample_dir: str, *, per_proc_batch_size=25, num_fid_samples=50000, num_classes=1000, rank=0, world_size=1, device="cuda",
-            max_iterations: Optional[int] = None) -> int:
-        """The loop of sample_50k.py:126-157 for this rank; returns the number of images written."""
-        os.makedirs(sample_dir, exist_ok=True)
+            max_iterations: Optional[int] = None, metrics=None, write_png: bool = True) -> int:
+        """The loop of sample_50k.py:126-157 for this rank; returns the number of images sampled.  `metrics` (a `dmvae_amd.fidelity.FidelityMetrics` on
+        `device`): each batch's device uint8 tensor and its file indices go to `metrics.update_uint8` before the PNG writer -- or, with `write_png=False`,
+        instead of it: nothing is written and `sample_dir` is not created."""
+        if not write_png and metrics is None:
+            raise ValueError("SamplePipeline.run: write_png=False without metrics would sample images and drop them")
+        if write_png:
+            os.makedirs(sample_dir, exist_ok=True)
         n = per_proc_batch_size
         ys, idx = labels_and_indices(num_fid_samples, num_classes, world_size, rank, n)
         latent_size = int(round(self.model.x_embedder.num_patches ** 0.5)) * self.model.patch_size
-        writer, done = _PngWriter(), 0
+        writer, done = _PngWriter() if write_png else None, 0
         try:
             for it, (yl, il) in enumerate(zip(ys, idx)):
                 if max_iterations is not None and it >= max_iterations:
@@ -205,12 +212,16 @@ class SamplePipeline:
                 z = torch.randn(n, self.model.in_channels, latent_size, latent_size, device=device)
                 y = torch.tensor(yl, device=device)
                 u8, _ = self.images_uint8(z, y)
-                host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
-                host.copy_(u8, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                writer.put(host, [os.path.join(sample_dir, f"{i:06d}.png") for i in il], ev)
+                if metrics is not None:
+                    metrics.update_uint8(u8, torch.tensor(il, dtype=torch.int64, device=device), nhwc=True)
+                if writer is not None:
+                    host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+                    host.copy_(u8, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    writer.put(host, [os.path.join(sample_dir, f"{i:06d}.png") for i in il], ev)
                 done += n
         finally:
-            writer.close()
+            if writer is not None:
+                writer.close()
         return done

@@ -1086,6 +1086,37 @@ size_t dmvae_ssim_workspace(size_t batch, int channels, int h, int w);
 int dmvae_ssim(const void* a, const void* b, int is_bf16, size_t batch, int channels, int h, int w, int from_pm1, double data_range, void* workspace,
                void* out, dmvae_stream_t stream);
 
+/* ---- sampler evaluation: torch-fidelity's resize in front of the Inception network and the Inception Score behind it (csrc/fidelity.hip) ------- */
+
+/* out [batch][channels][s][s] f32 = ((resize(img) - 128) / 128) of uint8 images img, [batch][h][w][channels] when nhwc != 0, else [batch][channels][h][w]:
+ * torch-fidelity's `interpolate_bilinear_2d_like_tensorflow1x` with align_corners=False (the TF1 rule: no half-pixel offset) and the normalisation of its
+ * Inception extractor, restated from their published form -- agreement with the library itself has not been run.  Per output (oy, ox), every operation in
+ * f32 and rounded once (no FMA contraction): sy = (float)((double)h / s), gy = (float)oy * sy, y0 = (int)gy, y1 = min(y0 + 1, h - 1), dy = gy - (float)y0,
+ * the same along x; top = a + (b - a) * dx over row y0 (a at x0, b at x1), bot = c + (d - c) * dx over row y1, out = ((top + (bot - top) * dy) - 128) / 128.
+ * Equal bit for bit to the index-select form on f32 tensors (tests/test_fidelity_cpu.py).  One launch, one thread per output, no workspace: the result is
+ * a function of the image alone and repeats bit for bit; nothing outside img is read and nothing outside out's batch * channels * s * s elements written.
+ * Any h, w, s, channels, batch >= 1.  -22 before any HIP call for a NULL pointer, a size below 1, or more than (2^31 - 1) * 256 outputs (the grid's reach).
+ * Reference: sample_50k.py:174-209 and evaluation/fid.py:8-48 (torch_fidelity.calculate_metrics over the sampled images). */
+int dmvae_resize_tf1_bilinear(const uint8_t* img, size_t batch, int channels, int h, int w, int nhwc, int s, float* out, dmvae_stream_t stream);
+/* Bytes of dmvae_inception_score's workspace: one f64 log-sum-exp and one f64 sum_c p log p per row, and splits * classes f64 marginals:
+ * (2 n + splits * classes) * 8; 0 where dmvae_inception_score would refuse (n, classes, splits).  A closed form: no GPU,
+ * the same value from every call.  Reference: sample_50k.py:174-209 and evaluation/fid.py:8-48. */
+size_t dmvae_inception_score_workspace(size_t n, int classes, size_t splits);
+/* scores [splits] f64 = the Inception Score of each split of the logits x [n][classes] (row pitch ld elements; dtype 0 f32, 1 bf16, 2 f64, every element
+ * widened to f64 exactly, everything after that f64), as torch-fidelity's `isc_features_to_metric` defines it, restated from its published form -- agreement
+ * with the library itself has not been run.  Position j of the sequence reads row r(j) = order[j] (int64 on the device; NULL: r(j) = j):
+ *   lse_j = m_j + log sum_c exp(x[r(j)][c] - m_j), m_j = max_c x[r(j)][c];  logp_jc = x[r(j)][c] - lse_j,  p_jc = exp(logp_jc);
+ *   split k covers k n / splits <= j < (k + 1) n / splits (integer division), n_k positions;  q_kc = (1 / n_k) sum_j p_jc;
+ *   scores[k] = exp((1 / n_k) sum_j sum_c p_jc (logp_jc - log q_kc)), evaluated as exp((1 / n_k) sum_j sum_c p log p - sum_c q log q).
+ * A term with p == 0 (or q == 0) adds 0, its limit; the reference's expression gives NaN there, which in f64 takes a logit more than 745 below its row's
+ * log-sum-exp.  Three launches, no atomics; the order of every sum is a function of (n, classes, splits) only: the result repeats bit for bit, and a table
+ * gives the bits that physically reordered rows give with order = NULL.  Nothing past row n or past column `classes` of a row is read.  The entries of
+ * `order` are trusted: the caller guarantees 0 <= order[j] < n (dmvae_amd/ops.py checks it on the device).  2 <= classes <= 65536, 1 <= splits <= n,
+ * n <= 2^31 - 1, ld >= classes; anything else, or a NULL logits / workspace / scores, returns -22 before any launch.
+ * Reference: sample_50k.py:174-209 and evaluation/fid.py:8-48 (`inception_score_mean` / `inception_score_std` are the mean and np.std of scores). */
+int dmvae_inception_score(const void* logits, int dtype, size_t n, int classes, size_t ld, const int64_t* order, size_t splits, void* workspace,
+                          double* scores, dmvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
