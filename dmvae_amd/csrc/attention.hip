@@ -320,6 +320,7 @@ extern "C" int dmvae_attention_qkv_lse_bf16(const void* qkv, void* out, void* ls
   using namespace dmvae_attn;
   DMVAE_CHECK_ARG(qkv && out && batch > 0 && heads > 0 && seq > 0, "attention_qkv_bf16: bad argument");
   DMVAE_CHECK_ARG(head_dim == ATT_D && seq <= ATT_KEYS, "attention_qkv_bf16: needs head_dim 64 and seq <= %d (got %d, %d)", ATT_KEYS, head_dim, seq);
+  if (attn_scale_check("attention_qkv_bf16", scale)) return -22;
   AttnArgs a = {};
   attn_operands_qkv(a, qkv, seq, heads, head_dim);
   a.out = (bf16*)out; a.D = head_dim; a.QD = head_dim; a.scale = scale; a.lse = (float*)lse;
@@ -333,6 +334,7 @@ extern "C" int dmvae_attention_heads_lse_bf16(const void* q, const void* k, cons
   DMVAE_CHECK_ARG(q && k && v && out && batch > 0 && heads > 0 && seq > 0, "attention_heads_bf16: bad argument");
   const int dpc = attn_resident_heads_check("attention_heads_bf16", seq, head_dim, head_dim_padded);      // the staged width
   if (dpc < 0) return dpc;
+  if (attn_scale_check("attention_heads_bf16", scale)) return -22;
   AttnArgs a = {};
   attn_operands_heads(a, q, k, v, seq, heads, head_dim, head_dim_padded);
   a.out = (bf16*)out; a.D = head_dim; a.QD = head_dim_padded; a.scale = scale; a.lse = (float*)lse;
@@ -347,6 +349,7 @@ extern "C" int dmvae_attention_qknorm_rope_bf16(const void* qkv, const void* q_w
   DMVAE_CHECK_ARG(qkv && q_weight && k_weight && cos_table && sin_table && out && batch > 0 && heads > 0 && seq > 0, "attention_qknorm_rope_bf16: bad argument");
   DMVAE_CHECK_ARG(seq <= ATT_KEYS && head_dim % 8 == 0 && head_dim >= 8 && head_dim <= 96,
                   "attention_qknorm_rope_bf16: needs seq <= %d and head_dim a multiple of 8 up to 96 (got %d, %d)", ATT_KEYS, seq, head_dim);
+  if (attn_scale_check("attention_qknorm_rope_bf16", scale)) return -22;
   AttnArgs a = {};
   attn_operands_qkv(a, qkv, seq, heads, head_dim);
   a.out = (bf16*)out; a.D = head_dim; a.QD = head_dim; a.scale = scale;

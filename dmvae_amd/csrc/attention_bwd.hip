@@ -940,6 +940,7 @@ extern "C" int dmvae_attention_bwd_qkv_lse_bf16(const void* qkv, const void* out
   using namespace dmvae_attn_bwd;
   DMVAE_CHECK_ARG(qkv && out && dout && dqkv && batch > 0 && heads > 0 && seq > 0, "attention_bwd_qkv_bf16: bad argument");
   DMVAE_CHECK_ARG(head_dim == 64 && seq <= KEYS, "attention_bwd_qkv_bf16: needs head_dim 64 and seq <= %d (got %d, %d)", KEYS, head_dim, seq);
+  if (attn_scale_check("attention_bwd_qkv_bf16", scale)) return -22;
   Args a = {};
   attn_operands_qkv(a, qkv, seq, heads, head_dim);
   attn_grads_qkv(a, dqkv, heads, head_dim);
@@ -953,6 +954,7 @@ extern "C" int dmvae_attention_bwd_heads_lse_bf16(const void* q, const void* k, 
   DMVAE_CHECK_ARG(q && k && v && out && dout && dq && dk && dv && batch > 0 && heads > 0 && seq > 0, "attention_bwd_heads_bf16: bad argument");
   const int dpc = attn_resident_heads_check("attention_bwd_heads_bf16", seq, head_dim, head_dim_padded);      // the staged width (q / k / dq / dk rows as attention.hip's entry takes them)
   if (dpc < 0) return dpc;
+  if (attn_scale_check("attention_bwd_heads_bf16", scale)) return -22;
   Args a = {};
   attn_operands_heads(a, q, k, v, seq, heads, head_dim, head_dim_padded);
   attn_grads_heads(a, dq, dk, dv);

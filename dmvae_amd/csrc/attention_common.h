@@ -44,6 +44,12 @@ static inline int attn_resident_heads_check(const char* name, int seq, int head_
                   "%s: needs seq <= %d, head_dim %% 8 == 0, q / k rows of 64, 96 or head_dim <= 96 channels (got %d, %d, %d)", name, ATT_RESIDENT_KEYS, seq, head_dim, head_dim_padded);
   return dpc;
 }
+// The scale every attention entry takes: the forward kernels fold it into the exponent of a base-2 power next to the row maximum of the RAW scores
+// (exp(scale (s - m)) with m = max s), which is the softmax only for scale > 0
+static inline int attn_scale_check(const char* name, float scale) {
+  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "%s: needs a finite scale > 0 (got %g)", name, (double)scale);
+  return 0;
+}
 // Row blocks per (sample, head) of a streaming kernel whose workgroups own `rows` rows: ceil(seq / rows), for any seq an int holds
 static inline int attn_row_blocks(int seq, int rows) { return (int)(((long long)seq + rows - 1) / rows); }
 // The four streaming entries' checks in their one order.  have: every operand pointer is non-null (`operands` lists them for the message); packed: one qkv tensor
@@ -59,7 +65,7 @@ static inline int attn_stream_check(const char* name, const char* operands, bool
   DMVAE_CHECK_ARG(head_dim == 64 || (!packed && head_dim == 72), packed ? "%s: needs head_dim 64 (got %d)" : "%s: needs head_dim 64 or 72 (got %d)", name, head_dim);
   DMVAE_CHECK_ARG(packed || head_dim_padded == head_dim || head_dim_padded == (head_dim + 31) / 32 * 32,
                   "%s: q / k rows hold head_dim channels or head_dim rounded up to 32 (got %d for head_dim %d)", name, head_dim_padded, head_dim);
-  DMVAE_CHECK_ARG(scale > 0.f && isfinite(scale), "%s: needs a finite scale > 0 (got %g)", name, (double)scale);
+  if (attn_scale_check(name, scale)) return -22;
   // the row stride (packed: 3 C) and the (sample, head) count are ints in the kernels; the flat grid is one dimension
   const long long bh = (long long)batch * heads, blocks = bh * attn_row_blocks(seq, block_rows);
   DMVAE_CHECK_ARG((!packed || 3LL * heads * head_dim <= 0x7fffffffLL) && bh <= 0x7fffffffLL && blocks <= 0x7fffffffLL,

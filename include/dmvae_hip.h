@@ -415,7 +415,8 @@ int dmvae_softmax_rows_bf16(const void* s, void* p, size_t rows, int cols, float
  * a q / k row holds: 64 or 96, or head_dim itself (<= 96; rows without padding: the kernel does not touch the chunks past head_dim and computes the same bits).
  * Both write the row statistics: lse f32 [batch * heads][seq] = scale * max_k(q.k) + log(sum_k exp(scale (q.k - max))) per query -- what
  * dmvae_attention_bwd_*_lse_bf16 rebuild the probabilities from (lse may be NULL: the kernel form without them).  Reference: models/dino_layers/attention.py:56-69;
- * diffusion/lightningdit/lightningdit.py:76-88 (F.scaled_dot_product_attention). */
+ * diffusion/lightningdit/lightningdit.py:76-88 (F.scaled_dot_product_attention).  Every resident attention entry (these two, dmvae_attention_qknorm_rope_bf16,
+ * dmvae_attention_bwd_*_lse_bf16) needs a finite scale > 0, as the streaming ones do: -22 otherwise, nothing launched. */
 int dmvae_attention_qkv_lse_bf16(const void* qkv, void* out, void* lse, int batch, int seq, int heads, int head_dim, float scale, dmvae_stream_t stream);
 int dmvae_attention_heads_lse_bf16(const void* q, const void* k, const void* v, void* out, void* lse, int batch, int seq, int heads, int head_dim,
                                    int head_dim_padded, float scale, dmvae_stream_t stream);
