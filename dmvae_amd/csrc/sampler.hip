@@ -16,97 +16,31 @@
 // The Heun step of the SDE sampler (integrators.py:37-48) is three passes around its two model evaluations -- perturb, predict (K1 and the predictor state),
 // correct --, and the "Tweedie" / "Euler" last steps (transport.py:279-288) one pass with a mode argument; autoguidance (lightningdit.py:450-465) is one pass
 // over the two models' outputs (dmvae_autoguidance_combine), its interval gate read from t on the device like the guidance kernel's.
-// Every kernel but the Euler-Maruyama one takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail.
-// A noise- or score-predicting model (transport.py:171-181) adds a prologue to every model-consuming pass -- the `_m` entry points, which share the bodies of
-// the velocity ones through a template parameter --: v = (c0 * x) + dv * (m / nsig) or (c0 * x) + dv * m, its three t-only coefficients host scalars in
+// Every pass takes any n: float4 / bf16x4 quads while all pointers allow it, then a scalar tail (quads_then_tail; ode_quads decides, launch launches).
+// A noise- or score-predicting model (transport.py:171-181) adds a prologue to every model-consuming pass -- the `_m` entry points, which launch the <true>
+// instantiation of the velocity ones' kernels --: v = (c0 * x) + dv * (m / nsig) or (c0 * x) + dv * m, its three t-only coefficients host scalars in
 // struct dmvae_model_terms, passed by value.  dmvae_model_velocity writes v alone (the ODE samplers' drift).
 #include <initializer_list>
+#include <type_traits>
 
 #include "common.h"
 #include "dmvae_hip.h"
 
 namespace dmvae_sampler {
-
-// sde_drift at (y, v): v + diff * ((rar * v - y) / var)   (transport.py:253-256 over get_score_from_velocity, path.py:74-89)
-__device__ __forceinline__ float sde_drift_one(float v, float y, float rar, float var, float diff) {
 #pragma clang fp contract(off)
-  const float score = (rar * v - y) / var;
-  return v + diff * score;
+
+// The loop of every pass: block-256 grid-stride over the nq quads -- f(width 4, first element) --, then over the scalar tail [4 nq, n) -- f(width 1, element).
+// The width arrives as a type, so f (a generic lambda) hands it on as a template argument.
+template <class F>
+__device__ __forceinline__ void quads_then_tail(size_t n, size_t nq, F f) {
+  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < nq; i += stride) f(std::integral_constant<int, 4>{}, 4 * i);
+  for (size_t e = 4 * nq + tid; e < n; e += stride) f(std::integral_constant<int, 1>{}, e);
 }
 
-// Transport.get_score of a noise / score model (transport.py:202-216): m / -sigma_t, or m itself
-__device__ __forceinline__ float model_score_one(const dmvae_model_terms& P, float m) {
-  return P.kind == DMVAE_MODEL_NOISE ? m / P.nsig : m;
-}
-
-// Transport.get_drift of a noise / score model at the state y (transport.py:171-181): (-drift_mean) + drift_var * score, with -drift_mean = c0 * y
-__device__ __forceinline__ float model_velocity_one(const dmvae_model_terms& P, float m, float y) {
-#pragma clang fp contract(off)
-  const float a = P.c0 * y;
-  const float b = P.dv * model_score_one(P, m);
-  return a + b;
-}
-
-// The model's output as the velocity: itself (M false: a velocity model), or through the prologue
-template <bool M>
-__device__ __forceinline__ float velocity_of(const dmvae_model_terms& P, float m, float y) {
-  if constexpr (M) return model_velocity_one(P, m, y);
-  else return m;
-}
-
-// One element of the Euler-Maruyama step: mean = x + sde_drift * dt, x' = mean + sqrt(2 diffusion) * (w sqrt(dt))
-__device__ __forceinline__ void euler_one(float x, float v, float w, float rar, float var, float diff, float dt, float sq2d, float sqdt, float& mean, float& xo) {
-#pragma clang fp contract(off)
-  const float drift = sde_drift_one(v, x, rar, var, diff);
-  mean = x + drift * dt;
-  xo = mean + sq2d * (w * sqdt);
-}
-
-template <typename TV>
-__global__ __launch_bounds__(256) void sde_euler_kernel(const float* __restrict__ x, const TV* __restrict__ v, const float* __restrict__ w,
-                                                        float* __restrict__ x_out, float* __restrict__ mean_out, size_t n4, float rar, float var,
-                                                        float diff, float dt, float sq2d, float sqdt) {
-#pragma clang fp contract(off)
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const float4 xv = reinterpret_cast<const float4*>(x)[i];
-    float vv[4];
-    if constexpr (sizeof(TV) == 2) {
-      const bf16x4 t = reinterpret_cast<const bf16x4*>(v)[i];
-#pragma unroll
-      for (int j = 0; j < 4; j++) vv[j] = (float)t[j];
-    } else {
-      const float4 t = reinterpret_cast<const float4*>(v)[i];
-      vv[0] = t.x; vv[1] = t.y; vv[2] = t.z; vv[3] = t.w;
-    }
-    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-    float wv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (w) { const float4 t = reinterpret_cast<const float4*>(w)[i]; wv[0] = t.x; wv[1] = t.y; wv[2] = t.z; wv[3] = t.w; }
-    float mo[4], xo[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) euler_one(xs[j], vv[j], wv[j], rar, var, diff, dt, sq2d, sqdt, mo[j], xo[j]);
-    if (mean_out) reinterpret_cast<float4*>(mean_out)[i] = make_float4(mo[0], mo[1], mo[2], mo[3]);
-    if (x_out) reinterpret_cast<float4*>(x_out)[i] = w ? make_float4(xo[0], xo[1], xo[2], xo[3]) : make_float4(mo[0], mo[1], mo[2], mo[3]);
-  }
-}
-
-// y [npix][c_stride] f32 (NHWC, first c channels used) -> out [npix][c] uint8 = trunc(clamp(127.5 * s + 128, 0, 255)); s optionally rounded
-// to bf16 first (what `.float()` of an autocast decoder output holds).  NaN -> 0 is not defined by the reference (float -> uint8 of NaN); here 0.
-__global__ __launch_bounds__(256) void image_to_u8_kernel(const float* __restrict__ y, uint8_t* __restrict__ out, size_t npix, int c, int c_stride,
-                                                          int round_bf16) {
-#pragma clang fp contract(off)
-  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
-    for (int j = 0; j < c; j++) {
-      float s = y[p * c_stride + j];
-      if (round_bf16) s = (float)(bf16)s;
-      float q = 127.5f * s + 128.0f;
-      q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);            // NaN compares false twice and converts to 0 below
-      out[p * c + j] = (uint8_t)(int)(q == q ? q : 0.f);
-    }
-  }
-}
-
-
-// ---- dopri5 (torchdiffeq's RKAdaptiveStepsizeODESolver; integrators.py:79-118) -------------------------------------------------------------
+// The prologue scalars of a noise / score model as a kernel argument: by value when M, an empty stand-in (last in the list: no bytes in the argument segment) otherwise
+struct no_terms {};
+template <bool M> using terms_arg = std::conditional_t<M, dmvae_model_terms, no_terms>;
 
 template <int W>
 __device__ __forceinline__ void load_w(const void* p, bool is_bf16, size_t e, float (&o)[W]) {
@@ -130,11 +64,93 @@ __device__ __forceinline__ void store_w(float* p, size_t e, const float (&v)[W])
   else p[e] = v[0];
 }
 
+template <int W>
+__device__ __forceinline__ void store_w(bf16* p, size_t e, const float (&v)[W]) {      // the guidance kernels': every value is a bf16 already, the conversion exact
+  if constexpr (W == 4) {
+    bf16x4 t;
+#pragma unroll
+    for (int j = 0; j < 4; j++) t[j] = (bf16)v[j];
+    *reinterpret_cast<bf16x4*>(p + e) = t;
+  } else {
+    p[e] = (bf16)v[0];
+  }
+}
+
+// sde_drift at (y, v): v + diff * ((rar * v - y) / var)   (transport.py:253-256 over get_score_from_velocity, path.py:74-89)
+__device__ __forceinline__ float sde_drift_one(float v, float y, float rar, float var, float diff) {
+  const float score = (rar * v - y) / var;
+  return v + diff * score;
+}
+
+// Transport.get_score of a noise / score model (transport.py:202-216): m / -sigma_t, or m itself
+__device__ __forceinline__ float model_score_one(const dmvae_model_terms& P, float m) {
+  return P.kind == DMVAE_MODEL_NOISE ? m / P.nsig : m;
+}
+
+// Transport.get_drift of a noise / score model at the state y (transport.py:171-181): (-drift_mean) + drift_var * score, with -drift_mean = c0 * y
+__device__ __forceinline__ float model_velocity_one(const dmvae_model_terms& P, float m, float y) {
+  const float a = P.c0 * y;
+  const float b = P.dv * model_score_one(P, m);
+  return a + b;
+}
+
+// The model's output as the velocity: itself (M false: a velocity model), or through the prologue
+template <bool M>
+__device__ __forceinline__ float velocity_of(const terms_arg<M>& P, float m, float y) {
+  if constexpr (M) return model_velocity_one(P, m, y);
+  else return m;
+}
+
+// The Euler-Maruyama step: mean = x + sde_drift * dt, x' = mean + sqrt(2 diffusion) * (w sqrt(dt)); w NULL: x_out = mean (the "Mean" last step).
+// M: v is a noise / score model's output, converted at x first
+template <int W, bool M>
+__device__ __forceinline__ void euler_at(const float* __restrict__ x, const void* v, int v_bf16, const float* __restrict__ w, float* __restrict__ x_out,
+                                         float* __restrict__ mean_out, size_t e, float rar, float var, float diff, float dt, float sq2d, float sqdt,
+                                         const terms_arg<M>& P) {
+  float y[W], vv[W], wv[W], mo[W], xo[W];
+  load_w<W>(x, false, e, y);
+  load_w<W>(v, v_bf16, e, vv);
+  if (w) load_w<W>(w, false, e, wv);
+#pragma unroll
+  for (int j = 0; j < W; j++) {
+    if (!w) wv[j] = 0.f;
+    const float drift = sde_drift_one(velocity_of<M>(P, vv[j], y[j]), y[j], rar, var, diff);
+    mo[j] = y[j] + drift * dt;
+    xo[j] = mo[j] + sq2d * (wv[j] * sqdt);
+  }
+  if (mean_out) store_w<W>(mean_out, e, mo);
+  if (x_out) store_w<W>(x_out, e, w ? xo : mo);
+}
+
+template <bool M>
+__global__ __launch_bounds__(256) void sde_euler_kernel(const float* __restrict__ x, const void* v, int v_bf16, const float* __restrict__ w, float* __restrict__ x_out,
+                                                        float* __restrict__ mean_out, size_t n, size_t nq, float rar, float var, float diff, float dt, float sq2d,
+                                                        float sqdt, terms_arg<M> P) {
+  quads_then_tail(n, nq, [&](auto W, size_t e) { euler_at<W, M>(x, v, v_bf16, w, x_out, mean_out, e, rar, var, diff, dt, sq2d, sqdt, P); });
+}
+
+// y [npix][c_stride] f32 (NHWC, first c channels used) -> out [npix][c] uint8 = trunc(clamp(127.5 * s + 128, 0, 255)); s optionally rounded
+// to bf16 first (what `.float()` of an autocast decoder output holds).  NaN -> 0 is not defined by the reference (float -> uint8 of NaN); here 0.
+__global__ __launch_bounds__(256) void image_to_u8_kernel(const float* __restrict__ y, uint8_t* __restrict__ out, size_t npix, int c, int c_stride,
+                                                          int round_bf16) {
+  for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < npix; p += (size_t)gridDim.x * 256) {
+    for (int j = 0; j < c; j++) {
+      float s = y[p * c_stride + j];
+      if (round_bf16) s = (float)(bf16)s;
+      float q = 127.5f * s + 128.0f;
+      q = q < 0.f ? 0.f : (q > 255.f ? 255.f : q);            // NaN compares false twice and converts to 0 below
+      out[p * c + j] = (uint8_t)(int)(q == q ? q : 0.f);
+    }
+  }
+}
+
+
+// ---- dopri5 (torchdiffeq's RKAdaptiveStepsizeODESolver; integrators.py:79-118) -------------------------------------------------------------
+
 // s = sum_{j < nk} c_j k_j, j ascending, products and sums rounded to f32 one by one.  round_bf16: the autocast matmul of torchdiffeq's
 // k.matmul(coef * dt) -- c_j and k_j rounded to bf16 (their products are exact in f32), the f32 sum rounded to bf16 at the end.
 template <int W>
 __device__ __forceinline__ void rk_sum(const dmvae_ode_terms& T, int round_bf16, size_t e, float (&s)[W]) {
-#pragma clang fp contract(off)
 #pragma unroll
   for (int j = 0; j < DMVAE_ODE_MAX_TERMS; j++) {             // unrolled: constant indices into the by-value struct (no scratch copy)
     if (j >= T.nk) break;
@@ -155,7 +171,6 @@ __device__ __forceinline__ void rk_sum(const dmvae_ode_terms& T, int round_bf16,
 
 template <int W>
 __device__ __forceinline__ void rk_combine_at(const float* __restrict__ y0, const dmvae_ode_terms& T, float* __restrict__ out, size_t e, int round_bf16) {
-#pragma clang fp contract(off)
   float s[W];
   rk_sum<W>(T, round_bf16, e, s);
   if (y0) {
@@ -169,16 +184,13 @@ __device__ __forceinline__ void rk_combine_at(const float* __restrict__ y0, cons
 
 __global__ __launch_bounds__(256) void ode_rk_combine_kernel(const float* __restrict__ y0, dmvae_ode_terms T, float* __restrict__ out, size_t n, size_t nq,
                                                              int round_bf16) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) rk_combine_at<4>(y0, T, out, 4 * i, round_bf16);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) rk_combine_at<1>(y0, T, out, e, round_bf16);
+  quads_then_tail(n, nq, [&](auto W, size_t e) { rk_combine_at<W>(y0, T, out, e, round_bf16); });
 }
 
 // err = rk_sum(c_err dt);  e = err / (atol + rtol * max(|y0|, |y1|))  (torch.max: a NaN operand gives NaN);  acc += e^2 in f64;  bad |= !isfinite(y1)
 template <int W>
 __device__ __forceinline__ void err_at(const float* __restrict__ y0, const float* __restrict__ y1, const dmvae_ode_terms& T, float* __restrict__ err_out,
                                        size_t e, float atol, float rtol, int round_bf16, double& acc, int& bad) {
-#pragma clang fp contract(off)
   float s[W], a[W], b[W];
   rk_sum<W>(T, round_bf16, e, s);
   load_w<W>(y0, false, e, a);
@@ -211,11 +223,9 @@ __device__ __forceinline__ void block_sum_flag_256(double& v, int& f) {   // f64
 __global__ __launch_bounds__(256) void ode_err_partial_kernel(const float* __restrict__ y0, const float* __restrict__ y1, dmvae_ode_terms T,
                                                               float* __restrict__ err_out, double* __restrict__ part, int* __restrict__ part_bad, size_t n,
                                                               size_t nq, float atol, float rtol, int round_bf16) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
   double acc = 0.0;
   int bad = 0;
-  for (size_t i = tid; i < nq; i += stride) err_at<4>(y0, y1, T, err_out, 4 * i, atol, rtol, round_bf16, acc, bad);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) err_at<1>(y0, y1, T, err_out, e, atol, rtol, round_bf16, acc, bad);
+  quads_then_tail(n, nq, [&](auto W, size_t e) { err_at<W>(y0, y1, T, err_out, e, atol, rtol, round_bf16, acc, bad); });
   block_sum_flag_256(acc, bad);
   if (threadIdx.x == 0) { part[blockIdx.x] = acc; part_bad[blockIdx.x] = bad; }
 }
@@ -237,7 +247,6 @@ __global__ __launch_bounds__(256) void ode_err_final_kernel(const double* __rest
 template <int W>
 __device__ __forceinline__ void dense_at(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ ym, const void* f0, const void* f1,
                                          int f_bf16, float dt, float x, float* __restrict__ out, size_t e) {
-#pragma clang fp contract(off)
   float Y0[W], Y1[W], YM[W], F0[W], F1[W], o[W];
   load_w<W>(y0, false, e, Y0);
   load_w<W>(y1, false, e, Y1);
@@ -261,9 +270,7 @@ __device__ __forceinline__ void dense_at(const float* __restrict__ y0, const flo
 
 __global__ __launch_bounds__(256) void ode_dense_kernel(const float* __restrict__ y0, const float* __restrict__ y1, const float* __restrict__ ym, const void* f0,
                                                         const void* f1, int f_bf16, float dt, float x, float* __restrict__ out, size_t n, size_t nq) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) dense_at<4>(y0, y1, ym, f0, f1, f_bf16, dt, x, out, 4 * i);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) dense_at<1>(y0, y1, ym, f0, f1, f_bf16, dt, x, out, e);
+  quads_then_tail(n, nq, [&](auto W, size_t e) { dense_at<W>(y0, y1, ym, f0, f1, f_bf16, dt, x, out, e); });
 }
 
 // The likelihood sampler's stage value (transport.py:402-459, Hutchinson's trace estimator): k_x = -v (exact in f32), k_logp[b] = sum_i g[b][i] * eps[b][i].
@@ -283,6 +290,7 @@ __device__ __forceinline__ void pack_at(const void* v, int v_bf16, const float* 
   store_w<W>(kx, e, o);
 }
 
+// Its own loop: 1024 threads stride over one sample, not a grid over the array (quads_then_tail's indexing)
 __global__ __launch_bounds__(1024) void ode_hutchinson_pack_kernel(const void* v, int v_bf16, const float* __restrict__ g, const float* __restrict__ eps,
                                                                    float* __restrict__ kx, float* __restrict__ klogp, size_t per, int quads) {
   __shared__ double red[1024];
@@ -306,7 +314,6 @@ __global__ __launch_bounds__(1024) void ode_hutchinson_pack_kernel(const void* v
 // every op, an f32 tensor keeps the three f32 roundings (no FMA).  gate: t[0] < cfg_interval_start -> the conditional value itself.
 template <typename T>
 __device__ __forceinline__ float cfg_one(float c, float u, float scale, bool gate) {
-#pragma clang fp contract(off)
   if (gate) return c;
   if constexpr (sizeof(T) == 2) {
     const float d = (float)(bf16)(c - u);
@@ -320,45 +327,25 @@ __device__ __forceinline__ float cfg_one(float c, float u, float scale, bool gat
 }
 
 // src / dst [2][half] with half = n * channels * hw elements ([2n, C, H, W] contiguous): element e of the first half is the conditional sample's, e + half the
-// unconditional one's.  Channels below k: both halves receive the guided value; the others are copied.  nq quads (hw % 4 == 0: a quad never straddles a channel).
+// unconditional one's.  Channels below k: both halves receive the guided value; the others are copied.  W == 4: hw % 4 == 0, a quad never straddles a channel.
+template <typename T, int W>
+__device__ __forceinline__ void cfg_at(const T* __restrict__ src, T* __restrict__ dst, size_t e, size_t half, size_t hw, int channels, int k, float scale, bool gate) {
+  float c[W], u[W];
+  load_w<W>(src, sizeof(T) == 2, e, c);
+  load_w<W>(src + half, sizeof(T) == 2, e, u);
+  if ((int)((e / hw) % (size_t)channels) < k) {
+#pragma unroll
+    for (int j = 0; j < W; j++) c[j] = u[j] = cfg_one<T>(c[j], u[j], scale, gate);
+  }
+  store_w<W>(dst, e, c);
+  store_w<W>(dst + half, e, u);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void cfg_combine_kernel(const T* __restrict__ src, T* __restrict__ dst, size_t half, size_t nq, size_t hw, int channels, int k,
                                                           float scale, const float* __restrict__ t, float interval_start) {
   const bool gate = t != nullptr && t[0] < interval_start;
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) {
-    const size_t e = 4 * i;
-    float c[4], u[4];
-    if constexpr (sizeof(T) == 2) {
-      const bf16x4 a = *reinterpret_cast<const bf16x4*>(src + e), b = *reinterpret_cast<const bf16x4*>(src + half + e);
-#pragma unroll
-      for (int j = 0; j < 4; j++) { c[j] = (float)a[j]; u[j] = (float)b[j]; }
-    } else {
-      const float4 a = *reinterpret_cast<const float4*>(src + e), b = *reinterpret_cast<const float4*>(src + half + e);
-      c[0] = a.x; c[1] = a.y; c[2] = a.z; c[3] = a.w;
-      u[0] = b.x; u[1] = b.y; u[2] = b.z; u[3] = b.w;
-    }
-    if ((int)((e / hw) % (size_t)channels) < k) {
-#pragma unroll
-      for (int j = 0; j < 4; j++) c[j] = u[j] = cfg_one<T>(c[j], u[j], scale, gate);
-    }
-    if constexpr (sizeof(T) == 2) {
-      bf16x4 a, b;
-#pragma unroll
-      for (int j = 0; j < 4; j++) { a[j] = (bf16)c[j]; b[j] = (bf16)u[j]; }      // exact: every value is a bf16 already
-      *reinterpret_cast<bf16x4*>(dst + e) = a;
-      *reinterpret_cast<bf16x4*>(dst + half + e) = b;
-    } else {
-      *reinterpret_cast<float4*>(dst + e) = make_float4(c[0], c[1], c[2], c[3]);
-      *reinterpret_cast<float4*>(dst + half + e) = make_float4(u[0], u[1], u[2], u[3]);
-    }
-  }
-  for (size_t e = 4 * nq + tid; e < half; e += stride) {
-    float c = (float)src[e], u = (float)src[half + e];
-    if ((int)((e / hw) % (size_t)channels) < k) c = u = cfg_one<T>(c, u, scale, gate);
-    dst[e] = (T)c;
-    dst[half + e] = (T)u;
-  }
+  quads_then_tail(half, nq, [&](auto W, size_t e) { cfg_at<T, W>(src, dst, e, half, hw, channels, k, scale, gate); });
 }
 
 // ---- Heun step of the SDE sampler (integrators.py:37-48) and the "Tweedie" / "Euler" last steps (transport.py:279-288) ------------------------------------
@@ -366,7 +353,6 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const T* __restrict__ 
 // xhat = x + sqrt(2 diffusion) * (w sqrt(dt))
 template <int W>
 __device__ __forceinline__ void heun_perturb_at(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ xhat, size_t e, float sq2d, float sqdt) {
-#pragma clang fp contract(off)
   float a[W], b[W], o[W];
   load_w<W>(x, false, e, a);
   load_w<W>(w, false, e, b);
@@ -377,16 +363,13 @@ __device__ __forceinline__ void heun_perturb_at(const float* __restrict__ x, con
 
 __global__ __launch_bounds__(256) void sde_heun_perturb_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ xhat, size_t n, size_t nq,
                                                                float sq2d, float sqdt) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) heun_perturb_at<4>(x, w, xhat, 4 * i, sq2d, sqdt);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_perturb_at<1>(x, w, xhat, e, sq2d, sqdt);
+  quads_then_tail(n, nq, [&](auto W, size_t e) { heun_perturb_at<W>(x, w, xhat, e, sq2d, sqdt); });
 }
 
 // K1 = sde_drift(xhat, v1);  xp = xhat + dt * K1.  M: v1 is a noise / score model's output, converted at xhat first
-template <int W, bool M = false>
+template <int W, bool M>
 __device__ __forceinline__ void heun_predict_at(const float* __restrict__ xhat, const void* v, int v_bf16, float* __restrict__ k1, float* __restrict__ xp, size_t e,
-                                                float rar, float var, float diff, float dt, const dmvae_model_terms& P = {}) {
-#pragma clang fp contract(off)
+                                                float rar, float var, float diff, float dt, const terms_arg<M>& P) {
   float y[W], vv[W], k[W], o[W];
   load_w<W>(xhat, false, e, y);
   load_w<W>(v, v_bf16, e, vv);
@@ -399,25 +382,16 @@ __device__ __forceinline__ void heun_predict_at(const float* __restrict__ xhat, 
   store_w<W>(xp, e, o);
 }
 
+template <bool M>
 __global__ __launch_bounds__(256) void sde_heun_predict_kernel(const float* __restrict__ xhat, const void* v, int v_bf16, float* __restrict__ k1, float* __restrict__ xp,
-                                                               size_t n, size_t nq, float rar, float var, float diff, float dt) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) heun_predict_at<4>(xhat, v, v_bf16, k1, xp, 4 * i, rar, var, diff, dt);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_predict_at<1>(xhat, v, v_bf16, k1, xp, e, rar, var, diff, dt);
-}
-
-__global__ __launch_bounds__(256) void sde_heun_predict_m_kernel(const float* __restrict__ xhat, const void* m, int m_bf16, dmvae_model_terms P, float* __restrict__ k1,
-                                                                 float* __restrict__ xp, size_t n, size_t nq, float rar, float var, float diff, float dt) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) heun_predict_at<4, true>(xhat, m, m_bf16, k1, xp, 4 * i, rar, var, diff, dt, P);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_predict_at<1, true>(xhat, m, m_bf16, k1, xp, e, rar, var, diff, dt, P);
+                                                               size_t n, size_t nq, float rar, float var, float diff, float dt, terms_arg<M> P) {
+  quads_then_tail(n, nq, [&](auto W, size_t e) { heun_predict_at<W, M>(xhat, v, v_bf16, k1, xp, e, rar, var, diff, dt, P); });
 }
 
 // K2 = sde_drift(xp, v2) with the coefficients at t + dt;  x = xhat + (0.5 dt) * (K1 + K2)
-template <int W, bool M = false>
+template <int W, bool M>
 __device__ __forceinline__ void heun_correct_at(const float* __restrict__ xhat, const float* __restrict__ xp, const float* __restrict__ k1, const void* v, int v_bf16,
-                                                float* __restrict__ out, size_t e, float rar, float var, float diff, float hdt, const dmvae_model_terms& P = {}) {
-#pragma clang fp contract(off)
+                                                float* __restrict__ out, size_t e, float rar, float var, float diff, float hdt, const terms_arg<M>& P) {
   float y[W], p[W], k[W], vv[W], o[W];
   load_w<W>(xhat, false, e, y);
   load_w<W>(xp, false, e, p);
@@ -431,28 +405,19 @@ __device__ __forceinline__ void heun_correct_at(const float* __restrict__ xhat, 
   store_w<W>(out, e, o);
 }
 
+template <bool M>
 __global__ __launch_bounds__(256) void sde_heun_correct_kernel(const float* __restrict__ xhat, const float* __restrict__ xp, const float* __restrict__ k1, const void* v,
-                                                               int v_bf16, float* __restrict__ out, size_t n, size_t nq, float rar, float var, float diff, float hdt) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) heun_correct_at<4>(xhat, xp, k1, v, v_bf16, out, 4 * i, rar, var, diff, hdt);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_correct_at<1>(xhat, xp, k1, v, v_bf16, out, e, rar, var, diff, hdt);
-}
-
-__global__ __launch_bounds__(256) void sde_heun_correct_m_kernel(const float* __restrict__ xhat, const float* __restrict__ xp, const float* __restrict__ k1, const void* m,
-                                                                 int m_bf16, dmvae_model_terms P, float* __restrict__ out, size_t n, size_t nq, float rar, float var,
-                                                                 float diff, float hdt) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) heun_correct_at<4, true>(xhat, xp, k1, m, m_bf16, out, 4 * i, rar, var, diff, hdt, P);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) heun_correct_at<1, true>(xhat, xp, k1, m, m_bf16, out, e, rar, var, diff, hdt, P);
+                                                               int v_bf16, float* __restrict__ out, size_t n, size_t nq, float rar, float var, float diff, float hdt,
+                                                               terms_arg<M> P) {
+  quads_then_tail(n, nq, [&](auto W, size_t e) { heun_correct_at<W, M>(xhat, xp, k1, v, v_bf16, out, e, rar, var, diff, hdt, P); });
 }
 
 // Tweedie: x / a + c * ((rar * v - x) / var).  Euler: x + (v * h), the product rounded to bf16 when v is bf16 (`bf16 tensor * python float` stays bf16).
 // M (a noise / score model's output m): Tweedie takes Transport.get_score -- m / nsig (f32) or m itself, and then c * m is a 0-d f32 tensor times a tensor of m's
 // type: a bf16 m makes it a bf16 product (c cast to bf16, the f32 product rounded to bf16) before it meets x / a --; Euler takes the converted velocity, which is f32 whatever m is.
-template <int W, bool M = false>
+template <int W, bool M>
 __device__ __forceinline__ void last_step_at(const float* __restrict__ x, const void* v, int v_bf16, float* __restrict__ out, size_t e, int mode, float a, float c,
-                                             float rar, float var, float h, const dmvae_model_terms& P = {}) {
-#pragma clang fp contract(off)
+                                             float rar, float var, float h, const terms_arg<M>& P) {
   float y[W], vv[W], o[W];
   load_w<W>(x, false, e, y);
   load_w<W>(v, v_bf16, e, vv);
@@ -479,44 +444,10 @@ __device__ __forceinline__ void last_step_at(const float* __restrict__ x, const 
   store_w<W>(out, e, o);
 }
 
+template <bool M>      // M: rar and var are not read
 __global__ __launch_bounds__(256) void sde_last_step_kernel(const float* __restrict__ x, const void* v, int v_bf16, float* __restrict__ out, size_t n, size_t nq, int mode,
-                                                            float a, float c, float rar, float var, float h) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) last_step_at<4>(x, v, v_bf16, out, 4 * i, mode, a, c, rar, var, h);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) last_step_at<1>(x, v, v_bf16, out, e, mode, a, c, rar, var, h);
-}
-
-__global__ __launch_bounds__(256) void sde_last_step_m_kernel(const float* __restrict__ x, const void* m, int m_bf16, dmvae_model_terms P, float* __restrict__ out, size_t n,
-                                                              size_t nq, int mode, float a, float c, float h) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) last_step_at<4, true>(x, m, m_bf16, out, 4 * i, mode, a, c, 0.f, 1.f, h, P);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) last_step_at<1, true>(x, m, m_bf16, out, e, mode, a, c, 0.f, 1.f, h, P);
-}
-
-// The Euler-Maruyama step of a noise / score model: the prologue at x, then euler_one; w NULL: x_out = mean (the "Mean" last step).  Any n.
-template <int W>
-__device__ __forceinline__ void euler_m_at(const float* __restrict__ x, const void* m, int m_bf16, const dmvae_model_terms& P, const float* __restrict__ w,
-                                           float* __restrict__ x_out, float* __restrict__ mean_out, size_t e, float rar, float var, float diff, float dt, float sq2d,
-                                           float sqdt) {
-  float y[W], mv[W], wv[W], mo[W], xo[W];
-  load_w<W>(x, false, e, y);
-  load_w<W>(m, m_bf16, e, mv);
-  if (w) load_w<W>(w, false, e, wv);
-#pragma unroll
-  for (int j = 0; j < W; j++) {
-    if (!w) wv[j] = 0.f;
-    euler_one(y[j], model_velocity_one(P, mv[j], y[j]), wv[j], rar, var, diff, dt, sq2d, sqdt, mo[j], xo[j]);
-  }
-  if (mean_out) store_w<W>(mean_out, e, mo);
-  if (x_out) store_w<W>(x_out, e, w ? xo : mo);
-}
-
-__global__ __launch_bounds__(256) void sde_euler_m_kernel(const float* __restrict__ x, const void* m, int m_bf16, dmvae_model_terms P, const float* __restrict__ w,
-                                                          float* __restrict__ x_out, float* __restrict__ mean_out, size_t n, size_t nq, float rar, float var, float diff,
-                                                          float dt, float sq2d, float sqdt) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) euler_m_at<4>(x, m, m_bf16, P, w, x_out, mean_out, 4 * i, rar, var, diff, dt, sq2d, sqdt);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) euler_m_at<1>(x, m, m_bf16, P, w, x_out, mean_out, e, rar, var, diff, dt, sq2d, sqdt);
+                                                            float a, float c, float rar, float var, float h, terms_arg<M> P) {
+  quads_then_tail(n, nq, [&](auto W, size_t e) { last_step_at<W, M>(x, v, v_bf16, out, e, mode, a, c, rar, var, h, P); });
 }
 
 // v alone, f32: the drift of the probability-flow ODE (Transport.get_drift) for a noise / score model
@@ -532,9 +463,7 @@ __device__ __forceinline__ void model_velocity_at(const float* __restrict__ x, c
 
 __global__ __launch_bounds__(256) void model_velocity_kernel(const float* __restrict__ x, const void* m, int m_bf16, dmvae_model_terms P, float* __restrict__ out, size_t n,
                                                              size_t nq) {
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) model_velocity_at<4>(x, m, m_bf16, P, out, 4 * i);
-  for (size_t e = 4 * nq + tid; e < n; e += stride) model_velocity_at<1>(x, m, m_bf16, P, out, e);
+  quads_then_tail(n, nq, [&](auto W, size_t e) { model_velocity_at<W>(x, m, m_bf16, P, out, e); });
 }
 
 // ---- autoguidance (LightningDiT.forward_with_autoguidance, lightningdit.py:450-465) ------------------------------------------------------------------------
@@ -552,20 +481,8 @@ __device__ __forceinline__ void autoguidance_at(const T* __restrict__ eps, const
 #pragma unroll
     for (int j = 0; j < W; j++) a[j] = cfg_one<T>(a[j], b[j], scale, false);
   }
-  if constexpr (sizeof(T) == 2) {
-    if constexpr (W == 4) {
-      bf16x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; j++) o[j] = (bf16)a[j];          // exact: every value is a bf16 already
-      *reinterpret_cast<bf16x4*>(dst + e) = o;
-      *reinterpret_cast<bf16x4*>(dst + half + e) = o;
-    } else {
-      dst[e] = dst[half + e] = (bf16)a[0];
-    }
-  } else {
-    store_w<W>(dst, e, a);
-    store_w<W>(dst + half, e, a);
-  }
+  store_w<W>(dst, e, a);
+  store_w<W>(dst + half, e, a);
 }
 
 template <typename T>
@@ -574,10 +491,10 @@ __global__ __launch_bounds__(256) void autoguidance_combine_kernel(const T* __re
                                                                    float hi) {
   const float t0 = t[0];
   const bool inside = t0 >= lo && t0 <= hi;
-  const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, stride = (size_t)gridDim.x * 256;
-  for (size_t i = tid; i < nq; i += stride) autoguidance_at<T, 4>(eps, ag, dst, 4 * i, half, per, per_eps, per_ag, scale, inside);
-  for (size_t e = 4 * nq + tid; e < half; e += stride) autoguidance_at<T, 1>(eps, ag, dst, e, half, per, per_eps, per_ag, scale, inside);
+  quads_then_tail(half, nq, [&](auto W, size_t e) { autoguidance_at<T, W>(eps, ag, dst, e, half, per, per_eps, per_ag, scale, inside); });
 }
+
+// ---- host side: the quads decision, the launch, the entry points ----------------------------------------------------------------------------------------------
 
 constexpr int kErrMaxParts = 1024;
 
@@ -589,13 +506,25 @@ inline int ode_grid(size_t n, size_t nq, int cap) {
 
 inline bool aligned(const void* p, size_t a) { return p == nullptr || ((uintptr_t)p % a) == 0; }
 
-// quads only when every pointer is aligned for them: f32 arrays to 16 bytes, bf16 arrays to 8
-inline size_t ode_quads(size_t n, const dmvae_ode_terms* T, std::initializer_list<const void*> f32s) {
+struct typed_ptr { const void* p; int is_bf16; };
+
+// How many quads a pass over n elements may take: n / 4 when every pointer is aligned for them -- f32 arrays (f32s, and T's f32 terms) to 16 bytes, bf16 arrays to 8;
+// NULL is an absent array --, else none
+inline size_t ode_quads(size_t n, const dmvae_ode_terms* T, std::initializer_list<const void*> f32s, std::initializer_list<typed_ptr> typed = {}) {
   bool ok = true;
   for (const void* p : f32s) ok = ok && aligned(p, 16);
+  for (const typed_ptr& t : typed) ok = ok && aligned(t.p, t.is_bf16 ? 8 : 16);
   if (T)
     for (int j = 0; j < T->nk; j++) ok = ok && aligned(T->k[j], ((T->k_bf16 >> j) & 1) ? 8 : 16);
   return ok ? n / 4 : 0;
+}
+
+// One pass: ode_grid(n, nq, cap) workgroups of 256 threads; every argument converted to the kernel's parameter type (void* -> float*, int -> bool, ...)
+template <class... P, class... A>
+inline int launch(void (*kernel)(P...), hipStream_t stream, size_t n, size_t nq, int cap, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(ode_grid(n, nq, cap)), dim3(256), 0, stream, (P)args...);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
 }
 
 inline bool terms_ok(const dmvae_ode_terms* T) {
@@ -607,26 +536,47 @@ inline bool terms_ok(const dmvae_ode_terms* T) {
 
 inline bool model_terms_ok(const dmvae_model_terms* P) { return P && (P->kind == DMVAE_MODEL_NOISE || P->kind == DMVAE_MODEL_SCORE); }
 
+// The model-consuming passes, behind their velocity and `_m` entry points: terms NULL -> the velocity instantiation
+
+static int euler_step(const void* x, const void* v, int v_bf16, const dmvae_model_terms* terms_or_null, const void* w, void* x_out, void* mean_out, size_t n, float rar,
+                      float var, float diff, float dt, float sq2d, float sqdt, hipStream_t stream) {
+  const size_t nq = ode_quads(n, nullptr, {x, w, x_out, mean_out}, {{v, v_bf16}});
+  return terms_or_null ? launch(sde_euler_kernel<true>, stream, n, nq, 2048, x, v, v_bf16 != 0, w, x_out, mean_out, n, nq, rar, var, diff, dt, sq2d, sqdt, *terms_or_null)
+                       : launch(sde_euler_kernel<false>, stream, n, nq, 2048, x, v, v_bf16 != 0, w, x_out, mean_out, n, nq, rar, var, diff, dt, sq2d, sqdt, no_terms{});
+}
+
+static int heun_predict(const void* xhat, const void* v1, int v_bf16, const dmvae_model_terms* terms_or_null, void* k1, void* xp, size_t n, float rar, float var,
+                        float diff, float dt, hipStream_t stream) {
+  const size_t nq = ode_quads(n, nullptr, {xhat, k1, xp}, {{v1, v_bf16}});
+  return terms_or_null ? launch(sde_heun_predict_kernel<true>, stream, n, nq, 2048, xhat, v1, v_bf16 != 0, k1, xp, n, nq, rar, var, diff, dt, *terms_or_null)
+                       : launch(sde_heun_predict_kernel<false>, stream, n, nq, 2048, xhat, v1, v_bf16 != 0, k1, xp, n, nq, rar, var, diff, dt, no_terms{});
+}
+
+static int heun_correct(const void* xhat, const void* xp, const void* k1, const void* v2, int v_bf16, const dmvae_model_terms* terms_or_null, void* x_out, size_t n,
+                        float rar2, float var2, float diff2, float half_dt, hipStream_t stream) {
+  const size_t nq = ode_quads(n, nullptr, {xhat, xp, k1, x_out}, {{v2, v_bf16}});
+  return terms_or_null ? launch(sde_heun_correct_kernel<true>, stream, n, nq, 2048, xhat, xp, k1, v2, v_bf16 != 0, x_out, n, nq, rar2, var2, diff2, half_dt, *terms_or_null)
+                       : launch(sde_heun_correct_kernel<false>, stream, n, nq, 2048, xhat, xp, k1, v2, v_bf16 != 0, x_out, n, nq, rar2, var2, diff2, half_dt, no_terms{});
+}
+
+static int last_step(const void* x, const void* v, int v_bf16, const dmvae_model_terms* terms_or_null, void* out, size_t n, int mode, float a, float c, float rar,
+                     float var, float h, hipStream_t stream) {
+  const size_t nq = ode_quads(n, nullptr, {x, out}, {{v, v_bf16}});
+  return terms_or_null ? launch(sde_last_step_kernel<true>, stream, n, nq, 2048, x, v, v_bf16 != 0, out, n, nq, mode, a, c, rar, var, h, *terms_or_null)
+                       : launch(sde_last_step_kernel<false>, stream, n, nq, 2048, x, v, v_bf16 != 0, out, n, nq, mode, a, c, rar, var, h, no_terms{});
+}
+
 }  // namespace dmvae_sampler
+
+using namespace dmvae_sampler;
 
 extern "C" int dmvae_sde_euler_step(const void* x, const void* v, int v_is_bf16, const void* w, void* x_out, void* mean_out, size_t n, float rar,
                                     float var, float diff, float dt, float sqrt_2diff, float sqrt_dt, hipStream_t stream) {
-  using namespace dmvae_sampler;
-  DMVAE_CHECK_ARG(x && v && (x_out || mean_out) && n > 0 && n % 4 == 0, "sde_euler_step: bad argument (n %% 4 == 0 required, got %zu)", n);
-  const size_t n4 = n / 4;
-  const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
-  if (v_is_bf16)
-    hipLaunchKernelGGL(sde_euler_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const float*)x, (const bf16*)v, (const float*)w, (float*)x_out,
-                       (float*)mean_out, n4, rar, var, diff, dt, sqrt_2diff, sqrt_dt);
-  else
-    hipLaunchKernelGGL(sde_euler_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)x, (const float*)v, (const float*)w, (float*)x_out,
-                       (float*)mean_out, n4, rar, var, diff, dt, sqrt_2diff, sqrt_dt);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  DMVAE_CHECK_ARG(x && v && (x_out || mean_out) && n > 0, "sde_euler_step: bad argument (x, v, x_out or mean_out non-NULL, n > 0)");
+  return euler_step(x, v, v_is_bf16, nullptr, w, x_out, mean_out, n, rar, var, diff, dt, sqrt_2diff, sqrt_dt, stream);
 }
 
 extern "C" int dmvae_image_to_u8(const void* y, void* out, size_t npix, int c, int c_stride, int round_bf16, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(y && out && npix > 0 && c > 0 && c <= c_stride, "image_to_u8: bad argument");
   const int grid = (int)((npix + 255) / 256 < 4096 ? (npix + 255) / 256 : 4096);
   hipLaunchKernelGGL(image_to_u8_kernel, dim3(grid), dim3(256), 0, stream, (const float*)y, (uint8_t*)out, npix, c, c_stride, round_bf16);
@@ -635,53 +585,40 @@ extern "C" int dmvae_image_to_u8(const void* y, void* out, size_t npix, int c, i
 }
 
 extern "C" int dmvae_ode_rk_combine(const void* y0, const dmvae_ode_terms* terms, void* out, size_t n, int round_bf16, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(terms_ok(terms) && out && n > 0, "ode_rk_combine: bad argument (1 <= nk <= %d non-NULL k, out, n > 0)", DMVAE_ODE_MAX_TERMS);
   const size_t nq = ode_quads(n, terms, {y0, out});
-  hipLaunchKernelGGL(ode_rk_combine_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)y0, *terms, (float*)out, n, nq, round_bf16);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return launch(ode_rk_combine_kernel, stream, n, nq, 2048, y0, *terms, out, n, nq, round_bf16);
 }
 
 extern "C" size_t dmvae_ode_error_ratio_workspace(size_t n) {
   (void)n;
-  return (size_t)dmvae_sampler::kErrMaxParts * (sizeof(double) + sizeof(int));
+  return (size_t)kErrMaxParts * (sizeof(double) + sizeof(int));
 }
 
 extern "C" int dmvae_ode_error_ratio(const void* y0, const void* y1, const dmvae_ode_terms* terms, float atol, float rtol, int round_bf16, void* err_out,
                                      void* workspace, void* result, size_t n, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(y0 && y1 && terms_ok(terms) && workspace && result && n > 0 && aligned(workspace, 8) && aligned(result, 8),
                   "ode_error_ratio: bad argument");
   const size_t nq = ode_quads(n, terms, {y0, y1, err_out});
-  const int grid = ode_grid(n, nq, kErrMaxParts);
   double* part = (double*)workspace;
   int* part_bad = (int*)(part + kErrMaxParts);
-  hipLaunchKernelGGL(ode_err_partial_kernel, dim3(grid), dim3(256), 0, stream, (const float*)y0, (const float*)y1, *terms, (float*)err_out, part, part_bad,
-                     n, nq, atol, rtol, round_bf16);
-  DMVAE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ode_err_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)part, (const int*)part_bad, grid, n, result);
+  if (const int rc = launch(ode_err_partial_kernel, stream, n, nq, kErrMaxParts, y0, y1, *terms, err_out, part, part_bad, n, nq, atol, rtol, round_bf16)) return rc;
+  hipLaunchKernelGGL(ode_err_final_kernel, dim3(1), dim3(256), 0, stream, (const double*)part, (const int*)part_bad, ode_grid(n, nq, kErrMaxParts), n, result);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int dmvae_ode_dense_output(const void* y0, const void* y1, const void* y_mid, const void* f0, const void* f1, int f_bf16, float dt, float x,
                                       void* out, size_t n, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(y0 && y1 && y_mid && f0 && f1 && out && n > 0, "ode_dense_output: bad argument");
-  bool ok = aligned(f0, (f_bf16 & 1) ? 8 : 16) && aligned(f1, (f_bf16 & 2) ? 8 : 16);
-  const size_t nq = ok ? ode_quads(n, nullptr, {y0, y1, y_mid, out}) : 0;
-  hipLaunchKernelGGL(ode_dense_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)y0, (const float*)y1, (const float*)y_mid, f0, f1,
-                     f_bf16, dt, x, (float*)out, n, nq);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  const size_t nq = ode_quads(n, nullptr, {y0, y1, y_mid, out}, {{f0, f_bf16 & 1}, {f1, f_bf16 & 2}});
+  return launch(ode_dense_kernel, stream, n, nq, 2048, y0, y1, y_mid, f0, f1, f_bf16, dt, x, out, n, nq);
 }
 
 extern "C" int dmvae_ode_hutchinson_pack(const void* v, int v_is_bf16, const void* g, const void* eps, void* k_x, void* k_logp, int batch, size_t per_sample,
                                          hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(v && g && eps && k_x && k_logp && batch > 0 && batch <= 65535 && per_sample > 0, "ode_hutchinson_pack: bad argument");
-  const bool quads = per_sample % 4 == 0 && aligned(v, v_is_bf16 ? 8 : 16) && aligned(g, 16) && aligned(eps, 16) && aligned(k_x, 16);
+  const bool quads = per_sample % 4 == 0 && ode_quads(per_sample, nullptr, {g, eps, k_x}, {{v, v_is_bf16}}) > 0;      // every sample starts on a quad and holds whole ones
   hipLaunchKernelGGL(ode_hutchinson_pack_kernel, dim3(batch), dim3(1024), 0, stream, v, v_is_bf16, (const float*)g, (const float*)eps, (float*)k_x, (float*)k_logp,
                      per_sample, (int)quads);
   DMVAE_CHECK_LAUNCH();
@@ -690,147 +627,87 @@ extern "C" int dmvae_ode_hutchinson_pack(const void* v, int v_is_bf16, const voi
 
 extern "C" int dmvae_cfg_combine(const void* out2n, int is_bf16, void* dst, int n, int channels, size_t hw, int k, float scale, const void* t_or_null,
                                  float interval_start, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(out2n && dst, "cfg_combine: out2n and dst must not be NULL");
   DMVAE_CHECK_ARG(dst != out2n, "cfg_combine: dst must not alias out2n");
   DMVAE_CHECK_ARG(n > 0 && channels > 0 && hw > 0 && k >= 0, "cfg_combine: bad argument (n > 0, channels > 0, hw > 0, k >= 0; got n %d, channels %d, hw %zu, k %d)", n,
                   channels, hw, k);
   if (k > channels) k = channels;
   const size_t half = (size_t)n * (size_t)channels * hw;
-  const size_t al = is_bf16 ? 8 : 16;                       // hw % 4 == 0 keeps a quad inside one channel and the second half as aligned as the first
-  const size_t nq = (hw % 4 == 0 && aligned(out2n, al) && aligned(dst, al)) ? half / 4 : 0;
-  const int grid = ode_grid(half, nq, 2048);
-  if (is_bf16)
-    hipLaunchKernelGGL(cfg_combine_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)out2n, (bf16*)dst, half, nq, hw, channels, k, scale,
-                       (const float*)t_or_null, interval_start);
-  else
-    hipLaunchKernelGGL(cfg_combine_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)out2n, (float*)dst, half, nq, hw, channels, k, scale,
-                       (const float*)t_or_null, interval_start);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  const size_t nq = hw % 4 == 0 ? ode_quads(half, nullptr, {}, {{out2n, is_bf16}, {dst, is_bf16}}) : 0;      // hw % 4 == 0 keeps a quad inside one channel and the second half as aligned as the first
+  return is_bf16 ? launch(cfg_combine_kernel<bf16>, stream, half, nq, 2048, out2n, dst, half, nq, hw, channels, k, scale, t_or_null, interval_start)
+                 : launch(cfg_combine_kernel<float>, stream, half, nq, 2048, out2n, dst, half, nq, hw, channels, k, scale, t_or_null, interval_start);
 }
 
 extern "C" int dmvae_sde_heun_perturb(const void* x, const void* w, void* xhat, size_t n, float sqrt_2diff, float sqrt_dt, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(x && w && xhat && n > 0, "sde_heun_perturb: bad argument (x, w, xhat non-NULL, n > 0)");
   const size_t nq = ode_quads(n, nullptr, {x, w, xhat});
-  hipLaunchKernelGGL(sde_heun_perturb_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, (const float*)w, (float*)xhat, n, nq, sqrt_2diff,
-                     sqrt_dt);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return launch(sde_heun_perturb_kernel, stream, n, nq, 2048, x, w, xhat, n, nq, sqrt_2diff, sqrt_dt);
 }
 
 extern "C" int dmvae_sde_heun_predict(const void* xhat, const void* v1, int v_is_bf16, void* k1, void* xp, size_t n, float rar, float var, float diff, float dt,
                                       hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(xhat && v1 && k1 && xp && n > 0, "sde_heun_predict: bad argument (xhat, v1, k1, xp non-NULL, n > 0)");
-  const size_t nq = aligned(v1, v_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, k1, xp}) : 0;
-  hipLaunchKernelGGL(sde_heun_predict_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, v1, v_is_bf16 != 0, (float*)k1, (float*)xp, n, nq,
-                     rar, var, diff, dt);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return heun_predict(xhat, v1, v_is_bf16, nullptr, k1, xp, n, rar, var, diff, dt, stream);
 }
 
 extern "C" int dmvae_sde_heun_correct(const void* xhat, const void* xp, const void* k1, const void* v2, int v_is_bf16, void* x_out, size_t n, float rar2, float var2,
                                       float diff2, float half_dt, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(xhat && xp && k1 && v2 && x_out && n > 0, "sde_heun_correct: bad argument (xhat, xp, k1, v2, x_out non-NULL, n > 0)");
-  const size_t nq = aligned(v2, v_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, xp, k1, x_out}) : 0;
-  hipLaunchKernelGGL(sde_heun_correct_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, (const float*)xp, (const float*)k1, v2,
-                     v_is_bf16 != 0, (float*)x_out, n, nq, rar2, var2, diff2, half_dt);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return heun_correct(xhat, xp, k1, v2, v_is_bf16, nullptr, x_out, n, rar2, var2, diff2, half_dt, stream);
 }
 
 extern "C" int dmvae_sde_last_step(const void* x, const void* v, int v_is_bf16, void* out, size_t n, int mode, float a, float c, float rar, float var, float h,
                                    hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(x && v && out && n > 0, "sde_last_step: bad argument (x, v, out non-NULL, n > 0)");
   DMVAE_CHECK_ARG(mode == DMVAE_LAST_STEP_TWEEDIE || mode == DMVAE_LAST_STEP_EULER, "sde_last_step: mode must be DMVAE_LAST_STEP_TWEEDIE or _EULER, got %d", mode);
-  const size_t nq = aligned(v, v_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, out}) : 0;
-  hipLaunchKernelGGL(sde_last_step_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, v, v_is_bf16 != 0, (float*)out, n, nq, mode, a, c, rar,
-                     var, h);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return last_step(x, v, v_is_bf16, nullptr, out, n, mode, a, c, rar, var, h, stream);
 }
 
 extern "C" int dmvae_autoguidance_combine(const void* eps, int c_eps, const void* ag, int c_ag, int is_bf16, void* dst, int n, size_t hw, int k, float scale,
                                           const void* t, float lo, float hi, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(eps && ag && dst && t, "autoguidance_combine: eps, ag, dst and t must not be NULL");
   DMVAE_CHECK_ARG(dst != eps && dst != ag, "autoguidance_combine: dst must not alias eps or ag");
   DMVAE_CHECK_ARG(n > 0 && hw > 0 && k > 0 && k <= c_eps && k <= c_ag,
                   "autoguidance_combine: bad argument (n > 0, hw > 0, 0 < k <= channels of eps and ag; got n %d, hw %zu, k %d, channels %d and %d)", n, hw, k, c_eps, c_ag);
   const size_t per = (size_t)k * hw, per_eps = (size_t)c_eps * hw, per_ag = (size_t)c_ag * hw, half = (size_t)n * per;
-  const size_t al = is_bf16 ? 8 : 16;                       // quads: every sample's first k channels start on a quad and hold whole quads, in all three arrays
-  const bool quads = per % 4 == 0 && per_eps % 4 == 0 && per_ag % 4 == 0 && aligned(eps, al) && aligned(ag, al) && aligned(dst, al);
-  const size_t nq = quads ? half / 4 : 0;
-  const int grid = ode_grid(half, nq, 2048);
-  if (is_bf16)
-    hipLaunchKernelGGL(autoguidance_combine_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)eps, (const bf16*)ag, (bf16*)dst, half, nq, per, per_eps, per_ag,
-                       scale, (const float*)t, lo, hi);
-  else
-    hipLaunchKernelGGL(autoguidance_combine_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)eps, (const float*)ag, (float*)dst, half, nq, per, per_eps,
-                       per_ag, scale, (const float*)t, lo, hi);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  const bool whole = per % 4 == 0 && per_eps % 4 == 0 && per_ag % 4 == 0;      // every sample's first k channels start on a quad and hold whole quads, in all three arrays
+  const size_t nq = whole ? ode_quads(half, nullptr, {}, {{eps, is_bf16}, {ag, is_bf16}, {dst, is_bf16}}) : 0;
+  return is_bf16 ? launch(autoguidance_combine_kernel<bf16>, stream, half, nq, 2048, eps, ag, dst, half, nq, per, per_eps, per_ag, scale, t, lo, hi)
+                 : launch(autoguidance_combine_kernel<float>, stream, half, nq, 2048, eps, ag, dst, half, nq, per, per_eps, per_ag, scale, t, lo, hi);
 }
 
 extern "C" int dmvae_sde_euler_step_m(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, const void* w, void* x_out, void* mean_out, size_t n,
                                       float rar, float var, float diff, float dt, float sqrt_2diff, float sqrt_dt, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(x && m && (x_out || mean_out) && n > 0, "sde_euler_step_m: bad argument (x, m, x_out or mean_out non-NULL, n > 0)");
   DMVAE_CHECK_ARG(model_terms_ok(terms), "sde_euler_step_m: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
-  const size_t nq = aligned(m, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, w, x_out, mean_out}) : 0;
-  hipLaunchKernelGGL(sde_euler_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, m, m_is_bf16 != 0, *terms, (const float*)w, (float*)x_out,
-                     (float*)mean_out, n, nq, rar, var, diff, dt, sqrt_2diff, sqrt_dt);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return euler_step(x, m, m_is_bf16, terms, w, x_out, mean_out, n, rar, var, diff, dt, sqrt_2diff, sqrt_dt, stream);
 }
 
 extern "C" int dmvae_sde_heun_predict_m(const void* xhat, const void* m1, int m_is_bf16, const dmvae_model_terms* terms, void* k1, void* xp, size_t n, float rar, float var,
                                         float diff, float dt, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(xhat && m1 && k1 && xp && n > 0, "sde_heun_predict_m: bad argument (xhat, m1, k1, xp non-NULL, n > 0)");
   DMVAE_CHECK_ARG(model_terms_ok(terms), "sde_heun_predict_m: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
-  const size_t nq = aligned(m1, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, k1, xp}) : 0;
-  hipLaunchKernelGGL(sde_heun_predict_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, m1, m_is_bf16 != 0, *terms, (float*)k1, (float*)xp, n,
-                     nq, rar, var, diff, dt);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return heun_predict(xhat, m1, m_is_bf16, terms, k1, xp, n, rar, var, diff, dt, stream);
 }
 
 extern "C" int dmvae_sde_heun_correct_m(const void* xhat, const void* xp, const void* k1, const void* m2, int m_is_bf16, const dmvae_model_terms* terms2, void* x_out,
                                         size_t n, float rar2, float var2, float diff2, float half_dt, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(xhat && xp && k1 && m2 && x_out && n > 0, "sde_heun_correct_m: bad argument (xhat, xp, k1, m2, x_out non-NULL, n > 0)");
   DMVAE_CHECK_ARG(model_terms_ok(terms2), "sde_heun_correct_m: terms2->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
-  const size_t nq = aligned(m2, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {xhat, xp, k1, x_out}) : 0;
-  hipLaunchKernelGGL(sde_heun_correct_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)xhat, (const float*)xp, (const float*)k1, m2,
-                     m_is_bf16 != 0, *terms2, (float*)x_out, n, nq, rar2, var2, diff2, half_dt);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return heun_correct(xhat, xp, k1, m2, m_is_bf16, terms2, x_out, n, rar2, var2, diff2, half_dt, stream);
 }
 
 extern "C" int dmvae_sde_last_step_m(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, void* out, size_t n, int mode, float a, float c, float h,
                                      hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(x && m && out && n > 0, "sde_last_step_m: bad argument (x, m, out non-NULL, n > 0)");
   DMVAE_CHECK_ARG(model_terms_ok(terms), "sde_last_step_m: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
   DMVAE_CHECK_ARG(mode == DMVAE_LAST_STEP_TWEEDIE || mode == DMVAE_LAST_STEP_EULER, "sde_last_step_m: mode must be DMVAE_LAST_STEP_TWEEDIE or _EULER, got %d", mode);
-  const size_t nq = aligned(m, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, out}) : 0;
-  hipLaunchKernelGGL(sde_last_step_m_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, m, m_is_bf16 != 0, *terms, (float*)out, n, nq, mode, a, c,
-                     h);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return last_step(x, m, m_is_bf16, terms, out, n, mode, a, c, 0.f, 1.f, h, stream);
 }
 
 extern "C" int dmvae_model_velocity(const void* x, const void* m, int m_is_bf16, const dmvae_model_terms* terms, void* out, size_t n, hipStream_t stream) {
-  using namespace dmvae_sampler;
   DMVAE_CHECK_ARG(x && m && out && n > 0, "model_velocity: bad argument (x, m, out non-NULL, n > 0)");
   DMVAE_CHECK_ARG(model_terms_ok(terms), "model_velocity: terms->kind must be DMVAE_MODEL_NOISE or DMVAE_MODEL_SCORE");
-  const size_t nq = aligned(m, m_is_bf16 ? 8 : 16) ? ode_quads(n, nullptr, {x, out}) : 0;
-  hipLaunchKernelGGL(model_velocity_kernel, dim3(ode_grid(n, nq, 2048)), dim3(256), 0, stream, (const float*)x, m, m_is_bf16 != 0, *terms, (float*)out, n, nq);
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  const size_t nq = ode_quads(n, nullptr, {x, out}, {{m, m_is_bf16}});
+  return launch(model_velocity_kernel, stream, n, nq, 2048, x, m, m_is_bf16 != 0, *terms, out, n, nq);
 }

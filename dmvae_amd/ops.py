@@ -1792,18 +1792,19 @@ class DitStackBwd:
 
 # ---- downstream consumers (sampler state update, image -> uint8) ---------------------------------------
 def sde_euler_step(x: torch.Tensor, v: torch.Tensor, w: Optional[torch.Tensor], rar: float, var: float, diff: float, dt: float, sqrt_2diff: float,
-                   sqrt_dt: float, need_mean: bool = False):
+                   sqrt_dt: float, need_mean: bool = False, *, terms=None):
     """One Euler-Maruyama step (integrators.py:27-35 with transport.py:254-257 / path.py:74-89 folded in) -> (x_new, mean_x or None); w = None:
-    x_new = x + drift * dt (the sampler's last step).  x, w f32; v bf16 or f32; all the same shape."""
-    x = _req(x, f32, "x")
-    assert v.is_cuda and v.is_contiguous() and v.dtype in (bf16, f32) and v.shape == x.shape
+    x_new = x + drift * dt (the sampler's last step).  x, w f32; v bf16 or f32; all the same shape; any number of elements.  `terms` = (kind, c0, dv, nsig),
+    formed by the host: v is a noise / score model's output, converted to the velocity c0 * x + dv * (v / nsig) (MODEL_NOISE) or c0 * x + dv * v (MODEL_SCORE)
+    -- transport.py:171-181 -- in f32 first."""
+    pt = None if terms is None else _model_terms(terms, "sde_euler_step")
+    _req_v(v, _req(x, f32, "x"), "v")
     if w is not None:
-        w = _req(w, f32, "w")
-        assert w.shape == x.shape
+        _same(_req(w, f32, "w"), x, "w")
     out = torch.empty_like(x)
     mean = torch.empty_like(x) if need_mean else None
-    check(_lib.lib().dmvae_sde_euler_step(x.data_ptr(), v.data_ptr(), int(v.dtype == bf16), _ptr(w), out.data_ptr(), _ptr(mean), x.numel(), float(rar),
-                                          float(var), float(diff), float(dt), float(sqrt_2diff), float(sqrt_dt), _stream()), "sde_euler_step")
+    _v_or_m("sde_euler_step", (x.data_ptr(), v.data_ptr(), int(v.dtype == bf16)), pt, (_ptr(w), out.data_ptr(), _ptr(mean), x.numel(), float(rar), float(var), float(diff),
+                                                                                     float(dt), float(sqrt_2diff), float(sqrt_dt), _stream()))
     return out, mean
 
 
@@ -1948,49 +1949,14 @@ def sde_heun_perturb(x: torch.Tensor, w: torch.Tensor, sqrt_2diff: float, sqrt_d
     return xhat
 
 
-def sde_heun_predict(xhat: torch.Tensor, v1: torch.Tensor, rar: float, var: float, diff: float, dt: float):
-    """The Heun step's predictor (integrators.py:37-48 with transport.py:253-256 / path.py:74-89 folded in) -> (k1, xp), both f32:
-    k1 = v1 + diff * ((rar * v1 - xhat) / var), xp = xhat + dt * k1.  xhat f32; v1 bf16 or f32, of xhat's shape."""
-    _req_v(v1, _req(xhat, f32, "xhat"), "v1")
-    k1, xp = torch.empty_like(xhat), torch.empty_like(xhat)
-    check(_lib.lib().dmvae_sde_heun_predict(xhat.data_ptr(), v1.data_ptr(), int(v1.dtype == bf16), k1.data_ptr(), xp.data_ptr(), xhat.numel(), float(rar), float(var),
-                                            float(diff), float(dt), _stream()), "sde_heun_predict")
-    return k1, xp
-
-
-def sde_heun_correct(xhat: torch.Tensor, xp: torch.Tensor, k1: torch.Tensor, v2: torch.Tensor, rar2: float, var2: float, diff2: float, half_dt: float) -> torch.Tensor:
-    """The Heun step's corrector (integrators.py:37-48): k2 = v2 + diff2 * ((rar2 * v2 - xp) / var2) with the coefficients at t + dt, then
-    xhat + half_dt * (k1 + k2).  xhat, xp, k1 f32; v2 bf16 or f32; one shape."""
-    _req(xhat, f32, "xhat")
-    for name, t in (("xp", xp), ("k1", k1)):
-        _same(_req(t, f32, name), xhat, name)
-    _req_v(v2, xhat, "v2")
-    out = torch.empty_like(xhat)
-    check(_lib.lib().dmvae_sde_heun_correct(xhat.data_ptr(), xp.data_ptr(), k1.data_ptr(), v2.data_ptr(), int(v2.dtype == bf16), out.data_ptr(), xhat.numel(),
-                                            float(rar2), float(var2), float(diff2), float(half_dt), _stream()), "sde_heun_correct")
-    return out
-
-
-LAST_STEP_TWEEDIE, LAST_STEP_EULER = 0, 1      # DMVAE_LAST_STEP_* of include/dmvae_hip.h
-
-
-def sde_last_step(x: torch.Tensor, v: torch.Tensor, mode: int, *, a: float = 1.0, c: float = 0.0, rar: float = 0.0, var: float = 1.0, h: float = 0.0) -> torch.Tensor:
-    """The sampler's "Tweedie" and "Euler" last steps (transport.py:279-288) in one launch.  LAST_STEP_TWEEDIE: x / a + c * ((rar * v - x) / var) with
-    a = alpha(t1), c = sigma(t1)^2 / a in f32.  LAST_STEP_EULER: x + (v * h), the product kept in bf16 for a bf16 v.  x f32; v bf16 or f32, of x's shape."""
-    if mode not in (LAST_STEP_TWEEDIE, LAST_STEP_EULER):
-        raise ValueError(f"sde_last_step: mode must be LAST_STEP_TWEEDIE or LAST_STEP_EULER, got {mode!r}")
-    _req_v(v, _req(x, f32, "x"), "v")
-    out = torch.empty_like(x)
-    check(_lib.lib().dmvae_sde_last_step(x.data_ptr(), v.data_ptr(), int(v.dtype == bf16), out.data_ptr(), x.numel(), int(mode), float(a), float(c), float(rar),
-                                         float(var), float(h), _stream()), "sde_last_step")
-    return out
-
-
 MODEL_NOISE, MODEL_SCORE = 1, 2      # DMVAE_MODEL_* of include/dmvae_hip.h
 
 
 def _model_terms(terms, name: str) -> "_lib.ModelTerms":
-    """(kind, c0, dv, nsig) -> struct dmvae_model_terms: the prologue of a noise / score model, v = c0 * x + dv * (m / nsig) or c0 * x + dv * m."""
+    """(kind, c0, dv, nsig) -> struct dmvae_model_terms: the prologue of a noise / score model, v = c0 * x + dv * (m / nsig) or c0 * x + dv * m.  A struct made
+    here before passes through."""
+    if isinstance(terms, _lib.ModelTerms):
+        return terms
     try:
         kind, c0, dv, nsig = terms
     except (TypeError, ValueError):
@@ -2000,58 +1966,84 @@ def _model_terms(terms, name: str) -> "_lib.ModelTerms":
     return _lib.ModelTerms(int(kind), float(c0), float(dv), float(nsig))
 
 
+def _v_or_m(name: str, head, pt, tail) -> None:
+    """One model-consuming pass: dmvae_<name>(*head, *tail) for a velocity model (pt None), dmvae_<name>_m(*head, &pt, *tail) for a noise / score model -- the
+    `_m` entry points take the terms after the model output and its type flag."""
+    if pt is None:
+        check(getattr(_lib.lib(), "dmvae_" + name)(*head, *tail), name)
+    else:
+        check(getattr(_lib.lib(), f"dmvae_{name}_m")(*head, ctypes.byref(pt), *tail), name + "_m")
+
+
+def sde_heun_predict(xhat: torch.Tensor, v1: torch.Tensor, rar: float, var: float, diff: float, dt: float, *, terms=None):
+    """The Heun step's predictor (integrators.py:37-48 with transport.py:253-256 / path.py:74-89 folded in) -> (k1, xp), both f32:
+    k1 = v1 + diff * ((rar * v1 - xhat) / var), xp = xhat + dt * k1.  xhat f32; v1 bf16 or f32, of xhat's shape.  `terms` (at t): v1 is a noise / score
+    model's output, converted to the velocity at xhat first."""
+    pt = None if terms is None else _model_terms(terms, "sde_heun_predict")
+    _req_v(v1, _req(xhat, f32, "xhat"), "v1")
+    k1, xp = torch.empty_like(xhat), torch.empty_like(xhat)
+    _v_or_m("sde_heun_predict", (xhat.data_ptr(), v1.data_ptr(), int(v1.dtype == bf16)), pt, (k1.data_ptr(), xp.data_ptr(), xhat.numel(), float(rar), float(var),
+                                                                                            float(diff), float(dt), _stream()))
+    return k1, xp
+
+
+def sde_heun_correct(xhat: torch.Tensor, xp: torch.Tensor, k1: torch.Tensor, v2: torch.Tensor, rar2: float, var2: float, diff2: float, half_dt: float, *,
+                     terms=None) -> torch.Tensor:
+    """The Heun step's corrector (integrators.py:37-48): k2 = v2 + diff2 * ((rar2 * v2 - xp) / var2) with the coefficients at t + dt, then
+    xhat + half_dt * (k1 + k2).  xhat, xp, k1 f32; v2 bf16 or f32; one shape.  `terms` (at t + dt): v2 is a noise / score model's output, converted to the
+    velocity at xp first."""
+    pt = None if terms is None else _model_terms(terms, "sde_heun_correct")
+    _req(xhat, f32, "xhat")
+    for name, t in (("xp", xp), ("k1", k1)):
+        _same(_req(t, f32, name), xhat, name)
+    _req_v(v2, xhat, "v2")
+    out = torch.empty_like(xhat)
+    _v_or_m("sde_heun_correct", (xhat.data_ptr(), xp.data_ptr(), k1.data_ptr(), v2.data_ptr(), int(v2.dtype == bf16)), pt,
+            (out.data_ptr(), xhat.numel(), float(rar2), float(var2), float(diff2), float(half_dt), _stream()))
+    return out
+
+
+LAST_STEP_TWEEDIE, LAST_STEP_EULER = 0, 1      # DMVAE_LAST_STEP_* of include/dmvae_hip.h
+
+
+def sde_last_step(x: torch.Tensor, v: torch.Tensor, mode: int, *, a: float = 1.0, c: float = 0.0, rar: float = 0.0, var: float = 1.0, h: float = 0.0,
+                  terms=None) -> torch.Tensor:
+    """The sampler's "Tweedie" and "Euler" last steps (transport.py:279-288) in one launch.  LAST_STEP_TWEEDIE: x / a + c * ((rar * v - x) / var) with
+    a = alpha(t1), c = sigma(t1)^2 / a in f32.  LAST_STEP_EULER: x + (v * h), the product kept in bf16 for a bf16 v.  x f32; v bf16 or f32, of x's shape.
+    `terms`: v is a noise / score model's output m, and rar / var are not used.  LAST_STEP_TWEEDIE: x / a + c * s with the model's own score s
+    (`Transport.get_score`: m / nsig for MODEL_NOISE, m for MODEL_SCORE -- then a bf16 m makes c * m a bf16 product, c cast to bf16 first, as a 0-d f32 tensor
+    times a bf16 tensor is).  LAST_STEP_EULER: x + v * h with the converted f32 velocity v."""
+    if mode not in (LAST_STEP_TWEEDIE, LAST_STEP_EULER):
+        raise ValueError(f"sde_last_step: mode must be LAST_STEP_TWEEDIE or LAST_STEP_EULER, got {mode!r}")
+    pt = None if terms is None else _model_terms(terms, "sde_last_step")
+    _req_v(v, _req(x, f32, "x"), "v")
+    out = torch.empty_like(x)
+    coeffs = (float(rar), float(var)) if pt is None else ()      # dmvae_sde_last_step_m takes neither
+    _v_or_m("sde_last_step", (x.data_ptr(), v.data_ptr(), int(v.dtype == bf16)), pt, (out.data_ptr(), x.numel(), int(mode), float(a), float(c), *coeffs, float(h),
+                                                                                    _stream()))
+    return out
+
+
 def sde_euler_step_m(x: torch.Tensor, m: torch.Tensor, terms, w: Optional[torch.Tensor], rar: float, var: float, diff: float, dt: float, sqrt_2diff: float,
                      sqrt_dt: float, need_mean: bool = False):
-    """`sde_euler_step` for a noise / score model's output m (bf16 or f32): the velocity v = c0 * x + dv * (m / nsig) (MODEL_NOISE) or c0 * x + dv * m
-    (MODEL_SCORE) -- transport.py:171-181 with `terms` = (kind, c0, dv, nsig) formed by the host -- in f32, then the step -> (x_new, mean_x or None).
-    w = None: x_new = x + drift * dt.  x, w f32; one shape; any number of elements."""
-    pt = _model_terms(terms, "sde_euler_step_m")
-    _req_v(m, _req(x, f32, "x"), "m")
-    if w is not None:
-        _same(_req(w, f32, "w"), x, "w")
-    out = torch.empty_like(x)
-    mean = torch.empty_like(x) if need_mean else None
-    check(_lib.lib().dmvae_sde_euler_step_m(x.data_ptr(), m.data_ptr(), int(m.dtype == bf16), ctypes.byref(pt), _ptr(w), out.data_ptr(), _ptr(mean), x.numel(),
-                                            float(rar), float(var), float(diff), float(dt), float(sqrt_2diff), float(sqrt_dt), _stream()), "sde_euler_step_m")
-    return out, mean
+    """`sde_euler_step` with `terms` required: m is a noise / score model's output."""
+    return sde_euler_step(x, m, w, rar, var, diff, dt, sqrt_2diff, sqrt_dt, need_mean, terms=_model_terms(terms, "sde_euler_step_m"))
 
 
 def sde_heun_predict_m(xhat: torch.Tensor, m1: torch.Tensor, terms, rar: float, var: float, diff: float, dt: float):
-    """`sde_heun_predict` for a noise / score model's output m1, converted to the velocity at xhat with `terms` (at t) first -> (k1, xp), both f32."""
-    pt = _model_terms(terms, "sde_heun_predict_m")
-    _req_v(m1, _req(xhat, f32, "xhat"), "m1")
-    k1, xp = torch.empty_like(xhat), torch.empty_like(xhat)
-    check(_lib.lib().dmvae_sde_heun_predict_m(xhat.data_ptr(), m1.data_ptr(), int(m1.dtype == bf16), ctypes.byref(pt), k1.data_ptr(), xp.data_ptr(), xhat.numel(),
-                                              float(rar), float(var), float(diff), float(dt), _stream()), "sde_heun_predict_m")
-    return k1, xp
+    """`sde_heun_predict` with `terms` required."""
+    return sde_heun_predict(xhat, m1, rar, var, diff, dt, terms=_model_terms(terms, "sde_heun_predict_m"))
 
 
 def sde_heun_correct_m(xhat: torch.Tensor, xp: torch.Tensor, k1: torch.Tensor, m2: torch.Tensor, terms2, rar2: float, var2: float, diff2: float,
                        half_dt: float) -> torch.Tensor:
-    """`sde_heun_correct` for a noise / score model's output m2, converted to the velocity at xp with `terms2` (at t + dt) first."""
-    pt = _model_terms(terms2, "sde_heun_correct_m")
-    _req(xhat, f32, "xhat")
-    for name, t in (("xp", xp), ("k1", k1)):
-        _same(_req(t, f32, name), xhat, name)
-    _req_v(m2, xhat, "m2")
-    out = torch.empty_like(xhat)
-    check(_lib.lib().dmvae_sde_heun_correct_m(xhat.data_ptr(), xp.data_ptr(), k1.data_ptr(), m2.data_ptr(), int(m2.dtype == bf16), ctypes.byref(pt), out.data_ptr(),
-                                              xhat.numel(), float(rar2), float(var2), float(diff2), float(half_dt), _stream()), "sde_heun_correct_m")
-    return out
+    """`sde_heun_correct` with `terms` required."""
+    return sde_heun_correct(xhat, xp, k1, m2, rar2, var2, diff2, half_dt, terms=_model_terms(terms2, "sde_heun_correct_m"))
 
 
 def sde_last_step_m(x: torch.Tensor, m: torch.Tensor, terms, mode: int, *, a: float = 1.0, c: float = 0.0, h: float = 0.0) -> torch.Tensor:
-    """`sde_last_step` for a noise / score model's output m.  LAST_STEP_TWEEDIE: x / a + c * s with the model's own score s (`Transport.get_score`: m / nsig for
-    MODEL_NOISE, m for MODEL_SCORE -- then a bf16 m makes c * m a bf16 product, c cast to bf16 first, as a 0-d f32 tensor times a bf16 tensor is).  LAST_STEP_EULER: x + v * h with the
-    converted f32 velocity v."""
-    if mode not in (LAST_STEP_TWEEDIE, LAST_STEP_EULER):
-        raise ValueError(f"sde_last_step_m: mode must be LAST_STEP_TWEEDIE or LAST_STEP_EULER, got {mode!r}")
-    pt = _model_terms(terms, "sde_last_step_m")
-    _req_v(m, _req(x, f32, "x"), "m")
-    out = torch.empty_like(x)
-    check(_lib.lib().dmvae_sde_last_step_m(x.data_ptr(), m.data_ptr(), int(m.dtype == bf16), ctypes.byref(pt), out.data_ptr(), x.numel(), int(mode), float(a), float(c),
-                                           float(h), _stream()), "sde_last_step_m")
-    return out
+    """`sde_last_step` with `terms` required."""
+    return sde_last_step(x, m, mode, a=a, c=c, h=h, terms=_model_terms(terms, "sde_last_step_m"))
 
 
 def model_velocity(x: torch.Tensor, m: torch.Tensor, terms, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -358,7 +358,7 @@ class sde:
 
     With `fused` (set by `Sampler.sample_sde`) a step calls the model and does the whole
     update on csrc/sampler.hip -- Euler-Maruyama in `ops.sde_euler_step`, Heun in `ops.sde_heun_perturb` / `sde_heun_predict` / `sde_heun_correct` around its
-    two evaluations; for a noise / score model their `_m` forms, which convert the model's output to the velocity first (`model_terms`) --; otherwise it
+    two evaluations; for a noise / score model with `terms=`, which converts the model's output to the velocity first (`model_terms`) --; otherwise it
     evaluates the caller's `drift` / `diffusion` callables like the reference."""
 
     def __init__(self, drift, diffusion, *, t0, t1, num_steps, sampler_type, fused=None):
@@ -410,26 +410,21 @@ class sde:
 
     def _euler_maruyama_step(self, x, mean_x, t, model, **model_kwargs):
         w_cur = self._noise(x)
-        terms = self._terms(t) if self._fused_ok(x) else None
-        if terms is not None:
+        if self._fused_ok(x):
+            terms = self._terms(t)
             m = model(x, _time_vector(x.size(0), t, x), **model_kwargs)
             assert m.shape == x.shape, "Output shape from ODE solver must match input shape"
             rar, var, diff, sq2d = self._coeffs(t)
-            return ops.sde_euler_step_m(x.contiguous(), m.contiguous(), terms, w_cur, rar, var, diff, float(self.dt), sq2d, float(th.sqrt(self.dt)),
-                                        need_mean=True)
-        if self._fused_ok(x) and x.numel() % 4 == 0:
-            tv = _time_vector(x.size(0), t, x)
-            v = model(x, tv, **model_kwargs)
-            assert v.shape == x.shape, "Output shape from ODE solver must match input shape"
-            rar, var, diff, sq2d = self._coeffs(t)
-            return ops.sde_euler_step(x.contiguous(), v.contiguous(), w_cur, rar, var, diff, float(self.dt), sq2d, float(th.sqrt(self.dt)),
-                                      need_mean=True)
-        t = _time_vector(x.size(0), t, x)
-        dw = w_cur * th.sqrt(self.dt)
-        drift = self.drift(x, t, model, **model_kwargs)
-        diffusion = self.diffusion(x, t)
-        mean_x = x + drift * self.dt
-        return mean_x + th.sqrt(2 * diffusion) * dw, mean_x
+            return ops.sde_euler_step(x.contiguous(), m.contiguous(), w_cur, rar, var, diff, float(self.dt), sq2d, float(th.sqrt(self.dt)),
+                                      need_mean=True, terms=terms)
+        # composed from tensor ops: the noise scaled by sqrt(dt) and by sqrt(2 diffusion), added to the deterministic part of the step
+        h = self.dt
+        tv = _time_vector(x.size(0), t, x)
+        noise = th.sqrt(h) * w_cur
+        f = self.drift(x, tv, model, **model_kwargs)
+        g = th.sqrt(2 * self.diffusion(x, tv))
+        mean_x = f * h + x
+        return g * noise + mean_x, mean_x
 
     def _heun_step(self, x, _, t, model, **model_kwargs):
         w_cur = self._noise(x)
@@ -443,17 +438,14 @@ class sde:
             v1 = model(xhat, _time_vector(n, t, x), **model_kwargs)
             assert v1.shape == x.shape, "Output shape from ODE solver must match input shape"
             # v1 is consumed here: a graphed model reuses its output buffer
-            k1, xp = (ops.sde_heun_predict(xhat, v1.contiguous(), rar, var, diff, float(self.dt)) if terms is None else
-                      ops.sde_heun_predict_m(xhat, v1.contiguous(), terms, rar, var, diff, float(self.dt)))
+            k1, xp = ops.sde_heun_predict(xhat, v1.contiguous(), rar, var, diff, float(self.dt), terms=terms)
             v2 = model(xp, _time_vector(n, t2, x), **model_kwargs)
             assert v2.shape == x.shape, "Output shape from ODE solver must match input shape"
-            if terms2 is None:
-                return ops.sde_heun_correct(xhat, xp, k1, v2.contiguous(), rar2, var2, diff2, float(0.5 * self.dt)), xhat
-            return ops.sde_heun_correct_m(xhat, xp, k1, v2.contiguous(), terms2, rar2, var2, diff2, float(0.5 * self.dt)), xhat
-        dw = w_cur * th.sqrt(self.dt)
+            return ops.sde_heun_correct(xhat, xp, k1, v2.contiguous(), rar2, var2, diff2, float(0.5 * self.dt), terms=terms2), xhat
+        noise = th.sqrt(self.dt) * w_cur
         t_cur = _time_vector(x.size(0), t, x)
         diffusion = self.diffusion(x, t_cur)
-        xhat = x + th.sqrt(2 * diffusion) * dw
+        xhat = x + th.sqrt(2 * diffusion) * noise
         k1 = self.drift(xhat, t_cur, model, **model_kwargs)
         xp = xhat + self.dt * k1
         k2 = self.drift(xp, t_cur + self.dt, model, **model_kwargs)
@@ -463,7 +455,7 @@ class sde:
         try:
             step = {"Euler": self._euler_maruyama_step, "Heun": self._heun_step}[self.sampler_type]
         except KeyError:
-            raise NotImplementedError("Smapler type not implemented.")
+            raise NotImplementedError(f"sde: sampler_type must be \"Euler\" or \"Heun\", got {self.sampler_type!r}") from None
         x, mean_x, samples = init, init, []
         for ti in self.t[:-1]:
             with th.no_grad():
@@ -863,43 +855,35 @@ class Sampler:
             return lambda x, t, model, **kw: x
         on_kernel = lambda x: FUSED_STATE_UPDATE and fused is not None and x.is_cuda and x.dtype == th.float32
         mt = fused[3] if fused is not None and len(fused) > 3 else ModelType.VELOCITY
-        terms = None if mt == ModelType.VELOCITY else (lambda: model_terms(ps, mt, te))      # a noise / score model: the `_m` kernels take the model's output itself; formed on the kernel route only
+        # What the kernels consume: a velocity model's drift (terms None), or a noise / score model's output itself with the prologue scalars, formed on the kernel route only
+        if mt == ModelType.VELOCITY:
+            terms, output = (lambda: None), self.drift
+        else:
+            terms, output = (lambda: model_terms(ps, mt, te)), (lambda x, t, model, **kw: model(x, t, **kw))
         if last_step == "Mean":
             def mean_step(x, t, model, **kw):
-                if on_kernel(x) and terms is not None:
+                if on_kernel(x):
                     rar, var = ps._score_coeffs(te)
                     diff = float(ps.compute_diffusion(te, te.view(1), form=fused[1], norm=fused[2]))
-                    return ops.sde_euler_step_m(x.contiguous(), model(x, t, **kw).contiguous(), terms(), None, float(rar), float(var), diff, float(last_step_size),
-                                                0.0, 0.0)[0]
-                if on_kernel(x) and x.numel() % 4 == 0:
-                    v = self.drift(x, t, model, **kw)
-                    rar, var = ps._score_coeffs(te)
-                    diff = float(ps.compute_diffusion(te, te.view(1), form=fused[1], norm=fused[2]))
-                    return ops.sde_euler_step(x.contiguous(), v.contiguous(), None, float(rar), float(var), diff, float(last_step_size), 0.0, 0.0)[0]
+                    return ops.sde_euler_step(x.contiguous(), output(x, t, model, **kw).contiguous(), None, float(rar), float(var), diff, float(last_step_size),
+                                              0.0, 0.0, terms=terms())[0]
                 return x + sde_drift(x, t, model, **kw) * last_step_size
             return mean_step
         if last_step == "Tweedie":
             alpha, sigma = ps.compute_alpha_t, ps.compute_sigma_t
 
             def tweedie_step(x, t, model, **kw):
-                if on_kernel(x) and terms is not None:          # Transport.get_score: the model's own score, not the one converted from the velocity
-                    a = alpha(te)[0]
-                    return ops.sde_last_step_m(x.contiguous(), model(x, t, **kw).contiguous(), terms(), ops.LAST_STEP_TWEEDIE, a=float(a),
-                                               c=float((sigma(te)[0] ** 2) / a))
-                if on_kernel(x):
-                    v = self.drift(x, t, model, **kw)
+                if on_kernel(x):          # with terms, Transport.get_score: the model's own score, not the one converted from the velocity (rar, var unused)
                     rar, var = ps._score_coeffs(te)
                     a = alpha(te)[0]
-                    return ops.sde_last_step(x.contiguous(), v.contiguous(), ops.LAST_STEP_TWEEDIE, a=float(a), c=float((sigma(te)[0] ** 2) / a), rar=float(rar),
-                                             var=float(var))
+                    return ops.sde_last_step(x.contiguous(), output(x, t, model, **kw).contiguous(), ops.LAST_STEP_TWEEDIE, a=float(a),
+                                             c=float((sigma(te)[0] ** 2) / a), rar=float(rar), var=float(var), terms=terms())
                 return x / alpha(t)[0][0] + (sigma(t)[0][0] ** 2) / alpha(t)[0][0] * self.score(x, t, model, **kw)
             return tweedie_step
         if last_step == "Euler":
             def euler_step(x, t, model, **kw):
-                if on_kernel(x) and terms is not None:
-                    return ops.sde_last_step_m(x.contiguous(), model(x, t, **kw).contiguous(), terms(), ops.LAST_STEP_EULER, h=float(last_step_size))
                 if on_kernel(x):
-                    return ops.sde_last_step(x.contiguous(), self.drift(x, t, model, **kw).contiguous(), ops.LAST_STEP_EULER, h=float(last_step_size))
+                    return ops.sde_last_step(x.contiguous(), output(x, t, model, **kw).contiguous(), ops.LAST_STEP_EULER, h=float(last_step_size), terms=terms())
                 return x + self.drift(x, t, model, **kw) * last_step_size
             return euler_step
         raise NotImplementedError()

@@ -791,7 +791,8 @@ int dmvae_mt_ema(const dmvae_mt_tensor* table, size_t n_tensors, const dmvae_mt_
  * passed as the f32 scalar the reference's graph holds:
  *   score = (rar * v - x) / var;  drift = v + diff * score;  mean = x + drift * dt;  x' = mean + sqrt_2diff * (w * sqrt_dt)
  * x, w, x_out, mean_out: [n] f32; v: [n] bf16 (v_is_bf16 != 0, the autocast model output) or f32.  w = NULL: x_out = mean (the
- * "Mean" / "Euler" last step, transport.py:275-295, with dt = last_step_size).  x_out or mean_out may be NULL.  n % 4 == 0.
+ * "Mean" / "Euler" last step, transport.py:275-295, with dt = last_step_size).  x_out or mean_out may be NULL.  Any n > 0
+ * (quads when every pointer is aligned for them -- f32 arrays to 16 bytes, a bf16 v to 8 --, a scalar tail otherwise).
  * Operation order and rounding are the reference's (no FMA contraction): bit-identical to the PyTorch-CPU f32 result for the same v. */
 int dmvae_sde_euler_step(const void* x, const void* v, int v_is_bf16, const void* w, void* x_out, void* mean_out, size_t n,
                          float rar, float var, float diff, float dt, float sqrt_2diff, float sqrt_dt, dmvae_stream_t stream);

@@ -93,6 +93,34 @@ def test_heun_step_kernels_bit_exact(form, norm, tval, vdtype):
 
 
 @pytest.mark.parametrize("vdtype", [torch.float32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("form,norm,tval", [("linear", 0.7, 0.9599), ("SBDM", 1.0, 0.3)])
+def test_euler_step_kernel_bit_exact_at_every_shape(form, norm, tval, vdtype):
+    """ops.sde_euler_step for a velocity model == the reference's Euler-Maruyama step and "Mean" last step (oracle.ref_cpu.sde_euler_step /
+    sde_drift_from_velocity on the CPU, as tests/test_gpu_sampler.py compares them at one shape) at every shape of SHAPES and at (1, 2, 3, 7) through the
+    offset view: 42 elements, no multiple of four, behind pointers that forbid quads.  The entry point takes any n > 0."""
+    import ctypes
+    from dmvae_amd import _lib, ops
+    t = torch.tensor(tval, dtype=torch.float32)
+    rar, var, diff, sq2d = _scalars(t, form, norm)
+    for shape, off in SHAPES + [((1, 2, 3, 7), 1)]:
+        x, w, v, _ = _inputs(shape)
+        v = v.to(vdtype)
+        tv = torch.ones(shape[0]) * t
+        x_ref, mean_ref = R.sde_euler_step(x, v.float(), w, tv, DT, form, norm)
+        d = lambda a: _dev(a, off)
+        out, mean = ops.sde_euler_step(d(x), d(v), d(w), rar, var, diff, float(DT), sq2d, float(torch.sqrt(DT)), need_mean=True)
+        assert _same(out, x_ref) and _same(mean, mean_ref), (shape, off, "step")
+        last, none = ops.sde_euler_step(d(x), d(v), None, rar, var, diff, 0.04, 0.0, 0.0)
+        assert none is None and _same(last, x + R.sde_drift_from_velocity(v.float(), x, tv, form, norm) * 0.04), (shape, off, "mean")
+    src, dst = torch.zeros(5, device=DEV), torch.ones(5, device=DEV)          # the C entry itself: n = 5 passes the argument check
+    torch.cuda.synchronize()
+    p, q = ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr())
+    assert _lib.lib().dmvae_sde_euler_step(p, p, 0, None, None, q, 5, 0.5, 0.5, 0.5, 0.1, 0.0, 0.0, None) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(dst, src)                                              # x = v = 0: the mean is 0
+
+
+@pytest.mark.parametrize("vdtype", [torch.float32, BF], ids=["f32", "bf16"])
 @pytest.mark.parametrize("tval", TIMES)
 @pytest.mark.parametrize("mode,h", [("Tweedie", 0.04), ("Euler", 0.04), ("Euler", 0.1)])
 def test_last_step_kernel_bit_exact(mode, h, tval, vdtype):

@@ -333,3 +333,31 @@ def test_ode_routes_take_the_drift_from_the_kernel(kind, method, num_steps, monk
         T.FUSED_STATE_UPDATE = True
     assert len(launches) == nfe and len(seen) == nfe                # the composed route launches no conversion kernel and evaluates as often
     assert plain.shape == xs.shape and torch.isfinite(plain).all()
+
+
+def test_euler_sde_on_an_odd_element_count_equals_the_composition(monkeypatch):
+    """`sample_sde(sampling_method="Euler", last_step="Mean")` on a (3, 1, 5, 1) state -- 15 elements, which the Euler-Maruyama kernel used to refuse, so that the
+    sampler composed such a step -- with the linear stub of the ODE check above as a velocity model: every state of the kernel route equals the composition's
+    (same noise stream), and the kernel route does launch `ops.sde_euler_step` for both steps and the last one.  The composition takes sqrt(2 diffusion) with the
+    device's sqrt, which is not correctly rounded on this stack (tests/test_gpu_sampler_methods.py); the "linear" form with norm 8 on the grid
+    linspace(0, 1 - 0.125, 3) = 0, 0.4375, 0.875 keeps its inputs at the exact squares 16 and 9, every product on the way exact in f32."""
+    from dmvae_amd import ops
+    from dmvae_amd import transport as T
+    calls, real = [], ops.sde_euler_step
+    monkeypatch.setattr(ops, "sde_euler_step", lambda *a, **kw: calls.append(a[0].numel()) or real(*a, **kw))
+    stub = lambda x, t, y: 0.3 * x + 0.1 * t.view(-1, 1, 1, 1) + 0.001 * y.view(-1, 1, 1, 1)
+    fn = T.Sampler(T.create_transport("Linear", "velocity")).sample_sde(sampling_method="Euler", diffusion_form="linear", diffusion_norm=8.0, last_step="Mean",
+                                                                        last_step_size=0.125, num_steps=3)
+    x0, labels = _inputs((3, 1, 5, 1))[0].to(DEV), torch.arange(3, device=DEV, dtype=torch.float32)
+    runs = []
+    for fused in (True, False):
+        T.FUSED_STATE_UPDATE = fused
+        try:
+            torch.manual_seed(11)
+            with torch.no_grad():
+                runs.append(torch.stack(fn(x0, stub, y=labels)))
+        finally:
+            T.FUSED_STATE_UPDATE = True
+    assert calls == [15, 15, 15]                                    # the kernel route only
+    assert runs[0].shape == (3, 3, 1, 5, 1) and runs[0].dtype == torch.float32 and torch.isfinite(runs[0]).all()
+    assert torch.equal(runs[0], runs[1])

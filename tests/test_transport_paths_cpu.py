@@ -196,3 +196,16 @@ def test_library_rejects_bad_model_terms_without_a_gpu():
     assert L.dmvae_sde_heun_correct_m(p, p, p, p, 0, ctypes.byref(bad), p, 4, 0.5, 0.5, 0.5, 0.05, None) == -22
     assert L.dmvae_sde_last_step_m(p, p, 0, ctypes.byref(ok), p, 4, 2, 1.0, 0.0, 0.0, None) == -22
     assert L.dmvae_sde_last_step_m(p, p, 0, ctypes.byref(bad), p, 4, 0, 1.0, 0.0, 0.0, None) == -22
+
+
+def test_library_rejects_a_bad_euler_step_without_a_gpu():
+    """`dmvae_sde_euler_step` takes any n > 0 (tests/test_gpu_sampler_methods.py launches n = 5); what it still refuses before it launches: n = 0, a NULL x,
+    and both outputs NULL."""
+    import ctypes
+    from dmvae_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert L.dmvae_sde_euler_step(p, p, 0, None, p, None, 0, 0.5, 0.5, 0.5, 0.1, 0.0, 0.0, None) == -22 and b"sde_euler_step" in L.dmvae_last_error()
+    assert L.dmvae_sde_euler_step(None, p, 0, None, p, None, 4, 0.5, 0.5, 0.5, 0.1, 0.0, 0.0, None) == -22
+    assert L.dmvae_sde_euler_step(p, p, 0, None, None, None, 4, 0.5, 0.5, 0.5, 0.1, 0.0, 0.0, None) == -22
