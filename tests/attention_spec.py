@@ -42,7 +42,14 @@ the scores, Dx_qj = scale sum_d (dq_ |k| + |q| dk_ + dq_ dk_), and to the output
 exp(2 max Dx) for the higher orders.
 
 Worst |error| / bound of the emulations over every shared case (tests/test_attention_spec_cpu.py prints them; the only arbiter the bars have): out 0.744, lse 0.065,
-dq 0.334, dk 0.388, dv 0.876; NR out 0.574.  No bar needed widening; the negative controls and what each reaches are listed in that module's docstring."""
+dq 0.334, dk 0.388, dv 0.876; NR out 0.574.  No bar needed widening; the negative controls and what each reaches are listed in that module's docstring.
+
+The streaming kernels (csrc/attention_stream.hip, csrc/attention_bwd_stream.hip; any S) compute the same operation and take the same `reference`; the second half of
+this file holds THEIR bars (bars_forward_stream, bars_backward_stream: the derivation stands in the comment above them -- the per-tile alpha and emc sites, the row-sum
+and P V depths per tile, delta as an output, both kinds of backward operands), three more input classes (ascending, descending, spike_last), the token counts at which
+one of their mechanisms changes (STREAM_TOKENS) and their emulations with the tile walk (emulate_forward_stream, emulate_backward_stream).  The resident bars, classes
+and emulations above are untouched by it.  Worst |error| / bound of the streaming emulations (tests/test_attention_stream_spec_cpu.py): out 0.726, lse 0.063; backward
+on the forward's own out / lse dq 0.243, dk 0.295, dv 0.834, delta 0.170; on bf16(o) / f32(lse) of the definition dq 0.433, dk 0.529, dv 0.886, delta 0.353."""
 import math
 
 import torch
@@ -56,6 +63,13 @@ TOKENS = [1, 31, 32, 33, 64, 65, 129, 200, 256, 257, 272, 288]
 ALL_CLASS_TOKENS = (33, 257, 288)
 CLASSES = ["randn", "negative", "randn4", "last", "zeroq", "offset", "spike"]
 HEAD_FORMS = [(40, 40), (40, 64), (64, 64), (72, 72), (72, 96), (96, 96)]      # (head dim, channels a q / k row holds)
+# the streaming kernels (any S; the second half of this file): 64-key tiles, the token counts at which one of their mechanisms changes, three more classes
+STREAM_TILE = 64
+STREAM_TOKENS = [1, 31, 32, 33, 63, 64, 65, 96, 97, 127, 128, 129, 255, 256, 257, 289, 320, 321, 513, 577]
+STREAM_ALL_CLASS_TOKENS = (257, 289, 320)          # one live key in the last tile, a ragged last tile, whole tiles
+STREAM_CLASSES = CLASSES + ["ascending", "descending", "spike_last"]
+STREAM_EVERYWHERE = ["randn", "negative", "ascending", "last"]
+STREAM_HEAD_FORMS = [(64, 64), (72, 72), (72, 96)]
 
 
 def classes_at(s):
@@ -68,6 +82,14 @@ def staged(d):
 
 def nblocks(s):
     return (s + 31) // 32
+
+
+def ntiles(s):
+    return (s + STREAM_TILE - 1) // STREAM_TILE
+
+
+def stream_classes_at(s):
+    return STREAM_CLASSES if s in STREAM_ALL_CLASS_TOKENS else STREAM_EVERYWHERE
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------------------------------
@@ -92,8 +114,13 @@ def make_case(kind, b, h, s, d, seed=0):
     last      q = g u, k = 0.2 linspace(0, 8) r u but the last key 8 r u: the last key takes >= 0.99 of every row (the only live key of its block at S = 32 k + 1);
     zeroq     zero queries: uniform rows, o = mean V, lse = log S;
     offset    k = a u + 0.1 randn, q = +- a u + 0.5 randn with scale a^2 = 80: |lse| ~ 80, where an f32 ulp is 8e-6;
-    spike     keys 0.05 r u but key spike_key(S) = 56 r u, q = g u: that key scores ~105 against < 1, so a row maximum that misses it overflows the power."""
-    g = _gen(CLASSES.index(kind), b, h, s, d, seed)
+    spike     keys 0.05 r u but key spike_key(S) = 56 r u, q = g u: that key scores ~105 against < 1, so a row maximum that misses it overflows the power.
+    The streaming kernels' three (nt = ceil(S / 64) tiles, tile(j) = j // 64):
+    ascending   q = g u, k_j = 8 (tile(j) + 1) / nt jit_j r u, jit in [0.9, 1] and 1 on the last live key of each tile: every tile raises the running maximum by
+                g / nt >= 0.8, so every tile's factor is < 1 and what tile 0 accumulated is rescaled nt - 1 times;
+    descending  the same with (nt - tile(j)) / nt: the first tile holds the maximum and every later factor is exactly 1;
+    spike_last  spike with the large key on S - 1, the last live key of the last tile."""
+    g = _gen(STREAM_CLASSES.index(kind), b, h, s, d, seed)
     G = b * h
     rn = lambda *sh: torch.randn(*sh, generator=g)
     u = rn(G, 1, d)
@@ -121,6 +148,16 @@ def make_case(kind, b, h, s, d, seed=0):
         coef = torch.full((1, s, 1), 0.05)
         coef[:, spike_key(s)] = 56.0
         q, k = gq * u, coef * r * u
+    elif kind == "spike_last":
+        coef = torch.full((1, s, 1), 0.05)
+        coef[:, s - 1] = 56.0
+        q, k = gq * u, coef * r * u
+    elif kind in ("ascending", "descending"):
+        nt, tile = ntiles(s), torch.arange(s) // STREAM_TILE
+        level = ((tile + 1) if kind == "ascending" else (nt - tile)).double() / nt
+        jit = 0.9 + 0.1 * torch.rand(G, s, 1, generator=g)
+        jit[:, torch.clamp((tile + 1) * STREAM_TILE, max=s) - 1] = 1.0          # the last live key of each tile
+        q, k = gq * u, (8 * level.view(1, s, 1) * jit * r * u).float()
     else:
         raise ValueError(kind)
     return dict(kind=kind, b=b, h=h, s=s, d=d, scale=d ** -0.5, q=q.to(BF), k=k.to(BF), v=v.to(BF), do=rn(G, s, d).to(BF))
@@ -138,11 +175,26 @@ def check_class(c, ref):
         assert float((ref["o"] - c["v"].double().mean(1, keepdim=True)).abs().max()) < 1e-12 and float((ref["lse"] - math.log(s)).abs().max()) < 1e-12
     elif kind == "offset":
         assert float(ref["lse"].abs().min()) >= 60.0, float(ref["lse"].abs().min())
-    elif kind == "spike" and s > 1:
-        j = spike_key(s)
+    elif kind in ("ascending", "descending") and ntiles(s) > 1:
+        tm = tile_max(x)
+        if kind == "ascending":      # every tile after the first raises the maximum by at least 0.5
+            gap = (tm[..., 1:] - torch.cummax(tm, -1).values[..., :-1]).min()
+        else:                        # the first tile holds the maximum, at least 0.5 above every later tile's
+            gap = (tm[..., :1] - tm[..., 1:]).min()
+        assert float(gap) >= 0.5, float(gap)
+    elif kind in ("spike", "spike_last") and s > 1:
+        j = spike_key(s) if kind == "spike" else s - 1
         rest = torch.cat([x[..., :j], x[..., j + 1:]], -1)
         assert float((x[..., j] - rest.max(-1).values).min()) >= 96.0      # > log(FLT_MAX) = 88.7
         assert float(ref["p"][..., j].min()) >= 1 - 1e-30
+
+
+def tile_max(x):
+    """[.., S] scaled scores -> [.., nt]: the maximum of every 64-key tile"""
+    s, nt = x.shape[-1], ntiles(x.shape[-1])
+    pad = torch.full(x.shape[:-1] + (nt * STREAM_TILE,), float("-inf"), dtype=x.dtype, device=x.device)
+    pad[..., :s] = x
+    return pad.view(*x.shape[:-1], nt, STREAM_TILE).max(-1).values
 
 
 def to_dev(c, dev):
@@ -377,3 +429,209 @@ def spread_items(total):
         it.add(extra)
         extra += total // 29 + 1
     return sorted(it)
+
+
+# ==== the streaming kernels (csrc/attention_stream.hip, csrc/attention_bwd_stream.hip; any S) =========================================================================
+# The same operation, so `reference` is the definition; the bars below are derived from THESE kernels' rounding sites (tests/test_attention_stream_spec_cpu.py,
+# tests/test_gpu_attention_stream_spec.py).  nt = ceil(S / 64) key (query) tiles; t(j) = j // 64; xm_t = the running maximum of the scaled scores after tile t
+# (xm_{nt-1} = xmax); u = 2^-8; one f32 rounding = 2^-24 of the value rounded.
+#
+# Forward (attention_stream_kernel).  The weight key j ends up with, in l and in the accumulators alike, is
+#     w_j = 2^(fma(s_j, ec, -fl(m_t ec))) * alpha_{t+1} ... alpha_{nt-1},      alpha_v = 2^(fl(fl(m_{v-1} - m_v) ec)),   t = t(j)
+# against exp(x_j - xmax); in exact arithmetic the exponents telescope.  Its relative error eps_s_j is the resident eps_j (scores E_x, ec's two roundings and the
+# fma's one, v_exp_f32 at 1 ulp: the same instructions) plus what the tile walk adds:
+#   emc_t     fl(m_t ec) is rounded per TILE (1 on |xm_t|): in the resident kernel it is common to the row and cancels in P; here keys of different tiles carry
+#             different roundings, so it stays:                                                                   2^-24 |xm_t(j)|
+#   alpha     for every later tile v: the difference (1) and its product with ec (1) on xm_v - xm_{v-1} -- summed over v that is the distance the maximum still
+#             travels, 2 (xmax - xm_t(j)) --, the power (2: v_exp_f32) and the multiply `l *= alpha` / `o *= alpha` (1):    2^-24 (2 (xmax - xm_t(j)) + 3 (nt - 1 - t(j)))
+#             (ec's own error multiplies the telescoped exponent x_j - xmax and is in eps_j already)
+#       eps_s_j = eps_j + 2^-24 (|xm_t(j)| + 2 (xmax - xm_t(j)) + 3 (nt - 1 - t(j)))
+#   row sum   the UNROUNDED p, 32 in-lane adds per tile and the half-wave sum at the end:     sum_depth = 32 nt + 1
+#   P V       p -> bf16 once; 64 keys per tile into the f32 accumulators:                     pv_depth = 64 nt
+#   lse       fl(fl(m scale) + __logf(l)): the resident expression on the streamed m and l:
+#       E_lse = 2^-24 (4 |xmax| + sum_depth + 6 (lse - xmax) + |lse|) + sum_j p_j eps_s_j
+#   out       o * (1 / l) -> bf16:
+#       E_o = sum_j p_j (u + eps_s_j) |v_jd| + (sum_j p_j |v_jd|) (sum_j p_j eps_s_j + (pv_depth + sum_depth + 3) 2^-24)
+# The mask of the ragged tile (score -inf, p = 0 exactly), the staging (copies) and the skipped waves round nothing.
+#
+# Backward (attention_bwd_stream_dq_kernel, attention_bwd_stream_dkdv_kernel); the sites its header lists, each against the resident derivation above:
+#   q, k, v, dO, O bf16 operands       the same: no term
+#   delta = dO . O, O as stored        the resident site (E_delta).  The order differs -- 8 KS in-lane fmas on exact products and one cross-half add, 33 / 41 roundings
+#                                      -- and stays under the resident depth D + 1 = 65 / 73, which is kept.  |O - o| is `o_bar`: the forward's bar B_o when the
+#                                      backward runs on the forward kernel's own out, u |o| when it runs on bf16(o) of the reference.
+#                                      delta is written to caller memory by the query pass: an OUTPUT, held to E_delta; the key pass reads those bits back
+#   scores, dP on the matrix cores     the same: E_x, E_dP with DP = 64 / 96 (five 16-channel steps at 72: under 96)
+#   p = __expf(scale s - L) in f32     the resident site (eps_b) in BOTH passes, no running maximum: eps_b = eps_j + 3 * 2^-24 (lse - xmax) + E_L with E_L = the
+#                                      forward's E_lse (its own lse) or 2^-24 |lse| (f32(lse) of the reference).  L and delta travel with a key-pass tile as f32
+#                                      copies: no rounding; a padded query's L = +inf gives p = 0 exactly, a padded key's p is a select
+#   P, scale dS -> bf16 once           the same (u; fl(fl(p (dP - delta)) scale): 4 * 2^-24).  Each pass rounds its own copy of the same f32 value
+#   dQ, dK, dV f32 sums, bf16 once     DIFFERS in depth: the query pass adds 64 keys per tile over nt tiles into dQ, the key pass 64 queries per tile over nt tiles
+#                                      into dK and dV: depth = 64 nt in both (resident: 32 nblk)
+def _tile_of_key(s, dev):
+    return torch.arange(s, device=dev) // STREAM_TILE
+
+
+def bars_forward_stream(q, k, v, scale, ref):
+    """-> dict o, lse (bounds on the bf16 out and the f32 lse) and the pieces bars_backward_stream reuses"""
+    s, d = q.shape[-2:]
+    dp, nt = staged(d), ntiles(s)
+    qa, ka, va = q.double().abs(), k.double().abs(), v.double().abs()
+    x, p, lse = ref["x"], ref["p"], ref["lse"]
+    xmax = x.max(-1, keepdim=True).values
+    e_x = dp * U24 * scale * qa @ ka.transpose(-1, -2)
+    eps_res = U24 * (3 * x.abs() + 3 * (x - xmax).abs() + 2) + e_x                        # the resident eps_j
+    tj = _tile_of_key(s, x.device)
+    xm = torch.cummax(tile_max(x), -1).values[..., tj]                                    # xm_t(j) per (query, key)
+    eps = eps_res + U24 * (xm.abs() + 2 * (xmax - xm) + 3 * (nt - 1 - tj).double())
+    sum_depth, pv_depth = 32 * nt + 1, 64 * nt
+    peps = (p * eps).sum(-1, keepdim=True)
+    lsum = lse.unsqueeze(-1) - xmax
+    e_lse = (U24 * (4 * xmax.abs() + sum_depth + 6 * lsum + lse.unsqueeze(-1).abs()) + peps).squeeze(-1)
+    a = p @ va
+    e_o = (p * (U8 + eps)) @ va + a * (peps + (pv_depth + sum_depth + 3) * U24) + TINY
+    return dict(o=bf16_bound(ref["o"], e_o), lse=e_lse + TINY, eps_res=eps_res, xmax=xmax, e_lse=e_lse)
+
+
+def bars_backward_stream(q, k, v, do, scale, ref, fwd, operands="kernel"):
+    """-> dict dq, dk, dv (bf16) and delta (f32).  fwd = bars_forward_stream(...).  operands: "kernel" -- out / lse are the forward kernel's own, within fwd['o'] /
+    fwd['lse'] of the definition; "reference" -- bf16(o) and f32(lse) of the definition"""
+    s, d = q.shape[-2:]
+    dp, nt = staged(d), ntiles(s)
+    qa, ka, va, da = q.double().abs(), k.double().abs(), v.double().abs(), do.double().abs()
+    p, lse = ref["p"], ref["lse"].unsqueeze(-1)
+    if operands == "kernel":
+        e_l, o_bar = fwd["e_lse"].unsqueeze(-1), fwd["o"]
+    else:
+        e_l, o_bar = U24 * lse.abs(), U8 * ref["o"].abs() + TINY
+    eps_b = fwd["eps_res"] + 3 * U24 * (lse - fwd["xmax"]) + e_l
+    depth = 64 * nt * U24
+    e_dv = (p * (U8 + eps_b + depth)).transpose(-1, -2) @ da + TINY
+    e_delta = (da * o_bar).sum(-1, keepdim=True) + (d + 1) * U24 * (da * ref["o"].abs()).sum(-1, keepdim=True)
+    e_dp = dp * U24 * da @ va.transpose(-1, -2)
+    t = scale * p * (ref["dP"] - ref["delta"]).abs()
+    w = t * (U8 + eps_b + 4 * U24) + scale * p * (e_dp + e_delta) + depth * t
+    return dict(dq=bf16_bound(ref["dq"], w @ ka + TINY), dk=bf16_bound(ref["dk"], w.transpose(-1, -2) @ qa + TINY), dv=bf16_bound(ref["dv"], e_dv),
+                delta=e_delta.squeeze(-1) + TINY)
+
+
+def reference_operands(ref):
+    """the backward's saved operands made from the definition: bf16(o) [G, S, D], f32(lse) [G, S]"""
+    return ref["o"].to(BF), ref["lse"].to(F32)
+
+
+# ---- emulations in kernel order (CPU) -----------------------------------------------------------------------------------------------------------------------------------
+_HALF_OF_KEY = (torch.arange(STREAM_TILE) % 8) // 4                    # the half-wave (lane >> 5) that holds a tile's key: register r of block kb is key
+_LANE_ORDER = [[kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg for kb in range(2) for r in range(16)] for kg in range(2)]       # kb * 32 + (r & 3) + 8 (r >> 2) + 4 kg
+
+FORWARD_STREAM_MUTANTS = ["leak", "alpha_o_only", "alpha_l_only", "alpha_sign", "half_max", "l_rounded", "lse_half", "stale_block"]
+BACKWARD_STREAM_MUTANTS = ["skip_one_q", "skip_one_k", "kpass_256", "p_from_max", "delta_unrounded_o", "ds_round_first", "pad_cols"]
+
+
+def emulate_forward_stream(q, k, v, scale, mutant=None):
+    """attention_stream_kernel: per 64-key tile the raw scores, the mask of the ragged tile, the running maximum (per half-wave, exchanged), alpha, `l *= alpha`,
+    `o *= alpha`, p = 2^(fma(s, ec, -m ec)), l += p in the lane's register order, P V on the bf16 p in four 16-key steps; then the half-wave sum, o * (1 / l) and
+    lse = m scale + log(l) -> (out bf16, lse f32, dict o32 = the unrounded o * (1 / l), m = the final raw maximum).
+    State is kept per half-wave (m, l: [G, S, 2]; a channel c of the accumulators sits in half (c % 8) // 4), which is what lets the mutants be one changed line."""
+    G, s, d = q.shape
+    nt = ntiles(s)
+    pad = nt * STREAM_TILE
+    qf = _f(q)
+    kp, vp = torch.zeros(G, pad, d), torch.zeros(G, pad, d)             # rows past S are staged as zeros
+    kp[:, :s], vp[:, :s] = _f(k), _f(v)
+    sf = torch.tensor(scale, dtype=F32)
+    ec = sf * torch.tensor(LOG2E_F32, dtype=F32)
+    chalf = (torch.arange(d) % 8) // 4
+    ninf = torch.tensor(float("-inf"))
+    m, l, o = torch.full((G, s, 2), float("-inf")), torch.zeros(G, s, 2), torch.zeros(G, s, d)
+    for t in range(nt):
+        kt, vt = kp[:, t * 64:t * 64 + 64], vp[:, t * 64:t * 64 + 64]
+        if mutant == "stale_block" and t > 0:                           # the tile's second block read from the other buffer: tile t - 1's image
+            kt, vt = torch.cat([kt[:, :32], kp[:, t * 64 - 32:t * 64]], 1), torch.cat([vt[:, :32], vp[:, t * 64 - 32:t * 64]], 1)
+        sc = qf @ kt.transpose(-1, -2)
+        lim = s - t * 64
+        if mutant == "leak" and lim < 64:
+            lim += 1                                                    # one padded key of the last tile left unmasked
+        sc = torch.where(torch.arange(64) < lim, sc, ninf)
+        tmh = torch.stack([sc[..., _HALF_OF_KEY == hh].max(-1).values for hh in range(2)], -1)
+        tm = tmh if mutant == "half_max" else tmh.max(-1, keepdim=True).values.expand(-1, -1, 2)      # xhalf_max
+        mn = torch.maximum(m, tm)
+        if mutant == "alpha_sign":
+            alpha = torch.where(torch.isinf(m), torch.zeros(()), torch.exp2((mn - m) * ec))
+        else:
+            alpha = torch.exp2((m - mn) * ec)                           # first tile: 2^(-inf) = 0
+        emc = mn * ec
+        m = mn
+        if mutant != "alpha_o_only":
+            l = l * alpha
+        if mutant != "alpha_l_only":
+            o = o * alpha[..., chalf]
+        e = torch.exp2((sc.double() * ec.double() - emc[..., _HALF_OF_KEY].double()).float())        # one rounding: the fma
+        eb = _bfr(e)
+        ea = eb if mutant == "l_rounded" else e
+        lh = []
+        for hh in range(2):
+            acc = l[..., hh]
+            for j in _LANE_ORDER[hh]:
+                acc = acc + ea[..., j]
+            lh.append(acc)
+        l = torch.stack(lh, -1)
+        for c in range(0, 64, 16):
+            o = o + eb[..., c:c + 16] @ vt[:, c:c + 16]
+    lt = l[..., 0] + l[..., 1]                                          # xhalf_sum
+    o32 = o * (1.0 / lt).unsqueeze(-1)
+    lse = m[..., 0] * sf + torch.log(l[..., 0] if mutant == "lse_half" else lt)
+    return o32.to(BF), lse, dict(o32=o32, m=m[..., 0])
+
+
+def emulate_backward_stream(q, k, v, o, do, lse, scale, rows=None, mutant=None, o32=None, m=None):
+    """the two passes -> dq, dk [G, S, rows or D] bf16, dv [G, S, D] bf16, delta [G, S] f32.  delta: per half-wave the in-lane chain over its 8-channel pieces, then
+    the cross-half add.  Both passes rebuild p = __expf(s scale - L) and dS = fl(fl(p (dP - delta)) scale) in f32 and round their own bf16 copy; the query pass adds
+    dS K over the key tiles in 16-key steps, the key pass P^T dO and dS^T Q over the query tiles in 16-query steps.  o32, m: the forward emulation's extras, for
+    the mutants that take the unrounded O or the running maximum."""
+    G, s, d = q.shape
+    nt, ks = ntiles(s), (4 if d == 64 else 5)
+    sf = torch.tensor(scale, dtype=F32)
+    l2e = torch.tensor(LOG2E_F32, dtype=F32)
+    qf, kf, vf, dof = _f(q), _f(k), _f(v), _f(do)
+    prod = dof * (o32 if mutant == "delta_unrounded_o" else _f(o))
+    dh = []
+    for hh in range(2):
+        acc = torch.zeros(G, s)
+        for kk in range(ks):
+            for c in range(kk * 16 + hh * 8, min(kk * 16 + hh * 8 + 8, d)):
+                acc = acc + prod[..., c]
+        dh.append(acc)
+    delta = (dh[0] + dh[1]).unsqueeze(-1)
+    xs = (qf @ kf.transpose(-1, -2)) * sf
+    dP = dof @ vf.transpose(-1, -2)
+    L = (m * sf if mutant == "p_from_max" else lse).unsqueeze(-1)
+    p = torch.exp2((xs - L) * l2e)                                      # __expf
+    if mutant == "ds_round_first":
+        ds_b = _bfr(_bfr(p * (dP - delta)) * sf)                        # dS -> bf16 BEFORE the scale
+    else:
+        ds_b = _bfr(p * (dP - delta) * sf)
+    pb = _bfr(p)
+    one_left = s - (nt - 1) * 64 == 33                                  # the last tile's second block holds exactly one live row
+    nq = s - 1 if mutant == "skip_one_q" and one_left else s            # keys the query pass walks
+    nk = s - 1 if mutant == "skip_one_k" and one_left else s            # queries the key pass walks
+    dq, dk, dv = torch.zeros(G, s, d), torch.zeros(G, s, d), torch.zeros(G, s, d)
+    for c in range(0, nq, 16):
+        e = min(c + 16, nq)
+        dq = dq + ds_b[..., c:e] @ kf[:, c:e]
+    for c in range(0, nk, 16):
+        e = min(c + 16, nk)
+        dv = dv + pb[:, c:e].transpose(-1, -2) @ dof[:, c:e]
+        dk = dk + ds_b[:, c:e].transpose(-1, -2) @ qf[:, c:e]
+    if mutant == "kpass_256" and d == 72:                               # four waves = 128 keys per workgroup on a grid of ceil(S / 256): keys 128 .. 255 of each
+        dead = (torch.arange(s) % 256) >= 128                           # 256 are nobody's, the caller's pre-fill stays
+        dk[:, dead], dv[:, dead] = float("nan"), float("nan")
+    dq, dk = dq.to(BF), dk.to(BF)
+    if rows is not None and rows > d:
+        dq, dk = pad_rows(dq, rows), pad_rows(dk, rows)
+        if mutant == "pad_cols":                                        # the products over the padded channels taken on what is not zero
+            dq[..., d:], dk[..., d:] = dq[..., :rows - d], dk[..., :rows - d]
+    return dq, dk, dv.to(BF), delta.squeeze(-1)
+
+
+def padded_columns_are_zero(t, d):
+    return t.shape[-1] == d or float(t[..., d:].float().abs().max()) == 0.0
