@@ -49,7 +49,25 @@ this file holds THEIR bars (bars_forward_stream, bars_backward_stream: the deriv
 and P V depths per tile, delta as an output, both kinds of backward operands), three more input classes (ascending, descending, spike_last), the token counts at which
 one of their mechanisms changes (STREAM_TOKENS) and their emulations with the tile walk (emulate_forward_stream, emulate_backward_stream).  The resident bars, classes
 and emulations above are untouched by it.  Worst |error| / bound of the streaming emulations (tests/test_attention_stream_spec_cpu.py): out 0.726, lse 0.063; backward
-on the forward's own out / lse dq 0.243, dk 0.295, dv 0.834, delta 0.170; on bf16(o) / f32(lse) of the definition dq 0.433, dk 0.529, dv 0.886, delta 0.353."""
+on the forward's own out / lse dq 0.243, dk 0.295, dv 0.834, delta 0.170; on bf16(o) / f32(lse) of the definition dq 0.433, dk 0.529, dv 0.886, delta 0.353.
+
+The d = 512 streaming kernels (csrc/attention_wide.hip, csrc/attention_wide_bwd.hip; one head, any S) take the same `reference` again; the third section of this file
+holds THEIR bars (bars_forward_wide, bars_backward_wide: the derivation stands in the comment above them -- 512-channel scores, quarter sums in the backward, 32-key
+tiles, delta = sum_k P dP from the kernel's own p with no term of the stored O, scale dS as hi + lo), the token counts (WIDE_TOKENS), make_case's `tile` parameter
+(32 here; 64 by default, so every earlier case keeps its bits) and the emulations with the 32-key tile walk (emulate_forward_wide, emulate_backward_wide).
+Worst |error| / bound, emulations (tests/test_attention_wide_spec_cpu.py) | MI355X (tests/test_gpu_attention_wide_spec.py):
+  out 0.612 | 0.491, lse 0.022 | 0.042; backward on the forward's own lse dq 0.826 | 0.846, dk 0.687 | 0.698, dv 0.660 | 0.646, delta 0.012 | 0.013;
+  on f32(lse) of the definition dq 0.829 | 0.848, dk 0.869 | 0.869, dv 0.750 | 0.751, delta 0.030 | 0.021.  No bar needed widening.
+Negative controls, one changed line of an emulation each, and the bar each leaves (|error| / bound):
+  leak out 108 (negative S 33), lse 26 (zeroq S 1025); mask_ignores_half out 117 (negative S 17); alpha_o_only lse 9.6e3 (ascending S 97); alpha_l_only out 1.2e6
+  (last S 97); half_max lse 3.1e4 (spike S 33); lse_half lse 1.8e5 (zeroq S 33); l_rounded lse 2.5 (negative S 33); stale_tile out 1.7e5 (randn4 S 97);
+  delta_from_O delta 33 / 40, dq 19 / 21 (last S 1025; own / made lse); ds_single_bf16 dq 3.9 (zeroq S 33), 3.5 (randn S 97), dk 2.7 (last S 33);
+  quarter_dropped dq 716, dk 671, dv 861, delta 921 (randn S 97); p_from_max dq 2.8e7 (zeroq S 1025); dk_noscale dk 3.8e3 (last S 33); skip_one_q delta 1.6e3
+  (last S 33), dq 1.0e3 (zeroq S 33); skip_one_k dv 105, dk 128 (randn S 33).  None is left "not told".
+  Inert (neither): pad_key_unselected and pad_query_finite_L.  Padded K, V, Q and dO rows are staged as zeros, so the p a padded key or query keeps (finite: L > -88
+  in every class) meets dP = 0 in delta's fmaf and zero rows in dQ, dK and dV: it adds +-0.  The emulations' outputs are bit-identical with and without (asserted).
+  What the wide bars do NOT see: one leaked key on randn at 1025 tokens (lse 0.17) -- at 512 channels the scores' worst-case f32 term is as wide as that leak; zeroq,
+  negative and offset at 1025 tokens are what see it."""
 import math
 
 import torch
@@ -70,6 +88,11 @@ STREAM_ALL_CLASS_TOKENS = (257, 289, 320)          # one live key in the last ti
 STREAM_CLASSES = CLASSES + ["ascending", "descending", "spike_last"]
 STREAM_EVERYWHERE = ["randn", "negative", "ascending", "last"]
 STREAM_HEAD_FORMS = [(64, 64), (72, 72), (72, 96)]
+# the d = 512 streaming kernels (single head, any S; the third section of this file): 32-key tiles, 64-query forward blocks, 32-row backward blocks
+WIDE_TILE = 32
+WIDE_D = 512
+WIDE_TOKENS = [1, 17, 31, 32, 33, 63, 64, 65, 95, 96, 97, 128, 129, 1025, 1296]
+WIDE_ALL_CLASS_TOKENS = (33, 97, 1025)          # one live key / row in the last tile: inside the first forward block, with an idle wave pair, and far out
 
 
 def classes_at(s):
@@ -84,12 +107,16 @@ def nblocks(s):
     return (s + 31) // 32
 
 
-def ntiles(s):
-    return (s + STREAM_TILE - 1) // STREAM_TILE
+def ntiles(s, tile=STREAM_TILE):
+    return (s + tile - 1) // tile
 
 
 def stream_classes_at(s):
     return STREAM_CLASSES if s in STREAM_ALL_CLASS_TOKENS else STREAM_EVERYWHERE
+
+
+def wide_classes_at(s):
+    return STREAM_CLASSES if s in WIDE_ALL_CLASS_TOKENS else STREAM_EVERYWHERE
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------------------------------
@@ -106,7 +133,7 @@ def spike_key(s):
     return c[-1] if c else s - 1
 
 
-def make_case(kind, b, h, s, d, seed=0):
+def make_case(kind, b, h, s, d, seed=0, tile=STREAM_TILE):
     """-> dict of q, k, v, do [G, S, D] bf16 on the CPU, scale = d ** -0.5.  Classes (u: one unit direction per item, r = sqrt(d) / 8 so that scores are those of d = 64):
     randn (x 1.5), randn4 (x 4: peaked rows);
     negative  q = -g u, k = c u, g in [14, 16], c in sqrt(d) [0.62, 1] (d = 64: [4.96, 8]): every scaled score in [-16, -8.6] -- a key left at score 0 takes the weight
@@ -115,11 +142,12 @@ def make_case(kind, b, h, s, d, seed=0):
     zeroq     zero queries: uniform rows, o = mean V, lse = log S;
     offset    k = a u + 0.1 randn, q = +- a u + 0.5 randn with scale a^2 = 80: |lse| ~ 80, where an f32 ulp is 8e-6;
     spike     keys 0.05 r u but key spike_key(S) = 56 r u, q = g u: that key scores ~105 against < 1, so a row maximum that misses it overflows the power.
-    The streaming kernels' three (nt = ceil(S / 64) tiles, tile(j) = j // 64):
+    The streaming kernels' three (nt = ceil(S / tile) tiles, tile(j) = j // tile; tile = 64, or 32 for the d = 512 kernels):
     ascending   q = g u, k_j = 8 (tile(j) + 1) / nt jit_j r u, jit in [0.9, 1] and 1 on the last live key of each tile: every tile raises the running maximum by
                 g / nt >= 0.8, so every tile's factor is < 1 and what tile 0 accumulated is rescaled nt - 1 times;
     descending  the same with (nt - tile(j)) / nt: the first tile holds the maximum and every later factor is exactly 1;
-    spike_last  spike with the large key on S - 1, the last live key of the last tile."""
+    spike_last  spike with the large key on S - 1, the last live key of the last tile.
+    With 32-key tiles the same 16 units of score are climbed in up to 41 steps (S = 1296): a step is g / nt >= 0.34 there, see check_class."""
     g = _gen(STREAM_CLASSES.index(kind), b, h, s, d, seed)
     G = b * h
     rn = lambda *sh: torch.randn(*sh, generator=g)
@@ -153,19 +181,19 @@ def make_case(kind, b, h, s, d, seed=0):
         coef[:, s - 1] = 56.0
         q, k = gq * u, coef * r * u
     elif kind in ("ascending", "descending"):
-        nt, tile = ntiles(s), torch.arange(s) // STREAM_TILE
-        level = ((tile + 1) if kind == "ascending" else (nt - tile)).double() / nt
+        nt, tj = ntiles(s, tile), torch.arange(s) // tile
+        level = ((tj + 1) if kind == "ascending" else (nt - tj)).double() / nt
         jit = 0.9 + 0.1 * torch.rand(G, s, 1, generator=g)
-        jit[:, torch.clamp((tile + 1) * STREAM_TILE, max=s) - 1] = 1.0          # the last live key of each tile
+        jit[:, torch.clamp((tj + 1) * tile, max=s) - 1] = 1.0          # the last live key of each tile
         q, k = gq * u, (8 * level.view(1, s, 1) * jit * r * u).float()
     else:
         raise ValueError(kind)
-    return dict(kind=kind, b=b, h=h, s=s, d=d, scale=d ** -0.5, q=q.to(BF), k=k.to(BF), v=v.to(BF), do=rn(G, s, d).to(BF))
+    return dict(kind=kind, b=b, h=h, s=s, d=d, tile=tile, scale=d ** -0.5, q=q.to(BF), k=k.to(BF), v=v.to(BF), do=rn(G, s, d).to(BF))
 
 
 def check_class(c, ref):
     """the assertion ON THE REFERENCE ALONE that a class does what it is for"""
-    kind, s = c["kind"], c["s"]
+    kind, s, tile = c["kind"], c["s"], c.get("tile", STREAM_TILE)
     x = ref["x"]
     if kind == "negative":
         assert float(x.max()) <= -8.0, float(x.max())
@@ -175,13 +203,16 @@ def check_class(c, ref):
         assert float((ref["o"] - c["v"].double().mean(1, keepdim=True)).abs().max()) < 1e-12 and float((ref["lse"] - math.log(s)).abs().max()) < 1e-12
     elif kind == "offset":
         assert float(ref["lse"].abs().min()) >= 60.0, float(ref["lse"].abs().min())
-    elif kind in ("ascending", "descending") and ntiles(s) > 1:
-        tm = tile_max(x)
+    elif kind in ("ascending", "descending") and ntiles(s, tile) > 1:
+        tm = tile_max(x, tile)
         if kind == "ascending":      # every tile after the first raises the maximum by at least 0.5
             gap = (tm[..., 1:] - torch.cummax(tm, -1).values[..., :-1]).min()
         else:                        # the first tile holds the maximum, at least 0.5 above every later tile's
             gap = (tm[..., :1] - tm[..., 1:]).min()
-        assert float(gap) >= 0.5, float(gap)
+        # 64-key tiles: 0.5 as ever.  32-key tiles: the step is g / nt with g >= 14 and nt up to 41; q and k are rounded to bf16, 2 * 2^-9 of a score of at
+        # most 16.1 = 0.063 on either side of a step, so 14 / nt - 0.13 is kept and 0.6 * 14 / nt asked (0.20 at 1296 tokens: a factor of exp(-0.2) = 0.82)
+        need = 0.5 if tile == STREAM_TILE else min(0.5, 0.6 * 14 / ntiles(s, tile))
+        assert float(gap) >= need, (float(gap), need)
     elif kind in ("spike", "spike_last") and s > 1:
         j = spike_key(s) if kind == "spike" else s - 1
         rest = torch.cat([x[..., :j], x[..., j + 1:]], -1)
@@ -189,12 +220,12 @@ def check_class(c, ref):
         assert float(ref["p"][..., j].min()) >= 1 - 1e-30
 
 
-def tile_max(x):
-    """[.., S] scaled scores -> [.., nt]: the maximum of every 64-key tile"""
-    s, nt = x.shape[-1], ntiles(x.shape[-1])
-    pad = torch.full(x.shape[:-1] + (nt * STREAM_TILE,), float("-inf"), dtype=x.dtype, device=x.device)
+def tile_max(x, tile=STREAM_TILE):
+    """[.., S] scaled scores -> [.., nt]: the maximum of every `tile`-key tile"""
+    s, nt = x.shape[-1], ntiles(x.shape[-1], tile)
+    pad = torch.full(x.shape[:-1] + (nt * tile,), float("-inf"), dtype=x.dtype, device=x.device)
     pad[..., :s] = x
-    return pad.view(*x.shape[:-1], nt, STREAM_TILE).max(-1).values
+    return pad.view(*x.shape[:-1], nt, tile).max(-1).values
 
 
 def to_dev(c, dev):
@@ -635,3 +666,229 @@ def emulate_backward_stream(q, k, v, o, do, lse, scale, rows=None, mutant=None, 
 
 def padded_columns_are_zero(t, d):
     return t.shape[-1] == d or float(t[..., d:].float().abs().max()) == 0.0
+
+
+# ==== the d = 512 streaming kernels (csrc/attention_wide.hip, csrc/attention_wide_bwd.hip; one head, any S) ===========================================================
+# The same operation, so `reference` is the definition; cases are make_case(kind, b, 1, s, 512, tile=32).  The bars below are derived from THESE kernels' rounding sites
+# (tests/test_attention_wide_spec_cpu.py, tests/test_gpu_attention_wide_spec.py).  nt = ceil(S / 32) key (row) tiles; t(j) = j // 32; xm_t = the running maximum of the
+# scaled scores after tile t; u = 2^-8; one f32 rounding = 2^-24 of the value rounded.
+#
+# Forward (attention_wide_kernel).  Two waves share 32 queries and run the same score and softmax instructions on the same data, each on its half of the output
+# channels: the sites are per (query, key) and per (query, channel) as in the streaming kernel, with other depths.
+#   scores    st accumulates KS = 32 sixteen-channel MFMA steps: an f32 sum of 512 exact products:        E_x = 512 2^-24 scale sum_d |q_d k_d|
+#   power     2^(fma(st, ec, -emc)), ec = fl(scale fl(log2 e)), v_exp_f32: the resident figure             eps_j = 2^-24 (3 |x_j| + 3 |x_j - xmax| + 2) + E_x_j
+#   emc       fl(mn ec) once per 32-key TILE (1 on |xm_t|): keys of different tiles carry different roundings: 2^-24 |xm_t(j)|
+#   alpha     2^(fl(fl(m - mn) ec)) for every later tile v: the difference and the product (2 on xm_v - xm_{v-1}; summed over v: 2 (xmax - xm_t(j))), the power (2) and
+#             the multiply `l *= alpha` / `o[db][r] *= alpha` (1):                                         2^-24 (2 (xmax - xm_t(j)) + 3 (nt - 1 - t(j)))
+#       eps_w_j = eps_j + 2^-24 (|xm_t(j)| + 2 (xmax - xm_t(j)) + 3 (nt - 1 - t(j)))
+#   row sum   `l += st[r]` on the UNROUNDED p: 16 in-lane adds per tile (a lane holds 16 of the tile's 32 keys), xhalf_sum at the end:    sum_depth = 16 nt + 1
+#   P V       to_afrag rounds p to bf16 once (u); two 16-key MFMA steps per tile into the f32 accumulators:                              pv_depth = 32 nt
+#   lse       fl(fl(m scale) + __logf(l)), the streaming expression:   E_lse = 2^-24 (4 |xmax| + sum_depth + 6 (lse - xmax) + |lse|) + sum_j p_j eps_w_j
+#   out       inv = 1 / l (1), o * inv (1), the accumulators' own rounding into bf16 is bf16_bound's; the 3 of the streaming form is kept:
+#       E_o = sum_j p_j (u + eps_w_j) |v_jd| + (sum_j p_j |v_jd|) (sum_j p_j eps_w_j + (pv_depth + sum_depth + 3) 2^-24)
+# The half-wave mask of the ragged tile (score -inf, p = 0 exactly), the staging, the idle wave pair and the choice of the lane that writes lse round nothing.
+#
+# Backward (attention_wide_bwd_dq_kernel, attention_wide_bwd_dkdv_kernel).  Both passes form the same f32 values (the same instructions on the same operands, the
+# key on the lane or the query on the lane), so one set of sites:
+#   scores, dP   per wave KS = 8 sixteen-channel steps over ITS 128 channels (128 2^-24 of that quarter's magnitudes), then xch_sum's three f32 adds ((0 + 1) + 2) + 3,
+#                each 2^-24 of a partial sum no larger than the whole magnitude sum:  E_xb = 131 2^-24 scale sum_d |q_d k_d|,  E_dP = 131 2^-24 sum_d |dO_qd v_jd|
+#   p            __expf(fl(st scale) - L) (or the contracted fma: one rounding fewer): the product (1 on |x|), the difference and the product with fl(log2 e)
+#                (3 on |x - L| <= |x - xmax| + (lse - xmax)), v_exp_f32 (2); L is the caller's f32 lse, off by E_L = the wide forward's E_lse (its own lse) or
+#                2^-24 |lse| (f32(lse) of the definition):       eps_b = 2^-24 (3 |x| + 3 |x - xmax| + 2) + E_xb + 3 * 2^-24 (lse - xmax) + E_L
+#   delta        sum_k p dP by fmaf over the kernel's OWN p and dP -- `o` is not read, there is no dO . O and no term of the stored O's rounding: a lane chains its 16
+#                keys of every tile (16 nt fmas), xhalf_sum adds the two halves (1).  An OUTPUT in caller memory; the key pass reads those bits back:
+#                    E_delta = sum_j p_j (eps_b_j |dP_j| + E_dP_j) + (16 nt + 1) 2^-24 sum_j p_j |dP_j|
+#   scale dS     x = fl(fl(p fl(dP - delta)) scale): three roundings on T = scale p |dP - delta|; p's eps_b on T; E_dP + E_delta on the difference.  x enters the
+#                matrix cores as hi + lo, hi = bf16(x), lo = bf16(x - hi): x - hi is exact in f32 and at most u |x|, so what is lost is at most u^2 |x| = 2^-16 |x|
+#                (the header's 2^-17-class figure with u as half an ulp of 2^-9; the sibling's single bf16 loses u |x|):
+#                    W_qj = T_qj (u^2 + eps_b + 3 * 2^-24) + scale p_qj (E_dP + E_delta)
+#   dQ, dK       per 32-row tile two 16-row steps, each a product on hi and one on lo into the same f32 accumulator: 64 nt summands, the lo half of them u times smaller:
+#                    E_dq = sum_j (W_qj + 64 nt (1 + u) 2^-24 T_qj) |k_jd|;  E_dk the same over the queries with |q_qd|
+#   dV           P -> bf16 once (u), two 16-query steps per tile: E_dv = sum_q p_qj (u + eps_b + 32 nt 2^-24) |dO_qd|
+# Padded rows round nothing: zero staging, the select (query pass), L = +inf (key pass).
+WIDE_QUARTER_DEPTH = WIDE_D // 4 + 3          # 128 products of a wave's quarter, three adds across the quarters
+
+
+def wide_ntiles(s):
+    return ntiles(s, WIDE_TILE)
+
+
+def make_wide_case(kind, s, b=1, seed=0):
+    return make_case(kind, b, 1, s, WIDE_D, seed=seed, tile=WIDE_TILE)
+
+
+def bars_forward_wide(q, k, v, scale, ref):
+    """-> dict o, lse (bounds on the bf16 out and the f32 lse) and the pieces bars_backward_wide reuses"""
+    s, d = q.shape[-2:]
+    nt = wide_ntiles(s)
+    qa, ka, va = q.double().abs(), k.double().abs(), v.double().abs()
+    x, p, lse = ref["x"], ref["p"], ref["lse"]
+    xmax = x.max(-1, keepdim=True).values
+    qk = scale * qa @ ka.transpose(-1, -2)
+    site = U24 * (3 * x.abs() + 3 * (x - xmax).abs() + 2)                                  # the power, without the scores' own term
+    tj = torch.arange(s, device=x.device) // WIDE_TILE
+    xm = torch.cummax(tile_max(x, WIDE_TILE), -1).values[..., tj]                          # xm_t(j) per (query, key)
+    eps = site + d * U24 * qk + U24 * (xm.abs() + 2 * (xmax - xm) + 3 * (nt - 1 - tj).double())
+    sum_depth, pv_depth = 16 * nt + 1, 32 * nt
+    peps = (p * eps).sum(-1, keepdim=True)
+    lsum = lse.unsqueeze(-1) - xmax
+    e_lse = (U24 * (4 * xmax.abs() + sum_depth + 6 * lsum + lse.unsqueeze(-1).abs()) + peps).squeeze(-1)
+    a = p @ va
+    e_o = (p * (U8 + eps)) @ va + a * (peps + (pv_depth + sum_depth + 3) * U24) + TINY
+    return dict(o=bf16_bound(ref["o"], e_o), lse=e_lse + TINY, site=site, qk=qk, xmax=xmax, e_lse=e_lse)
+
+
+def bars_backward_wide(q, k, v, do, scale, ref, fwd, operands="kernel"):
+    """-> dict dq, dk, dv (bf16) and delta (f32).  fwd = bars_forward_wide(...).  operands: "kernel" -- lse is the wide forward's own, within fwd['lse'] of the
+    definition; "reference" -- f32(lse) of the definition.  (`o` is not an operand: the kernel does not read it.)"""
+    s, d = q.shape[-2:]
+    nt = wide_ntiles(s)
+    qa, ka, va, da = q.double().abs(), k.double().abs(), v.double().abs(), do.double().abs()
+    p, lse = ref["p"], ref["lse"].unsqueeze(-1)
+    e_l = fwd["e_lse"].unsqueeze(-1) if operands == "kernel" else U24 * lse.abs()
+    eps_b = fwd["site"] + WIDE_QUARTER_DEPTH * U24 * fwd["qk"] + 3 * U24 * (lse - fwd["xmax"]) + e_l
+    e_dp = WIDE_QUARTER_DEPTH * U24 * da @ va.transpose(-1, -2)
+    dpa = ref["dP"].abs()
+    e_delta = (p * (eps_b * dpa + e_dp)).sum(-1, keepdim=True) + (16 * nt + 1) * U24 * (p * dpa).sum(-1, keepdim=True)
+    t = scale * p * (ref["dP"] - ref["delta"]).abs()
+    w = t * (U8 * U8 + eps_b + 3 * U24) + scale * p * (e_dp + e_delta) + 64 * nt * (1 + U8) * U24 * t
+    e_dv = (p * (U8 + eps_b + 32 * nt * U24)).transpose(-1, -2) @ da + TINY
+    return dict(dq=bf16_bound(ref["dq"], w @ ka + TINY), dk=bf16_bound(ref["dk"], w.transpose(-1, -2) @ qa + TINY), dv=bf16_bound(ref["dv"], e_dv),
+                delta=e_delta.squeeze(-1) + TINY)
+
+
+# ---- emulations in kernel order (CPU) -----------------------------------------------------------------------------------------------------------------------------------
+_W_HALF = (torch.arange(WIDE_TILE) % 8) // 4                           # the half-wave (kg = lane >> 5) that holds a tile's key: register r is key (r & 3) + 8 (r >> 2) + 4 kg
+_W_LANE_ORDER = [[(r & 3) + 8 * (r >> 2) + 4 * kg for r in range(16)] for kg in range(2)]
+
+FORWARD_WIDE_MUTANTS = ["leak", "mask_ignores_half", "alpha_o_only", "alpha_l_only", "half_max", "lse_half", "l_rounded", "stale_tile"]
+BACKWARD_WIDE_MUTANTS = ["delta_from_O", "ds_single_bf16", "quarter_dropped", "p_from_max", "dk_noscale", "skip_one_q", "skip_one_k", "pad_key_unselected",
+                         "pad_query_finite_L"]
+
+
+def emulate_forward_wide(q, k, v, scale, mutant=None):
+    """attention_wide_kernel: per 32-key tile the raw scores, the half-wave mask of the ragged tile (register index < lim = S - 32 t - 4 kg), the running maximum (per
+    half-wave, exchanged), alpha, `l *= alpha`, `o *= alpha`, p = 2^(fma(s, ec, -m ec)), l += p in the lane's register order, P V on the bf16 p in two 16-key steps;
+    then the half-wave sum, o * (1 / l) and lse = m scale + log(l) -> (out bf16, lse f32, dict m = the final raw maximum).  State per half-wave (m, l: [G, S, 2];
+    channel c of the accumulators sits in half (c % 8) // 4: registers 4 r4 .. 4 r4 + 3 are channels 32 db + 8 r4 + 4 kg + 0 .. 3)."""
+    G, s, d = q.shape
+    nt = wide_ntiles(s)
+    pad = nt * WIDE_TILE
+    kp, vp = torch.zeros(G, pad, d), torch.zeros(G, pad, d)             # rows past S are staged as zeros
+    kp[:, :s], vp[:, :s] = _f(k), _f(v)
+    raw = _f(q) @ kp.transpose(-1, -2)
+    sf = torch.tensor(scale, dtype=F32)
+    ec = sf * torch.tensor(LOG2E_F32, dtype=F32)
+    chalf = (torch.arange(d) % 8) // 4
+    ninf = torch.tensor(float("-inf"))
+    idx = torch.arange(WIDE_TILE) - 4 * _W_HALF                         # (r & 3) + 8 (r >> 2) of the register that holds the key
+    m, l, o = torch.full((G, s, 2), float("-inf")), torch.zeros(G, s, 2), torch.zeros(G, s, d)
+    for t in range(nt):
+        tt = t - 1 if mutant == "stale_tile" and t > 0 else t          # the K / V image of tile t - 1: the other buffer
+        sc, vt = raw[..., tt * 32:tt * 32 + 32], vp[:, tt * 32:tt * 32 + 32]
+        if t * 32 + 32 > s:                                             # the last tile of a ragged S
+            lim = s - t * 32 + (1 if mutant == "leak" else 0)           # leak: one padded key left unmasked
+            sc = torch.where(idx < lim - (0 if mutant == "mask_ignores_half" else 4 * _W_HALF), sc, ninf)
+        tmh = torch.stack([sc[..., _W_HALF == hh].max(-1).values for hh in range(2)], -1)
+        tm = tmh if mutant == "half_max" else tmh.max(-1, keepdim=True).values.expand(-1, -1, 2)      # xhalf_max
+        mn = torch.maximum(m, tm)
+        alpha = torch.exp2((m - mn) * ec)                               # first tile: 2^(-inf) = 0
+        emc = mn * ec
+        m = mn
+        if mutant != "alpha_o_only":
+            l = l * alpha
+        if mutant != "alpha_l_only":
+            o = o * alpha[..., chalf]
+        e = torch.exp2((sc.double() * ec.double() - emc[..., _W_HALF].double()).float())            # one rounding: the fma
+        eb = _bfr(e)
+        ea = eb if mutant == "l_rounded" else e
+        lh = []
+        for hh in range(2):
+            acc = l[..., hh]
+            for j in _W_LANE_ORDER[hh]:
+                acc = acc + ea[..., j]
+            lh.append(acc)
+        l = torch.stack(lh, -1)
+        for c in (0, 16):
+            o = o + eb[..., c:c + 16] @ vt[:, c:c + 16]
+    lt = l[..., 0] + l[..., 1]                                          # xhalf_sum
+    o32 = o * (1.0 / lt).unsqueeze(-1)
+    lse = m[..., 0] * sf + torch.log(l[..., 0] if mutant == "lse_half" else lt)
+    return o32.to(BF), lse, dict(m=m[..., 0])
+
+
+def emulate_backward_wide(q, k, v, o, do, lse, scale, mutant=None, m=None):
+    """the two passes on rows padded to whole 32-row tiles, as staged (zero rows) -> dq, dk, dv [G, S, 512] bf16, delta [G, S] f32.  Scores and dP: per 128-channel
+    quarter, the quarters added ((0 + 1) + 2) + 3.  p = __expf(s scale - L): a padded query has L = +inf in both passes, a padded key is a select in the query pass
+    (the key pass does not store its padded keys).  First walk: delta by fmaf down the lane's 16 keys of every tile, per half-wave, then the cross-half add.  Second
+    walk and key pass: x = fl(fl(p (dP - delta)) scale), hi = bf16(x), lo = bf16(x - hi); dQ += hi K, += lo K per 16-key step; dV += P^T dO, dK += hi^T Q, += lo^T Q
+    per 16-query step.  `o` is used by the mutant delta_from_O alone, `m` (the forward emulation's final raw maximum) by p_from_max."""
+    G, s, d = q.shape
+    nt = wide_ntiles(s)
+    pad = nt * WIDE_TILE
+    sf = torch.tensor(scale, dtype=F32)
+    l2e = torch.tensor(LOG2E_F32, dtype=F32)
+
+    def rows(t):
+        z = torch.zeros(G, pad, d)
+        z[:, :s] = _f(t)
+        return z
+    qf, kf, vf, dof = rows(q), rows(k), rows(v), rows(do)
+    nquart = 3 if mutant == "quarter_dropped" else 4
+
+    def quarters(a, b):
+        part = [a[..., w * 128:w * 128 + 128] @ b[..., w * 128:w * 128 + 128].transpose(-1, -2) for w in range(nquart)]
+        acc = part[0]
+        for w in range(1, nquart):
+            acc = acc + part[w]
+        return acc
+    xs = quarters(qf, kf) * sf
+    dP = quarters(dof, vf)
+    live = torch.arange(pad) < s
+    L = torch.full((G, pad), float("inf"))
+    L[:, :s] = m * sf if mutant == "p_from_max" else lse
+    p = torch.exp2((xs - L.unsqueeze(-1)) * l2e)                        # __expf; rows of padded queries are 0
+    # ---- query pass ----
+    nq = s - 1 if mutant == "skip_one_q" and s % 32 == 1 else pad       # keys the query pass walks: the single live key of the last tile not walked
+    pq = p if mutant == "pad_key_unselected" else torch.where(live, p, torch.zeros(()))
+    if mutant == "delta_from_O":                                        # the sibling kernel's site: dO . O on the stored bf16 O
+        delta = torch.zeros(G, pad)
+        delta[:, :s] = (_f(do) * _f(o)).sum(-1)
+    else:
+        dh = []
+        for hh in range(2):
+            acc = torch.zeros(G, pad, dtype=D64)
+            for t in range((nq + 31) // 32):
+                for j in _W_LANE_ORDER[hh]:
+                    if t * 32 + j < nq:
+                        acc = (pq[..., t * 32 + j].double() * dP[..., t * 32 + j].double() + acc).float().double()      # fmaf
+            dh.append(acc.float())
+        delta = dh[0] + dh[1]                                           # xhalf_sum
+
+    def hi_lo(pp, dl, unscaled=False):
+        x = pp * (dP - dl.unsqueeze(-1))
+        x = x if unscaled else x * sf
+        hi = _bfr(x)
+        return hi, (torch.zeros_like(hi) if mutant == "ds_single_bf16" else _bfr(x - hi))
+    hi, lo = hi_lo(pq, delta)
+    dq = torch.zeros(G, pad, d)
+    for c in range(0, nq, 16):
+        e = min(c + 16, nq)
+        dq = dq + hi[..., c:e] @ kf[:, c:e]
+        dq = dq + lo[..., c:e] @ kf[:, c:e]
+    # ---- key pass: L and delta of a tile's queries travel with it; the delta bits are the query pass's ----
+    pk, dk_delta = p, delta.clone()
+    if mutant == "pad_query_finite_L" and pad > s:                      # the unselected loads of row S - 1
+        Lk = L.clone()
+        Lk[:, s:], dk_delta[:, s:] = L[:, s - 1:s], delta[:, s - 1:s]
+        pk = torch.exp2((xs - Lk.unsqueeze(-1)) * l2e)
+    nk = s - 1 if mutant == "skip_one_k" and s % 32 == 1 else pad       # queries the key pass walks
+    hk, lk = hi_lo(pk, dk_delta, unscaled=mutant == "dk_noscale")
+    pb = _bfr(pk)
+    dk, dv = torch.zeros(G, pad, d), torch.zeros(G, pad, d)
+    for c in range(0, nk, 16):
+        e = min(c + 16, nk)
+        dv = dv + pb[:, c:e].transpose(-1, -2) @ dof[:, c:e]
+        dk = dk + hk[:, c:e].transpose(-1, -2) @ qf[:, c:e]
+        dk = dk + lk[:, c:e].transpose(-1, -2) @ qf[:, c:e]
+    return dq[:, :s].to(BF), dk[:, :s].to(BF), dv[:, :s].to(BF), delta[:, :s].contiguous()
