@@ -9,16 +9,37 @@
 //   gated_residual   : x += bf16( gate[b] * y )
 //
 // All HBM-bound single passes with 8- or 16-byte accesses.  GEMMs go through the library, attention through the batched GEMM + softmax kernels.
+//
+// Shape of the RMSNorm family: the forward kernel in two bodies over the same three expressions, rmsnorm_modulate_kernel<RES, SW> (4 channels per lane) and
+// rmsnorm_modulate8_kernel<RES, SW8> (8), and ONE launch function, rmsnorm_modulate_launch<RES>, behind the three forward entries, which are their argument
+// checks plus a call to it.  The backward's two-kernel route is
+// dit_rows.h's rmsnorm_rowstat_kernel + rmsnorm_modulate_bwd_apply_kernel here, its single-pass route (more than RM_MAX_SEQ tokens) rmsnorm_modulate_bwd_kernel<SW>;
+// both end in dit_rows.h's modulate_bwd_final_kernel<true> and the weight kernel.  What this file shares with dit_variants.hip and dit_stack.hip -- the sweep
+// dispatch (one instantiation per SW = 1 .. 8), the argument rules, the blocks-per-sample rule, the per-element backward expressions -- lives in dit_rows.h.
 // Tests: tests/test_gpu_dit_forms.py launches every instantiation below (both channel-per-lane forms at each SW, both RMSNorm backward routes, the generic and the
 // 16-lane QK kernels, the grid-stride loops past their caps) against tests/dit_kernels_spec.py; tests/test_gpu_dit.py runs the model widths 128 .. 2048.
 #include "common.h"
-#include <cstdlib>
-#include <type_traits>
+#include "dit_rows.h"
 #include "dmvae_hip.h"
 
+using namespace dmvae_dit_rows;
 namespace dmvae_dit {
 
-constexpr int MAX_SWEEPS = 8;  // C <= 2048
+// The forward kernels' three expressions, shared by the 4- and the 8-channel body.  `#pragma clang fp contract(off)` is lexical, so each helper carries its own:
+// every form evaluates them exactly as written, and the fused and unfused routes agree to the bit.
+__device__ __forceinline__ float sumsq4(const f32x4 v) {      // a quad's sum of squares
+#pragma clang fp contract(off)
+  return (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+}
+__device__ __forceinline__ float gated_add(float x, bf16 gate, bf16 r) {      // the gated residual of one element
+#pragma clang fp contract(off)
+  return x + (float)(bf16)((float)gate * (float)r);
+}
+// `1 + scale` is a bf16 tensor in the reference's autocast graph (bf16 scale): rounded before it multiplies
+__device__ __forceinline__ bf16 norm_modulate(float x, float rs, float w, bf16 scale, bf16 shift) {
+#pragma clang fp contract(off)
+  return (bf16)(x * rs * w * (float)(bf16)(1.f + (float)scale) + (float)shift);
+}
 
 // one wave per row; mod: [B][stride] bf16 (the adaLN Linear's output), shift_off < 0: no shift
 // RES: first x[row] += bf16(gate[b] * r[row]) (the previous sub-layer's gated residual, written back), then the norm of the updated row.
@@ -28,7 +49,7 @@ __global__ __launch_bounds__(256) void rmsnorm_modulate_kernel(const float* x, c
                                                                bf16* __restrict__ y, int rows, int rows_per_sample, int C, int stride, int shift_off,
                                                                int scale_off, float eps, const bf16* __restrict__ r, const bf16* __restrict__ gmod,
                                                                int gstride, int gate_off, float* xo) {   // RES: updated rows go to xo (== x: in place); y == null: no norm
-#pragma clang fp contract(off)   // both instantiations evaluate the expressions exactly as written: fused and unfused routes agree to the bit
+#pragma clang fp contract(off)
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float* xr = x + (size_t)row * C;
@@ -43,10 +64,10 @@ __global__ __launch_bounds__(256) void rmsnorm_modulate_kernel(const float* x, c
         const bf16x4 rv = *reinterpret_cast<const bf16x4*>(r + (size_t)row * C + c);
         const bf16x4 g = *reinterpret_cast<const bf16x4*>(gmod + (size_t)(row / rows_per_sample) * gstride + gate_off + c);
 #pragma unroll
-        for (int e = 0; e < 4; e++) v[k][e] += (float)(bf16)((float)g[e] * (float)rv[e]);
+        for (int e = 0; e < 4; e++) v[k][e] = gated_add(v[k][e], g[e], rv[e]);
         *reinterpret_cast<f32x4*>(xo + (size_t)row * C + c) = v[k];
       }
-      ss += (v[k][0] * v[k][0] + v[k][1] * v[k][1]) + (v[k][2] * v[k][2] + v[k][3] * v[k][3]);
+      ss += sumsq4(v[k]);
     }
   }
   if (RES && !y) return;                       // gated residual only (wave-uniform)
@@ -71,12 +92,9 @@ __global__ __launch_bounds__(256) void rmsnorm_modulate_kernel(const float* x, c
   for (int k = 0; k < SW; k++) {
     const int c = k * 256 + lane * 4;
     if (c < C) {
-      const f32x4 g = gv[k];
-      const bf16x4 sc = scv[k], sh = shv[k];
       bf16x4 o;
 #pragma unroll
-      for (int e = 0; e < 4; e++)  // `1 + scale` is a bf16 tensor in the reference's autocast graph (bf16 scale): rounded before it multiplies
-        o[e] = (bf16)(v[k][e] * rs * g[e] * (float)(bf16)(1.f + (float)sc[e]) + (float)sh[e]);
+      for (int e = 0; e < 4; e++) o[e] = norm_modulate(v[k][e], rs, gv[k][e], scv[k][e], shv[k][e]);
       *reinterpret_cast<bf16x4*>(yr + c) = o;
     }
   }
@@ -84,7 +102,9 @@ __global__ __launch_bounds__(256) void rmsnorm_modulate_kernel(const float* x, c
 
 // The same kernel with EIGHT channels per lane (C % 8 == 0): 32-B f32 and 16-B bf16 accesses per lane -- half the memory instructions, and the bf16 result leaves
 // in 16-B stores (1 KiB per wave-instruction; the 4-channel form's 8-B stores are store-issue-bound on the large calls: 2.95 TB/s at batch 64).
-// SW8 = ceil(C / 512).  Per-row arithmetic as above; the sum of squares is taken in this kernel's own lane order, so the two forms differ in the last f32 bit of rs.
+// SW8 = ceil(C / 512).  Per-row arithmetic as above; the sum of squares is taken in this kernel's own lane order (quad0 + quad1 per sweep), so the two forms differ
+// in the last f32 bit of rs.  A second body, not a VEC parameter of the first: the merged template compiles the eight-channel instantiations to another schedule
+// (the same registers, 50 fewer moves), which measured 2 % slower on the fused call at batch 64 (profiles/r28_dit_rows_refactor_ab.txt).
 template <bool RES, int SW8>
 __global__ __launch_bounds__(256) void rmsnorm_modulate8_kernel(const float* x, const float* __restrict__ w, const bf16* __restrict__ mod,
                                                                 bf16* __restrict__ y, int rows, int rows_per_sample, int C, int stride, int shift_off,
@@ -107,14 +127,13 @@ __global__ __launch_bounds__(256) void rmsnorm_modulate8_kernel(const float* x, 
         const bf16x8 g = *reinterpret_cast<const bf16x8*>(gmod + (size_t)(row / rows_per_sample) * gstride + gate_off + c);
 #pragma unroll
         for (int e = 0; e < 4; e++) {
-          v0[k][e] += (float)(bf16)((float)g[e] * (float)rv[e]);
-          v1[k][e] += (float)(bf16)((float)g[4 + e] * (float)rv[4 + e]);
+          v0[k][e] = gated_add(v0[k][e], g[e], rv[e]);
+          v1[k][e] = gated_add(v1[k][e], g[4 + e], rv[4 + e]);
         }
         *reinterpret_cast<f32x4*>(xo + (size_t)row * C + c) = v0[k];
         *reinterpret_cast<f32x4*>(xo + (size_t)row * C + c + 4) = v1[k];
       }
-      ss += ((v0[k][0] * v0[k][0] + v0[k][1] * v0[k][1]) + (v0[k][2] * v0[k][2] + v0[k][3] * v0[k][3])) +
-            ((v1[k][0] * v1[k][0] + v1[k][1] * v1[k][1]) + (v1[k][2] * v1[k][2] + v1[k][3] * v1[k][3]));
+      ss += sumsq4(v0[k]) + sumsq4(v1[k]);
     }
   }
   if (RES && !y) return;
@@ -142,8 +161,8 @@ __global__ __launch_bounds__(256) void rmsnorm_modulate8_kernel(const float* x, 
       bf16x8 o;
 #pragma unroll
       for (int e = 0; e < 4; e++) {
-        o[e] = (bf16)(v0[k][e] * rs * g0[k][e] * (float)(bf16)(1.f + (float)scv[k][e]) + (float)shv[k][e]);
-        o[4 + e] = (bf16)(v1[k][e] * rs * g1[k][e] * (float)(bf16)(1.f + (float)scv[k][4 + e]) + (float)shv[k][4 + e]);
+        o[e] = norm_modulate(v0[k][e], rs, g0[k][e], scv[k][e], shv[k][e]);
+        o[4 + e] = norm_modulate(v1[k][e], rs, g1[k][e], scv[k][4 + e], shv[k][4 + e]);
       }
       *reinterpret_cast<bf16x8*>(yr + c) = o;
     }
@@ -248,8 +267,8 @@ __global__ __launch_bounds__(256) void gated_residual_bwd_kernel(const float* __
       bf16x8 o;
 #pragma unroll
       for (int e = 0; e < 4; e++) {
-        o[e] = (bf16)((float)g[e] * d0[e]); o[4 + e] = (bf16)((float)g[4 + e] * d1[e]);
-        acc[e] += d0[e] * (float)v[e]; acc[4 + e] += d1[e] * (float)v[4 + e];
+        o[e] = gated_residual_bwd_dy((float)g[e], d0[e]); o[4 + e] = gated_residual_bwd_dy((float)g[4 + e], d1[e]);
+        acc[e] += gated_residual_bwd_dgate(d0[e], (float)v[e]); acc[4 + e] += gated_residual_bwd_dgate(d1[e], (float)v[4 + e]);
       }
       *reinterpret_cast<bf16x8*>(dy + off) = o;
     }
@@ -293,7 +312,6 @@ __global__ void swiglu_bwd_kernel(const bf16* __restrict__ dh, const bf16* __res
 //   dx += rs * (g - n * mean(g * n)),  g = da * w * m;   dshift[b] = sum_n da;   dscale[b] = sum_n da * n * w;   dw = sum_rows da * m * n.
 // grid (BPS, B): the block's 4 waves walk the rows of sample b; part: [B][BPS][3][C] (dshift, dscale, dw contributions of the block)
 constexpr int RM_MAX_SEQ = 4096;   // row statistics of the two-kernel RMSNorm backward live in the workspace up to this many tokens per sample
-constexpr int RM_BPS = 32;   // blocks per sample: 4 waves x 2 rows each at N = 256 tokens
 // SW = ceil(C / 256) sweeps per row: seven f32x4 arrays of that length live in registers (224 VGPRs at the 2048-channel maximum, 140 at 1152)
 template <int SW>
 __global__ __launch_bounds__(256) void rmsnorm_modulate_bwd_kernel(const bf16* __restrict__ da, const float* __restrict__ x, const float* __restrict__ w,
@@ -380,34 +398,10 @@ __global__ __launch_bounds__(256) void rmsnorm_modulate_bwd_kernel(const bf16* _
   float* po = part + ((size_t)b * gridDim.x + blockIdx.x) * 3 * C;
   for (int i = threadIdx.x; i < 3 * C; i += 256) po[i] = red[i] + red[3 * C + i];
 }
-// second stage, grid (C/256, B): dmod[b][shift_off + c] = sum_blk part[b][blk][0][c] (skipped when shift_off < 0), dmod[b][scale_off + c] = ... [1] ...;
-// wpart[b][c] = sum_blk part[b][blk][2][c];  third stage: dw[c] (+)= sum_b wpart[b][c]
-// Two-kernel form of the same backward (used when the row statistics fit the workspace): (A) one wave per row -> rstd and m2 = mean_c(g * xhat),
-// g = da * w * bf16(1 + scale); (B) one thread per 4 columns walking the block's rows with fully coalesced row accesses, 12 accumulators per thread and no
+// second stage (dit_rows.h::modulate_bwd_final_kernel<true>): the sample's partial sums in block order -> dmod and wpart[b][c]; third stage: dw[c] (+)= sum_b wpart[b][c]
+// Two-kernel form of the same backward (used when the row statistics fit the workspace): (A) dit_rows.h::rmsnorm_rowstat_kernel, one wave per row -> rstd and
+// m2 = mean_c(g * xhat); (B) one thread per 4 columns walking the block's rows with fully coalesced row accesses, 12 accumulators per thread and no
 // cross-lane work -- the single-pass kernel above keeps 7 x SW f32x4 arrays per lane and two dependent wave reductions per row, and is latency-bound.
-__global__ __launch_bounds__(256) void rmsnorm_rowstat_kernel(const bf16* __restrict__ da, const float* __restrict__ x, const float* __restrict__ w,
-                                                              const bf16* __restrict__ mod, float2* __restrict__ rowstat, int rows, int N, int C, int stride,
-                                                              int scale_off, float eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const bf16* mrow = mod + (size_t)(row / N) * stride + scale_off;
-  float ss = 0.f, s2 = 0.f;
-  for (int c = lane * 4; c < C; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(x + (size_t)row * C + c);
-    const bf16x4 d = *reinterpret_cast<const bf16x4*>(da + (size_t)row * C + c);
-    const f32x4 gw = *reinterpret_cast<const f32x4*>(w + c);
-    const bf16x4 sc = *reinterpret_cast<const bf16x4*>(mrow + c);
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      ss += v[e] * v[e];
-      s2 += (float)d[e] * gw[e] * (float)(bf16)(1.f + (float)sc[e]) * v[e];
-    }
-  }
-  const float rs = rsqrtf(wave_sum(ss) / (float)C + eps);
-  const float m2 = wave_sum(s2) * rs / (float)C;
-  if (lane == 0) rowstat[row] = make_float2(rs, m2);
-}
-
 __global__ __launch_bounds__(512) void rmsnorm_modulate_bwd_apply_kernel(const bf16* __restrict__ da, const float* __restrict__ x, const float* __restrict__ w,
                                                                          const bf16* __restrict__ mod, const float2* __restrict__ rowstat,
                                                                          float* __restrict__ dx_io, float* __restrict__ part, int N, int C, int stride,
@@ -429,10 +423,9 @@ __global__ __launch_bounds__(512) void rmsnorm_modulate_bwd_apply_kernel(const b
     f32x4 o = *reinterpret_cast<const f32x4*>(dx_io + row * C + c);
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-      const float nh = v[e] * st.x, dv = (float)d[e];
-      const float g = dv * gw[e] * gm[e];
-      o[e] += st.x * (g - nh * st.y);
-      a0[e] += dv; a1[e] += dv * nh * gw[e]; a2[e] += dv * gm[e] * nh;
+      const rms_bwd_terms t = rmsnorm_modulate_bwd_terms(v[e], (float)d[e], gw[e], gm[e], st);
+      o[e] += t.dx;
+      a0[e] += t.dshift; a1[e] += t.dscale; a2[e] += t.dw;
     }
     *reinterpret_cast<f32x4*>(dx_io + row * C + c) = o;
   }
@@ -442,19 +435,6 @@ __global__ __launch_bounds__(512) void rmsnorm_modulate_bwd_apply_kernel(const b
   *reinterpret_cast<f32x4*>(po + 2 * C + c) = a2;
 }
 
-__global__ void rmsnorm_modulate_bwd_final_kernel(const float* __restrict__ part, float* __restrict__ dmod, float* __restrict__ wpart, int bps, int C,
-                                                  int stride, int shift_off, int scale_off) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (c >= C) return;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-  for (int k = 0; k < bps; k++) {
-    const float* q = part + ((size_t)b * bps + k) * 3 * C;
-    s0 += q[c]; s1 += q[C + c]; s2 += q[2 * C + c];
-  }
-  if (shift_off >= 0) dmod[(size_t)b * stride + shift_off + c] = s0;
-  dmod[(size_t)b * stride + scale_off + c] = s1;
-  wpart[(size_t)b * C + c] = s2;
-}
 __global__ void rmsnorm_modulate_bwd_weight_kernel(const float* __restrict__ wpart, float* __restrict__ dw, int B, int C, int accumulate) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
@@ -552,86 +532,46 @@ __global__ __launch_bounds__(256) void colsum2_kernel(const float* __restrict__ 
 }  // namespace dmvae_dit
 using namespace dmvae_dit;
 
-// The eight-channel kernels whenever the width allows -- chosen by the WIDTH only, never by the row count: a 2B-sample call must equal two B-sample calls bit for bit
-// (train.DMDTrainer's batched cond / uncond evaluation), and the two forms sum a row's squares in different lane orders.  46.9 vs 51.1 us at batch 64, 15.6 vs 14.7 at
-// batch 16 (profiles/r5_dit_norm_passes.txt)
+// The one launch of the forward kernel: RES = false reads x_in and writes y; RES = true writes x_out = x_in + bf16(gate * r) (x_out == x_in: in place) and, when y is
+// given, the norm of the updated row.  Arguments are checked by the entries.
+// Eight channels per lane whenever the width and every offset allow -- chosen by the WIDTH and ALIGNMENT only, never by the row count: a 2B-sample call must equal
+// two B-sample calls bit for bit (train.DMDTrainer's batched cond / uncond evaluation), and the two forms sum a row's squares in different lane orders.  46.9 vs
+// 51.1 us at batch 64, 15.6 vs 14.7 at batch 16 (profiles/r5_dit_norm_passes.txt)
+template <bool RES>
+static int rmsnorm_modulate_launch(const void* x_in, void* x_out, void* y, const void* r, const void* gate_mod, int gate_stride, int gate_off, const void* w,
+                                   const void* mod, int rows, int rows_per_sample, int c, int mod_stride, int shift_off, int scale_off, float eps,
+                                   hipStream_t stream) {
+  const bool eight = c % 8 == 0 && mod_stride % 8 == 0 && scale_off % 8 == 0 && (shift_off < 0 || shift_off % 8 == 0) && gate_off % 8 == 0 && gate_stride % 8 == 0;
+#define DMVAE_RMS_FWD(KERNEL, SWEEPS)                                                                                                                         \
+  hipLaunchKernelGGL((KERNEL<RES, SWEEPS>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,      \
+                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off,           \
+                     (float*)x_out)
+  return by_sweeps(c, [&](auto sw) {
+    constexpr int SW = decltype(sw)::value;       // sweeps of 256 channels; a sweep of the eight-channel form covers two
+    if (eight) DMVAE_RMS_FWD(rmsnorm_modulate8_kernel, (SW + 1) / 2);
+    else DMVAE_RMS_FWD(rmsnorm_modulate_kernel, SW);
+    DMVAE_CHECK_LAUNCH();
+    return 0;
+  });
+#undef DMVAE_RMS_FWD
+}
 
 extern "C" int dmvae_rmsnorm_modulate_bf16(const void* x, const void* w, const void* mod, void* y, int rows, int rows_per_sample, int c, int mod_stride,
                                            int shift_off, int scale_off, float eps, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && w && mod && y && rows > 0 && rows_per_sample > 0, "rmsnorm_modulate_bf16: bad argument");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= MAX_SWEEPS * 256, "rmsnorm_modulate_bf16: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(scale_off >= 0 && scale_off % 4 == 0 && (shift_off < 0 || shift_off % 4 == 0) && mod_stride % 4 == 0 && scale_off + c <= mod_stride,
-                  "rmsnorm_modulate_bf16: modulation offsets must be multiples of 4 inside the row");
-  if (c % 8 == 0 && mod_stride % 8 == 0 && scale_off % 8 == 0 && (shift_off < 0 || shift_off % 8 == 0)) {
-    switch ((c + 511) / 512) {
-      case 1: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<false, 1>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-      case 2: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<false, 2>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-      case 3: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<false, 3>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-      default: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<false, 4>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-    }
-  } else
-  switch ((c + 255) / 256) {
-    case 1: hipLaunchKernelGGL((rmsnorm_modulate_kernel<false, 1>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-    case 2: hipLaunchKernelGGL((rmsnorm_modulate_kernel<false, 2>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-    case 3: hipLaunchKernelGGL((rmsnorm_modulate_kernel<false, 3>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-    case 4: hipLaunchKernelGGL((rmsnorm_modulate_kernel<false, 4>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-    case 5: hipLaunchKernelGGL((rmsnorm_modulate_kernel<false, 5>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-    case 6: hipLaunchKernelGGL((rmsnorm_modulate_kernel<false, 6>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-    default: hipLaunchKernelGGL((rmsnorm_modulate_kernel<false, 8>), dim3((rows + 3) / 4), dim3(256), 0, stream, (float*)const_cast<void*>(x), (const float*)w,
-                     (const bf16*)mod, (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr); break;
-  }
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  DMVAE_CHECK_ARG(row_width_ok(c), "rmsnorm_modulate_bf16: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(mod_offsets_ok(c, mod_stride, shift_off, scale_off), "rmsnorm_modulate_bf16: modulation offsets must be multiples of 4 inside the row");
+  return rmsnorm_modulate_launch<false>(x, nullptr, y, nullptr, nullptr, 0, 0, w, mod, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, stream);
 }
 
 extern "C" int dmvae_gated_residual_rmsnorm_modulate(void* x, const void* r, const void* gate_mod, int gate_stride, int gate_off, const void* w,
                                                      const void* mod, void* y, int rows, int rows_per_sample, int c, int mod_stride, int shift_off,
                                                      int scale_off, float eps, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && r && gate_mod && w && mod && y && rows > 0 && rows_per_sample > 0, "gated_residual_rmsnorm_modulate: bad argument");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= MAX_SWEEPS * 256, "gated_residual_rmsnorm_modulate: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(scale_off >= 0 && scale_off % 4 == 0 && (shift_off < 0 || shift_off % 4 == 0) && mod_stride % 4 == 0 && scale_off + c <= mod_stride &&
-                      gate_off >= 0 && gate_off % 4 == 0 && gate_stride % 4 == 0 && gate_off + c <= gate_stride,
+  DMVAE_CHECK_ARG(row_width_ok(c), "gated_residual_rmsnorm_modulate: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(mod_offsets_ok(c, mod_stride, shift_off, scale_off) && gate_offset_ok(c, gate_stride, gate_off),
                   "gated_residual_rmsnorm_modulate: modulation offsets must be multiples of 4 inside the row");
-  if (c % 8 == 0 && mod_stride % 8 == 0 && scale_off % 8 == 0 && (shift_off < 0 || shift_off % 8 == 0) && gate_off % 8 == 0 && gate_stride % 8 == 0) {
-    switch ((c + 511) / 512) {
-      case 1: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 1>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-      case 2: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 2>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-      case 3: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 3>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-      default: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 4>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-    }
-  } else
-  switch ((c + 255) / 256) {
-    case 1: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 1>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-    case 2: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 2>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-    case 3: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 3>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-    case 4: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 4>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-    case 5: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 5>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-    case 6: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 6>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-    default: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 8>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const float*)w, (const bf16*)mod, (bf16*)y, rows,
-                     rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x); break;
-  }
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return rmsnorm_modulate_launch<true>(x, x, y, r, gate_mod, gate_stride, gate_off, w, mod, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, stream);
 }
 
 // Out-of-place form for the training route, where the residual stream before the update is kept for the backward pass: x_out = x_in + bf16(gate * r), and,
@@ -640,40 +580,10 @@ extern "C" int dmvae_gated_residual_out(const void* x_in, void* x_out, const voi
                                         const void* mod, void* y, int rows, int rows_per_sample, int c, int mod_stride, int shift_off, int scale_off,
                                         float eps, hipStream_t stream) {
   DMVAE_CHECK_ARG(x_in && x_out && r && gate_mod && rows > 0 && rows_per_sample > 0 && (!y || (w && mod)), "gated_residual_out: bad argument");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= MAX_SWEEPS * 256, "gated_residual_out: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(gate_off >= 0 && gate_off % 4 == 0 && gate_stride % 4 == 0 && gate_off + c <= gate_stride &&
-                      (!y || (scale_off >= 0 && scale_off % 4 == 0 && (shift_off < 0 || shift_off % 4 == 0) && mod_stride % 4 == 0 && scale_off + c <= mod_stride)),
+  DMVAE_CHECK_ARG(row_width_ok(c), "gated_residual_out: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(gate_offset_ok(c, gate_stride, gate_off) && (!y || mod_offsets_ok(c, mod_stride, shift_off, scale_off)),
                   "gated_residual_out: modulation offsets must be multiples of 4 inside the row");
-  if (c % 8 == 0 && mod_stride % 8 == 0 && scale_off % 8 == 0 && (shift_off < 0 || shift_off % 8 == 0) && gate_off % 8 == 0 && gate_stride % 8 == 0) {
-    switch ((c + 511) / 512) {
-      case 1: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 1>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-      case 2: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 2>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-      case 3: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 3>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-      default: hipLaunchKernelGGL((rmsnorm_modulate8_kernel<true, 4>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-    }
-  } else
-  switch ((c + 255) / 256) {
-    case 1: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 1>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-    case 2: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 2>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-    case 3: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 3>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-    case 4: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 4>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-    case 5: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 5>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-    case 6: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 6>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-    default: hipLaunchKernelGGL((rmsnorm_modulate_kernel<true, 8>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const float*)w, (const bf16*)mod, (bf16*)y,
-                     rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off, (float*)x_out); break;
-  }
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return rmsnorm_modulate_launch<true>(x_in, x_out, y, r, gate_mod, gate_stride, gate_off, w, mod, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, stream);
 }
 
 namespace dmvae_dit {
@@ -755,7 +665,7 @@ extern "C" int dmvae_gated_residual_f32(void* x, const void* y, const void* mod,
 
 // ---- backward entry points -----------------------------------------------------------------------------------------------------------
 extern "C" size_t dmvae_dit_bwd_workspace(int batch, int c) {
-  const size_t a = ((size_t)batch * RM_BPS * 3 + batch) * (size_t)c * sizeof(float) + (size_t)batch * RM_MAX_SEQ * sizeof(float2),
+  const size_t a = ((size_t)batch * MAX_BPS * 3 + batch) * (size_t)c * sizeof(float) + (size_t)batch * RM_MAX_SEQ * sizeof(float2),
                b = (size_t)2048 * 2 * 128 * sizeof(float);
   return a > b ? a : b;
 }
@@ -783,18 +693,12 @@ extern "C" int dmvae_rmsnorm_modulate_bwd(const void* da, const void* x, const v
                                           void* workspace, size_t workspace_bytes, int batch, int seq, int c, int mod_stride, int shift_off,
                                           int scale_off, float eps, int accumulate, hipStream_t stream) {
   DMVAE_CHECK_ARG(da && x && w && mod && dx_io && dmod && workspace && batch > 0 && seq > 0, "rmsnorm_modulate_bwd: bad argument");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= MAX_SWEEPS * 256, "rmsnorm_modulate_bwd: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(scale_off >= 0 && scale_off % 4 == 0 && (shift_off < 0 || shift_off % 4 == 0) && mod_stride % 4 == 0 && scale_off + c <= mod_stride,
-                  "rmsnorm_modulate_bwd: modulation offsets must be multiples of 4 inside the row");
+  DMVAE_CHECK_ARG(row_width_ok(c), "rmsnorm_modulate_bwd: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(mod_offsets_ok(c, mod_stride, shift_off, scale_off), "rmsnorm_modulate_bwd: modulation offsets must be multiples of 4 inside the row");
   DMVAE_CHECK_ARG(workspace_bytes >= dmvae_dit_bwd_workspace(batch, c), "rmsnorm_modulate_bwd: workspace too small");
-  const size_t lds = (size_t)2 * 3 * c * sizeof(float);
-  // blocks per sample: enough blocks to fill the chip (~1024), few enough that the per-block partial sums (3 * c floats through LDS and the workspace) stay small
-  // next to the rows a block walks -- 32 at batch 16 (2 rows per wave at 256 tokens), 16 at batch 64
-  int bps = 1024 / batch;
-  bps = bps > RM_BPS ? RM_BPS : (bps < 4 ? 4 : bps);
-  constexpr bool split_ok = true;
-  if (split_ok && seq <= RM_MAX_SEQ) {
-    float2* rowstat = reinterpret_cast<float2*>((float*)workspace + ((size_t)batch * RM_BPS * 3 + batch) * (size_t)c);
+  const int bps = blocks_per_sample(batch);       // the per-block partial sums: 3 * c floats through the workspace (and LDS on the single-pass route)
+  if (seq <= RM_MAX_SEQ) {
+    float2* rowstat = reinterpret_cast<float2*>((float*)workspace + ((size_t)batch * MAX_BPS * 3 + batch) * (size_t)c);
     const int rows = batch * seq;
     hipLaunchKernelGGL(rmsnorm_rowstat_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x, (const float*)w, (const bf16*)mod,
                        rowstat, rows, seq, c, mod_stride, scale_off, eps);
@@ -804,28 +708,19 @@ extern "C" int dmvae_rmsnorm_modulate_bwd(const void* da, const void* x, const v
                        (const bf16*)mod, rowstat, (float*)dx_io, (float*)workspace, seq, c, mod_stride, scale_off);
     DMVAE_CHECK_LAUNCH();
   } else {
-  auto go = [&](auto sw) -> int {
-    constexpr int SW = decltype(sw)::value;
-    DMVAE_LDS_OPTIN((size_t)2 * 3 * MAX_SWEEPS * 256 * sizeof(float), rmsnorm_modulate_bwd_kernel<SW>);   // the widest row's: `lds` varies with c
-    hipLaunchKernelGGL(rmsnorm_modulate_bwd_kernel<SW>, dim3(bps, batch), dim3(256), lds, stream, (const bf16*)da, (const float*)x, (const float*)w,
-                       (const bf16*)mod, (float*)dx_io, (float*)workspace, seq, c, mod_stride, scale_off, eps);
-    return 0;
-  };
-  int rc = 0;
-  switch ((c + 255) / 256) {
-    case 1: rc = go(std::integral_constant<int, 1>{}); break;
-    case 2: rc = go(std::integral_constant<int, 2>{}); break;
-    case 3: rc = go(std::integral_constant<int, 3>{}); break;
-    case 4: rc = go(std::integral_constant<int, 4>{}); break;
-    case 5: rc = go(std::integral_constant<int, 5>{}); break;
-    case 6: rc = go(std::integral_constant<int, 6>{}); break;
-    default: rc = go(std::integral_constant<int, 8>{}); break;
+    const size_t lds = (size_t)2 * 3 * c * sizeof(float);
+    const int rc = by_sweeps(c, [&](auto sw) -> int {
+      constexpr int SW = decltype(sw)::value;
+      DMVAE_LDS_OPTIN((size_t)2 * 3 * MAX_SWEEPS * 256 * sizeof(float), rmsnorm_modulate_bwd_kernel<SW>);   // the widest row's: `lds` varies with c
+      hipLaunchKernelGGL(rmsnorm_modulate_bwd_kernel<SW>, dim3(bps, batch), dim3(256), lds, stream, (const bf16*)da, (const float*)x, (const float*)w,
+                         (const bf16*)mod, (float*)dx_io, (float*)workspace, seq, c, mod_stride, scale_off, eps);
+      DMVAE_CHECK_LAUNCH();
+      return 0;
+    });
+    if (rc) return rc;
   }
-  if (rc) return rc;
-  DMVAE_CHECK_LAUNCH();
-  }
-  float* wpart = (float*)workspace + (size_t)batch * RM_BPS * 3 * c;
-  hipLaunchKernelGGL(rmsnorm_modulate_bwd_final_kernel, dim3((c + 255) / 256, batch), dim3(256), 0, stream, (const float*)workspace, (float*)dmod, wpart,
+  float* wpart = (float*)workspace + (size_t)batch * MAX_BPS * 3 * c;
+  hipLaunchKernelGGL(modulate_bwd_final_kernel<true>, dim3((c + 255) / 256, batch), dim3(256), 0, stream, (const float*)workspace, (float*)dmod, wpart,
                      bps, c, mod_stride, shift_off, scale_off);
   DMVAE_CHECK_LAUNCH();
   if (dw) {

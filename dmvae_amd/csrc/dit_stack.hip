@@ -2,11 +2,11 @@
 // train_dmd.py:565-575, train_diffusion.py:290-297) -- what functional.DitStackFn adds to csrc/dit.hip's per-block kernels:
 //
 //   rms_gate_bwd_kernel<APPLY, GATE>   one pass over the f32 residual-stream gradient dt per sub-layer boundary:
-//        APPLY: dt += RMSNorm+modulate backward of da (the row statistics come from dit.hip::rmsnorm_rowstat_kernel), with the per-sample partial sums of
-//               d shift / d scale / d norm-weight;
+//        APPLY: dt += RMSNorm+modulate backward of da (the row statistics come from dit_rows.h::rmsnorm_rowstat_kernel, launched here as in dit.hip), with the
+//               per-sample partial sums of d shift / d scale / d norm-weight;
 //        GATE:  dy = bf16(gate[b] * dt) of the NEXT gated residual down the backward pass (its branch output y read here), with the partial sums of d gate.
-//        The per-block route ran these as two kernels (rmsnorm_modulate_bwd_apply_kernel + gated_residual_bwd_kernel, the second on 80 workgroups); fused, dt is
-//        read once and written once per boundary.
+//        The per-block route runs these as two kernels (dit.hip's rmsnorm_modulate_bwd_apply_kernel + gated_residual_bwd_kernel, the second on 80 workgroups);
+//        fused, dt is read once and written once per boundary.  All three kernels call the same per-element functions of dit_rows.h.
 //        PARTS = false is the dx-only form (dmvae_dit_boundary_bwd_dx) for a frozen model's input gradient.
 //   dit_bwd_finalize / dit_bwd_weight  ONE reduction of every boundary's partial sums at the end of the backward pass (57 boundaries for 28 blocks) into the
 //        bf16 adaLN-chunk gradients d mod [L][B][6C] and the 2 L norm-weight gradients, instead of two small launches per boundary.
@@ -15,8 +15,10 @@
 //   colsum2_batched_kernel             the deferred second stage of qknorm_rope_bwd's norm-weight gradients, all layers in one launch.
 // Every reduction is two-stage with a fixed order: reruns are bit-identical.
 #include "common.h"
+#include "dit_rows.h"
 #include "dmvae_hip.h"
 
+using namespace dmvae_dit_rows;
 namespace dmvae_dit_stack {
 
 // grid (bps, B); thread t owns columns 4 t .. 4 t + 3 of every row of its block's row range (fully coalesced row accesses, no cross-lane work).
@@ -54,22 +56,21 @@ __global__ __launch_bounds__(512) void rms_gate_bwd_kernel(const bf16* __restric
       const f32x4 v = *reinterpret_cast<const f32x4*>(x + off);
       const bf16x4 d = *reinterpret_cast<const bf16x4*>(da + off);
 #pragma unroll
-      for (int e = 0; e < 4; e++) {   // dit.hip::rmsnorm_modulate_bwd_apply_kernel's expressions
-        const float nh = v[e] * st.x, dv = (float)d[e];
-        const float g = dv * gw[e] * gm[e];
-        o[e] += st.x * (g - nh * st.y);
-        if constexpr (PARTS) { a0[e] += dv; a1[e] += dv * nh * gw[e]; a2[e] += dv * gm[e] * nh; }
+      for (int e = 0; e < 4; e++) {
+        const rms_bwd_terms t = rmsnorm_modulate_bwd_terms(v[e], (float)d[e], gw[e], gm[e], st);
+        o[e] += t.dx;
+        if constexpr (PARTS) { a0[e] += t.dshift; a1[e] += t.dscale; a2[e] += t.dw; }
       }
       *reinterpret_cast<f32x4*>(dx_io + off) = o;
     }
-    if constexpr (GATE) {   // dit.hip::gated_residual_bwd_kernel's expressions
+    if constexpr (GATE) {
       bf16x4 q;
 #pragma unroll
-      for (int e = 0; e < 4; e++) q[e] = (bf16)(gg[e] * o[e]);
+      for (int e = 0; e < 4; e++) q[e] = gated_residual_bwd_dy(gg[e], o[e]);
       if constexpr (PARTS) {
         const bf16x4 yv = *reinterpret_cast<const bf16x4*>(y + off);
 #pragma unroll
-        for (int e = 0; e < 4; e++) a3[e] += o[e] * (float)yv[e];
+        for (int e = 0; e < 4; e++) a3[e] += gated_residual_bwd_dgate(o[e], (float)yv[e]);
       }
       *reinterpret_cast<bf16x4*>(dy + off) = q;
     }
@@ -82,29 +83,6 @@ __global__ __launch_bounds__(512) void rms_gate_bwd_kernel(const bf16* __restric
     *reinterpret_cast<f32x4*>(po + 2 * C + c) = a2;
   }
   if constexpr (GATE) *reinterpret_cast<f32x4*>(po + 3 * C + c) = a3;
-}
-
-// rstd and m2 = mean_c(g * xhat), g = da * w * bf16(1 + scale), per row -- one wave per row (dit.hip::rmsnorm_rowstat_kernel, restated here: kernels are per translation unit)
-__global__ __launch_bounds__(256) void rowstat_kernel(const bf16* __restrict__ da, const float* __restrict__ x, const float* __restrict__ w, const bf16* __restrict__ mod,
-                                                      float2* __restrict__ rowstat, int rows, int N, int C, int stride, int scale_off, float eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const bf16* mrow = mod + (size_t)(row / N) * stride + scale_off;
-  float ss = 0.f, s2 = 0.f;
-  for (int c = lane * 4; c < C; c += 256) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(x + (size_t)row * C + c);
-    const bf16x4 d = *reinterpret_cast<const bf16x4*>(da + (size_t)row * C + c);
-    const f32x4 gw = *reinterpret_cast<const f32x4*>(w + c);
-    const bf16x4 sc = *reinterpret_cast<const bf16x4*>(mrow + c);
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-      ss += v[e] * v[e];
-      s2 += (float)d[e] * gw[e] * (float)(bf16)(1.f + (float)sc[e]) * v[e];
-    }
-  }
-  const float rs = rsqrtf(wave_sum(ss) / (float)C + eps);
-  const float m2 = wave_sum(s2) * rs / (float)C;
-  if (lane == 0) rowstat[row] = make_float2(rs, m2);
 }
 
 // One reduction for the whole stack.  Boundary slots (dmvae_dit_stack_slots): s = 2 l: norm1 of block l (+ the MLP gate of block l - 1 when l > 0);
@@ -233,13 +211,9 @@ __global__ __launch_bounds__(256) void rows_wgrad_mfma_kernel(const bf16* __rest
 }  // namespace dmvae_dit_stack
 using namespace dmvae_dit_stack;
 
-static inline int stack_bps(int batch) {   // blocks per sample of the boundary kernels: ~1024 workgroups in all (dit.hip's rule)
-  int bps = 1024 / batch;
-  return bps > 32 ? 32 : (bps < 4 ? 4 : bps);
-}
-extern "C" int dmvae_dit_stack_bps(int batch) { return stack_bps(batch); }
+extern "C" int dmvae_dit_stack_bps(int batch) { return blocks_per_sample(batch); }   // of the boundary kernels
 extern "C" size_t dmvae_dit_stack_part_bytes(int layers, int batch, int c) {
-  return (size_t)(2 * layers + 1) * batch * stack_bps(batch) * 4 * (size_t)c * sizeof(float);
+  return (size_t)(2 * layers + 1) * batch * blocks_per_sample(batch) * 4 * (size_t)c * sizeof(float);
 }
 extern "C" size_t dmvae_dit_stack_workspace(int layers, int batch, int seq, int c) {   // wpart [2 L][B][C] f32 + rowstat [B * seq] float2
   return (size_t)2 * layers * batch * (size_t)c * sizeof(float) + (size_t)batch * seq * sizeof(float2);
@@ -250,14 +224,14 @@ extern "C" int dmvae_dit_boundary_bwd(const void* da, const void* x, const void*
                                       int batch, int seq, int c, hipStream_t stream) {
   const bool apply = da != nullptr, gate = y != nullptr;
   DMVAE_CHECK_ARG((apply || gate) && dx_io && part_slot && batch > 0 && seq > 0, "dit_boundary_bwd: nothing to do or null buffers");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= 2048, "dit_boundary_bwd: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(!apply || (x && w && mod && rowstat && scale_off >= 0 && scale_off % 4 == 0 && mod_stride % 4 == 0 && scale_off + c <= mod_stride),
+  DMVAE_CHECK_ARG(row_width_ok(c), "dit_boundary_bwd: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(!apply || (x && w && mod && rowstat && mod_offsets_ok(c, mod_stride, -1, scale_off)),
                   "dit_boundary_bwd: the norm half needs x, w, mod, rowstat and a scale offset that is a multiple of 4 inside the modulation row");
-  DMVAE_CHECK_ARG(!gate || (gate_mod && dy && gate_off >= 0 && gate_off % 4 == 0 && gate_stride % 4 == 0 && gate_off + c <= gate_stride),
+  DMVAE_CHECK_ARG(!gate || (gate_mod && dy && gate_offset_ok(c, gate_stride, gate_off)),
                   "dit_boundary_bwd: the gate half needs gate_mod, dy and a gate offset that is a multiple of 4 inside the modulation row");
-  const int rows = batch * seq, bps = stack_bps(batch);
+  const int rows = batch * seq, bps = blocks_per_sample(batch);
   if (apply) {
-    hipLaunchKernelGGL(rowstat_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x, (const float*)w, (const bf16*)mod,
+    hipLaunchKernelGGL(rmsnorm_rowstat_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x, (const float*)w, (const bf16*)mod,
                        (float2*)rowstat, rows, seq, c, mod_stride, scale_off, eps);
     DMVAE_CHECK_LAUNCH();
   }
@@ -280,14 +254,14 @@ extern "C" int dmvae_dit_boundary_bwd_dx(const void* da, const void* x, const vo
                                          hipStream_t stream) {
   const bool apply = da != nullptr, gate = gate_mod != nullptr;
   DMVAE_CHECK_ARG((apply || gate) && dx_io && batch > 0 && seq > 0, "dit_boundary_bwd_dx: nothing to do or null buffers");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= 2048, "dit_boundary_bwd_dx: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(!apply || (x && w && mod && rowstat && scale_off >= 0 && scale_off % 4 == 0 && mod_stride % 4 == 0 && scale_off + c <= mod_stride),
+  DMVAE_CHECK_ARG(row_width_ok(c), "dit_boundary_bwd_dx: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(!apply || (x && w && mod && rowstat && mod_offsets_ok(c, mod_stride, -1, scale_off)),
                   "dit_boundary_bwd_dx: the norm half needs x, w, mod, rowstat and a scale offset that is a multiple of 4 inside the modulation row");
-  DMVAE_CHECK_ARG(!gate || (dy && gate_off >= 0 && gate_off % 4 == 0 && gate_stride % 4 == 0 && gate_off + c <= gate_stride),
+  DMVAE_CHECK_ARG(!gate || (dy && gate_offset_ok(c, gate_stride, gate_off)),
                   "dit_boundary_bwd_dx: the gate half needs dy and a gate offset that is a multiple of 4 inside the modulation row");
-  const int rows = batch * seq, bps = stack_bps(batch);
+  const int rows = batch * seq, bps = blocks_per_sample(batch);
   if (apply) {
-    hipLaunchKernelGGL(rowstat_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x, (const float*)w, (const bf16*)mod,
+    hipLaunchKernelGGL(rmsnorm_rowstat_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x, (const float*)w, (const bf16*)mod,
                        (float2*)rowstat, rows, seq, c, mod_stride, scale_off, eps);
     DMVAE_CHECK_LAUNCH();
   }
@@ -309,7 +283,7 @@ extern "C" int dmvae_dit_stack_finalize(const void* part, void* dmod, void* work
   DMVAE_CHECK_ARG(part && dmod && workspace && dw_table && layers > 0 && batch > 0 && c > 0 && c % 4 == 0, "dit_stack_finalize: bad argument");
   DMVAE_CHECK_ARG(workspace_bytes >= dmvae_dit_stack_workspace(layers, batch, seq, c), "dit_stack_finalize: workspace too small");
   hipLaunchKernelGGL(dit_bwd_finalize_kernel, dim3((c + 255) / 256, batch, 2 * layers + 1), dim3(256), 0, stream, (const float*)part, (bf16*)dmod, (float*)workspace,
-                     layers, batch, stack_bps(batch), c);
+                     layers, batch, blocks_per_sample(batch), c);
   DMVAE_CHECK_LAUNCH();
   hipLaunchKernelGGL(dit_bwd_weight_kernel, dim3((c + 255) / 256, 2 * layers), dim3(256), 0, stream, (const float*)workspace, (float* const*)dw_table, batch, c,
                      accumulate);

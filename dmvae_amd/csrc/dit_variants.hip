@@ -7,14 +7,15 @@
 //   head_split         : qkv [B][N][3][H][D] -> q, k [B*H][N][Dp] (zero-padded), v [B*H][N][D] with norm in {none, rms} and rope in {off, on}
 //   gelu_tanh          : y = bf16( 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) )                          (nn.GELU(approximate="tanh") of timm's Mlp)
 //
-// and their backward kernels.  Tests: tests/test_gpu_dit_variants.py against tests/dit_variants_spec.py.
+// and their backward kernels.  The LayerNorm entries share dit_rows.h with csrc/dit.hip: the sweep dispatch by_sweeps (the row kernels here are instantiated per
+// SW = ceil(C / 256)), the width / modulation-offset / gate-offset rules, the blocks-per-sample rule and the backward's last stage modulate_bwd_final_kernel<false>.
+// Tests: tests/test_gpu_dit_variants.py against tests/dit_variants_spec.py.
 #include "common.h"
+#include "dit_rows.h"
 #include "dmvae_hip.h"
 
+using namespace dmvae_dit_rows;
 namespace dmvae_dit_var {
-
-constexpr int MAX_SWEEPS = 8;   // C <= 2048: a row of 8 x 256 channels, four per lane; the row kernels are instantiated per sweep count SW = ceil(C / 256)
-constexpr int LN_BPS = 32;      // blocks per sample of the backward's second kernel (rows of its partial sums)
 
 // Row statistics of a row held in registers, one wave per row.  mean first, then the variance as the sum of squared DEVIATIONS taken from the registers -- never
 // E[x^2] - mean^2: the residual stream is f32 and its rows can carry a large common offset.  The deviations are re-centred once (d -= mean(d)): x - mean is exact
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(256) void layernorm_modulate_kernel(const float* x,
 // ---- backward: a = bf16(xh * m + shift), xh = (x - mean) * rs, m = bf16(1 + scale[b]) ------------------------------------------------------------------
 //   g = da * m;  dx += rs * (g - mean_c(g) - xh * mean_c(g * xh));  dscale[b] = sum_n da * xh;  dshift[b] = sum_n da.
 // (A) one wave per row -> (the two parts of the mean, rs), (mean(g), mean(g * xh)); (B) one thread per four columns walking its block's rows, partial sums part[B][bps][2][C];
-// (C) dmod[b] = the sum of the sample's partials in block order: a fixed order, identical run to run.
+// (C) dit_rows.h::modulate_bwd_final_kernel<false>: dmod[b] = the sum of the sample's partials in block order: a fixed order, identical run to run.
 template <int SW>
 __global__ __launch_bounds__(256) void layernorm_rowstat_kernel(const bf16* __restrict__ da, const float* __restrict__ x, const bf16* __restrict__ mod,
                                                                 float4* __restrict__ rowstat, int rows, int N, int C, int stride, int scale_off, float eps) {
@@ -169,19 +170,6 @@ __global__ __launch_bounds__(512) void layernorm_modulate_bwd_apply_kernel(const
   float* po = part + ((size_t)b * gridDim.x + blockIdx.x) * 2 * C;
   *reinterpret_cast<f32x4*>(po + c) = a0;
   *reinterpret_cast<f32x4*>(po + C + c) = a1;
-}
-
-__global__ void layernorm_modulate_bwd_final_kernel(const float* __restrict__ part, float* __restrict__ dmod, int bps, int C, int stride, int shift_off,
-                                                    int scale_off) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-  if (c >= C) return;
-  float s0 = 0.f, s1 = 0.f;
-  for (int k = 0; k < bps; k++) {
-    const float* q = part + ((size_t)b * bps + k) * 2 * C;
-    s0 += q[c]; s1 += q[C + c];
-  }
-  if (shift_off >= 0) dmod[(size_t)b * stride + shift_off + c] = s0;
-  dmod[(size_t)b * stride + scale_off + c] = s1;
 }
 
 // ---- head split -------------------------------------------------------------------------------------------------------------------------------------------
@@ -366,35 +354,17 @@ __global__ void gelu_tanh_bwd_kernel(const bf16* __restrict__ dy, const bf16* __
 }  // namespace dmvae_dit_var
 using namespace dmvae_dit_var;
 
-// LAUNCH with `SW` = ceil(c / 256) as a constant expression (c validated: 4 .. 2048)
-#define DMVAE_BY_SWEEPS(c, LAUNCH)                                    \
-  switch (((c) + 255) / 256) {                                        \
-    case 1: { constexpr int SW = 1; LAUNCH; } break;                  \
-    case 2: { constexpr int SW = 2; LAUNCH; } break;                  \
-    case 3: { constexpr int SW = 3; LAUNCH; } break;                  \
-    case 4: { constexpr int SW = 4; LAUNCH; } break;                  \
-    case 5: { constexpr int SW = 5; LAUNCH; } break;                  \
-    case 6: { constexpr int SW = 6; LAUNCH; } break;                  \
-    case 7: { constexpr int SW = 7; LAUNCH; } break;                  \
-    default: { constexpr int SW = 8; LAUNCH; } break;                 \
-  }
-
-static bool ln_offsets_ok(int c, int mod_stride, int shift_off, int scale_off) {
-  return scale_off >= 0 && scale_off % 4 == 0 && (shift_off < 0 || (shift_off % 4 == 0 && shift_off + c <= mod_stride)) && mod_stride % 4 == 0 &&
-         scale_off + c <= mod_stride;
-}
-static bool ln_gate_ok(int c, int gate_stride, int gate_off) { return gate_off >= 0 && gate_off % 4 == 0 && gate_stride % 4 == 0 && gate_off + c <= gate_stride; }
-
 extern "C" int dmvae_layernorm_modulate_bf16(const void* x, const void* mod, void* y, int rows, int rows_per_sample, int c, int mod_stride, int shift_off,
                                              int scale_off, float eps, hipStream_t stream) {
   DMVAE_CHECK_ARG(x && mod && y && rows > 0 && rows_per_sample > 0, "layernorm_modulate_bf16: bad argument");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= MAX_SWEEPS * 256, "layernorm_modulate_bf16: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(ln_offsets_ok(c, mod_stride, shift_off, scale_off), "layernorm_modulate_bf16: modulation offsets must be multiples of 4 inside the row");
-  DMVAE_BY_SWEEPS(c, hipLaunchKernelGGL((layernorm_modulate_kernel<false, SW>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const bf16*)mod,
-                                        (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0,
-                                        (float*)nullptr));
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  DMVAE_CHECK_ARG(row_width_ok(c), "layernorm_modulate_bf16: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(mod_offsets_ok(c, mod_stride, shift_off, scale_off), "layernorm_modulate_bf16: modulation offsets must be multiples of 4 inside the row");
+  return by_sweeps(c, [&](auto sw) {
+    hipLaunchKernelGGL((layernorm_modulate_kernel<false, decltype(sw)::value>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x, (const bf16*)mod,
+                       (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)nullptr, (const bf16*)nullptr, 0, 0, (float*)nullptr);
+    DMVAE_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 // x_out == x_in: in place (the inference route); x_out another buffer: the training route keeps the stream before the update for its backward pass
@@ -402,41 +372,46 @@ extern "C" int dmvae_gated_residual_layernorm_modulate(const void* x_in, void* x
                                                        const void* mod, void* y, int rows, int rows_per_sample, int c, int mod_stride, int shift_off,
                                                        int scale_off, float eps, hipStream_t stream) {
   DMVAE_CHECK_ARG(x_in && x_out && r && gate_mod && mod && y && rows > 0 && rows_per_sample > 0, "gated_residual_layernorm_modulate: bad argument");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= MAX_SWEEPS * 256, "gated_residual_layernorm_modulate: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(ln_offsets_ok(c, mod_stride, shift_off, scale_off) && ln_gate_ok(c, gate_stride, gate_off),
+  DMVAE_CHECK_ARG(row_width_ok(c), "gated_residual_layernorm_modulate: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(mod_offsets_ok(c, mod_stride, shift_off, scale_off) && gate_offset_ok(c, gate_stride, gate_off),
                   "gated_residual_layernorm_modulate: modulation offsets must be multiples of 4 inside the row");
-  DMVAE_BY_SWEEPS(c, hipLaunchKernelGGL((layernorm_modulate_kernel<true, SW>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const bf16*)mod,
-                                        (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride,
-                                        gate_off, (float*)x_out));
-  DMVAE_CHECK_LAUNCH();
-  return 0;
+  return by_sweeps(c, [&](auto sw) {
+    hipLaunchKernelGGL((layernorm_modulate_kernel<true, decltype(sw)::value>), dim3((rows + 3) / 4), dim3(256), 0, stream, (const float*)x_in, (const bf16*)mod,
+                       (bf16*)y, rows, rows_per_sample, c, mod_stride, shift_off, scale_off, eps, (const bf16*)r, (const bf16*)gate_mod, gate_stride, gate_off,
+                       (float*)x_out);
+    DMVAE_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 extern "C" size_t dmvae_layernorm_modulate_bwd_workspace(int batch, int seq, int c) {
   if (batch <= 0 || seq <= 0 || c <= 0) return 0;
-  return (size_t)batch * LN_BPS * 2 * (size_t)c * sizeof(float) + (size_t)batch * (size_t)seq * 2 * sizeof(float4);
+  return (size_t)batch * MAX_BPS * 2 * (size_t)c * sizeof(float) + (size_t)batch * (size_t)seq * 2 * sizeof(float4);
 }
 
 extern "C" int dmvae_layernorm_modulate_bwd(const void* da, const void* x, const void* mod, void* dx_io, void* dmod, void* workspace, size_t workspace_bytes,
                                             int batch, int seq, int c, int mod_stride, int shift_off, int scale_off, float eps, hipStream_t stream) {
   DMVAE_CHECK_ARG(da && x && mod && dx_io && dmod && workspace && batch > 0 && seq > 0, "layernorm_modulate_bwd: bad argument");
-  DMVAE_CHECK_ARG(c % 4 == 0 && c >= 4 && c <= MAX_SWEEPS * 256, "layernorm_modulate_bwd: width must be a multiple of 4 up to 2048 (got %d)", c);
-  DMVAE_CHECK_ARG(ln_offsets_ok(c, mod_stride, shift_off, scale_off), "layernorm_modulate_bwd: modulation offsets must be multiples of 4 inside the row");
+  DMVAE_CHECK_ARG(row_width_ok(c), "layernorm_modulate_bwd: width must be a multiple of 4 up to 2048 (got %d)", c);
+  DMVAE_CHECK_ARG(mod_offsets_ok(c, mod_stride, shift_off, scale_off), "layernorm_modulate_bwd: modulation offsets must be multiples of 4 inside the row");
   DMVAE_CHECK_ARG(workspace_bytes >= dmvae_layernorm_modulate_bwd_workspace(batch, seq, c), "layernorm_modulate_bwd: workspace too small");
   DMVAE_CHECK_ARG((size_t)batch * (size_t)seq <= 0x7fffffffu - 4, "layernorm_modulate_bwd: too many rows");
-  int bps = 1024 / batch;
-  bps = bps > LN_BPS ? LN_BPS : (bps < 4 ? 4 : bps);
-  float4* rowstat = reinterpret_cast<float4*>((float*)workspace + (size_t)batch * LN_BPS * 2 * (size_t)c);   // 16-byte aligned: the offset is a multiple of 4 floats
+  const int bps = blocks_per_sample(batch);
+  float4* rowstat = reinterpret_cast<float4*>((float*)workspace + (size_t)batch * MAX_BPS * 2 * (size_t)c);   // 16-byte aligned: the offset is a multiple of 4 floats
   const int rows = batch * seq;
-  DMVAE_BY_SWEEPS(c, hipLaunchKernelGGL(layernorm_rowstat_kernel<SW>, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x, (const bf16*)mod,
-                                        rowstat, rows, seq, c, mod_stride, scale_off, eps));
-  DMVAE_CHECK_LAUNCH();
+  const int rc = by_sweeps(c, [&](auto sw) {
+    hipLaunchKernelGGL(layernorm_rowstat_kernel<decltype(sw)::value>, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16*)da, (const float*)x,
+                       (const bf16*)mod, rowstat, rows, seq, c, mod_stride, scale_off, eps);
+    DMVAE_CHECK_LAUNCH();
+    return 0;
+  });
+  if (rc) return rc;
   const int bt = ((c / 4) + 63) / 64 * 64;
   hipLaunchKernelGGL(layernorm_modulate_bwd_apply_kernel, dim3(bps, batch), dim3(bt), 0, stream, (const bf16*)da, (const float*)x, (const bf16*)mod, rowstat,
                      (float*)dx_io, (float*)workspace, seq, c, mod_stride, scale_off);
   DMVAE_CHECK_LAUNCH();
-  hipLaunchKernelGGL(layernorm_modulate_bwd_final_kernel, dim3((c + 255) / 256, batch), dim3(256), 0, stream, (const float*)workspace, (float*)dmod, bps, c,
-                     mod_stride, shift_off, scale_off);
+  hipLaunchKernelGGL(modulate_bwd_final_kernel<false>, dim3((c + 255) / 256, batch), dim3(256), 0, stream, (const float*)workspace, (float*)dmod, (float*)nullptr,
+                     bps, c, mod_stride, shift_off, scale_off);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

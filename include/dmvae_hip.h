@@ -502,7 +502,8 @@ int dmvae_gelu_bwd(const void* dy, const void* x, void* dx, size_t n, dmvae_stre
 /* ---- LightningDiT inference path (diffusion/lightningdit/lightningdit.py:175-273; teacher / student evaluations of the DMD loss,
  * train_dmd.py:211-217).  Residual stream f32, Linear operands / results bf16; rounding sites follow the reference's autocast graph.
  * mod: the adaLN Linear's output [B][mod_stride] bf16; *_off: element offsets of the shift / scale / gate chunks inside a row.
- * rmsnorm_modulate: y = bf16( RMSNorm(x; w, eps) * bf16(1 + scale[b]) + shift[b] ), shift_off < 0: no shift (`wo_shift`).  c % 4 == 0, c <= 2048.
+ * rmsnorm_modulate: y = bf16( RMSNorm(x; w, eps) * bf16(1 + scale[b]) + shift[b] ), shift_off < 0: no shift (`wo_shift`).  c % 4 == 0, c <= 2048,
+ *   offsets % 4 == 0 with every chunk (shift, scale, gate) inside its row: anything else is refused, forward and backward.
  * qknorm_rope: qkv [B][N][3][H][D] bf16 -> q, k: per-head RMSNorm (bf16 result) * weight, 2-D rotary embedding with the [N][D] cos / sin
  *   tables (pos_embed.py:96-135), bf16, head-major [B*H][N][Dp] zero-padded to Dp >= D; v copied head-major [B*H][N][D].  D even, Dp <= 128.
  * swiglu: out[rows][hidden] = bf16( bf16(silu(x1)) * x2 ), x12 = [x1 | x2] (swiglu_ffn.py:31-36).  hidden % 8 == 0.

@@ -454,7 +454,7 @@ RMS_FWD = [dict(b=3, n=5, c=c) for c in W4 + W8] + \
            dict(b=3, n=5, c=1152, stride=6 * 1152, shift_off=0, scale_off=1152, gate_off=2 * 1152 + 4, gstride=6 * 1152 + 4)]        # the gate's
 RMS_BWD = [dict(b=1, n=5, c=4), dict(b=1, n=33, c=252), dict(b=3, n=40, c=260), dict(b=40, n=64, c=1152), dict(b=300, n=3, c=516), dict(b=2, n=300, c=2044),
            dict(b=2, n=37, c=2048), dict(b=3, n=40, c=260, hard=True)]
-RMS_BWD_FALLBACK = [dict(b=1, n=4097, c=c) for c in (8, 260, 516, 772, 1028, 1284, 2048)] + [dict(b=2, n=4100, c=8)]
+RMS_BWD_FALLBACK = [dict(b=1, n=4097, c=c) for c in (8, 260, 516, 772, 1028, 1284, 1540, 2048)] + [dict(b=2, n=4100, c=8)]
 GATED = [dict(b=b, n=n, c=c) for c in (8, 264, 1152, 2048) for n in (1, 7, 37) for b in (1, 5)]
 SWIGLU = [dict(rows=r, hid=h) for h in (8, 40, 3072) for r in (1, 7, 300)]
 QK_GENERIC = [dict(b=1, n=3, heads=1, d=2), dict(b=2, n=5, heads=3, d=6), dict(b=1, n=7, heads=5, d=36), dict(b=2, n=3, heads=3, d=70), dict(b=1, n=5, heads=3, d=126)]

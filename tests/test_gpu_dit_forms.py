@@ -78,9 +78,10 @@ def _rms_out(c, shift, xo, y):
 
 @pytest.mark.parametrize("case", S.RMS_FWD, ids=S.case_id)
 def test_rmsnorm_forward_forms(case):
-    """dmvae_rmsnorm_modulate_bf16 -> rmsnorm_modulate{8}_kernel<false, SW>, dmvae_gated_residual_rmsnorm_modulate and dmvae_gated_residual_out -> <true, SW>.
+    """All three entries through csrc/dit.hip::rmsnorm_modulate_launch<RES>: dmvae_rmsnorm_modulate_bf16 -> rmsnorm_modulate{8}_kernel<false, SW>,
+    dmvae_gated_residual_rmsnorm_modulate and dmvae_gated_residual_out -> <true, SW>.
     Four channels per lane (c % 8 != 0, or an offset / stride that is 4 mod 8): SW = ceil(c / 256) -> 1: c 4, 252; 2: 260, 508; 3: 516, 764; 4: 772, 1020; 5: 1028,
-    1276 and 1152 with the misaligned chunks; 6: 1284, 1532; 8 (default): 1540, 1788, 1796, 2044.  Eight per lane: SW8 = ceil(c / 512) -> 1: 8, 512; 2: 520, 768,
+    1276 and 1152 with the misaligned chunks; 6: 1284, 1532; 7: 1540, 1788; 8: 1796, 2044.  Eight per lane: SW8 = ceil(c / 512) -> 1: 8, 512; 2: 520, 768,
     1024; 3: 1032, 1152, 1536; 4: 1544, 2048.  15 rows: the last block has 3 live waves and the sample changes inside a block."""
     c = to_dev(S.rms_case(**case))
     shape, w_ = c["x"].shape, c["c"]
@@ -159,7 +160,7 @@ def test_rmsnorm_backward_two_kernel_route(case):
 @pytest.mark.parametrize("case", S.RMS_BWD_FALLBACK, ids=S.case_id)
 def test_rmsnorm_backward_single_kernel_route(case):
     """dmvae_rmsnorm_modulate_bwd with seq > 4096: rmsnorm_modulate_bwd_kernel<SW>, dynamic LDS 24 c bytes -> SW 1: c 8; 2: 260; 3: 516; 4: 772; 5: 1028; 6: 1284;
-    8 (default): 2048; and two samples at c = 8."""
+    7: 1540; 8: 2048; and two samples at c = 8."""
     _rms_bwd_case(case)
 
 
@@ -266,7 +267,8 @@ def test_qknorm_rope_16_lane_kernels(case):
 def test_refusals_launch_nothing():
     from dmvae_amd import ops
     g = torch.Generator().manual_seed(0)
-    for w_, stride, shift_off, scale_off in ((2052, None, 0, None), (6, None, 0, None), (8, None, 2, None), (8, 12, 0, 8)):
+    # too wide; not a multiple of 4; shift offset 2; scale chunk past the row; SHIFT chunk past the row (12 + 8 > 16)
+    for w_, stride, shift_off, scale_off in ((2052, None, 0, None), (6, None, 0, None), (8, None, 2, None), (8, 12, 0, 8), (8, 16, 12, 0)):
         stride = 6 * w_ if stride is None else stride
         scale_off = w_ if scale_off is None else scale_off
         x, r = torch.randn(2, 3, w_, generator=g).to(DEV), torch.randn(2, 3, w_, generator=g).to(DEV).to(BF)

@@ -1,16 +1,19 @@
 #!/usr/bin/env python
 """HBM-bound passes of the LightningDiT block (csrc/dit.hip, dit_stack.hip) at the DMD stage's and the diffusion trainer's shapes: microseconds per call and achieved
 TB/s on the algorithmic bytes (every tensor once).  Cold inputs: the calls rotate over enough buffers to defeat the 256-MB Infinity Cache.
-    python tools/bench_dit_norms.py"""
-import os, sys
+    python tools/bench_dit_norms.py [--reps 6]"""
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from dmvae_amd import ops
 BF = torch.bfloat16
 C, N, H = 1152, 256, 16
+ap = argparse.ArgumentParser()
+ap.add_argument("--reps", type=int, default=6, help="timed passes over the rotating buffers per item")
+REPS = ap.parse_args().reps
 
 
-def t(fns, reps=6):
+def t(fns, reps=REPS):
     for f in fns: f()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
