@@ -282,6 +282,14 @@ SIGNATURES = {
     "dmvae_resize_tf1_bilinear": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "dmvae_inception_score_workspace": (c_size_t, [c_size_t, c_int, c_size_t]),
     "dmvae_inception_score": (c_int, [c_void_p, c_int, c_size_t, c_int, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    # precision / recall radii and membership, KID's MMD^2: f64 Gram tiles with streaming epilogues (csrc/manifold.hip)
+    "dmvae_knn_radius_workspace": (c_size_t, [c_size_t]),
+    "dmvae_knn_radius": (c_int, [c_void_p, c_int, c_size_t, c_int, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    "dmvae_manifold_member_workspace": (c_size_t, [c_size_t, c_size_t]),
+    "dmvae_manifold_member": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dmvae_kid_mmd2_workspace": (c_size_t, [c_size_t, c_size_t]),
+    "dmvae_kid_mmd2": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int,
+                               c_double, c_double, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -2208,6 +2208,102 @@ def inception_score(logits: torch.Tensor, order: Optional[torch.Tensor] = None, 
     return scores
 
 
+# ---- precision / recall and KID (csrc/manifold.hip) ------------------------------------------------------
+_MANIFOLD_DTYPES = {f32: 0, torch.float64: 2}
+
+
+def _feature_rows(t: torch.Tensor, name: str, f: Optional[int] = None):
+    """A [n, F] f32 / f64 GPU tensor with unit stride along F (any row pitch >= F: a view of a wider buffer is taken as it is) -> (tensor, n, F, pitch)."""
+    if not t.is_cuda:
+        raise _lib.DmvaeHipError(f"{name}: expected a GPU tensor; dmvae_amd has no CPU path")
+    if t.dtype not in _MANIFOLD_DTYPES:
+        raise TypeError(f"{name}: expected float32 or float64, got {t.dtype}")
+    if t.dim() != 2 or t.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty [n, F], got {tuple(t.shape)}")
+    n, width = t.shape
+    if f is not None and width != f:
+        raise ValueError(f"{name}: expected {f} features, got {width}")
+    if width % 16 or not 16 <= width <= 4096:
+        raise ValueError(f"{name}: F must be a multiple of 16 in [16, 4096], got {width}")
+    if t.stride(1) != 1 or (n > 1 and t.stride(0) < width):
+        t = t.contiguous()
+    return t, n, width, (t.stride(0) if n > 1 else width)
+
+
+def _out_vector(out: Optional[torch.Tensor], n: int, dtype, device, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(n, dtype=dtype, device=device)
+    _req(out, dtype, name)
+    if tuple(out.shape) != (n,) or out.device != device:
+        raise ValueError(f"{name}: expected [{n}] on {device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def knn_radius(x: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, F] f32 / f64 -> f64 [N]: the squared distance from each row to its k-th nearest other row -- the (k + 1)-th smallest of d2(i, .) over all rows,
+    self included at exactly 0 (torch-fidelity's `cdist(...).kthvalue(k + 1)`, squared), in f64 with nothing N x N in memory (include/dmvae_hip.h:
+    dmvae_knn_radius).  1 <= k <= 8, N > k.  Deterministic.  `out`: a contiguous f64 [N] on x's device to write into."""
+    x, n, f, ld = _feature_rows(x, "x")
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError(f"k: expected 1 <= k <= 8, got {k}")
+    if n <= k:
+        raise ValueError(f"x: {n} row(s) have no {k}-th neighbour")
+    lib = _lib.lib()
+    ws = torch.empty(max(lib.dmvae_knn_radius_workspace(n) // 8, 1), dtype=torch.float64, device=x.device)
+    out = _out_vector(out, n, torch.float64, x.device, "out")
+    check(lib.dmvae_knn_radius(x.data_ptr(), _MANIFOLD_DTYPES[x.dtype], n, f, ld, k, ws.data_ptr(), out.data_ptr(), _stream()), "knn_radius")
+    return out
+
+
+def manifold_member(q: torch.Tensor, r: torch.Tensor, radius2: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q [Nq, F], r [Nr, F] (one dtype, f32 / f64), radius2 f64 [Nr] -> uint8 [Nq]: 1 where the query lies inside (`<=`) the ball of some reference row, in
+    f64 with nothing Nq x Nr in memory (include/dmvae_hip.h: dmvae_manifold_member).  Deterministic.  `out`: a contiguous uint8 [Nq] to write into."""
+    q, nq, f, ldq = _feature_rows(q, "q")
+    r, nr, _, ldr = _feature_rows(r, "r", f)
+    if r.dtype != q.dtype or r.device != q.device:
+        raise TypeError(f"r: expected {q.dtype} on {q.device}, got {r.dtype} on {r.device}")
+    _req(radius2, torch.float64, "radius2")
+    if tuple(radius2.shape) != (nr,) or radius2.device != q.device:
+        raise ValueError(f"radius2: expected [{nr}] on {q.device}, got {tuple(radius2.shape)} on {radius2.device}")
+    lib = _lib.lib()
+    ws = torch.empty(max(lib.dmvae_manifold_member_workspace(nq, nr) // 8, 1), dtype=torch.float64, device=q.device)
+    out = _out_vector(out, nq, torch.uint8, q.device, "out")
+    check(lib.dmvae_manifold_member(q.data_ptr(), nq, ldq, r.data_ptr(), nr, ldr, _MANIFOLD_DTYPES[q.dtype], f, radius2.data_ptr(), ws.data_ptr(),
+                                    out.data_ptr(), _stream()), "manifold_member")
+    return out
+
+
+def kid_mmd2(x: torch.Tensor, y: torch.Tensor, idx1: torch.Tensor, idx2: torch.Tensor, degree: int = 3, gamma: Optional[float] = None, coef0: float = 1.0,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N1, F], y [N2, F] (one dtype, f32 / f64), idx1 / idx2 int64 [S, m] (row indices into x / y) -> f64 [S]: the unbiased polynomial-kernel MMD^2 of each
+    subset, K(a, b) = (gamma a.b + coef0)^degree, gamma None = 1 / F (include/dmvae_hip.h: dmvae_kid_mmd2).  Deterministic; a subset's value does not depend
+    on its slot.  The tables' ranges are checked on the device first (one reduction each, one synchronisation): the kernels trust them."""
+    x, n1, f, ldx = _feature_rows(x, "x")
+    y, n2, _, ldy = _feature_rows(y, "y", f)
+    if y.dtype != x.dtype or y.device != x.device:
+        raise TypeError(f"y: expected {x.dtype} on {x.device}, got {y.dtype} on {y.device}")
+    _req(idx1, torch.int64, "idx1")
+    _req(idx2, torch.int64, "idx2")
+    if idx1.dim() != 2 or idx1.numel() == 0 or idx2.shape != idx1.shape or idx1.device != x.device or idx2.device != x.device:
+        raise ValueError(f"idx1 / idx2: expected two non-empty [S, m] on {x.device}, got {tuple(idx1.shape)} and {tuple(idx2.shape)}")
+    subsets, m = idx1.shape
+    degree = int(degree)
+    if m < 2:
+        raise ValueError(f"idx1: a subset needs m >= 2 rows, got {m}")
+    if not 1 <= degree <= 8:
+        raise ValueError(f"degree: expected 1 <= degree <= 8, got {degree}")
+    lo1, hi1, lo2, hi2 = torch.stack(torch.aminmax(idx1) + torch.aminmax(idx2)).tolist()
+    if lo1 < 0 or hi1 >= n1 or lo2 < 0 or hi2 >= n2:
+        raise ValueError(f"idx1 / idx2: every entry must be a row index in [0, {n1}) / [0, {n2}), got ranges [{lo1}, {hi1}] and [{lo2}, {hi2}]")
+    lib = _lib.lib()
+    ws = torch.empty(max(lib.dmvae_kid_mmd2_workspace(subsets, m) // 8, 1), dtype=torch.float64, device=x.device)
+    out = _out_vector(out, subsets, torch.float64, x.device, "out")
+    check(lib.dmvae_kid_mmd2(x.data_ptr(), n1, ldx, y.data_ptr(), n2, ldy, _MANIFOLD_DTYPES[x.dtype], f, idx1.data_ptr(), idx2.data_ptr(), subsets, m, degree,
+                             float(1.0 / f if gamma is None else gamma), float(coef0), ws.data_ptr(), out.data_ptr(), _stream()), "kid_mmd2")
+    return out
+
+
 # ---- input pipeline (csrc/data.hip) ---------------------------------------------------------------
 def lanczos_kmax(n_in: int, n_out: int) -> int:
     """Taps allotted per output index for a LANCZOS resize of one axis from n_in to n_out samples (PIL's ksize).  Host only."""

@@ -1120,6 +1120,49 @@ size_t dmvae_inception_score_workspace(size_t n, int classes, size_t splits);
 int dmvae_inception_score(const void* logits, int dtype, size_t n, int classes, size_t ld, const int64_t* order, size_t splits, void* workspace,
                           double* scores, dmvae_stream_t stream);
 
+/* ---- all-pairs metrics of the evaluation tail: precision / recall radii and membership, KID's MMD^2 (csrc/manifold.hip) ------------------------ */
+
+/* The three entry points below restate torch-fidelity's `prc` and `kid` (the metrics sample_50k.py:185-199 and evaluation/fid.py:15-45 name in their
+ * calculate_metrics call) from their published form; agreement with the library itself has not been run.  They share one tile routine: G[i][j] =
+ * sum_f a[i][f] * b[j][f] over rows of pitch ld >= f, dtype 0 f32 or 2 f64 (widened exactly), accumulated on v_mfma_f64_16x16x4_f64 in ascending steps of
+ * four f from zero -- a function of the two rows alone, wherever the pair falls in a tile or the grid.  |a_i|^2 is the G[i][i] of that routine, and
+ * d2(i, j) = max(0, (|a_i|^2 + |b_j|^2) - 2 G[i][j]): two equal rows are at distance exactly 0.  f % 16 == 0, 16 <= f <= 4096.  Nothing rows x rows is ever
+ * stored; no allocation, no synchronisation, no atomics: every result repeats bit for bit.  Rows past the counts are never read. */
+
+/* Bytes of dmvae_knn_radius's workspace: n f64 norms and 9 f64 per (column split, row), (n + s(n) * n * 9) * 8 with s(n) = min(ceil(n / 64),
+ * ceil(512 / ceil(n / 64))); 0 for n < 2 or n > 2^30 - 64.  A closed form: no GPU.  Reference: sample_50k.py:185-199 and evaluation/fid.py:15-45. */
+size_t dmvae_knn_radius_workspace(size_t n);
+/* radius2 [n] f64 = the (k + 1)-th smallest of d2(i, j) over all j of x [n][f] itself, self included, the self distance DEFINED as exactly 0 (set, not
+ * computed): torch-fidelity's `calc_cdist_part(batch, features).kthvalue(neighborhood + 1)`, squared.  Each lane keeps the 9 smallest values of its rows,
+ * lanes and column splits are merged by selection of exact values: nothing but the Gram's own sum order enters the result, which does not depend on the
+ * split.  1 <= k <= 8, k < n <= 2^30 - 64 (every launch stays below 2^32 threads), ld >= f; anything else, or a NULL pointer, returns -22 before any launch.
+ * Reference: sample_50k.py:185-199 and evaluation/fid.py:15-45 (`prc=True`, neighborhood 3). */
+int dmvae_knn_radius(const void* x, int dtype, size_t n, int f, size_t ld, int k, void* workspace, double* radius2, dmvae_stream_t stream);
+/* Bytes of dmvae_manifold_member's workspace: nq + nr f64 norms and one byte per (column split, query) rounded up to 8:
+ * (nq + nr) * 8 + ceil(s * nq / 8) * 8 with s = min(ceil(nr / 64), ceil(512 / ceil(nq / 64))); 0 for a count outside [1, 2^30 - 64].  No GPU.
+ * Reference: sample_50k.py:185-199 and evaluation/fid.py:15-45. */
+size_t dmvae_manifold_member_workspace(size_t nq, size_t nr);
+/* member [nq] uint8 = 1 where some j has d2(q_i, r_j) <= radius2[j] (`<=`, as the library's `(dist <= radii).any(dim=1)`), else 0; q [nq][f] and r [nr][f]
+ * of one dtype, radius2 f64 [nr].  One owner per output byte, written with vector stores.  precision is the mean of member(fake, real, radius2(real)), recall
+ * the mean of member(real, fake, radius2(fake)).  -22 before any launch for a NULL pointer, a count outside [1, 2^30 - 64], f out of range, a pitch below f.
+ * Reference: sample_50k.py:185-199 and evaluation/fid.py:15-45. */
+int dmvae_manifold_member(const void* q, size_t nq, size_t ldq, const void* r, size_t nr, size_t ldr, int dtype, int f, const double* radius2,
+                          void* workspace, uint8_t* member, dmvae_stream_t stream);
+/* Bytes of dmvae_kid_mmd2's workspace: one f64 partial per (subset, xx / yy / xy, 64 x 64 tile), subsets * 3 * ceil(m / 64)^2 * 8; 0 where dmvae_kid_mmd2
+ * would refuse (subsets, m).  No GPU.  Reference: sample_50k.py:185-199 and evaluation/fid.py:15-45. */
+size_t dmvae_kid_mmd2_workspace(size_t subsets, size_t m);
+/* mmd2 [subsets] f64 = the unbiased estimate of torch-fidelity's `polynomial_mmd` per subset: subset s takes rows idx1[s][0 .. m) of x [n1][f] and
+ * idx2[s][0 .. m) of y [n2][f] (int64 tables on the device, as dmvae_inception_score takes its order table), K(a, b) = (gamma * a.b + coef0)^degree with the
+ * power by repeated multiplication (p = base; p = p * base, degree - 1 times; the product and the sum of the base are rounded separately), and
+ *   mmd2 = (sum_{i != j} K(x_i, x_j) + sum_{i != j} K(y_i, y_j)) / (m (m - 1)) - 2 sum_{i, j} K(x_i, y_j) / (m m),
+ * the diagonal left out by position.  Tile sums (lane, then an xor tree, then waves 0..3) go to the workspace and one workgroup per subset adds them in a
+ * fixed order: the value of a subset depends on its rows alone, not on its slot.  The tables' entries are trusted (dmvae_amd/ops.py checks their range on
+ * the device).  2 <= m <= 2^20, m <= n1, n2 <= 2^30 - 64, 1 <= degree <= 8, subsets >= 1, subsets * 3 * ceil(m / 64)^2 <= 2^24 - 1 (one launch); anything else, or a NULL pointer, returns -22 before any launch.
+ * Reference: sample_50k.py:185-199 and evaluation/fid.py:15-45 (`kid=True`, kid_subsets 100, kid_subset_size 1000; the library's defaults degree 3,
+ * gamma 1 / f, coef0 1). */
+int dmvae_kid_mmd2(const void* x, size_t n1, size_t ldx, const void* y, size_t n2, size_t ldy, int dtype, int f, const int64_t* idx1, const int64_t* idx2,
+                   size_t subsets, size_t m, int degree, double gamma, double coef0, void* workspace, double* mmd2, dmvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
