@@ -290,6 +290,11 @@ SIGNATURES = {
     "dmvae_kid_mmd2_workspace": (c_size_t, [c_size_t, c_size_t]),
     "dmvae_kid_mmd2": (c_int, [c_void_p, c_size_t, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int,
                                c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    # the FID Inception-v3 extractor: exact-f32 implicit-GEMM conv + BN affine + ReLU, 3x3 pools, global average, input pass (csrc/inception.hip)
+    "dmvae_conv2d_f32_fwd": (c_int, [c_void_p] * 5 + [c_int] * 13 + [c_void_p]),
+    "dmvae_pool2d_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
+    "dmvae_global_avgpool_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "dmvae_inception_input": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

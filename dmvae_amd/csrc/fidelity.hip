@@ -1,6 +1,6 @@
 // The arithmetic around the Inception network in the evaluation tail of sample_50k.py:174-209 and evaluation/fid.py:8-48 (torch-fidelity's FID / Inception
-// Score over the sampled images): the uint8 -> f32 resize to the network's input size, and the Inception Score of its logits.  The network itself is not part
-// of this library (dmvae_amd/fidelity.py takes it as a module).  torch-fidelity is on none of the machines this was developed on: the two definitions below
+// Score over the sampled images): the uint8 -> f32 resize to the network's input size, and the Inception Score of its logits.  The network's own kernels are
+// csrc/inception.hip (dmvae_amd/fidelity.py takes the network as a module).  torch-fidelity is on none of the machines this was developed on: the two definitions below
 // restate its published `interpolate_bilinear_2d_like_tensorflow1x` (align_corners=False) and `isc_features_to_metric`, tests/fidelity_spec.py restates them in
 // numpy, and agreement with the library itself has not been run.
 //

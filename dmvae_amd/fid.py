@@ -3,9 +3,10 @@ bicubic resize and the uint8 quantisation in front) with the same protocol -- `u
 state layout, so that statistics files written by either side load in the other.
 
 What runs where: the resize + quantisation (evaluation/fid.py:61-64) and the f64 feature statistics `sum += X.sum(0)`, `cov_sum += X^T X` (torchmetrics'
-`update`) are HIP kernels of this package (csrc/fid.hip: no ATen interpolate, no vendor GEMM).  The feature extractor is NOT built here: the Inception
-weights are on no image this package was developed on, so `feature` is either a module mapping uint8 [B, 3, S, S] to [B, F] or the int that asks torchmetrics
-for its `NoTrainInceptionV3` (an ImportError without torchmetrics).  `compute()` runs once per evaluation, in f64 on the host: mean and covariance from the
+`update`) are HIP kernels of this package (csrc/fid.hip: no ATen interpolate, no vendor GEMM).  `feature` is either a module mapping uint8 [B, 3, S, S] to
+[B, F] -- the package's own Inception network is `dmvae_amd.models.inception.InceptionV3Compat` (`FID(feature=InceptionV3Compat.from_checkpoint(path))`;
+the weight file is not shipped) -- or the int that asks torchmetrics for its `NoTrainInceptionV3` (an ImportError without torchmetrics).  `compute()` runs
+once per evaluation, in f64 on the host: mean and covariance from the
 sums, then `frechet_distance` through `torch.linalg.eigvals`.
 
 CPU tensors take the stock PyTorch composition behind `DMVAE_ALLOW_STOCK=1`, like every other module (dmvae_amd/_stock.py)."""

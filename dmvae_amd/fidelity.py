@@ -16,8 +16,9 @@ torch-fidelity is on none of the machines this package was developed on.  The ke
 from their published form (include/dmvae_hip.h gives the definitions, tests/fidelity_spec.py and tests/manifold_spec.py restate them in numpy); AGREEMENT
 WITH THE LIBRARY ITSELF HAS NOT BEEN RUN, for the two all-pairs definitions as for the first two.
 
-Not built here: the Inception network and its weights (`extractor` is the caller's module, as in `fid.FID`), an adapter around torch-fidelity's own extractor
-class, a shadow of `get_fid_is` (it needs that network), `ppl`, and torch-fidelity's shuffle of the file list -- the split assignment and KID's subsets
+The Inception network is `dmvae_amd.models.inception.InceptionV3Compat` (`FidelityMetrics(net.extractor(), num_features=2048)`); `extractor` may be any
+other module with its contract.  Not here: the network's weight file, an adapter around torch-fidelity's own extractor
+class, a shadow of `get_fid_is` (it needs that weight file), `ppl`, and torch-fidelity's shuffle of the file list -- the split assignment and KID's subsets
 here depend on the image indices and `rng_seed` only.
 
 CPU tensors take the stock PyTorch composition behind `DMVAE_ALLOW_STOCK=1`, like every other module (dmvae_amd/_stock.py)."""

@@ -2362,6 +2362,111 @@ def image_preprocess(pack: torch.Tensor, table: torch.Tensor, taps: torch.Tensor
     return res
 
 
+# ---- the FID Inception-v3 extractor's kernels, NHWC f32 (csrc/inception.hip) -------------------------
+POOL_MAX_S2, POOL_MAX_S1P1, POOL_AVG_S1P1 = 0, 1, 2
+
+
+def pack_conv_weight_f32(w: torch.Tensor) -> torch.Tensor:
+    """f32 [cout, cin, kh, kw] (any device) -> the operand of `conv2d_f32`, f32 [chunks, cout, 16] (include/dmvae_hip.h: dmvae_conv2d_f32_fwd): K in the
+    order (ky, kx, ci) cut into chunks of 16, each chunk stored as its 4 x 4 transpose.  cin == 3: every tap padded to 4 channels and the taps to a multiple
+    of 4, with zeros.  A permutation (and zeros): the values keep the checkpoint's bits."""
+    if w.dtype != f32 or w.dim() != 4:
+        raise TypeError(f"w: expected a 4-D float32 [cout, cin, kh, kw], got {w.dtype} {tuple(w.shape)}")
+    cout, cin, kh, kw = w.shape
+    k = w.detach().permute(0, 2, 3, 1).reshape(cout, kh * kw, cin)
+    if cin == 3:
+        taps = (kh * kw + 3) // 4 * 4
+        k = torch.nn.functional.pad(k, (0, 1, 0, taps - kh * kw))
+    elif cin % 16:
+        raise ValueError(f"w: cin must be 3 or a multiple of 16, got {cin}")
+    k = k.reshape(cout, -1, 4, 4).transpose(2, 3).reshape(cout, -1, 16)
+    return k.permute(1, 0, 2).contiguous()
+
+
+def _slice_out(out: Optional[torch.Tensor], shape, c: int, c_offset: int, like: torch.Tensor, name: str) -> torch.Tensor:
+    """The [B, Ho, Wo, pitch] f32 buffer a kernel writes channels [c_offset, c_offset + c) of (a new [B, Ho, Wo, c] when `out` is None)."""
+    if out is None:
+        if c_offset:
+            raise ValueError(f"{name}: c_offset without out")
+        return torch.empty(*shape, c, dtype=f32, device=like.device)
+    _req(out, f32, "out")
+    if out.dim() != 4 or tuple(out.shape[:3]) != tuple(shape) or out.device != like.device or c_offset < 0 or c_offset + c > out.shape[3]:
+        raise ValueError(f"{name}: out must be [{', '.join(map(str, shape))}, >= {c_offset + c}] on {like.device}, got {tuple(out.shape)} on {out.device}")
+    return out
+
+
+def conv2d_f32(x: torch.Tensor, w_packed: torch.Tensor, kernel: Tuple[int, int], stride: int = 1, padding: Tuple[int, int] = (0, 0),
+               scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None, relu: bool = False, out: Optional[torch.Tensor] = None,
+               c_offset: int = 0) -> torch.Tensor:
+    """x [B, H, W, cin] f32 (NHWC), w_packed from `pack_conv_weight_f32` -> act(conv(x, w) * scale + shift) in exact f32 (one k-ordered fma chain per
+    output, bit-identical whatever the batch; include/dmvae_hip.h: dmvae_conv2d_f32_fwd), written into channels [c_offset, c_offset + cout) of `out`
+    [B, Ho, Wo, pitch] (default: a new [B, Ho, Wo, cout]), which is returned.  The forms the library builds are the Inception network's; others raise."""
+    x = _req(x, f32, "x")
+    w_packed = _req(w_packed, f32, "w_packed")
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, H, W, cin], got {tuple(x.shape)}")
+    b, h, w_, cin = x.shape
+    (kh, kw), (ph, pw), stride = (int(v) for v in kernel), (int(v) for v in padding), int(stride)
+    chunks = (kh * kw + 3) // 4 if cin == 3 else kh * kw * cin // 16
+    if w_packed.dim() != 3 or w_packed.shape[0] != chunks or w_packed.shape[2] != 16 or w_packed.device != x.device:
+        raise ValueError(f"w_packed: expected [{chunks}, cout, 16] on {x.device} for cin {cin} and a ({kh}, {kw}) kernel, got {tuple(w_packed.shape)} on "
+                         f"{w_packed.device}")
+    cout = w_packed.shape[1]
+    for name, v in (("scale", scale), ("shift", shift)):
+        if v is not None and (_req(v, f32, name).shape != (cout,) or v.device != x.device):
+            raise ValueError(f"{name}: expected [{cout}] on {x.device}, got {tuple(v.shape)} on {v.device}")
+    if stride < 1 or h + 2 * ph < kh or w_ + 2 * pw < kw:
+        raise ValueError(f"conv2d_f32: a {h} x {w_} image, kernel ({kh}, {kw}), stride {stride}, padding ({ph}, {pw})")
+    ho, wo = (h + 2 * ph - kh) // stride + 1, (w_ + 2 * pw - kw) // stride + 1
+    out = _slice_out(out, (b, ho, wo), cout, int(c_offset), x, "conv2d_f32")
+    check(_lib.lib().dmvae_conv2d_f32_fwd(x.data_ptr(), w_packed.data_ptr(), _ptr(scale), _ptr(shift), out.data_ptr(), b, h, w_, cin, cout, kh, kw, stride,
+                                          ph, pw, int(bool(relu)), int(c_offset), out.shape[3], _stream()), "conv2d_f32_fwd")
+    return out
+
+
+def pool2d_f32(x: torch.Tensor, mode: int, out: Optional[torch.Tensor] = None, c_offset: int = 0) -> torch.Tensor:
+    """x [B, H, W, C] f32 (NHWC) -> its 3 x 3 pool (POOL_MAX_S2: maximum, stride 2; POOL_MAX_S1P1: maximum, stride 1, padding 1; POOL_AVG_S1P1: average,
+    stride 1, padding 1, count_include_pad=False) in channels [c_offset, c_offset + C) of `out` (include/dmvae_hip.h: dmvae_pool2d_f32)."""
+    x = _req(x, f32, "x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, H, W, C], got {tuple(x.shape)}")
+    b, h, w_, c = x.shape
+    mode = int(mode)
+    if mode == POOL_MAX_S2 and (h < 3 or w_ < 3):
+        raise ValueError(f"pool2d_f32: the stride-2 pool needs H, W >= 3, got {h} x {w_}")
+    ho, wo = ((h - 3) // 2 + 1, (w_ - 3) // 2 + 1) if mode == POOL_MAX_S2 else (h, w_)
+    out = _slice_out(out, (b, ho, wo), c, int(c_offset), x, "pool2d_f32")
+    check(_lib.lib().dmvae_pool2d_f32(x.data_ptr(), out.data_ptr(), mode, b, h, w_, c, int(c_offset), out.shape[3], _stream()), "pool2d_f32")
+    return out
+
+
+def global_avgpool_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, H, W, C] f32 (NHWC) -> [B, C] f32: the mean over the pixels, summed in a fixed order in f64 and rounded once (dmvae_global_avgpool_f32).
+    `out`: a contiguous f32 [B, C] on x's device to write into."""
+    x = _req(x, f32, "x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, H, W, C], got {tuple(x.shape)}")
+    b, h, w_, c = x.shape
+    if out is None:
+        out = torch.empty(b, c, dtype=f32, device=x.device)
+    elif tuple(_req(out, f32, "out").shape) != (b, c) or out.device != x.device:
+        raise ValueError(f"global_avgpool_f32: out must be [{b}, {c}] on {x.device}, got {tuple(out.shape)} on {out.device}")
+    check(_lib.lib().dmvae_global_avgpool_f32(x.data_ptr(), out.data_ptr(), b, h, w_, c, _stream()), "global_avgpool_f32")
+    return out
+
+
+def inception_input(x: torch.Tensor) -> torch.Tensor:
+    """x [B, 3, H, W] (NCHW) uint8 -> f32 [B, H, W, 3] = (x - 128) / 128, or f32 (already normalised) -> the same values in NHWC
+    (include/dmvae_hip.h: dmvae_inception_input)."""
+    x = _req(x, torch.uint8 if x.dtype == torch.uint8 else f32, "x")
+    if x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, 3, H, W], got {tuple(x.shape)}")
+    b, _, h, w_ = x.shape
+    out = torch.empty(b, h, w_, 3, dtype=f32, device=x.device)
+    check(_lib.lib().dmvae_inception_input(x.data_ptr(), int(x.dtype == torch.uint8), out.data_ptr(), b, h, w_, _stream()), "inception_input")
+    return out
+
+
 # ---- losses ---------------------------------------------------------------------------------------
 def _loss_ws(device) -> torch.Tensor:
     return workspace(_lib.lib().dmvae_loss_workspace(), device, slot="loss")

@@ -1163,6 +1163,36 @@ size_t dmvae_kid_mmd2_workspace(size_t subsets, size_t m);
 int dmvae_kid_mmd2(const void* x, size_t n1, size_t ldx, const void* y, size_t n2, size_t ldy, int dtype, int f, const int64_t* idx1, const int64_t* idx2,
                    size_t subsets, size_t m, int degree, double gamma, double coef0, void* workspace, double* mmd2, dmvae_stream_t stream);
 
+/* ---- the FID Inception-v3 feature extractor's kernels, NHWC f32 (csrc/inception.hip; dmvae_amd/models/inception.py) ----------------------------- */
+
+/* y[pixel][out_c_offset + co] = act(fma(sum_k w[co][k] x[pixel's field][k], scale[co], shift[co])) for the B Ho Wo output pixels of a convolution of x
+ * [batch][h][w][cin] f32 (NHWC) with zero padding: exact f32 on v_mfma_f32_16x16x4_f32, each output ONE chain acc = fma(w_k, x_k, acc) from 0 over k in the
+ * order (ky, kx, ci) ascending -- no split-K, no atomics -- so a pixel's value depends on its receptive field and the weights alone (not on batch, its
+ * position in the batch or the tiling) and repeats bit for bit.  scale / shift f32 [cout], NULL = 1 / 0 (the BatchNorm affine of an eval-mode conv block; the
+ * weights themselves are never folded); relu != 0: max(., 0).  y is f32 with out_c_pitch channels per pixel, of which [out_c_offset, out_c_offset + cout)
+ * are written (a branch of a concat writes its slice; every other element keeps its bits).  Ho = (h + 2 pad_h - kh) / stride + 1, Wo likewise.
+ * w_packed f32 [chunks][cout][16]: K cut into chunks of 16 -- cin % 16 == 0: chunk = (tap, 16 channels), chunks = kh kw cin / 16; cin == 3: chunk = 4 taps x
+ * {3 channels, 0}, chunks = ceil(kh kw / 4), missing taps zero -- and inside a chunk position 4 q + s holds k = 4 s + q (the 4 x 4 transpose: lane group q's
+ * ds_read_b128).  The values are the checkpoint's bits.  Forms (kh, kw) / stride / (pad_h, pad_w): (1,1)/1/(0,0); (3,3)/1 or 2/(0,0); (3,3)/1/(1,1);
+ * (5,5)/1/(2,2); (1,7)/1/(0,3); (7,1)/1/(3,0); (1,3)/1/(0,1); (3,1)/1/(1,0).  cin == 3 or cin % 16 == 0; cout % 16 == 0; out_c_offset % 4 == 0,
+ * out_c_pitch % 4 == 0, out_c_offset + cout <= out_c_pitch; any batch, h, w (h, w <= 32768) no smaller than the kernel.  Anything else, or a NULL x /
+ * w_packed / y, returns -22 before any launch.  Nothing outside x, w_packed, scale, shift is read.  A Linear is the (1,1) form at h = w = 1.
+ * Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209 (the Inception network both run their images through). */
+int dmvae_conv2d_f32_fwd(const float* x, const float* w_packed, const float* scale, const float* shift, float* y, int batch, int h, int w, int cin,
+                         int cout, int kh, int kw, int stride, int pad_h, int pad_w, int relu, int out_c_offset, int out_c_pitch, dmvae_stream_t stream);
+/* 3 x 3 pools of x [batch][h][w][c] f32 into channels [out_c_offset, out_c_offset + c) of y (pitch out_c_pitch, as above).  mode 0: maximum, stride 2, no
+ * padding (h, w >= 3; Ho = (h - 3) / 2 + 1); 1: maximum, stride 1, padding 1, the padding never a candidate; 2: average, stride 1, padding 1,
+ * count_include_pad=False: the f32 sum of the taps inside the image in (ky, kx) raster order divided by their number.  c % 4 == 0; offset and pitch as
+ * above; -22 before any launch otherwise.  Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209. */
+int dmvae_pool2d_f32(const float* x, float* y, int mode, int batch, int h, int w, int c, int out_c_offset, int out_c_pitch, dmvae_stream_t stream);
+/* y [batch][c] f32 = the mean over the h w pixels of x [batch][h][w][c] f32: added in ascending pixel order in f64, divided in f64, rounded once.
+ * -22 before any launch for a NULL pointer or a size below 1.  Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209. */
+int dmvae_global_avgpool_f32(const float* x, float* y, int batch, int h, int w, int c, dmvae_stream_t stream);
+/* y [batch][h][w][3] f32 (NHWC) from x [batch][3][h][w] (NCHW): is_u8 != 0: uint8, y = (x - 128) / 128 (exact in f32: torch-fidelity's normalisation of a
+ * uint8 image); else f32, copied (an input that is already normalised).  -22 before any launch for a NULL pointer or a size below 1.
+ * Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209. */
+int dmvae_inception_input(const void* x, int is_u8, float* y, int batch, int h, int w, dmvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

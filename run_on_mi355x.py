@@ -27,7 +27,10 @@ process (train_tokenizer.py:382-383,415,424): multi-tensor HIP kernels over the 
 
 `evaluation.fid` (`from evaluation.fid import FID`, train_tokenizer.py:20, train_dmd.py:20) is an opt-in as well: `--hip-fid` in front of the script path (in any
 order with the other two), DMVAE_HIP_FID=1 or `install_shadow(ref, fid=True)` registers `dmvae_amd.fid` under that path: the resize and the f64 feature
-statistics on this build's kernels.  `FID()` as the scripts call it (feature=2048) still needs torchmetrics for the Inception network itself.
+statistics on this build's kernels.  `FID()` as the scripts call it (feature=2048) still needs torchmetrics for the Inception network itself -- unless an
+Inception weight file is named: `--inception-weights=/path/to/pt_inception-2015-12-05.pth` (implies --hip-fid) or `install_shadow(ref, fid=True,
+inception_weights=path)` registers `dmvae_amd.models.inception.fid_module(path)` instead, `dmvae_amd.fid`'s names with an `FID` whose int `feature` (2048
+only) builds this build's `InceptionV3Compat` from that file: the network on the exact-f32 kernels, no torchmetrics.
 
 `evaluation.metrics` (`PSNR`, `SSIM`, `LPIPS`) is an opt-in too: `--hip-metrics`, DMVAE_HIP_METRICS=1 or `install_shadow(ref, metrics=True)` registers
 `dmvae_amd.metrics` under that path: `SSIM` on this build's f64 kernel with no torchmetrics import, `PSNR` unchanged, `LPIPS` a NotImplementedError (its AlexNet
@@ -81,13 +84,17 @@ def install_optim() -> dict:
 
 
 def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False, all_paths: bool = False, fid: bool = False,
-                   metrics: bool = False) -> dict:
+                   metrics: bool = False, inception_weights: str | None = None) -> dict:
     """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve).
     dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them).
     optim: also replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (`install_optim`; not part of the returned dict).
     all_paths: also let the transport mirror build the GVP / VP plans (`dmvae_amd.transport.enable_all_paths`; default: left as it is).
     fid: also shadow evaluation.fid with this build's `dmvae_amd.fid` (default: the reference's own file serves it).
-    metrics: also shadow evaluation.metrics with this build's `dmvae_amd.metrics` (default: the reference's own file serves it)."""
+    metrics: also shadow evaluation.metrics with this build's `dmvae_amd.metrics` (default: the reference's own file serves it).
+    inception_weights (with fid): a state_dict file of torch-fidelity's Inception network; evaluation.fid becomes
+    `dmvae_amd.models.inception.fid_module(path)`, whose `FID(feature=2048)` runs this build's network instead of asking torchmetrics for one."""
+    if inception_weights and not fid:
+        raise ValueError("install_shadow: inception_weights needs fid=True")
     out = {}
     shadows = dict(SHADOWS)
     if dinodisc:
@@ -101,6 +108,8 @@ def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bo
         for i in range(1, len(parts)):
             _package(".".join(parts[:i]), ref_dir)
         mod = importlib.import_module(target)
+        if path == "evaluation.fid" and inception_weights:
+            mod = importlib.import_module("dmvae_amd.models.inception").fid_module(inception_weights)
         sys.modules[path] = mod
         setattr(sys.modules[".".join(parts[:-1])], parts[-1], mod)
         out[path] = mod
@@ -133,8 +142,11 @@ def main(argv) -> int:
     hip_optim = importlib.import_module("dmvae_amd.optim").requested()      # DMVAE_HIP_OPTIM=1
     hip_fid = os.environ.get("DMVAE_HIP_FID", "0") not in ("", "0")
     hip_metrics = os.environ.get("DMVAE_HIP_METRICS", "0") not in ("", "0")
-    while argv and argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid", "--hip-metrics"):
-        if argv[0] == "--hip-dinodisc":
+    weights = None
+    while argv and (argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid", "--hip-metrics") or argv[0].startswith("--inception-weights=")):
+        if argv[0].startswith("--inception-weights="):
+            weights, hip_fid = argv[0].split("=", 1)[1], True
+        elif argv[0] == "--hip-dinodisc":
             hip_dinodisc = True
         elif argv[0] == "--hip-fid":
             hip_fid = True
@@ -148,7 +160,7 @@ def main(argv) -> int:
         return 0
     if argv[0] == "--check":
         ref = argv[1] if len(argv) > 1 else None
-        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid, metrics=hip_metrics).items():
+        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid, metrics=hip_metrics, inception_weights=weights).items():
             print(f"{path:40s} -> {mod.__name__}")
         if hip_optim:
             for path, obj in install_optim().items():
@@ -156,7 +168,7 @@ def main(argv) -> int:
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid, metrics=hip_metrics)      # the script's --path_type selects
+    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid, metrics=hip_metrics, inception_weights=weights)      # the script's --path_type selects
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])
