@@ -295,6 +295,10 @@ SIGNATURES = {
     "dmvae_pool2d_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 7 + [c_void_p]),
     "dmvae_global_avgpool_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "dmvae_inception_input": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # the evaluation LPIPS (AlexNet): scaling-layer input pass, f64 head with fixed-order partials (csrc/lpips_eval.hip)
+    "dmvae_lpips_input": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "dmvae_lpips_head_workspace": (c_size_t, [c_size_t, c_int, c_int, c_int]),
+    "dmvae_lpips_head": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -3,7 +3,8 @@
 // ReLU in its epilogue, the three 3 x 3 pools, the global average and the NCHW -> NHWC input pass.
 //
 // dmvae_conv2d_f32_fwd: M = B Ho Wo output pixels x N = Cout channels, K = kh kw Cin in the order (ky, kx, ci).  K is cut into chunks of 16 (one tap, 16
-// channels; for the first layer's Cin = 3 one chunk is 4 taps x {3 channels, one zero}, which is exact).  A workgroup of four waves owns a 64 x 64 tile; wave
+// channels; for a first layer's Cin = 3 one chunk is 4 taps x {3 channels, one zero}, which is exact: Inception's 3 x 3 stride 2 is 9 taps in 3 chunks, the
+// evaluation LPIPS' AlexNet 11 x 11 stride 4 padding 2 is 121 taps in 31 chunks, the last holding one real tap and three zero ones).  A workgroup of four waves owns a 64 x 64 tile; wave
 // v owns pixels 16 v .. 16 v + 15 of it and all 64 channels as four independent 16 x 16 accumulators of v_mfma_f32_16x16x4_f32, the only MFMA opcode of
 // this file.  The weights are the MFMA's A operand (row = channel) and the activations its B operand (column = pixel): a lane then holds four CONSECUTIVE
 // channels of one pixel, and the epilogue is one 16-B store per accumulator into the (wider) NHWC output.
@@ -235,7 +236,11 @@ extern "C" int dmvae_conv2d_f32_fwd(const float* x, const float* w_packed, const
                                     hipStream_t stream) {
   using namespace dmvae_inception;
   DMVAE_CHECK_ARG(x && w_packed && y, "conv2d_f32_fwd: NULL pointer (x, w_packed and y are required; scale and shift may be NULL)");
-  DMVAE_CHECK_ARG(conv_form_ok(kh, kw, stride, pad_h, pad_w),
+  const bool form11 = kh == 11 && kw == 11;                          // AlexNet's first layer (dmvae_amd/models/lpips_alex.py): one more form of the CIN3 loader
+  DMVAE_CHECK_ARG(!form11 || (stride == 4 && pad_h == 2 && pad_w == 2),
+                  "conv2d_f32_fwd: kernel (11, 11) is built at stride 4 padding (2, 2) only, got stride %d padding (%d, %d)", stride, pad_h, pad_w);
+  DMVAE_CHECK_ARG(!form11 || cin == 3, "conv2d_f32_fwd: kernel (11, 11) is built for cin 3 only, got cin %d", cin);
+  DMVAE_CHECK_ARG(form11 || conv_form_ok(kh, kw, stride, pad_h, pad_w),
                   "conv2d_f32_fwd: kernel (%d, %d) stride %d padding (%d, %d) is not built: 1x1; 3x3 stride 1 or 2 pad 0; 3x3 pad 1; 5x5 pad 2; (1,7) pad (0,3); "
                   "(7,1) pad (3,0); (1,3) pad (0,1); (3,1) pad (1,0)", kh, kw, stride, pad_h, pad_w);
   DMVAE_CHECK_ARG(cin == 3 || (cin >= 16 && cin % 16 == 0), "conv2d_f32_fwd: cin must be 3 or a multiple of 16, got %d", cin);

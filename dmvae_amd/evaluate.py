@@ -33,15 +33,19 @@ def psnr(img1: torch.Tensor, img2: torch.Tensor, reduce: str = "sum") -> torch.T
 
 
 @torch.inference_mode()
-def evaluate(vae, loader: Iterable, num_samples: int, device=None, fid=None, autocast: Optional[bool] = None, ssim: bool = False) -> dict:
+def evaluate(vae, loader: Iterable, num_samples: int, device=None, fid=None, autocast: Optional[bool] = None, ssim: bool = False, lpips=None) -> dict:
     """`loader` yields `(images, labels)` pairs (the reference's eval_data.dataloader) or bare image batches, images [B, 3, H, W] in [-1, 1];
     `num_samples` is the size of the whole evaluation set (eval_data.num_samples).  Every rank runs its shard of the loader; the four sums are
     all-reduced like train_tokenizer.py:357.  Leaves `vae` in train mode, like the reference (:367).  Returns python floats:
     {"PSNR", "latent_mean", "latent_scale", "FID" (None without `fid`), "batches", "images"}.
     ssim=True adds "SSIM": `dmvae_amd.metrics.ssim01(x01, s01)` (evaluation/metrics.py:16-23 on the [0, 1] images; csrc/ssim.hip, f64) summed over every
-    rank's images in a fifth slot of the same accumulator and divided by `num_samples`, PSNR's convention.  Without it nothing changes."""
+    rank's images in a fifth slot of the same accumulator and divided by `num_samples`, PSNR's convention.  Without it nothing changes.
+    lpips=net (a `dmvae_amd.models.lpips_alex.LPIPSAlex` with its weights loaded, on `device`) adds "LPIPS": the per-image f64 values of
+    `net(x_rec.clamp(-1, 1), images)` (evaluation/metrics.py:26-29; the reconstruction is clamped to the range the metric is defined on, as the FID path
+    clamps before it quantises) summed in one more slot of the accumulator, all-reduced with it and divided by `num_samples`.  Without it nothing changes."""
     if ssim:
         from .metrics import ssim01                                 # metrics imports this module's psnr
+    i_lpips = 5 if ssim else 4
     vae.eval()
     if device is None:
         p = next(vae.parameters(), None)
@@ -49,7 +53,8 @@ def evaluate(vae, loader: Iterable, num_samples: int, device=None, fid=None, aut
     device = torch.device(device)
     if autocast is None:
         autocast = device.type == "cuda"
-    acc = torch.zeros(5 if ssim else 4, dtype=torch.float64, device=device)      # psnr sum, latent_mean sum, latent_scale sum, batches, [ssim sum] (+ images, local only)
+    # psnr sum, latent_mean sum, latent_scale sum, batches, [ssim sum], [lpips sum] (+ images, local only)
+    acc = torch.zeros(i_lpips + (lpips is not None), dtype=torch.float64, device=device)
     images = 0
     with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(autocast)):
         for sample in loader:
@@ -66,6 +71,8 @@ def evaluate(vae, loader: Iterable, num_samples: int, device=None, fid=None, aut
             acc[0] += psnr(x01, s01, reduce="sum").double()
             if ssim:
                 acc[4] += ssim01(x01, s01).sum()
+            if lpips is not None:
+                acc[i_lpips] += lpips(x_rec.float().clamp(-1, 1), sample.float(), check_range=False).sum()
             images += int(sample.shape[0])
             if fid is not None:
                 fid.update(x01, False)
@@ -78,6 +85,8 @@ def evaluate(vae, loader: Iterable, num_samples: int, device=None, fid=None, aut
     out = {"PSNR": v[0] / num_samples, "latent_mean": v[1] / nb, "latent_scale": v[2] / nb, "FID": None, "batches": int(v[3]), "images": images}
     if ssim:
         out["SSIM"] = v[4] / num_samples
+    if lpips is not None:
+        out["LPIPS"] = v[i_lpips] / num_samples
     if fid is not None:
         f = fid.compute()
         out["FID"] = float(f.item() if hasattr(f, "item") else f)

@@ -9,9 +9,12 @@ first: the value is that of `SSIM(pred.float(), gt.float())`.
 
 CPU tensors take a plain-torch f64 composition behind `DMVAE_ALLOW_STOCK=1`, like every other module (dmvae_amd/_stock.py).
 
-`LPIPS` is not built (see its message)."""
+`LPIPS(img1, img2, net_type='alex')` is `dmvae_amd.models.lpips_alex.LPIPSAlex` once a network is configured (`configure_lpips`, DMVAE_LPIPS_ALEX_WEIGHTS,
+`run_on_mi355x.py --lpips-weights=PATH`): the weight files are not part of this package, and without one it raises NotImplementedError, as do the net types
+'vgg' and 'squeeze', which are not built."""
 from __future__ import annotations
 
+import os
 from typing import Tuple
 
 import torch
@@ -19,7 +22,7 @@ import torch
 from . import _stock, ops
 from .evaluate import psnr as PSNR
 
-__all__ = ["PSNR", "SSIM", "LPIPS", "ssim01"]
+__all__ = ["PSNR", "SSIM", "LPIPS", "ssim01", "configure_lpips", "lpips_network"]
 
 _WIN, _SIGMA, _K1, _K2 = 11, 1.5, 0.01, 0.03
 
@@ -72,8 +75,54 @@ def SSIM(pred: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0) -> Tuple
     return v.float(), v.mean().float()
 
 
+_lpips_net = None                       # the configured LPIPSAlex
+_lpips_env_path = None                  # the file the environment variable's network was built from
+
+
+def configure_lpips(net_or_path):
+    """Gives `LPIPS` its network: a `dmvae_amd.models.lpips_alex.LPIPSAlex`, the path of one state_dict file (`LPIPSAlex.from_checkpoint`), a
+    (trunk_path, lin_path) pair (`LPIPSAlex.from_checkpoints`), or None to unconfigure.  Returns the network.  The weight files are not part of this package."""
+    global _lpips_net, _lpips_env_path
+    from .models.lpips_alex import LPIPSAlex
+    if net_or_path is None or isinstance(net_or_path, LPIPSAlex):
+        net = net_or_path
+    elif isinstance(net_or_path, (tuple, list)):
+        net = LPIPSAlex.from_checkpoints(*net_or_path)
+    else:
+        net = LPIPSAlex.from_checkpoint(net_or_path)
+    _lpips_net, _lpips_env_path = net, None
+    return net
+
+
+def lpips_network():
+    """The network `LPIPS` runs: the one `configure_lpips` was given, else one built (once) from the file DMVAE_LPIPS_ALEX_WEIGHTS names, else None."""
+    global _lpips_net, _lpips_env_path
+    if _lpips_net is not None and _lpips_env_path is None:
+        return _lpips_net                                            # configured explicitly
+    path = os.environ.get("DMVAE_LPIPS_ALEX_WEIGHTS", "")
+    if path != (_lpips_env_path or ""):                              # the variable appeared, moved or went away: so does what it configured
+        configure_lpips(path or None)
+        _lpips_env_path = path or None
+    return _lpips_net
+
+
+@torch.no_grad()
 def LPIPS(img1, img2, net_type="alex"):
-    """evaluation/metrics.py:26-29 builds torchmetrics' LearnedPerceptualImagePatchSimilarity, whose AlexNet backbone and linear heads are weights neither this
-    package nor the reference repo holds; `dmvae_amd.losses` / utils/lpips.py is the TRAINING loss's VGG16 LPIPS, a different network with different numbers."""
-    raise NotImplementedError("metrics.LPIPS is not built: the reference's evaluation LPIPS is torchmetrics' AlexNet network, whose weights are not part of this "
-                              "package or of the reference repo, and utils/lpips.py is the training loss's VGG16 -- not a substitute for it")
+    """evaluation/metrics.py:26-29: [T, 3, H, W] images in [-1, 1] -> torchmetrics' LearnedPerceptualImagePatchSimilarity(net_type, reduction='mean'), an f32
+    scalar on the inputs' device: the mean over the images of `LPIPSAlex.forward` (dmvae_amd/models/lpips_alex.py: the library's published definition restated
+    -- the library cannot be run where this package is developed -- on the exact-f32 convolution kernels and an f64 head; the mean is taken over the f64
+    values and rounded once).  The AlexNet backbone and the linear heads are weights neither this package nor the reference repo holds: name them with
+    `configure_lpips`, DMVAE_LPIPS_ALEX_WEIGHTS or `run_on_mi355x.py --lpips-weights=PATH`.  `dmvae_amd.losses` / utils/lpips.py is the TRAINING loss's VGG16
+    LPIPS, a different network with different numbers."""
+    if net_type in ("vgg", "squeeze"):
+        raise NotImplementedError(f"metrics.LPIPS: net_type {net_type!r} is not built (only 'alex', the reference's default, is)")
+    if net_type != "alex":
+        raise ValueError(f"metrics.LPIPS: net_type must be 'alex', 'vgg' or 'squeeze', got {net_type!r}")
+    net = lpips_network()
+    if net is None:
+        raise NotImplementedError("metrics.LPIPS has no network: the reference's evaluation LPIPS is torchmetrics' AlexNet network, whose weights are not part of "
+                                  "this package or of the reference repo (configure_lpips(path), DMVAE_LPIPS_ALEX_WEIGHTS or --lpips-weights=PATH names "
+                                  "them), and utils/lpips.py is the training loss's VGG16 -- not a substitute for it")
+    if torch.is_tensor(img1) and next(net.parameters()).device != img1.device:
+        net.to(img1.device)
+    return net(img1, img2).mean().float()

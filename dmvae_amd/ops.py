@@ -2369,7 +2369,7 @@ POOL_MAX_S2, POOL_MAX_S1P1, POOL_AVG_S1P1 = 0, 1, 2
 def pack_conv_weight_f32(w: torch.Tensor) -> torch.Tensor:
     """f32 [cout, cin, kh, kw] (any device) -> the operand of `conv2d_f32`, f32 [chunks, cout, 16] (include/dmvae_hip.h: dmvae_conv2d_f32_fwd): K in the
     order (ky, kx, ci) cut into chunks of 16, each chunk stored as its 4 x 4 transpose.  cin == 3: every tap padded to 4 channels and the taps to a multiple
-    of 4, with zeros.  A permutation (and zeros): the values keep the checkpoint's bits."""
+    of 4, with zeros (3 x 3: 9 taps -> 3 chunks; AlexNet's 11 x 11: 121 taps -> 31 chunks).  A permutation (and zeros): the values keep the checkpoint's bits."""
     if w.dtype != f32 or w.dim() != 4:
         raise TypeError(f"w: expected a 4-D float32 [cout, cin, kh, kw], got {w.dtype} {tuple(w.shape)}")
     cout, cin, kh, kw = w.shape
@@ -2400,7 +2400,7 @@ def conv2d_f32(x: torch.Tensor, w_packed: torch.Tensor, kernel: Tuple[int, int],
                c_offset: int = 0) -> torch.Tensor:
     """x [B, H, W, cin] f32 (NHWC), w_packed from `pack_conv_weight_f32` -> act(conv(x, w) * scale + shift) in exact f32 (one k-ordered fma chain per
     output, bit-identical whatever the batch; include/dmvae_hip.h: dmvae_conv2d_f32_fwd), written into channels [c_offset, c_offset + cout) of `out`
-    [B, Ho, Wo, pitch] (default: a new [B, Ho, Wo, cout]), which is returned.  The forms the library builds are the Inception network's; others raise."""
+    [B, Ho, Wo, pitch] (default: a new [B, Ho, Wo, cout]), which is returned.  The forms the library builds are the Inception network's and, for cin 3, AlexNet's (11, 11) stride 4 padding (2, 2); others raise."""
     x = _req(x, f32, "x")
     w_packed = _req(w_packed, f32, "w_packed")
     if x.dim() != 4 or x.numel() == 0:
@@ -2464,6 +2464,50 @@ def inception_input(x: torch.Tensor) -> torch.Tensor:
     b, _, h, w_ = x.shape
     out = torch.empty(b, h, w_, 3, dtype=f32, device=x.device)
     check(_lib.lib().dmvae_inception_input(x.data_ptr(), int(x.dtype == torch.uint8), out.data_ptr(), b, h, w_, _stream()), "inception_input")
+    return out
+
+
+# ---- the evaluation LPIPS' input pass and head (csrc/lpips_eval.hip) ---------------------------------
+def lpips_input(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
+    """img1, img2 [B, 3, H, W] (NCHW) f32 or bf16 (one dtype; bf16 is widened exactly) -> f32 [2 B, H, W, 3] (NHWC): rows 0 .. B are img1, rows B .. 2 B are
+    img2, every value (x - shift) / scale, the library's ScalingLayer in f32 bit for bit (include/dmvae_hip.h: dmvae_lpips_input)."""
+    img1 = _req(img1, bf16 if img1.dtype == bf16 else f32, "img1")
+    img2 = _req(img2, img1.dtype, "img2")
+    if img1.dim() != 4 or img1.shape[1] != 3 or img1.numel() == 0:
+        raise ValueError(f"img1: expected a non-empty [B, 3, H, W], got {tuple(img1.shape)}")
+    if img2.shape != img1.shape or img2.device != img1.device:
+        raise ValueError(f"img2: expected {tuple(img1.shape)} on {img1.device}, got {tuple(img2.shape)} on {img2.device}")
+    b, _, h, w_ = img1.shape
+    out = torch.empty(2 * b, h, w_, 3, dtype=f32, device=img1.device)
+    check(_lib.lib().dmvae_lpips_input(img1.data_ptr(), img2.data_ptr(), int(img1.dtype == bf16), out.data_ptr(), b, h, w_, _stream()), "lpips_input")
+    return out
+
+
+def lpips_head(f: torch.Tensor, lin: torch.Tensor, eps: float = 1e-8, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """f [2 P, H, W, C] f32 (NHWC; image i is paired with image P + i), lin [C] f32 -> f64 [P]: one LPIPS level,
+    mean over the pixels of sum_c lin[c] (n1[c] - n2[c])^2 with n = f / sqrt(eps + sum_c f[c]^2), in f64 with fixed-order sums (include/dmvae_hip.h:
+    dmvae_lpips_head).  `out`: a contiguous f64 [P] to write into; accumulate=True adds the level's value to it instead."""
+    f = _req(f, f32, "f")
+    lin = _req(lin, f32, "lin")
+    if f.dim() != 4 or f.numel() == 0 or f.shape[0] % 2:
+        raise ValueError(f"f: expected a non-empty [2 P, H, W, C], got {tuple(f.shape)}")
+    n2, h, w_, c = f.shape
+    pairs = n2 // 2
+    if tuple(lin.shape) != (c,) or lin.device != f.device:
+        raise ValueError(f"lin: expected [{c}] on {f.device}, got {tuple(lin.shape)} on {lin.device}")
+    if f.data_ptr() % 16 or lin.data_ptr() % 16:
+        raise ValueError("lpips_head: f and lin must be 16-byte aligned")
+    if out is None:
+        if accumulate:
+            raise ValueError("lpips_head: accumulate without out")
+        out = torch.empty(pairs, dtype=torch.float64, device=f.device)
+    elif tuple(_req(out, torch.float64, "out").shape) != (pairs,) or out.device != f.device:
+        raise ValueError(f"lpips_head: out must be [{pairs}] on {f.device}, got {tuple(out.shape)} on {out.device}")
+    lib = _lib.lib()
+    nbytes = lib.dmvae_lpips_head_workspace(pairs, h, w_, c)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=f.device)
+    check(lib.dmvae_lpips_head(f.data_ptr(), lin.data_ptr(), pairs, h, w_, c, float(eps), int(bool(accumulate)), ws.data_ptr(), out.data_ptr(), _stream()),
+          "lpips_head")
     return out
 
 

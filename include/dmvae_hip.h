@@ -1174,7 +1174,8 @@ int dmvae_kid_mmd2(const void* x, size_t n1, size_t ldx, const void* y, size_t n
  * w_packed f32 [chunks][cout][16]: K cut into chunks of 16 -- cin % 16 == 0: chunk = (tap, 16 channels), chunks = kh kw cin / 16; cin == 3: chunk = 4 taps x
  * {3 channels, 0}, chunks = ceil(kh kw / 4), missing taps zero -- and inside a chunk position 4 q + s holds k = 4 s + q (the 4 x 4 transpose: lane group q's
  * ds_read_b128).  The values are the checkpoint's bits.  Forms (kh, kw) / stride / (pad_h, pad_w): (1,1)/1/(0,0); (3,3)/1 or 2/(0,0); (3,3)/1/(1,1);
- * (5,5)/1/(2,2); (1,7)/1/(0,3); (7,1)/1/(3,0); (1,3)/1/(0,1); (3,1)/1/(1,0).  cin == 3 or cin % 16 == 0; cout % 16 == 0; out_c_offset % 4 == 0,
+ * (5,5)/1/(2,2); (1,7)/1/(0,3); (7,1)/1/(3,0); (1,3)/1/(0,1); (3,1)/1/(1,0); and, for cin == 3 only, (11,11)/4/(2,2) (121 taps in 31 chunks, the last one
+ * tap: the first layer of the evaluation LPIPS' AlexNet, evaluation/metrics.py:26-29; a bias is scale = NULL, shift = bias).  cin == 3 or cin % 16 == 0; cout % 16 == 0; out_c_offset % 4 == 0,
  * out_c_pitch % 4 == 0, out_c_offset + cout <= out_c_pitch; any batch, h, w (h, w <= 32768) no smaller than the kernel.  Anything else, or a NULL x /
  * w_packed / y, returns -22 before any launch.  Nothing outside x, w_packed, scale, shift is read.  A Linear is the (1,1) form at h = w = 1.
  * Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209 (the Inception network both run their images through). */
@@ -1192,6 +1193,31 @@ int dmvae_global_avgpool_f32(const float* x, float* y, int batch, int h, int w, 
  * uint8 image); else f32, copied (an input that is already normalised).  -22 before any launch for a NULL pointer or a size below 1.
  * Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209. */
 int dmvae_inception_input(const void* x, int is_u8, float* y, int batch, int h, int w, dmvae_stream_t stream);
+
+/* ---- the evaluation LPIPS (AlexNet): input pass and head (csrc/lpips_eval.hip; dmvae_amd/models/lpips_alex.py) --------------------------------- */
+
+/* y [2 batch][h][w][3] f32 (NHWC) from x1 and x2, both [batch][3][h][w] (NCHW; is_bf16 != 0: bf16, widened exactly; else f32): rows 0 .. batch are x1, rows
+ * batch .. 2 batch are x2, y = (x - shift[ch]) / scale[ch] with shift (-.030, -.088, -.188) and scale (.458, .448, .450) as f32: the ScalingLayer of
+ * torchmetrics' LearnedPerceptualImagePatchSimilarity restated from its published form (the library cannot be run where this package is developed), one f32
+ * subtraction and one IEEE f32 division, nothing contracted -- the bits of the torch expression on f32 tensors.  -22 before any launch for a NULL pointer or a
+ * size below 1.  Reference: evaluation/metrics.py:26-29. */
+int dmvae_lpips_input(const void* x1, const void* x2, int is_bf16, float* y, int batch, int h, int w, dmvae_stream_t stream);
+/* Bytes of dmvae_lpips_head's workspace: one f64 partial per (pair, workgroup), pairs * nb * 8 with nb = ceil(h w / ppb), ppb = gpb * max(1, 32768 / (8 c)
+ * / gpb) pixels per workgroup, gpb = 256 / L, L = min(64, the power of two >= c / 4); 0 where dmvae_lpips_head would refuse (pairs, h, w, c).  No GPU.
+ * Reference: evaluation/metrics.py:26-29. */
+size_t dmvae_lpips_head_workspace(size_t pairs, int h, int w, int c);
+/* One level of the LPIPS head: f [2 pairs][h][w][c] f32 (NHWC; image i is paired with image pairs + i), lin [c] f32 (the level's 1 x 1 "lin" weights, no
+ * bias) ->   v[i] = (1 / (h w)) sum_{pixels} sum_c lin[c] (n1[c] - n2[c])^2,   n = f * (1 / sqrt(eps + sum_c f[c]^2))   per pixel,
+ * out[i] = v[i], or with accumulate != 0 out[i] = out[i] + v[i] (one addition: five calls build the network's value in level order).  Every element is
+ * widened to f64 on load and everything after that is f64; nothing normalised is written.  The sums over channels, over pixels and over the workgroup
+ * partials (workspace) each run in an order that is a function of (h, w, c) alone, no atomics: a pair's value has the same bits alone, at any position of any
+ * batch and on every run.  The difference is formed and then squared (no contraction): swapped halves give the same bits, identical halves exactly 0.0, and a
+ * pixel whose channels are all zero on both sides adds 0 (eps > 0 is required).  pairs >= 1, 1 <= h, w <= 32768, c % 4 == 0 and 4 <= c <= 1024,
+ * pairs * nb <= 2^31 - 1 (one launch), eps finite and positive; anything else, or a NULL pointer, returns -22 before any launch.  Nothing outside f's
+ * 2 pairs h w c elements and lin's c is read; workspace (dmvae_lpips_head_workspace bytes) and out [pairs] f64 are what is written.  The definition is
+ * restated from the library's published form; the library cannot be run where this package is developed.  Reference: evaluation/metrics.py:26-29. */
+int dmvae_lpips_head(const float* f, const float* lin, size_t pairs, int h, int w, int c, double eps, int accumulate, void* workspace, double* out,
+                     dmvae_stream_t stream);
 
 #ifdef __cplusplus
 }

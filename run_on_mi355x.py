@@ -8,6 +8,7 @@
     python run_on_mi355x.py --hip-optim /path/to/dmvae/train_tokenizer.py ...                          (or DMVAE_HIP_OPTIM=1)
     python run_on_mi355x.py --hip-fid /path/to/dmvae/train_tokenizer.py ...                            (or DMVAE_HIP_FID=1)
     python run_on_mi355x.py --hip-metrics /path/to/dmvae/script.py ...                                 (or DMVAE_HIP_METRICS=1)
+    python run_on_mi355x.py --lpips-weights=/path/to/lpips_alex.pth /path/to/dmvae/script.py ...       (implies --hip-metrics)
 
 The reference's drivers import their model code by module path (`from models.vae import VAE`, `from utils.lpips import LPIPS`,
 `from diffusion.lightningdit.lightningdit import LightningDiT_models`, `from diffusion.transport import create_transport`; train_tokenizer.py:10-17,
@@ -34,7 +35,9 @@ only) builds this build's `InceptionV3Compat` from that file: the network on the
 
 `evaluation.metrics` (`PSNR`, `SSIM`, `LPIPS`) is an opt-in too: `--hip-metrics`, DMVAE_HIP_METRICS=1 or `install_shadow(ref, metrics=True)` registers
 `dmvae_amd.metrics` under that path: `SSIM` on this build's f64 kernel with no torchmetrics import, `PSNR` unchanged, `LPIPS` a NotImplementedError (its AlexNet
-weights are not here).  Without the opt-in the reference's file keeps serving it.
+weights are not here) -- unless a weight file is named: `--lpips-weights=/path/to/state_dict.pth` (implies --hip-metrics), DMVAE_LPIPS_ALEX_WEIGHTS or
+`install_shadow(ref, metrics=True, lpips_weights=path)` hands it to `dmvae_amd.metrics.configure_lpips`, and `LPIPS` is then this build's
+`dmvae_amd.models.lpips_alex.LPIPSAlex` (net_type 'alex' only).  Without the opt-in the reference's file keeps serving it.
 
 The GVP / VP paths of `diffusion.transport` are off in the mirror by default (`dmvae_amd.transport.enable_all_paths`).  Running a script turns them on -- the
 script's own `--path_type` is the selection --; `--check` and a bare `install_shadow(ref)` leave the switch alone (`install_shadow(ref, all_paths=True)` asks)."""
@@ -84,7 +87,7 @@ def install_optim() -> dict:
 
 
 def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bool = False, all_paths: bool = False, fid: bool = False,
-                   metrics: bool = False, inception_weights: str | None = None) -> dict:
+                   metrics: bool = False, inception_weights: str | None = None, lpips_weights: str | None = None) -> dict:
     """Register the mirrors; returns {shadowed module path: module}.  `ref_dir`: root of the reference checkout (None: only the shadowed modules resolve).
     dinodisc: also shadow models.dinodisc / models.DinoDisc with this build's (default: the reference's own file serves them).
     optim: also replace torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (`install_optim`; not part of the returned dict).
@@ -92,9 +95,13 @@ def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bo
     fid: also shadow evaluation.fid with this build's `dmvae_amd.fid` (default: the reference's own file serves it).
     metrics: also shadow evaluation.metrics with this build's `dmvae_amd.metrics` (default: the reference's own file serves it).
     inception_weights (with fid): a state_dict file of torch-fidelity's Inception network; evaluation.fid becomes
-    `dmvae_amd.models.inception.fid_module(path)`, whose `FID(feature=2048)` runs this build's network instead of asking torchmetrics for one."""
+    `dmvae_amd.models.inception.fid_module(path)`, whose `FID(feature=2048)` runs this build's network instead of asking torchmetrics for one.
+    lpips_weights (with metrics): a state_dict file of the evaluation LPIPS' AlexNet trunk and lin heads (`LPIPSAlex.from_checkpoint`); it is loaded here and
+    handed to `dmvae_amd.metrics.configure_lpips`, so that evaluation.metrics.LPIPS computes instead of raising."""
     if inception_weights and not fid:
         raise ValueError("install_shadow: inception_weights needs fid=True")
+    if lpips_weights and not metrics:
+        raise ValueError("install_shadow: lpips_weights needs metrics=True")
     out = {}
     shadows = dict(SHADOWS)
     if dinodisc:
@@ -110,6 +117,8 @@ def install_shadow(ref_dir: str | None = None, dinodisc: bool = False, optim: bo
         mod = importlib.import_module(target)
         if path == "evaluation.fid" and inception_weights:
             mod = importlib.import_module("dmvae_amd.models.inception").fid_module(inception_weights)
+        if path == "evaluation.metrics" and lpips_weights:
+            mod.configure_lpips(lpips_weights)
         sys.modules[path] = mod
         setattr(sys.modules[".".join(parts[:-1])], parts[-1], mod)
         out[path] = mod
@@ -142,10 +151,12 @@ def main(argv) -> int:
     hip_optim = importlib.import_module("dmvae_amd.optim").requested()      # DMVAE_HIP_OPTIM=1
     hip_fid = os.environ.get("DMVAE_HIP_FID", "0") not in ("", "0")
     hip_metrics = os.environ.get("DMVAE_HIP_METRICS", "0") not in ("", "0")
-    weights = None
-    while argv and (argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid", "--hip-metrics") or argv[0].startswith("--inception-weights=")):
+    weights = lpips_weights = None
+    while argv and (argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid", "--hip-metrics") or argv[0].startswith(("--inception-weights=", "--lpips-weights="))):
         if argv[0].startswith("--inception-weights="):
             weights, hip_fid = argv[0].split("=", 1)[1], True
+        elif argv[0].startswith("--lpips-weights="):
+            lpips_weights, hip_metrics = argv[0].split("=", 1)[1], True
         elif argv[0] == "--hip-dinodisc":
             hip_dinodisc = True
         elif argv[0] == "--hip-fid":
@@ -160,7 +171,8 @@ def main(argv) -> int:
         return 0
     if argv[0] == "--check":
         ref = argv[1] if len(argv) > 1 else None
-        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid, metrics=hip_metrics, inception_weights=weights).items():
+        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid, metrics=hip_metrics, inception_weights=weights,
+                                         lpips_weights=lpips_weights).items():
             print(f"{path:40s} -> {mod.__name__}")
         if hip_optim:
             for path, obj in install_optim().items():
@@ -168,7 +180,8 @@ def main(argv) -> int:
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid, metrics=hip_metrics, inception_weights=weights)      # the script's --path_type selects
+    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid, metrics=hip_metrics, inception_weights=weights,
+                   lpips_weights=lpips_weights)      # the script's --path_type selects
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])
