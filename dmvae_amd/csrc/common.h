@@ -90,6 +90,33 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// ---- the f64 sums of the evaluation kernels (ssim, lpips_eval, fidelity, manifold; the butterfly also parity_dit, diffaug) ------------------------------
+// These kernels promise the same bits on every run, alone or in any batch; that promise IS the order of the additions below.  Change none of it.
+//
+// One wave (all 64 lanes active): the xor butterfly at distances 32, 16, 8, 4, 2, 1 -- step o replaces every lane's v by v + (the v of lane ^ o).  The two
+// lanes of a pair add the same two values (a + b and b + a: the same bits), so after the last step every lane holds the sum of one fixed binary tree.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// One workgroup of exactly 256 threads, every thread calls: the butterfly per wave, lane 0 of wave w stores to wsum[w], ONE barrier, then
+// ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3] in every thread: every thread gets the sum.  (Not (w0 + w1) + (w2 + w3): parity_dit.hip::block_sum_d_waves and
+// diffaug.hip add the waves that way, parity.hip and sampler.hip through LDS trees; those are other bits and other functions.)  There is no barrier after
+// the reads: a caller that writes wsum[4] again -- a second call on the same array -- puts a __syncthreads() between the two.
+__device__ __forceinline__ double block_sum_f64(double v, double* wsum) {
+  v = wave_sum_f64(v);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+// One owner's n partial sums, 256 threads: thread t adds src[t], src[t + 256], ... in ascending order onto 0.0, then block_sum_f64 (and its rule for wsum).
+__device__ __forceinline__ double sum_partials_f64(const double* __restrict__ src, size_t n, double* wsum) {
+  double s = 0.0;
+  for (size_t i = threadIdx.x; i < n; i += 256) s += src[i];
+  return block_sum_f64(s, wsum);
+}
+
 __device__ __forceinline__ float bf2f(bf16 v) { return (float)v; }
 // v_rcp_f32 (1 ulp), not an IEEE division: `1.0f / y` compiles to v_div_scale x2 + v_rcp + four FMAs + v_div_fmas + v_div_fixup -- ten instructions per element in
 // kernels (GroupNorm backward: 23 of ~37 VALU instructions per element were the two divisions' sequences) whose results are rounded to bf16 anyway.

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ s
     acc += (double)s;
   }
   __shared__ double red[4];
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  acc = wave_sum_f64(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) part[(size_t)b * RED_CH + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);

@@ -18,7 +18,7 @@
 //   marginal_kernel  one workgroup of 16 waves per (split, 64 classes): wave w sums p over the split's positions j0 + w, j0 + w + 16, ... in ascending order
 //                    (a 256-B run of a row per wave and position), the 16 partial sums are added in wave order and divided by n_k.
 //   finalize_kernel  one workgroup per split: exp((1 / n_k) sum_j e_j - sum_c q log q), both sums strided over 256 threads in ascending order and combined by
-//                    the fixed tree of block_sum.  Algebraically the mean over j of sum_c p (log p - log q), the reference's per-row KL form.
+//                    the fixed tree of block_sum_f64 (common.h).  Algebraically the mean over j of sum_c p (log p - log q), the reference's per-row KL form.
 // Nothing past row n or past column `classes` of a row is read: a lane past the last class reads nothing (row_kernel) or the last class (marginal_kernel,
 // dropped).  The table's entries are NOT checked here (dmvae_amd/ops.py checks them on the device before the launch).
 #include <math.h>
@@ -62,22 +62,6 @@ __global__ __launch_bounds__(256) void resize_kernel(const uint8_t* __restrict__
   const float top = a + (bb - a) * dx;
   const float bot = cc + (d - cc) * dx;
   out[p] = ((top + (bot - top) * dy) - 128.0f) / 128.0f;
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// every thread of a 256-thread workgroup calls; every thread gets the sum; wsum may be reused after the call
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-  v = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double r = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-  __syncthreads();
-  return r;
 }
 
 __host__ __device__ inline size_t split_start(size_t k, size_t n, size_t splits) { return k * n / splits; }      // k <= splits <= n < 2^31: no overflow
@@ -142,14 +126,15 @@ __global__ __launch_bounds__(256) void finalize_kernel(const double* __restrict_
   __shared__ double wsum[4];
   for (size_t k = blockIdx.x; k < splits; k += gridDim.x) {
     const size_t j0 = split_start(k, n, splits), j1 = split_start(k + 1, n, splits);
-    double a = 0.0, b = 0.0;
-    for (size_t j = j0 + threadIdx.x; j < j1; j += 256) a += ent[j];
+    const double a = sum_partials_f64(ent + j0, j1 - j0, wsum);
+    double b = 0.0;
     for (int c = threadIdx.x; c < classes; c += 256) {
       const double q = marg[k * (size_t)classes + c];
       b += q == 0.0 ? 0.0 : q * log(q);
     }
-    a = block_sum(a, wsum);
-    b = block_sum(b, wsum);
+    __syncthreads();                       // block_sum_f64's rule: wsum is written again, every thread has read a's four wave sums
+    b = block_sum_f64(b, wsum);
+    __syncthreads();                       // the same, for the next split's first sum
     if (threadIdx.x == 0) scores[k] = exp(a / (double)(j1 - j0) - b);
   }
 }

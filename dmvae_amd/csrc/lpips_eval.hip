@@ -12,7 +12,7 @@
 // is written.  The plan is a function of (h, w, c) alone (plan_for): a group of L = min(64, pow2ceil(c / 4)) lanes owns one pixel, lane g of it the channel
 // quads g, g + L, ... (R = ceil(c / 4 / L) <= 4 float4 per side, kept in registers between the two channel sums); a workgroup of 256 threads owns
 // 256 / L pixels per iteration and `iters` iterations, about 32 KB of f per workgroup.  Orders: a lane adds its own channels ascending, the L lanes of a group
-// an xor-shuffle tree (every lane ends with the same bits), a group its pixels in iteration order, the groups of a workgroup block_sum's tree; the workgroup's
+// an xor-shuffle tree (every lane ends with the same bits), a group its pixels in iteration order, the groups of a workgroup block_sum_f64's tree (common.h); the workgroup's
 // sum goes to partial[pair * nb + block] and finalize_kernel -- one workgroup per pair -- adds the nb partials in a fixed order, divides by h w and stores or
 // (accumulate) adds to out[pair].  No atomics: an image pair's value depends on its own features and the shape alone, the same bits alone, at any position
 // of any batch, and on every run.  The difference is formed as n1 - n2 and then squared with contraction off: swapping the halves changes no bit, and
@@ -49,14 +49,6 @@ inline bool plan_for(int h, int w, int c, Plan* p) {
   const size_t ppb = (size_t)p->gpb * (size_t)p->iters;
   p->nb = (p->hw + ppb - 1) / ppb;
   return true;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* wsum) {      // every thread calls; the result is valid in thread 0
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
 template <int R>
@@ -125,17 +117,14 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ f, 
     for (int o = L >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     if (ok) acc += v;
   }
-  const double s = block_sum(gl == 0 ? acc : 0.0, wsum);
+  const double s = block_sum_f64(gl == 0 ? acc : 0.0, wsum);
   if (t == 0) partial[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void finalize_kernel(const double* __restrict__ partial, size_t nb, double count, int accumulate, double* __restrict__ out) {
 #pragma clang fp contract(off)
   __shared__ double wsum[4];
-  const double* __restrict__ src = partial + (size_t)blockIdx.x * nb;
-  double s = 0.0;
-  for (size_t i = threadIdx.x; i < nb; i += 256) s += src[i];
-  s = block_sum(s, wsum);
+  const double s = sum_partials_f64(partial + (size_t)blockIdx.x * nb, nb, wsum);
   if (threadIdx.x == 0) {
     const double v = s / count;
     out[blockIdx.x] = accumulate ? out[blockIdx.x] + v : v;

@@ -256,12 +256,6 @@ __global__ __launch_bounds__(256) void member_or_kernel(const uint8_t* __restric
   member[i] = v;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // partials [subset][which][tile row][tile column], which = 0 xx, 1 yy, 2 xy
 template <typename T>
 __global__ __launch_bounds__(256, 2) void kid_kernel(const T* __restrict__ x, size_t ldx, const T* __restrict__ y, size_t ldy, int f,
@@ -292,10 +286,8 @@ __global__ __launch_bounds__(256, 2) void kid_kernel(const T* __restrict__ x, si
       sum += (pr < m && pc < m && (which == 2 || pr != pc)) ? p : 0.0;      // positions past m and the diagonal of xx / yy add nothing
     }
   }
-  sum = wave_sum_f64(sum);
-  if (lane == 0) wsum[w] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) partials[flat] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  sum = block_sum_f64(sum, wsum);
+  if (threadIdx.x == 0) partials[flat] = sum;
 }
 
 __global__ __launch_bounds__(256) void kid_finalize_kernel(const double* __restrict__ partials, size_t m, unsigned tiles, double* __restrict__ mmd2) {
@@ -304,14 +296,8 @@ __global__ __launch_bounds__(256) void kid_finalize_kernel(const double* __restr
   const size_t s = blockIdx.x, per = (size_t)tiles * tiles;
   double tot[3];
   for (int which = 0; which < 3; which++) {
-    const double* __restrict__ p = partials + (s * 3 + which) * per;
-    double v = 0.0;
-    for (size_t i = threadIdx.x; i < per; i += 256) v += p[i];
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    tot[which] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-    __syncthreads();
+    tot[which] = sum_partials_f64(partials + (s * 3 + which) * per, per, wsum);
+    __syncthreads();                       // wsum is written again by the next sum
   }
   if (threadIdx.x == 0) {
     const double md = (double)m;

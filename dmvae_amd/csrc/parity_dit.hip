@@ -10,13 +10,8 @@
 
 namespace dmvae_parity_dit {
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ double block_sum_d_waves(double v, double* sh) {   // 256 threads; fixed order: butterfly per wave, then the four waves (parity.hip::block_sum_d_tree adds in another)
-  v = wave_sum_d(v);
+  v = wave_sum_f64(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -165,7 +160,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_fwd_kernel(const float* __res
     const float* w = which == 0 ? wq : wk;
     double s = 0.0;
     for (int d = lane; d < D; d += 64) { const double t = src[d]; s += t * t; }
-    s = wave_sum_d(s);
+    s = wave_sum_f64(s);
     const float rs = (float)(1.0 / sqrt(s / D + (double)eps));
     if (lane == 0) rstd[(size_t)which * rows + row] = rs;
     for (int d = lane; d < Dp; d += 64) {
@@ -213,7 +208,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(const float* __res
       const float xh = x[d] * rs;
       dot += (double)(dvd * w[d]) * (double)xh;
     }
-    dot = wave_sum_d(dot) / D;
+    dot = wave_sum_f64(dot) / D;
     for (int d = lane; d < D; d += 64) {
       const int dp = d ^ 1;
       const float dvd = g[d] * cosb[(size_t)n * D + d] + ((dp & 1) ? g[dp] : -g[dp]) * sinb[(size_t)n * D + dp];

@@ -45,14 +45,6 @@ __host__ __device__ inline size_t tiles_of(int h, int w) {
   return (size_t)((w - (WIN - 1) + TW - 1) / TW) * (size_t)((h - (WIN - 1) + TH - 1) / TH);
 }
 
-__device__ __forceinline__ double block_sum(double v, double* wsum) {      // every thread calls; the result is valid in thread 0
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-}
-
 __device__ __forceinline__ double ssim_value(double mp, double mt, double epp, double ett, double ept, double c1, double c2) {
 #pragma clang fp contract(off)
   const double mpp = mp * mp, mtt = mt * mt, mpt = mp * mt;
@@ -160,16 +152,13 @@ __global__ __launch_bounds__(256) void tile_kernel(const T* __restrict__ a, cons
     if (oy < h - (WIN - 1)) s = v0;
     if (oy + 1 < h - (WIN - 1)) s += v1;
   }
-  s = block_sum(s, wsum);
+  s = block_sum_f64(s, wsum);
   if (t == 0) partial[blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(256) void finalize_kernel(const double* __restrict__ partial, size_t per_image, double count, double* __restrict__ out) {
   __shared__ double wsum[4];
-  const double* __restrict__ src = partial + (size_t)blockIdx.x * per_image;
-  double s = 0.0;
-  for (size_t i = threadIdx.x; i < per_image; i += 256) s += src[i];
-  s = block_sum(s, wsum);
+  const double s = sum_partials_f64(partial + (size_t)blockIdx.x * per_image, per_image, wsum);
   if (threadIdx.x == 0) out[blockIdx.x] = s / count;
 }
 

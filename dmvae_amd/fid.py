@@ -40,6 +40,48 @@ def mean_cov(s: torch.Tensor, cov_sum: torch.Tensor, n: int) -> Tuple[torch.Tens
     return mu, (cov_sum - n * torch.outer(mu, mu)) / (n - 1)
 
 
+def check_feature_width(num, who: str) -> int:
+    """F % 16 == 0, 16 <= F <= 4096: the range of the accumulate kernel (dmvae_fid_accumulate) and of the Gram tiles (csrc/manifold.hip) -> int(num).
+    `who` names the object and its argument: "FID: the feature width", "FeatureBank: num_features"."""
+    num = int(num)
+    if num % 16 or not 16 <= num <= 4096:
+        raise ValueError(f"{who} must be a multiple of 16 in [16, 4096], got {num}")
+    return num
+
+
+def accumulate_features(features: torch.Tensor, s: torch.Tensor, c: torch.Tensor, who: str) -> int:
+    """One batch of features [B, F] (or [F]: one row) into the f64 states, s [F] += X.sum(0), c [F, F] += X^T X -> B.  f32, bf16 and f64 go in as they are,
+    anything else as f32.  GPU features need the states on their device and run `ops.fid_accumulate`; CPU features take the stock route behind
+    DMVAE_ALLOW_STOCK=1, on the states' device.  An empty batch changes nothing.  `who` is the public method the messages name."""
+    if features.dim() == 1:
+        features = features.unsqueeze(0)
+    if features.dim() != 2 or features.shape[1] != s.shape[0]:
+        raise ValueError(f"{who}: expected [B, {s.shape[0]}], got {tuple(features.shape)}")
+    if features.dtype not in (torch.float32, torch.bfloat16, torch.float64):
+        features = features.float()
+    if features.shape[0] == 0:
+        return 0
+    if features.is_cuda:
+        if features.device != s.device:
+            raise ValueError(f"{who}: features on {features.device}, states on {s.device}; move the object with .to(device)")
+        ops.fid_accumulate(features, s, c)
+    else:
+        _stock.require_opt_in(who, "CPU features")
+        x = features.double().to(s.device)
+        s += x.sum(dim=0)
+        c += x.t().mm(x)
+    return features.shape[0]
+
+
+def summed_on_host(states):
+    """A list of state tensors of one device -> the same list in f64 on the host, summed over the ranks where dmvae_amd.dist runs more than one: one flat
+    device buffer (the states themselves are left alone, so a second call counts nothing twice), one collective, one copy.  Counts are exact in f64 below 2^53."""
+    flat = torch.cat([t.to(torch.float64).reshape(-1) for t in states])
+    if dist.initialized() and dist.get_world_size() > 1:
+        dist.allreduce(flat)
+    return [part.view(t.shape) for part, t in zip(flat.cpu().split([t.numel() for t in states]), states)]
+
+
 def _stock_resize_u8(imgs: torch.Tensor, size: int) -> torch.Tensor:
     """evaluation/fid.py:61-64 as written: the CPU route."""
     if imgs.size(-1) != size or imgs.size(-2) != size:
@@ -79,10 +121,7 @@ class FID(nn.Module):
                 probe = torch.zeros(1, 3, self.eval_size, self.eval_size, dtype=torch.uint8, device=p.device if p is not None else "cpu")
                 with torch.no_grad():
                     num = feature(probe).shape[-1]
-            num = int(num)
-        if num % 16 or not 16 <= num <= 4096:
-            raise ValueError(f"FID: the feature width must be a multiple of 16 in [16, 4096] (dmvae_fid_accumulate), got {num}")
-        self.num_features = num
+        self.num_features = num = check_feature_width(num, "FID: the feature width")
         for side in _SIDES:
             self.register_buffer(f"{side}_features_sum", torch.zeros(num, dtype=torch.float64))
             self.register_buffer(f"{side}_features_cov_sum", torch.zeros(num, num, dtype=torch.float64))
@@ -104,44 +143,15 @@ class FID(nn.Module):
     @torch.no_grad()
     def update_features(self, features: torch.Tensor, real: bool) -> None:
         """features [B, F] (f32, bf16 or f64; anything else is taken as f32) into the real or the fake states, in f64."""
-        if features.dim() == 1:
-            features = features.unsqueeze(0)
-        if features.dim() != 2 or features.shape[1] != self.num_features:
-            raise ValueError(f"FID.update_features: expected [B, {self.num_features}], got {tuple(features.shape)}")
-        if features.dtype not in (torch.float32, torch.bfloat16, torch.float64):
-            features = features.float()
         side = "real" if real else "fake"
         s, c, n = (getattr(self, f"{side}_features_{k}") for k in ("sum", "cov_sum", "num_samples"))
-        if features.shape[0] == 0:
-            return
-        if features.is_cuda:
-            if not s.is_cuda:
-                raise ValueError(f"FID.update_features: features on {features.device}, states on {s.device}; move the FID object with .to(device)")
-            ops.fid_accumulate(features, s, c)
-        else:
-            _stock.require_opt_in("FID.update_features", "CPU features")
-            x = features.double().to(s.device)
-            s += x.sum(dim=0)
-            c += x.t().mm(x)
-        n += features.shape[0]
+        n += accumulate_features(features, s, c, "FID.update_features")
 
     # ---- the value ---------------------------------------------------------------------------------
     def _host_states(self):
-        """The six states, summed over the ranks where dmvae_amd.dist runs more than one, on the host: one device buffer (the states themselves are left alone,
-        so a second call does not count anything twice), one collective, one copy."""
-        parts = []
-        for side in _SIDES:
-            parts += [getattr(self, f"{side}_features_sum"), getattr(self, f"{side}_features_cov_sum").reshape(-1),
-                      getattr(self, f"{side}_features_num_samples").to(torch.float64).reshape(1)]      # counts are exact in f64 below 2^53
-        flat = torch.cat(parts)
-        if dist.initialized() and dist.get_world_size() > 1:
-            dist.allreduce(flat)
-        flat = flat.cpu()
-        f, out, o = self.num_features, {}, 0
-        for side in _SIDES:
-            out[side] = (flat[o:o + f], flat[o + f:o + f + f * f].view(f, f), int(flat[o + f + f * f].item()))
-            o += f + f * f + 1
-        return out
+        """side -> (sum, cov_sum, count) of the six states as `summed_on_host` returns them."""
+        host = summed_on_host([getattr(self, f"{side}_features_{k}") for side in _SIDES for k in ("sum", "cov_sum", "num_samples")])
+        return {side: (host[3 * i], host[3 * i + 1], int(host[3 * i + 2].item())) for i, side in enumerate(_SIDES)}
 
     def compute(self) -> torch.Tensor:
         """-> 0-d f64 tensor on the host.  RuntimeError below two samples on either side, as torchmetrics raises."""

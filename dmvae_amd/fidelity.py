@@ -32,7 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import _stock, dist, ops
-from .fid import frechet_distance, mean_cov
+from .fid import accumulate_features, check_feature_width, frechet_distance, mean_cov, summed_on_host
 
 __all__ = ["FeatureBank", "FidelityMetrics", "InceptionScore", "kid_subset_tables", "row_order"]
 
@@ -80,6 +80,83 @@ def _stock_inception_score(logits: torch.Tensor, order: torch.Tensor, splits: in
     return torch.stack(out)
 
 
+class _RowBank:
+    """The f32 rows of every batch seen so far, [N, width] on the device of the first batch, with each row's global image index (int64 [N]): a pair of
+    buffers that doubles when full.  What `InceptionScore` keeps of the logits and `FeatureBank` of the features; `what` is their name for the rows.
+    No host synchronisation in `update`."""
+
+    def __init__(self, width: int, what: str):
+        self.width, self._what = int(width), what
+        self.reset()
+
+    def reset(self) -> None:
+        self._rows: Optional[torch.Tensor] = None
+        self._index: Optional[torch.Tensor] = None
+        self._n = 0
+
+    def __len__(self) -> int:
+        return self._n
+
+    def _apply(self, fn) -> None:
+        """The device `FidelityMetrics.to(...)` moves its buffers to, for the rows; their dtypes stay f32 / int64 whatever else `fn` converts."""
+        if self._rows is not None:
+            dev = fn(self._rows[:0]).device
+            self._rows, self._index = self._rows.to(dev), self._index.to(dev)
+
+    @property
+    def device(self) -> Optional[torch.device]:
+        return None if self._rows is None else self._rows.device
+
+    @property
+    def rows(self) -> torch.Tensor:
+        """f32 [N, width]: the rows in arrival order (a view of the buffer)."""
+        return torch.empty(0, self.width) if self._rows is None else self._rows[:self._n]
+
+    @property
+    def index(self) -> torch.Tensor:
+        return torch.empty(0, dtype=torch.int64) if self._index is None else self._index[:self._n]
+
+    @torch.no_grad()
+    def update(self, rows: torch.Tensor, index: Optional[torch.Tensor], who: str) -> None:
+        """rows [B, width] (stored as f32); index: int64 [B], each row's global image index (default: arrival order, N .. N + B - 1).  `who`: the public
+        method the messages name."""
+        if rows.dim() != 2 or rows.shape[1] != self.width:
+            raise ValueError(f"{who}: expected [B, {self.width}], got {tuple(rows.shape)}")
+        b = rows.shape[0]
+        if b == 0:
+            return
+        if not rows.is_cuda:
+            _stock.require_opt_in(who, f"CPU {self._what}")
+        dev = rows.device
+        if index is None:
+            index = torch.arange(self._n, self._n + b, dtype=torch.int64, device=dev)
+        index = torch.as_tensor(index).to(dev, torch.int64).reshape(-1)
+        if index.numel() != b:
+            raise ValueError(f"{who}: {index.numel()} indices for {b} rows")
+        if self._rows is not None and self._rows.device != dev:
+            raise ValueError(f"{who}: {self._what} on {dev}, earlier rows on {self._rows.device}")
+        if self._rows is None or self._n + b > self._rows.shape[0]:
+            cap = max(self._n + b, 2 * (0 if self._rows is None else self._rows.shape[0]), 64)
+            grown = torch.empty(cap, self.width, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int64, device=dev)
+            if self._n:
+                grown[0][:self._n].copy_(self._rows[:self._n])
+                grown[1][:self._n].copy_(self._index[:self._n])
+            self._rows, self._index = grown
+        self._rows[self._n:self._n + b].copy_(rows)
+        self._index[self._n:self._n + b].copy_(index)
+        self._n += b
+
+    def gathered(self, skip: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(rows, index) of every rank, rank-major, where dmvae_amd.dist runs more than one (equal counts per rank, as sample_50k.py:137 asserts); `skip`:
+        this rank's rows as they are."""
+        rows, index = self.rows, self.index
+        if not skip and dist.initialized() and dist.get_world_size() > 1:
+            world = dist.get_world_size()
+            rows = dist.all_gather_into(torch.empty(world * self._n, self.width, dtype=torch.float32, device=rows.device), rows)
+            index = dist.all_gather_into(torch.empty(world * self._n, dtype=torch.int64, device=index.device), index)
+        return rows, index
+
+
 class InceptionScore:
     """The logits of every image seen so far, f32 [N, num_classes] on the device of the first batch (a buffer that doubles when full: 50 000 x 1008 f32 are
     200 MB) with each row's global image index, and the Inception Score of their splits on the HIP kernel.  No host synchronisation before `scores`."""
@@ -88,67 +165,31 @@ class InceptionScore:
         if not 2 <= int(num_classes) <= 65536:
             raise ValueError(f"InceptionScore: num_classes must lie in [2, 65536] (dmvae_inception_score), got {num_classes}")
         self.num_classes = int(num_classes)
-        self.reset()
+        self._bank = _RowBank(self.num_classes, "logits")
 
     def reset(self) -> None:
-        self._logits: Optional[torch.Tensor] = None
-        self._index: Optional[torch.Tensor] = None
-        self._n = 0
+        self._bank.reset()
 
     def __len__(self) -> int:
-        return self._n
+        return len(self._bank)
 
     @property
     def logits(self) -> torch.Tensor:
         """f32 [N, num_classes]: the rows in arrival order (a view of the buffer)."""
-        return torch.empty(0, self.num_classes) if self._logits is None else self._logits[:self._n]
+        return self._bank.rows
 
     @property
     def index(self) -> torch.Tensor:
-        return torch.empty(0, dtype=torch.int64) if self._index is None else self._index[:self._n]
+        return self._bank.index
 
-    @torch.no_grad()
     def update_logits(self, logits: torch.Tensor, index: Optional[torch.Tensor] = None) -> None:
         """logits [B, num_classes] (stored as f32); index: int64 [B], each row's global image index (default: arrival order, N .. N + B - 1)."""
-        if logits.dim() != 2 or logits.shape[1] != self.num_classes:
-            raise ValueError(f"InceptionScore.update_logits: expected [B, {self.num_classes}], got {tuple(logits.shape)}")
-        b = logits.shape[0]
-        if b == 0:
-            return
-        if not logits.is_cuda:
-            _stock.require_opt_in("InceptionScore.update_logits", "CPU logits")
-        dev = logits.device
-        if index is None:
-            index = torch.arange(self._n, self._n + b, dtype=torch.int64, device=dev)
-        index = torch.as_tensor(index).to(dev, torch.int64).reshape(-1)
-        if index.numel() != b:
-            raise ValueError(f"InceptionScore.update_logits: {index.numel()} indices for {b} rows")
-        if self._logits is not None and self._logits.device != dev:
-            raise ValueError(f"InceptionScore.update_logits: logits on {dev}, earlier rows on {self._logits.device}")
-        if self._logits is None or self._n + b > self._logits.shape[0]:
-            cap = max(self._n + b, 2 * (0 if self._logits is None else self._logits.shape[0]), 64)
-            grown = torch.empty(cap, self.num_classes, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int64, device=dev)
-            if self._n:
-                grown[0][:self._n].copy_(self._logits[:self._n])
-                grown[1][:self._n].copy_(self._index[:self._n])
-            self._logits, self._index = grown
-        self._logits[self._n:self._n + b].copy_(logits)
-        self._index[self._n:self._n + b].copy_(index)
-        self._n += b
-
-    def _gathered(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(logits, index) of every rank, rank-major, where dmvae_amd.dist runs more than one (equal counts per rank, as sample_50k.py:137 asserts)."""
-        logits, index = self.logits, self.index
-        if dist.initialized() and dist.get_world_size() > 1:
-            world = dist.get_world_size()
-            logits = dist.all_gather_into(torch.empty(world * self._n, self.num_classes, dtype=torch.float32, device=logits.device), logits)
-            index = dist.all_gather_into(torch.empty(world * self._n, dtype=torch.int64, device=index.device), index)
-        return logits, index
+        self._bank.update(logits, index, "InceptionScore.update_logits")
 
     @torch.no_grad()
     def scores(self, splits: int = 10, shuffle: bool = True, rng_seed: int = 0) -> torch.Tensor:
         """-> f64 [splits] on the logits' device: the score of each split of the rows in `row_order`.  The same value on every rank."""
-        logits, index = self._gathered()
+        logits, index = self._bank.gathered()
         n, splits = logits.shape[0], int(splits)
         if splits < 1 or n < splits:
             raise ValueError(f"InceptionScore.scores: {n} row(s) for {splits} split(s)")
@@ -217,7 +258,7 @@ def _stock_kid_mmd2(x: torch.Tensor, y: torch.Tensor, idx1: torch.Tensor, idx2: 
     return torch.stack(out)
 
 
-class FeatureBank:
+class FeatureBank(_RowBank):
     """The f32 features of every image seen so far, [N, num_features] on the device of the first batch (a buffer that doubles when full: 50 000 x 2048 f32
     are 410 MB), with each row's global image index: what KID and precision / recall need of either side.  No host synchronisation in `update`.
     Where dmvae_amd.dist runs more than one rank, a bank fed by `update` holds THIS RANK'S SHARD (the ranks' rows are gathered when the values are computed),
@@ -226,75 +267,31 @@ class FeatureBank:
     refused when the values are computed."""
 
     def __init__(self, num_features: int):
-        num_features = int(num_features)
-        if num_features % 16 or not 16 <= num_features <= 4096:
-            raise ValueError(f"FeatureBank: num_features must be a multiple of 16 in [16, 4096] (csrc/manifold.hip), got {num_features}")
-        self.num_features = num_features
-        self.reset()
-
-    def reset(self) -> None:
-        self._features: Optional[torch.Tensor] = None
-        self._index: Optional[torch.Tensor] = None
-        self._n = 0
-        self.is_global = False
-
-    def __len__(self) -> int:
-        return self._n
-
-    def _apply(self, fn) -> None:
-        """The device `FidelityMetrics.to(...)` moves its buffers to, for the rows; their dtypes stay f32 / int64 whatever else `fn` converts."""
-        if self._features is not None:
-            dev = fn(self._features[:0]).device
-            self._features, self._index = self._features.to(dev), self._index.to(dev)
+        super().__init__(check_feature_width(num_features, "FeatureBank: num_features"), "features")
 
     @property
-    def device(self) -> Optional[torch.device]:
-        return None if self._features is None else self._features.device
+    def num_features(self) -> int:
+        return self.width
 
     @property
     def features(self) -> torch.Tensor:
         """f32 [N, num_features]: the rows in arrival order (a view of the buffer)."""
-        return torch.empty(0, self.num_features) if self._features is None else self._features[:self._n]
+        return self.rows
 
-    @property
-    def index(self) -> torch.Tensor:
-        return torch.empty(0, dtype=torch.int64) if self._index is None else self._index[:self._n]
+    def reset(self) -> None:
+        super().reset()
+        self.is_global = False
 
-    @torch.no_grad()
     def update(self, features: torch.Tensor, index: Optional[torch.Tensor] = None) -> None:
         """features [B, num_features] (stored as f32); index: int64 [B], each row's global image index (default: arrival order, N .. N + B - 1)."""
-        if features.dim() != 2 or features.shape[1] != self.num_features:
-            raise ValueError(f"FeatureBank.update: expected [B, {self.num_features}], got {tuple(features.shape)}")
         if self.is_global:
             raise ValueError("FeatureBank.update: this bank was loaded from a file and holds the whole set on every rank; reset() it before feeding shards")
-        b = features.shape[0]
-        if b == 0:
-            return
-        if not features.is_cuda:
-            _stock.require_opt_in("FeatureBank.update", "CPU features")
-        dev = features.device
-        if index is None:
-            index = torch.arange(self._n, self._n + b, dtype=torch.int64, device=dev)
-        index = torch.as_tensor(index).to(dev, torch.int64).reshape(-1)
-        if index.numel() != b:
-            raise ValueError(f"FeatureBank.update: {index.numel()} indices for {b} rows")
-        if self._features is not None and self._features.device != dev:
-            raise ValueError(f"FeatureBank.update: features on {dev}, earlier rows on {self._features.device}")
-        if self._features is None or self._n + b > self._features.shape[0]:
-            cap = max(self._n + b, 2 * (0 if self._features is None else self._features.shape[0]), 64)
-            grown = torch.empty(cap, self.num_features, dtype=torch.float32, device=dev), torch.empty(cap, dtype=torch.int64, device=dev)
-            if self._n:
-                grown[0][:self._n].copy_(self._features[:self._n])
-                grown[1][:self._n].copy_(self._index[:self._n])
-            self._features, self._index = grown
-        self._features[self._n:self._n + b].copy_(features)
-        self._index[self._n:self._n + b].copy_(index)
-        self._n += b
+        super().update(features, index, "FeatureBank.update")
 
     def save(self, path) -> None:
         """An .npz with `features` f32 [N, num_features] and `index` int64 [N]: the WHOLE set -- every rank's rows, rank-major (a collective where
         dmvae_amd.dist runs more than one rank: every rank calls, rank 0 writes) -- which is what `load` expects."""
-        features, index = self._gathered()
+        features, index = self.gathered(self.is_global)
         if not (dist.initialized() and dist.get_world_size() > 1) or dist.get_rank() == 0:
             np.savez(path, features=features.cpu().numpy(), index=index.cpu().numpy())
 
@@ -305,25 +302,15 @@ class FeatureBank:
             features, index = np.asarray(z["features"], dtype=np.float32), np.asarray(z["index"], dtype=np.int64)
         if features.ndim != 2 or features.shape[1] != self.num_features or index.shape != (features.shape[0],):
             raise ValueError(f"FeatureBank.load: features {features.shape} / index {index.shape} do not fit {self.num_features} features")
-        dev = device if device is not None else (self._features.device if self._features is not None else "cpu")
+        dev = device if device is not None else (self.device or "cpu")
         self.reset()
         self.update(torch.from_numpy(features).to(dev), torch.from_numpy(index))
         self.is_global = True
 
-    def _gathered(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(features, index) of every rank, rank-major, where dmvae_amd.dist runs more than one (equal counts per rank, as sample_50k.py:137 asserts); a
-        bank loaded from a file already holds them and is returned as it is."""
-        features, index = self.features, self.index
-        if not self.is_global and dist.initialized() and dist.get_world_size() > 1:
-            world = dist.get_world_size()
-            features = dist.all_gather_into(torch.empty(world * self._n, self.num_features, dtype=torch.float32, device=features.device), features)
-            index = dist.all_gather_into(torch.empty(world * self._n, dtype=torch.int64, device=index.device), index)
-        return features, index
-
     def ordered(self) -> Tuple[torch.Tensor, np.ndarray]:
         """-> (the gathered features, int64 [N] host table): position j of the sequence in ascending image index is row table[j].  An image index that
         occurs twice is refused: the same rows were fed on several ranks (or without indices on several ranks), and every radius and subset would be wrong."""
-        features, index = self._gathered()
+        features, index = self.gathered(self.is_global)       # a bank loaded from a file already holds every rank's rows
         index = index.cpu().numpy()
         order = row_order(index, shuffle=False)
         if len(order) > 1 and (np.diff(index[order]) == 0).any():
@@ -343,9 +330,7 @@ class FidelityMetrics(nn.Module):
 
     def __init__(self, extractor, *, num_features: int, num_classes: int = 1008, eval_size: int = 299, keep_features: bool = False):
         super().__init__()
-        num_features = int(num_features)
-        if num_features % 16 or not 16 <= num_features <= 4096:
-            raise ValueError(f"FidelityMetrics: num_features must be a multiple of 16 in [16, 4096] (dmvae_fid_accumulate), got {num_features}")
+        num_features = check_feature_width(num_features, "FidelityMetrics: num_features")
         if not callable(extractor):
             raise TypeError(f"extractor must be a module / callable, got {type(extractor).__name__}")
         self.extractor, self.num_features, self.eval_size = extractor, num_features, int(eval_size)
@@ -375,21 +360,24 @@ class FidelityMetrics(nn.Module):
             self.bank.reset()
 
     # ---- accumulation ------------------------------------------------------------------------------
+    def _resized(self, images: torch.Tensor, nhwc: bool, who: str) -> Optional[torch.Tensor]:
+        """uint8 images -> the extractor's f32 input [B, 3, eval_size, eval_size] (None for an empty batch): the resize kernel, or its stock form on the CPU."""
+        if images.dtype != torch.uint8 or images.dim() != 4:
+            raise TypeError(f"{who}: expected a 4-D uint8 tensor, got {images.dtype} {tuple(images.shape)}")
+        if images.shape[0] == 0:
+            return None
+        if images.is_cuda:
+            return ops.resize_tf1_bilinear(images.contiguous(), self.eval_size, nhwc)
+        _stock.require_opt_in(who, "CPU images")
+        return _stock_resize_tf1_bilinear(images, self.eval_size, nhwc)
+
     @torch.no_grad()
     def update_uint8(self, images: torch.Tensor, index: Optional[torch.Tensor] = None, nhwc: bool = True) -> None:
         """images uint8 [B, H, W, 3] (nhwc, the layout of `VAE.decode_uint8`) or [B, 3, H, W]; index: int64 [B], the images' global indices (default:
         arrival order).  Resize kernel -> extractor -> both accumulators.  No host synchronisation."""
-        if images.dtype != torch.uint8 or images.dim() != 4:
-            raise TypeError(f"FidelityMetrics.update_uint8: expected a 4-D uint8 tensor, got {images.dtype} {tuple(images.shape)}")
-        if images.shape[0] == 0:
-            return
-        if images.is_cuda:
-            x = ops.resize_tf1_bilinear(images.contiguous(), self.eval_size, nhwc)
-        else:
-            _stock.require_opt_in("FidelityMetrics.update_uint8", "CPU images")
-            x = _stock_resize_tf1_bilinear(images, self.eval_size, nhwc)
-        features, logits = self.extractor(x)
-        self.update_features(features, logits, index)
+        x = self._resized(images, nhwc, "FidelityMetrics.update_uint8")
+        if x is not None:
+            self.update_features(*self.extractor(x), index)
 
     @torch.no_grad()
     def update_features(self, features: torch.Tensor, logits: torch.Tensor, index: Optional[torch.Tensor] = None) -> None:
@@ -398,22 +386,13 @@ class FidelityMetrics(nn.Module):
                 or logits.shape[0] != features.shape[0]):
             raise ValueError(f"FidelityMetrics.update_features: expected [B, {self.num_features}] and [B, {self.isc.num_classes}], got "
                              f"{tuple(features.shape)} and {tuple(logits.shape)}")
-        if features.dtype not in (torch.float32, torch.bfloat16, torch.float64):
-            features = features.float()
-        s, c = self.features_sum, self.features_cov_sum
-        if features.device != s.device:
-            raise ValueError(f"FidelityMetrics.update_features: features on {features.device}, states on {s.device}; move the object with .to(device)")
+        if features.device != self.features_sum.device:       # stricter than accumulate_features: the logits and the bank stay where the features are
+            raise ValueError(f"FidelityMetrics.update_features: features on {features.device}, states on {self.features_sum.device}; move the object "
+                             "with .to(device)")
         self.isc.update_logits(logits, index)
-        if features.is_cuda:
-            ops.fid_accumulate(features, s, c)
-        else:
-            _stock.require_opt_in("FidelityMetrics.update_features", "CPU features")
-            x = features.double()
-            s += x.sum(dim=0)
-            c += x.t().mm(x)
+        self.num_samples += accumulate_features(features, self.features_sum, self.features_cov_sum, "FidelityMetrics.update_features")
         if self.bank is not None:
             self.bank.update(features, index)
-        self.num_samples += features.shape[0]
 
     # ---- the real side's features (KID, precision / recall) ---------------------------------------
     @torch.no_grad()
@@ -428,16 +407,9 @@ class FidelityMetrics(nn.Module):
     @torch.no_grad()
     def update_reference_uint8(self, images: torch.Tensor, index: Optional[torch.Tensor] = None, nhwc: bool = True) -> None:
         """REAL images, as `update_uint8` takes the sampled ones: resize kernel -> extractor -> `reference_bank`.  No effect on the fake side's states."""
-        if images.dtype != torch.uint8 or images.dim() != 4:
-            raise TypeError(f"FidelityMetrics.update_reference_uint8: expected a 4-D uint8 tensor, got {images.dtype} {tuple(images.shape)}")
-        if images.shape[0] == 0:
-            return
-        if images.is_cuda:
-            x = ops.resize_tf1_bilinear(images.contiguous(), self.eval_size, nhwc)
-        else:
-            _stock.require_opt_in("FidelityMetrics.update_reference_uint8", "CPU images")
-            x = _stock_resize_tf1_bilinear(images, self.eval_size, nhwc)
-        self.update_reference_features(self.extractor(x)[0], index)
+        x = self._resized(images, nhwc, "FidelityMetrics.update_reference_uint8")
+        if x is not None:
+            self.update_reference_features(self.extractor(x)[0], index)
 
     def load_reference_features(self, path) -> None:
         """An .npz written by `FeatureBank.save` (`features` [N, F], `index` [N]) as the real side, on the device of the states.  The file is the WHOLE real
@@ -481,15 +453,12 @@ class FidelityMetrics(nn.Module):
     def statistics(self) -> Tuple[torch.Tensor, torch.Tensor, int]:
         """-> (mu f64 [F], sigma f64 [F, F], n) of the images seen so far, on the host, summed over the ranks where dmvae_amd.dist runs more than one (one
         device buffer, one collective, one copy; the states themselves are left alone)."""
-        flat = torch.cat([self.features_sum, self.features_cov_sum.reshape(-1),
-                          torch.tensor([float(self.num_samples)], dtype=torch.float64, device=self.features_sum.device)])
-        if dist.initialized() and dist.get_world_size() > 1:
-            dist.allreduce(flat)
-        flat, f = flat.cpu(), self.num_features
-        n = int(flat[-1].item())
+        s, c, n = summed_on_host([self.features_sum, self.features_cov_sum,
+                                  torch.tensor(float(self.num_samples), dtype=torch.float64, device=self.features_sum.device)])
+        n = int(n.item())
         if n < 2:
             raise RuntimeError(f"FidelityMetrics.statistics: {n} sample(s); a covariance needs two")
-        return (*mean_cov(flat[:f], flat[f:f + f * f].view(f, f), n), n)
+        return (*mean_cov(s, c, n), n)
 
     def _banks(self, what: str) -> Tuple[FeatureBank, FeatureBank]:
         if self.bank is None:

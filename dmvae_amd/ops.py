@@ -2098,27 +2098,40 @@ def image_to_u8(y: torch.Tensor, channels: int, round_bf16: bool = False) -> tor
 
 
 # ---- FID (csrc/fid.hip) ---------------------------------------------------------------------------
-_FID_DTYPES = {f32: 0, bf16: 1, torch.float64: 2}
+_ROW_DTYPES = {f32: 0, bf16: 1, torch.float64: 2}       # the dtype codes of the evaluation kernels' C ABI (fid, fidelity, manifold)
+_F32_F64 = (f32, torch.float64)
+
+
+def _feature_rows(t: torch.Tensor, name: str, f: Optional[int] = None, *, dtypes=_F32_F64, width_rule: bool = True, empty_ok: bool = False, shape: str = "[n, F]"):
+    """A [n, F] GPU tensor of one of `dtypes` with unit stride along F (any row pitch >= F: a view of a wider buffer is taken as it is, anything else is
+    copied) -> (tensor, n, F, pitch).  f: the width it must have; width_rule: F a multiple of 16 in [16, 4096], the Gram tiles' range (False: the library
+    checks what it needs); empty_ok: n = 0 is left to the library."""
+    if not t.is_cuda:
+        raise _lib.DmvaeHipError(f"{name}: expected a GPU tensor; dmvae_amd has no CPU path")
+    if t.dtype not in dtypes:
+        names = [str(d).replace("torch.", "") for d in dtypes]
+        raise TypeError(f"{name}: expected {', '.join(names[:-1])} or {names[-1]}, got {t.dtype}")
+    if t.dim() != 2 or (t.numel() == 0 and not empty_ok):
+        raise ValueError(f"{name}: expected {'' if empty_ok else 'a non-empty '}{shape}, got {tuple(t.shape)}")
+    n, width = t.shape
+    if f is not None and width != f:
+        raise ValueError(f"{name}: expected {f} features, got {width}")
+    if width_rule and (width % 16 or not 16 <= width <= 4096):
+        raise ValueError(f"{name}: F must be a multiple of 16 in [16, 4096], got {width}")
+    if t.stride(1) != 1 or (n > 1 and t.stride(0) < width):
+        t = t.contiguous()
+    return t, n, width, (t.stride(0) if n > 1 else width)
 
 
 def fid_accumulate(features: torch.Tensor, sum: torch.Tensor, cov_sum: torch.Tensor) -> None:
     """In place: sum [F] += features.sum(0), cov_sum [F, F] += features^T features, f64 states, features [N, F] f32 / bf16 / f64 with unit stride along F (any
     row pitch >= F: a column slice of a wider buffer is taken as it is).  Deterministic and exactly symmetric (include/dmvae_hip.h: dmvae_fid_accumulate)."""
-    if not features.is_cuda:
-        raise _lib.DmvaeHipError("features: expected a GPU tensor; dmvae_amd has no CPU path")
-    if features.dtype not in _FID_DTYPES:
-        raise TypeError(f"features: expected float32, bfloat16 or float64, got {features.dtype}")
-    if features.dim() != 2:
-        raise ValueError(f"features: expected [N, F], got {tuple(features.shape)}")
-    n, f = features.shape
-    if features.stride(1) != 1 or (n > 1 and features.stride(0) < f):
-        features = features.contiguous()
-    ld = features.stride(0) if n > 1 else f
+    features, n, f, ld = _feature_rows(features, "features", dtypes=tuple(_ROW_DTYPES), width_rule=False, empty_ok=True, shape="[N, F]")
     _req(sum, torch.float64, "sum")
     _req(cov_sum, torch.float64, "cov_sum")
     if tuple(sum.shape) != (f,) or tuple(cov_sum.shape) != (f, f) or sum.device != features.device or cov_sum.device != features.device:
         raise ValueError(f"fid_accumulate: states must be [{f}] and [{f}, {f}] on {features.device}, got {tuple(sum.shape)} and {tuple(cov_sum.shape)}")
-    check(_lib.lib().dmvae_fid_accumulate(features.data_ptr(), _FID_DTYPES[features.dtype], n, f, ld, sum.data_ptr(), cov_sum.data_ptr(), _stream()),
+    check(_lib.lib().dmvae_fid_accumulate(features.data_ptr(), _ROW_DTYPES[features.dtype], n, f, ld, sum.data_ptr(), cov_sum.data_ptr(), _stream()),
           "fid_accumulate")
 
 
@@ -2180,16 +2193,7 @@ def inception_score(logits: torch.Tensor, order: Optional[torch.Tensor] = None, 
     [splits]: the Inception Score of each split of the row sequence logits[order[0]], logits[order[1]], ... (order: int64 [n] on the logits' device, every row
     index in [0, n); None: the rows as they lie), everything in f64 (include/dmvae_hip.h: dmvae_inception_score).  Deterministic; a table gives the bits that
     physically reordered rows give.  The table's range is checked on the device first (one reduction, one synchronisation): the kernels trust it."""
-    if not logits.is_cuda:
-        raise _lib.DmvaeHipError("logits: expected a GPU tensor; dmvae_amd has no CPU path")
-    if logits.dtype not in _FID_DTYPES:
-        raise TypeError(f"logits: expected float32, bfloat16 or float64, got {logits.dtype}")
-    if logits.dim() != 2 or logits.numel() == 0:
-        raise ValueError(f"logits: expected a non-empty [n, classes], got {tuple(logits.shape)}")
-    n, classes = logits.shape
-    if logits.stride(1) != 1 or (n > 1 and logits.stride(0) < classes):
-        logits = logits.contiguous()
-    ld = logits.stride(0) if n > 1 else classes
+    logits, n, classes, ld = _feature_rows(logits, "logits", dtypes=tuple(_ROW_DTYPES), width_rule=False, shape="[n, classes]")
     splits = int(splits)
     if not 1 <= splits <= n:
         raise ValueError(f"splits: expected 1 <= splits <= n = {n}, got {splits}")
@@ -2203,33 +2207,12 @@ def inception_score(logits: torch.Tensor, order: Optional[torch.Tensor] = None, 
     lib = _lib.lib()
     ws = torch.empty(max(lib.dmvae_inception_score_workspace(n, classes, splits) // 8, 1), dtype=torch.float64, device=logits.device)
     scores = torch.empty(splits, dtype=torch.float64, device=logits.device)
-    check(lib.dmvae_inception_score(logits.data_ptr(), _FID_DTYPES[logits.dtype], n, classes, ld, _ptr(order), splits, ws.data_ptr(), scores.data_ptr(),
+    check(lib.dmvae_inception_score(logits.data_ptr(), _ROW_DTYPES[logits.dtype], n, classes, ld, _ptr(order), splits, ws.data_ptr(), scores.data_ptr(),
                                     _stream()), "inception_score")
     return scores
 
 
 # ---- precision / recall and KID (csrc/manifold.hip) ------------------------------------------------------
-_MANIFOLD_DTYPES = {f32: 0, torch.float64: 2}
-
-
-def _feature_rows(t: torch.Tensor, name: str, f: Optional[int] = None):
-    """A [n, F] f32 / f64 GPU tensor with unit stride along F (any row pitch >= F: a view of a wider buffer is taken as it is) -> (tensor, n, F, pitch)."""
-    if not t.is_cuda:
-        raise _lib.DmvaeHipError(f"{name}: expected a GPU tensor; dmvae_amd has no CPU path")
-    if t.dtype not in _MANIFOLD_DTYPES:
-        raise TypeError(f"{name}: expected float32 or float64, got {t.dtype}")
-    if t.dim() != 2 or t.numel() == 0:
-        raise ValueError(f"{name}: expected a non-empty [n, F], got {tuple(t.shape)}")
-    n, width = t.shape
-    if f is not None and width != f:
-        raise ValueError(f"{name}: expected {f} features, got {width}")
-    if width % 16 or not 16 <= width <= 4096:
-        raise ValueError(f"{name}: F must be a multiple of 16 in [16, 4096], got {width}")
-    if t.stride(1) != 1 or (n > 1 and t.stride(0) < width):
-        t = t.contiguous()
-    return t, n, width, (t.stride(0) if n > 1 else width)
-
-
 def _out_vector(out: Optional[torch.Tensor], n: int, dtype, device, name: str) -> torch.Tensor:
     if out is None:
         return torch.empty(n, dtype=dtype, device=device)
@@ -2252,7 +2235,7 @@ def knn_radius(x: torch.Tensor, k: int, out: Optional[torch.Tensor] = None) -> t
     lib = _lib.lib()
     ws = torch.empty(max(lib.dmvae_knn_radius_workspace(n) // 8, 1), dtype=torch.float64, device=x.device)
     out = _out_vector(out, n, torch.float64, x.device, "out")
-    check(lib.dmvae_knn_radius(x.data_ptr(), _MANIFOLD_DTYPES[x.dtype], n, f, ld, k, ws.data_ptr(), out.data_ptr(), _stream()), "knn_radius")
+    check(lib.dmvae_knn_radius(x.data_ptr(), _ROW_DTYPES[x.dtype], n, f, ld, k, ws.data_ptr(), out.data_ptr(), _stream()), "knn_radius")
     return out
 
 
@@ -2269,7 +2252,7 @@ def manifold_member(q: torch.Tensor, r: torch.Tensor, radius2: torch.Tensor, out
     lib = _lib.lib()
     ws = torch.empty(max(lib.dmvae_manifold_member_workspace(nq, nr) // 8, 1), dtype=torch.float64, device=q.device)
     out = _out_vector(out, nq, torch.uint8, q.device, "out")
-    check(lib.dmvae_manifold_member(q.data_ptr(), nq, ldq, r.data_ptr(), nr, ldr, _MANIFOLD_DTYPES[q.dtype], f, radius2.data_ptr(), ws.data_ptr(),
+    check(lib.dmvae_manifold_member(q.data_ptr(), nq, ldq, r.data_ptr(), nr, ldr, _ROW_DTYPES[q.dtype], f, radius2.data_ptr(), ws.data_ptr(),
                                     out.data_ptr(), _stream()), "manifold_member")
     return out
 
@@ -2299,7 +2282,7 @@ def kid_mmd2(x: torch.Tensor, y: torch.Tensor, idx1: torch.Tensor, idx2: torch.T
     lib = _lib.lib()
     ws = torch.empty(max(lib.dmvae_kid_mmd2_workspace(subsets, m) // 8, 1), dtype=torch.float64, device=x.device)
     out = _out_vector(out, subsets, torch.float64, x.device, "out")
-    check(lib.dmvae_kid_mmd2(x.data_ptr(), n1, ldx, y.data_ptr(), n2, ldy, _MANIFOLD_DTYPES[x.dtype], f, idx1.data_ptr(), idx2.data_ptr(), subsets, m, degree,
+    check(lib.dmvae_kid_mmd2(x.data_ptr(), n1, ldx, y.data_ptr(), n2, ldy, _ROW_DTYPES[x.dtype], f, idx1.data_ptr(), idx2.data_ptr(), subsets, m, degree,
                              float(1.0 / f if gamma is None else gamma), float(coef0), ws.data_ptr(), out.data_ptr(), _stream()), "kid_mmd2")
     return out
 
