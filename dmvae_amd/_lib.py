@@ -299,6 +299,9 @@ SIGNATURES = {
     "dmvae_lpips_input": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dmvae_lpips_head_workspace": (c_size_t, [c_size_t, c_int, c_int, c_int]),
     "dmvae_lpips_head": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p]),
+    # the evaluation LPIPS' VGG16 / SqueezeNet trunks: stride-2 maximum pools (csrc/inception.hip), the head with the normalisation selected (csrc/lpips_eval.hip)
+    "dmvae_maxpool2d_f32": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "dmvae_lpips_head_form": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

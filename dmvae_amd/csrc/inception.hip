@@ -23,6 +23,11 @@
 // dmvae_pool2d_f32: one thread per (output pixel, 4 channels), taps in (ky, kx) raster order, taps outside the image skipped (a maximum never sees the
 // padding; the average divides by the number of taps inside, count_include_pad=False).  dmvae_global_avgpool_f32: one thread per (image, channel), the
 // H W values added in ascending order in f64, divided in f64, rounded once.  dmvae_inception_input: one thread per output element.
+//
+// dmvae_maxpool2d_f32: the stride-2 maximum pools without padding of the evaluation LPIPS' VGG16 (2 x 2) and SqueezeNet 1.1 (3 x 3, ceil_mode) trunks
+// (dmvae_amd/models/lpips_eval.py), laid out as dmvae_pool2d_f32: one thread per (output pixel, 4 channels), float4 loads, every tap range-checked.  Those
+// trunks' convolutions are forms the conv kernel already has: for Cin = 3 the loader walks (3, 3) padding 1 (VGG's first layer) tap by tap as it does
+// (3, 3) stride 2, and a Fire module's two expands write their channel slices of one buffer through out_c_offset.
 #include <math.h>
 
 #include "common.h"
@@ -195,6 +200,35 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x, 
   *reinterpret_cast<float4*>(y + pix * (size_t)c_pitch + c_off + cc) = r;
 }
 
+// K x K maximum at stride 2 without padding (K = 2: floor, VGG16's pool; K = 3: ceil_mode, SqueezeNet 1.1's): every window starts inside the image (the host
+// sizes ho, wo so), and a window that hangs over the bottom or right edge takes the maximum of the elements that exist -- its first element always does.
+template <int K>
+__global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total, int h, int w, int c, int ho, int wo,
+                                                      int c_off, int c_pitch) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int c4 = c >> 2;
+  const int cc = (int)(i % (size_t)c4) * 4;
+  const size_t pix = i / (size_t)c4;
+  const int ox = (int)(pix % (size_t)wo), oy = (int)((pix / (size_t)wo) % (size_t)ho);
+  const size_t b = pix / ((size_t)wo * ho);
+  const float* xb = x + b * (size_t)h * w * c + cc;
+  float4 r = *reinterpret_cast<const float4*>(xb + ((size_t)(2 * oy) * w + 2 * ox) * c);
+#pragma unroll
+  for (int ky = 0; ky < K; ky++) {
+    const int iy = 2 * oy + ky;
+    if (iy >= h) continue;
+#pragma unroll
+    for (int kx = 0; kx < K; kx++) {
+      const int ix = 2 * ox + kx;
+      if (ix >= w || (ky == 0 && kx == 0)) continue;
+      const float4 v = *reinterpret_cast<const float4*>(xb + ((size_t)iy * w + ix) * c);
+      r = make_float4(v.x > r.x ? v.x : r.x, v.y > r.y ? v.y : r.y, v.z > r.z ? v.z : r.z, v.w > r.w ? v.w : r.w);
+    }
+  }
+  *reinterpret_cast<float4*>(y + pix * (size_t)c_pitch + c_off + cc) = r;
+}
+
 __global__ __launch_bounds__(256) void global_avgpool_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total, int hw, int c) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -288,6 +322,31 @@ extern "C" int dmvae_pool2d_f32(const float* x, float* y, int mode, int batch, i
   const size_t total = (size_t)batch * ho * wo * (size_t)(c / 4);
   DMVAE_CHECK_ARG((total + 255) / 256 <= GRID_MAX, "pool2d_f32: %zu outputs exceed the grid's 2^31 - 1 blocks of 256", total);
   hipLaunchKernelGGL(pool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, y, total, h, w, c, ho, wo, mode, out_c_offset, out_c_pitch);
+  DMVAE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int dmvae_maxpool2d_f32(const float* x, float* y, int batch, int h, int w, int c, int kernel, int stride, int ceil_mode, int out_c_offset,
+                                   int out_c_pitch, hipStream_t stream) {
+  using namespace dmvae_inception;
+  DMVAE_CHECK_ARG(x && y, "maxpool2d_f32: NULL pointer");
+  const bool form2 = kernel == 2 && stride == 2 && ceil_mode == 0, form3 = kernel == 3 && stride == 2 && ceil_mode == 1;
+  DMVAE_CHECK_ARG(form2 || form3, "maxpool2d_f32: kernel %d stride %d ceil_mode %d is not built: kernel 2 stride 2 ceil_mode 0; kernel 3 stride 2 ceil_mode 1",
+                  kernel, stride, ceil_mode);
+  DMVAE_CHECK_ARG(batch >= 1 && h >= 1 && w >= 1 && h <= 32768 && w <= 32768, "maxpool2d_f32: batch >= 1 and 1 <= h, w <= 32768 required, got %d x %d x %d", batch,
+                  h, w);
+  DMVAE_CHECK_ARG(h >= kernel && w >= kernel, "maxpool2d_f32: the pool has no padding and needs h, w >= %d, got %d x %d", kernel, h, w);
+  DMVAE_CHECK_ARG(c >= 4 && c % 4 == 0, "maxpool2d_f32: c must be a multiple of 4, got %d", c);
+  DMVAE_CHECK_ARG(out_c_offset >= 0 && out_c_offset % 4 == 0 && out_c_pitch % 4 == 0 && (long long)out_c_offset + c <= (long long)out_c_pitch,
+                  "maxpool2d_f32: channels [%d, %d + %d) do not fit an output of pitch %d (offset and pitch multiples of 4)", out_c_offset, out_c_offset, c,
+                  out_c_pitch);
+  const int ho = form2 ? h / 2 : (h - 2) / 2 + 1, wo = form2 ? w / 2 : (w - 2) / 2 + 1;      // ceil((h - 3) / 2) + 1 = (h - 2) / 2 + 1 for h >= 3
+  const size_t pixels = (size_t)batch * ho * wo, quads = (size_t)(c / 4);      // < 2^61; the product is formed only once it is known to fit
+  DMVAE_CHECK_ARG(pixels <= GRID_MAX * 256 / quads, "maxpool2d_f32: %zu pixels x %zu channel quads exceed the grid's 2^31 - 1 blocks of 256", pixels, quads);
+  const size_t total = pixels * quads;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (form2) hipLaunchKernelGGL(maxpool_kernel<2>, grid, dim3(256), 0, stream, x, y, total, h, w, c, ho, wo, out_c_offset, out_c_pitch);
+  else hipLaunchKernelGGL(maxpool_kernel<3>, grid, dim3(256), 0, stream, x, y, total, h, w, c, ho, wo, out_c_offset, out_c_pitch);
   DMVAE_CHECK_LAUNCH();
   return 0;
 }

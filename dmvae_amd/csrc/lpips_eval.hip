@@ -15,7 +15,9 @@
 // an xor-shuffle tree (every lane ends with the same bits), a group its pixels in iteration order, the groups of a workgroup block_sum_f64's tree (common.h); the workgroup's
 // sum goes to partial[pair * nb + block] and finalize_kernel -- one workgroup per pair -- adds the nb partials in a fixed order, divides by h w and stores or
 // (accumulate) adds to out[pair].  No atomics: an image pair's value depends on its own features and the shape alone, the same bits alone, at any position
-// of any batch, and on every run.  The difference is formed as n1 - n2 and then squared with contraction off: swapping the halves changes no bit, and
+// of any batch, and on every run.  dmvae_lpips_head_form is the same kernel with the normalisation selected: form 0 the one above (the same bits as
+// dmvae_lpips_head), form 1 n = f * (1 / (sqrt(sum_c f[c]^2) + eps)), the reference's own normalize_tensor (utils/lpips.py:156-158; the evaluation twin of
+// the training loss, dmvae_amd/models/lpips_eval.py).  The difference is formed as n1 - n2 and then squared with contraction off: swapping the halves changes no bit, and
 // identical halves give exactly 0.0.  eps > 0 is required, so a pixel whose channels are all zero on both sides gives n = 0 / sqrt(eps) = 0 and adds 0.
 //   A pixel past h w is never loaded and adds nothing; a channel quad past c / 4 (c / 4 no multiple of L) likewise.  Nothing outside f's 2 pairs h w c
 // elements and lin's c elements is read; partial[pairs * nb] and out[pairs] are all that is written.
@@ -51,7 +53,9 @@ inline bool plan_for(int h, int w, int c, Plan* p) {
   return true;
 }
 
-template <int R>
+// FORM 0: r = 1 / sqrt(eps + s) (torchmetrics' normalisation); FORM 1: r = 1 / (sqrt(s) + eps) (the reference's own normalize_tensor, utils/lpips.py:156-158).
+// The one changed operation; every load, order and sum is shared.
+template <int R, int FORM>
 __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ f, const float* __restrict__ lin, size_t pairs, size_t hw, int c, int L, int iters,
                                                    unsigned nb, double eps, double* __restrict__ partial) {
 #pragma clang fp contract(off)
@@ -101,7 +105,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ f, 
       s1 += __shfl_xor(s1, o, 64);
       s2 += __shfl_xor(s2, o, 64);
     }
-    const double r1 = 1.0 / sqrt(eps + s1), r2 = 1.0 / sqrt(eps + s2);
+    const double r1 = FORM == 0 ? 1.0 / sqrt(eps + s1) : 1.0 / (sqrt(s1) + eps), r2 = FORM == 0 ? 1.0 / sqrt(eps + s2) : 1.0 / (sqrt(s2) + eps);
     double v = 0.0;
 #pragma unroll
     for (int j = 0; j < R; j++) {
@@ -166,29 +170,48 @@ extern "C" size_t dmvae_lpips_head_workspace(size_t pairs, int h, int w, int c) 
   return pairs * p.nb * sizeof(double);
 }
 
-extern "C" int dmvae_lpips_head(const float* f, const float* lin, size_t pairs, int h, int w, int c, double eps, int accumulate, void* workspace, double* out,
-                                hipStream_t stream) {
-  using namespace dmvae_lpips_eval;
-  DMVAE_CHECK_ARG(f && lin && workspace && out, "lpips_head: NULL pointer");
-  DMVAE_CHECK_ARG(pairs >= 1 && h >= 1 && w >= 1 && h <= 32768 && w <= 32768, "lpips_head: pairs >= 1 and 1 <= h, w <= 32768 required, got %zu x %d x %d", pairs,
+namespace dmvae_lpips_eval {
+
+// dmvae_lpips_head (form 0, named "lpips_head") and dmvae_lpips_head_form: one validation, one plan, one launch sequence.
+static int head_launch(const char* name, const float* f, const float* lin, size_t pairs, int h, int w, int c, double eps, int form, int accumulate,
+                       void* workspace, double* out, hipStream_t stream) {
+  DMVAE_CHECK_ARG(f && lin && workspace && out, "%s: NULL pointer", name);
+  DMVAE_CHECK_ARG(form == 0 || form == 1, "%s: form must be 0 (f / sqrt(eps + sum f^2)) or 1 (f / (sqrt(sum f^2) + eps)), got %d", name, form);
+  DMVAE_CHECK_ARG(pairs >= 1 && h >= 1 && w >= 1 && h <= 32768 && w <= 32768, "%s: pairs >= 1 and 1 <= h, w <= 32768 required, got %zu x %d x %d", name, pairs,
                   h, w);
-  DMVAE_CHECK_ARG(c >= 4 && c % 4 == 0 && c <= C_MAX, "lpips_head: c must be a multiple of 4 in [4, %d], got %d", C_MAX, c);
-  DMVAE_CHECK_ARG(__builtin_isfinite(eps) && eps > 0.0, "lpips_head: eps must be finite and positive (an all-zero pixel is 0 / sqrt(eps)), got %g", eps);
+  DMVAE_CHECK_ARG(c >= 4 && c % 4 == 0 && c <= C_MAX, "%s: c must be a multiple of 4 in [4, %d], got %d", name, C_MAX, c);
+  DMVAE_CHECK_ARG(__builtin_isfinite(eps) && eps > 0.0, "%s: eps must be finite and positive (an all-zero pixel is 0 / sqrt(eps)), got %g", name, eps);
   Plan p;
-  DMVAE_CHECK_ARG(plan_for(h, w, c, &p), "lpips_head: no plan for %d x %d x %d", h, w, c);
-  DMVAE_CHECK_ARG(pairs <= GRID_MAX / p.nb, "lpips_head: %zu pairs x %zu workgroups exceed the grid's 2^31 - 1 blocks", pairs, p.nb);
+  DMVAE_CHECK_ARG(plan_for(h, w, c, &p), "%s: no plan for %d x %d x %d", name, h, w, c);
+  DMVAE_CHECK_ARG(pairs <= GRID_MAX / p.nb, "%s: %zu pairs x %zu workgroups exceed the grid's 2^31 - 1 blocks", name, pairs, p.nb);
   const dim3 grid((unsigned)(pairs * p.nb)), block(256);
   double* ws = (double*)workspace;
-#define DMVAE_LPIPS_HEAD(R_) hipLaunchKernelGGL(head_kernel<R_>, grid, block, 0, stream, f, lin, pairs, p.hw, c, p.L, p.iters, (unsigned)p.nb, eps, ws)
-  switch (p.R) {
-    case 1: DMVAE_LPIPS_HEAD(1); break;
-    case 2: DMVAE_LPIPS_HEAD(2); break;
-    case 3: DMVAE_LPIPS_HEAD(3); break;
-    default: DMVAE_LPIPS_HEAD(4); break;
+#define DMVAE_LPIPS_HEAD(R_, F_) \
+  hipLaunchKernelGGL((head_kernel<R_, F_>), grid, block, 0, stream, f, lin, pairs, p.hw, c, p.L, p.iters, (unsigned)p.nb, eps, ws)
+#define DMVAE_LPIPS_HEAD_R(F_) \
+  switch (p.R) {               \
+    case 1: DMVAE_LPIPS_HEAD(1, F_); break; \
+    case 2: DMVAE_LPIPS_HEAD(2, F_); break; \
+    case 3: DMVAE_LPIPS_HEAD(3, F_); break; \
+    default: DMVAE_LPIPS_HEAD(4, F_); break; \
   }
+  if (form == 0) { DMVAE_LPIPS_HEAD_R(0) } else { DMVAE_LPIPS_HEAD_R(1) }
+#undef DMVAE_LPIPS_HEAD_R
 #undef DMVAE_LPIPS_HEAD
   DMVAE_CHECK_LAUNCH();
   hipLaunchKernelGGL(finalize_kernel, dim3((unsigned)pairs), block, 0, stream, (const double*)ws, p.nb, (double)p.hw, accumulate != 0, out);
   DMVAE_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace dmvae_lpips_eval
+
+extern "C" int dmvae_lpips_head(const float* f, const float* lin, size_t pairs, int h, int w, int c, double eps, int accumulate, void* workspace, double* out,
+                                hipStream_t stream) {
+  return dmvae_lpips_eval::head_launch("lpips_head", f, lin, pairs, h, w, c, eps, 0, accumulate, workspace, out, stream);
+}
+
+extern "C" int dmvae_lpips_head_form(const float* f, const float* lin, size_t pairs, int h, int w, int c, double eps, int form, int accumulate, void* workspace,
+                                     double* out, hipStream_t stream) {
+  return dmvae_lpips_eval::head_launch("lpips_head_form", f, lin, pairs, h, w, c, eps, form, accumulate, workspace, out, stream);
 }

@@ -40,7 +40,8 @@ def evaluate(vae, loader: Iterable, num_samples: int, device=None, fid=None, aut
     {"PSNR", "latent_mean", "latent_scale", "FID" (None without `fid`), "batches", "images"}.
     ssim=True adds "SSIM": `dmvae_amd.metrics.ssim01(x01, s01)` (evaluation/metrics.py:16-23 on the [0, 1] images; csrc/ssim.hip, f64) summed over every
     rank's images in a fifth slot of the same accumulator and divided by `num_samples`, PSNR's convention.  Without it nothing changes.
-    lpips=net (a `dmvae_amd.models.lpips_alex.LPIPSAlex` with its weights loaded, on `device`) adds "LPIPS": the per-image f64 values of
+    lpips=net (a `dmvae_amd.models.lpips_alex.LPIPSAlex`, or a `dmvae_amd.models.lpips_eval.LPIPSVGG` / `LPIPSSqueeze`, with its weights loaded, on
+    `device`) adds "LPIPS": the per-image f64 values of
     `net(x_rec.clamp(-1, 1), images)` (evaluation/metrics.py:26-29; the reconstruction is clamped to the range the metric is defined on, as the FID path
     clamps before it quantises) summed in one more slot of the accumulator, all-reduced with it and divided by `num_samples`.  Without it nothing changes."""
     if ssim:

@@ -10,8 +10,9 @@ first: the value is that of `SSIM(pred.float(), gt.float())`.
 CPU tensors take a plain-torch f64 composition behind `DMVAE_ALLOW_STOCK=1`, like every other module (dmvae_amd/_stock.py).
 
 `LPIPS(img1, img2, net_type='alex')` is `dmvae_amd.models.lpips_alex.LPIPSAlex` once a network is configured (`configure_lpips`, DMVAE_LPIPS_ALEX_WEIGHTS,
-`run_on_mi355x.py --lpips-weights=PATH`): the weight files are not part of this package, and without one it raises NotImplementedError, as do the net types
-'vgg' and 'squeeze', which are not built."""
+`run_on_mi355x.py --lpips-weights=PATH`): the weight files are not part of this package, and without one it raises NotImplementedError.  net_type 'vgg'
+and 'squeeze' are `dmvae_amd.models.lpips_eval.LPIPSVGG` / `LPIPSSqueeze` in the same way (`configure_lpips(path, net_type=...)`,
+DMVAE_LPIPS_VGG_WEIGHTS / DMVAE_LPIPS_SQUEEZE_WEIGHTS, `--lpips-vgg-weights=PATH` / `--lpips-squeeze-weights=PATH`); one network is kept per type."""
 from __future__ import annotations
 
 import os
@@ -75,50 +76,85 @@ def SSIM(pred: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0) -> Tuple
     return v.float(), v.mean().float()
 
 
-_lpips_net = None                       # the configured LPIPSAlex
-_lpips_env_path = None                  # the file the environment variable's network was built from
+_LPIPS_TYPES = ("alex", "vgg", "squeeze")
+_LPIPS_ENV = {"alex": "DMVAE_LPIPS_ALEX_WEIGHTS", "vgg": "DMVAE_LPIPS_VGG_WEIGHTS", "squeeze": "DMVAE_LPIPS_SQUEEZE_WEIGHTS"}
+_LPIPS_FLAG = {"alex": "--lpips-weights", "vgg": "--lpips-vgg-weights", "squeeze": "--lpips-squeeze-weights"}
+_lpips_net = {t: None for t in _LPIPS_TYPES}                # net_type -> the configured network
+_lpips_env_path = {t: None for t in _LPIPS_TYPES}           # net_type -> the file the environment variable's network was built from
 
 
-def configure_lpips(net_or_path):
-    """Gives `LPIPS` its network: a `dmvae_amd.models.lpips_alex.LPIPSAlex`, the path of one state_dict file (`LPIPSAlex.from_checkpoint`), a
-    (trunk_path, lin_path) pair (`LPIPSAlex.from_checkpoints`), or None to unconfigure.  Returns the network.  The weight files are not part of this package."""
-    global _lpips_net, _lpips_env_path
-    from .models.lpips_alex import LPIPSAlex
-    if net_or_path is None or isinstance(net_or_path, LPIPSAlex):
-        net = net_or_path
-    elif isinstance(net_or_path, (tuple, list)):
-        net = LPIPSAlex.from_checkpoints(*net_or_path)
+def _lpips_class(net_type):
+    if net_type == "alex":
+        from .models.lpips_alex import LPIPSAlex
+        return LPIPSAlex
+    from .models import lpips_eval
+    return {"vgg": lpips_eval.LPIPSVGG, "squeeze": lpips_eval.LPIPSSqueeze}[net_type]
+
+
+def _lpips_env(net_type):
+    """The file the type's environment variable names, "" when unset."""
+    if net_type == "alex":
+        return os.environ.get("DMVAE_LPIPS_ALEX_WEIGHTS", "")
+    if net_type == "vgg":
+        return os.environ.get("DMVAE_LPIPS_VGG_WEIGHTS", "")
+    return os.environ.get("DMVAE_LPIPS_SQUEEZE_WEIGHTS", "")
+
+
+def _lpips_type(net_type):
+    if net_type not in _LPIPS_TYPES:
+        raise ValueError(f"metrics.LPIPS: net_type must be 'alex', 'vgg' or 'squeeze', got {net_type!r}")
+    return net_type
+
+
+def configure_lpips(net_or_path, net_type=None):
+    """Gives `LPIPS` its network of one type: a `dmvae_amd.models.lpips_alex.LPIPSAlex`, `dmvae_amd.models.lpips_eval.LPIPSVGG` or `LPIPSSqueeze` (the
+    module selects its type), the path of one state_dict file (`from_checkpoint` of net_type's class, default 'alex'), a (trunk_path, lin_path) pair
+    (`from_checkpoints`), or None to unconfigure net_type -- all three types when no net_type is given.  One network is kept per type.  Returns the
+    network.  The weight files are not part of this package."""
+    if net_or_path is None:
+        for t in _LPIPS_TYPES if net_type is None else (_lpips_type(net_type),):
+            _lpips_net[t], _lpips_env_path[t] = None, None
+        return None
+    own = [t for t in _LPIPS_TYPES if isinstance(net_or_path, _lpips_class(t))]
+    if own:
+        if net_type is not None and net_type != own[0]:
+            raise ValueError(f"metrics.configure_lpips: a {type(net_or_path).__name__} is net_type {own[0]!r}, not {net_type!r}")
+        kind, net = own[0], net_or_path
     else:
-        net = LPIPSAlex.from_checkpoint(net_or_path)
-    _lpips_net, _lpips_env_path = net, None
+        kind = _lpips_type("alex" if net_type is None else net_type)
+        cls = _lpips_class(kind)
+        net = cls.from_checkpoints(*net_or_path) if isinstance(net_or_path, (tuple, list)) else cls.from_checkpoint(net_or_path)
+    _lpips_net[kind], _lpips_env_path[kind] = net, None
     return net
 
 
-def lpips_network():
-    """The network `LPIPS` runs: the one `configure_lpips` was given, else one built (once) from the file DMVAE_LPIPS_ALEX_WEIGHTS names, else None."""
-    global _lpips_net, _lpips_env_path
-    if _lpips_net is not None and _lpips_env_path is None:
-        return _lpips_net                                            # configured explicitly
-    path = os.environ.get("DMVAE_LPIPS_ALEX_WEIGHTS", "")
-    if path != (_lpips_env_path or ""):                              # the variable appeared, moved or went away: so does what it configured
-        configure_lpips(path or None)
-        _lpips_env_path = path or None
-    return _lpips_net
+def lpips_network(net_type="alex"):
+    """The network `LPIPS` runs for net_type: the one `configure_lpips` was given, else one built (once) from the file DMVAE_LPIPS_ALEX_WEIGHTS /
+    DMVAE_LPIPS_VGG_WEIGHTS / DMVAE_LPIPS_SQUEEZE_WEIGHTS names, else None."""
+    kind = _lpips_type(net_type)
+    if _lpips_net[kind] is not None and _lpips_env_path[kind] is None:
+        return _lpips_net[kind]                                      # configured explicitly
+    path = _lpips_env(kind)
+    if path != (_lpips_env_path[kind] or ""):                        # the variable appeared, moved or went away: so does what it configured
+        configure_lpips(path or None, kind)
+        _lpips_env_path[kind] = path or None
+    return _lpips_net[kind]
 
 
 @torch.no_grad()
 def LPIPS(img1, img2, net_type="alex"):
     """evaluation/metrics.py:26-29: [T, 3, H, W] images in [-1, 1] -> torchmetrics' LearnedPerceptualImagePatchSimilarity(net_type, reduction='mean'), an f32
-    scalar on the inputs' device: the mean over the images of `LPIPSAlex.forward` (dmvae_amd/models/lpips_alex.py: the library's published definition restated
-    -- the library cannot be run where this package is developed -- on the exact-f32 convolution kernels and an f64 head; the mean is taken over the f64
-    values and rounded once).  The AlexNet backbone and the linear heads are weights neither this package nor the reference repo holds: name them with
-    `configure_lpips`, DMVAE_LPIPS_ALEX_WEIGHTS or `run_on_mi355x.py --lpips-weights=PATH`.  `dmvae_amd.losses` / utils/lpips.py is the TRAINING loss's VGG16
-    LPIPS, a different network with different numbers."""
-    if net_type in ("vgg", "squeeze"):
-        raise NotImplementedError(f"metrics.LPIPS: net_type {net_type!r} is not built (only 'alex', the reference's default, is)")
-    if net_type != "alex":
-        raise ValueError(f"metrics.LPIPS: net_type must be 'alex', 'vgg' or 'squeeze', got {net_type!r}")
-    net = lpips_network()
+    scalar on the inputs' device: the mean over the images of the configured network's `forward` (dmvae_amd/models/lpips_alex.py, lpips_eval.py: the
+    library's published definition restated -- the library cannot be run where this package is developed -- on the exact-f32 convolution kernels and an f64
+    head; the mean is taken over the f64 values and rounded once).  The backbones and the linear heads are weights this package does not hold: name them
+    with `configure_lpips(path, net_type)`, DMVAE_LPIPS_{ALEX,VGG,SQUEEZE}_WEIGHTS or `run_on_mi355x.py --lpips-weights=PATH` /
+    `--lpips-vgg-weights=PATH` / `--lpips-squeeze-weights=PATH`.  `dmvae_amd.losses` / utils/lpips.py is the TRAINING loss: VGG16 in bf16 with the
+    reference's own normalisation (`LPIPSVGG(normalize="reference")` is its exact-f32 twin), not torchmetrics' 'vgg' numbers."""
+    kind = _lpips_type(net_type)
+    net = lpips_network(kind)
+    if net is None and kind != "alex":
+        raise NotImplementedError(f"metrics.LPIPS: net_type {kind!r} is not built in this process: no weights configured (configure_lpips(path, "
+                                  f"net_type={kind!r}), {_LPIPS_ENV[kind]}, {_LPIPS_FLAG[kind]}=PATH)")
     if net is None:
         raise NotImplementedError("metrics.LPIPS has no network: the reference's evaluation LPIPS is torchmetrics' AlexNet network, whose weights are not part of "
                                   "this package or of the reference repo (configure_lpips(path), DMVAE_LPIPS_ALEX_WEIGHTS or --lpips-weights=PATH names "

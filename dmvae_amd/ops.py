@@ -2423,6 +2423,26 @@ def pool2d_f32(x: torch.Tensor, mode: int, out: Optional[torch.Tensor] = None, c
     return out
 
 
+def maxpool2d_f32(x: torch.Tensor, kernel: int, stride: int, ceil_mode: bool = False, out: Optional[torch.Tensor] = None, c_offset: int = 0) -> torch.Tensor:
+    """x [B, H, W, C] f32 (NHWC) -> its stride-2 maximum pool without padding in channels [c_offset, c_offset + C) of `out`: kernel 2 / stride 2 (VGG16's,
+    Ho = H // 2) or kernel 3 / stride 2 / ceil_mode (SqueezeNet 1.1's, Ho = ceil((H - 3) / 2) + 1, a window over the edge takes the elements that exist);
+    other forms raise (include/dmvae_hip.h: dmvae_maxpool2d_f32)."""
+    x = _req(x, f32, "x")
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, H, W, C], got {tuple(x.shape)}")
+    b, h, w_, c = x.shape
+    kernel, stride, ceil_mode = int(kernel), int(stride), bool(ceil_mode)
+    if (kernel, stride, ceil_mode) not in ((2, 2, False), (3, 2, True)):
+        raise ValueError(f"maxpool2d_f32: kernel {kernel} stride {stride} ceil_mode {ceil_mode} is not built (2 / 2 / False and 3 / 2 / True are)")
+    if h < kernel or w_ < kernel:
+        raise ValueError(f"maxpool2d_f32: the pool needs H, W >= {kernel}, got {h} x {w_}")
+    ho, wo = (h // 2, w_ // 2) if kernel == 2 else ((h - 2) // 2 + 1, (w_ - 2) // 2 + 1)
+    out = _slice_out(out, (b, ho, wo), c, int(c_offset), x, "maxpool2d_f32")
+    check(_lib.lib().dmvae_maxpool2d_f32(x.data_ptr(), out.data_ptr(), b, h, w_, c, kernel, stride, int(ceil_mode), int(c_offset), out.shape[3], _stream()),
+          "maxpool2d_f32")
+    return out
+
+
 def global_avgpool_f32(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [B, H, W, C] f32 (NHWC) -> [B, C] f32: the mean over the pixels, summed in a fixed order in f64 and rounded once (dmvae_global_avgpool_f32).
     `out`: a contiguous f32 [B, C] on x's device to write into."""
@@ -2466,14 +2486,18 @@ def lpips_input(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def lpips_head(f: torch.Tensor, lin: torch.Tensor, eps: float = 1e-8, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+def lpips_head(f: torch.Tensor, lin: torch.Tensor, eps: float = 1e-8, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+               form: int = 0) -> torch.Tensor:
     """f [2 P, H, W, C] f32 (NHWC; image i is paired with image P + i), lin [C] f32 -> f64 [P]: one LPIPS level,
     mean over the pixels of sum_c lin[c] (n1[c] - n2[c])^2 with n = f / sqrt(eps + sum_c f[c]^2), in f64 with fixed-order sums (include/dmvae_hip.h:
-    dmvae_lpips_head).  `out`: a contiguous f64 [P] to write into; accumulate=True adds the level's value to it instead."""
+    dmvae_lpips_head).  `out`: a contiguous f64 [P] to write into; accumulate=True adds the level's value to it instead.  form=1: n = f / (sqrt(sum_c
+    f[c]^2) + eps), the reference's own normalisation (utils/lpips.py:156-158), through dmvae_lpips_head_form; form=0 is the entry above."""
     f = _req(f, f32, "f")
     lin = _req(lin, f32, "lin")
     if f.dim() != 4 or f.numel() == 0 or f.shape[0] % 2:
         raise ValueError(f"f: expected a non-empty [2 P, H, W, C], got {tuple(f.shape)}")
+    if form not in (0, 1):
+        raise ValueError(f"lpips_head: form must be 0 or 1, got {form!r}")
     n2, h, w_, c = f.shape
     pairs = n2 // 2
     if tuple(lin.shape) != (c,) or lin.device != f.device:
@@ -2489,6 +2513,10 @@ def lpips_head(f: torch.Tensor, lin: torch.Tensor, eps: float = 1e-8, out: Optio
     lib = _lib.lib()
     nbytes = lib.dmvae_lpips_head_workspace(pairs, h, w_, c)
     ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=f.device)
+    if form == 1:
+        check(lib.dmvae_lpips_head_form(f.data_ptr(), lin.data_ptr(), pairs, h, w_, c, float(eps), 1, int(bool(accumulate)), ws.data_ptr(), out.data_ptr(),
+                                        _stream()), "lpips_head_form")
+        return out
     check(lib.dmvae_lpips_head(f.data_ptr(), lin.data_ptr(), pairs, h, w_, c, float(eps), int(bool(accumulate)), ws.data_ptr(), out.data_ptr(), _stream()),
           "lpips_head")
     return out

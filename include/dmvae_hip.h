@@ -1186,6 +1186,14 @@ int dmvae_conv2d_f32_fwd(const float* x, const float* w_packed, const float* sca
  * count_include_pad=False: the f32 sum of the taps inside the image in (ky, kx) raster order divided by their number.  c % 4 == 0; offset and pitch as
  * above; -22 before any launch otherwise.  Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209. */
 int dmvae_pool2d_f32(const float* x, float* y, int mode, int batch, int h, int w, int c, int out_c_offset, int out_c_pitch, dmvae_stream_t stream);
+/* The stride-2 maximum pools without padding of the evaluation LPIPS' VGG16 and SqueezeNet 1.1 trunks (dmvae_amd/models/lpips_eval.py), x [batch][h][w][c]
+ * f32 into channels [out_c_offset, out_c_offset + c) of y (pitch out_c_pitch, as above).  Forms kernel / stride / ceil_mode: 2 / 2 / 0 (Ho = h / 2) and
+ * 3 / 2 / 1 (Ho = ceil((h - 3) / 2) + 1: a window that hangs over the bottom or right edge takes the maximum of the elements that exist; every window
+ * starts inside the image).  A new entry: dmvae_pool2d_f32's modes are unchanged.  h, w >= kernel, c % 4 == 0, offset and pitch as above, at most 2^31 - 1
+ * blocks of 256 outputs; anything else, or a NULL pointer, returns -22 before any launch.  Reference: evaluation/metrics.py:26-29 (net_type 'vgg',
+ * 'squeeze'). */
+int dmvae_maxpool2d_f32(const float* x, float* y, int batch, int h, int w, int c, int kernel, int stride, int ceil_mode, int out_c_offset, int out_c_pitch,
+                        dmvae_stream_t stream);
 /* y [batch][c] f32 = the mean over the h w pixels of x [batch][h][w][c] f32: added in ascending pixel order in f64, divided in f64, rounded once.
  * -22 before any launch for a NULL pointer or a size below 1.  Reference: evaluation/fid.py:8-48 and sample_50k.py:174-209. */
 int dmvae_global_avgpool_f32(const float* x, float* y, int batch, int h, int w, int c, dmvae_stream_t stream);
@@ -1218,6 +1226,13 @@ size_t dmvae_lpips_head_workspace(size_t pairs, int h, int w, int c);
  * restated from the library's published form; the library cannot be run where this package is developed.  Reference: evaluation/metrics.py:26-29. */
 int dmvae_lpips_head(const float* f, const float* lin, size_t pairs, int h, int w, int c, double eps, int accumulate, void* workspace, double* out,
                      dmvae_stream_t stream);
+/* dmvae_lpips_head with the normalisation selected.  form 0: n = f * (1 / sqrt(eps + sum_c f[c]^2)), the library's -- the same kernel, plan, orders and
+ * bits as dmvae_lpips_head.  form 1: n = f * (1 / (sqrt(sum_c f[c]^2) + eps)), the reference's own normalize_tensor (utils/lpips.py:156-158, eps 1e-10): the
+ * exact-f32 / f64 twin of the bf16 training loss.  One operation differs; the loads, the f64 arithmetic, the fixed orders, the workspace
+ * (dmvae_lpips_head_workspace) and every refusal are shared, and an all-zero pixel adds 0 in both forms.  A form other than 0 or 1 returns -22 before any
+ * launch.  Reference: evaluation/metrics.py:26-29 (net_type 'vgg'), utils/lpips.py:86-94. */
+int dmvae_lpips_head_form(const float* f, const float* lin, size_t pairs, int h, int w, int c, double eps, int form, int accumulate, void* workspace,
+                          double* out, dmvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
     python run_on_mi355x.py --hip-fid /path/to/dmvae/train_tokenizer.py ...                            (or DMVAE_HIP_FID=1)
     python run_on_mi355x.py --hip-metrics /path/to/dmvae/script.py ...                                 (or DMVAE_HIP_METRICS=1)
     python run_on_mi355x.py --lpips-weights=/path/to/lpips_alex.pth /path/to/dmvae/script.py ...       (implies --hip-metrics)
+    python run_on_mi355x.py --lpips-vgg-weights=PATH --lpips-squeeze-weights=PATH /path/to/dmvae/script.py ...   (net_type 'vgg' / 'squeeze'; imply --hip-metrics)
 
 The reference's drivers import their model code by module path (`from models.vae import VAE`, `from utils.lpips import LPIPS`,
 `from diffusion.lightningdit.lightningdit import LightningDiT_models`, `from diffusion.transport import create_transport`; train_tokenizer.py:10-17,
@@ -37,7 +38,8 @@ only) builds this build's `InceptionV3Compat` from that file: the network on the
 `dmvae_amd.metrics` under that path: `SSIM` on this build's f64 kernel with no torchmetrics import, `PSNR` unchanged, `LPIPS` a NotImplementedError (its AlexNet
 weights are not here) -- unless a weight file is named: `--lpips-weights=/path/to/state_dict.pth` (implies --hip-metrics), DMVAE_LPIPS_ALEX_WEIGHTS or
 `install_shadow(ref, metrics=True, lpips_weights=path)` hands it to `dmvae_amd.metrics.configure_lpips`, and `LPIPS` is then this build's
-`dmvae_amd.models.lpips_alex.LPIPSAlex` (net_type 'alex' only).  Without the opt-in the reference's file keeps serving it.
+`dmvae_amd.models.lpips_alex.LPIPSAlex` for net_type 'alex'; `--lpips-vgg-weights=PATH` and `--lpips-squeeze-weights=PATH` (or DMVAE_LPIPS_VGG_WEIGHTS /
+DMVAE_LPIPS_SQUEEZE_WEIGHTS) name the files of `dmvae_amd.models.lpips_eval.LPIPSVGG` / `LPIPSSqueeze` for net_type 'vgg' / 'squeeze'.  Without the opt-in the reference's file keeps serving it.
 
 The GVP / VP paths of `diffusion.transport` are off in the mirror by default (`dmvae_amd.transport.enable_all_paths`).  Running a script turns them on -- the
 script's own `--path_type` is the selection --; `--check` and a bare `install_shadow(ref)` leave the switch alone (`install_shadow(ref, all_paths=True)` asks)."""
@@ -152,9 +154,13 @@ def main(argv) -> int:
     hip_fid = os.environ.get("DMVAE_HIP_FID", "0") not in ("", "0")
     hip_metrics = os.environ.get("DMVAE_HIP_METRICS", "0") not in ("", "0")
     weights = lpips_weights = None
-    while argv and (argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid", "--hip-metrics") or argv[0].startswith(("--inception-weights=", "--lpips-weights="))):
+    lpips_more = {}                                  # net_type -> file, for the evaluation LPIPS' 'vgg' and 'squeeze' networks
+    while argv and (argv[0] in ("--hip-dinodisc", "--hip-optim", "--hip-fid", "--hip-metrics") or
+                    argv[0].startswith(("--inception-weights=", "--lpips-weights=", "--lpips-vgg-weights=", "--lpips-squeeze-weights="))):
         if argv[0].startswith("--inception-weights="):
             weights, hip_fid = argv[0].split("=", 1)[1], True
+        elif argv[0].startswith(("--lpips-vgg-weights=", "--lpips-squeeze-weights=")):
+            lpips_more[argv[0].split("-")[3]], hip_metrics = argv[0].split("=", 1)[1], True
         elif argv[0].startswith("--lpips-weights="):
             lpips_weights, hip_metrics = argv[0].split("=", 1)[1], True
         elif argv[0] == "--hip-dinodisc":
@@ -169,19 +175,24 @@ def main(argv) -> int:
     if not argv:
         print(__doc__)
         return 0
+    def more_lpips(shadowed):                        # after install_shadow: the shadowed evaluation.metrics is dmvae_amd.metrics
+        for net_type, path in lpips_more.items():
+            net = shadowed["evaluation.metrics"].configure_lpips(path, net_type=net_type)
+            print(f"evaluation.metrics.LPIPS(net_type={net_type!r}) -> {type(net).__module__}.{type(net).__name__} ({path})")
     if argv[0] == "--check":
         ref = argv[1] if len(argv) > 1 else None
-        for path, mod in install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid, metrics=hip_metrics, inception_weights=weights,
-                                         lpips_weights=lpips_weights).items():
+        shadowed = install_shadow(ref, dinodisc=hip_dinodisc, fid=hip_fid, metrics=hip_metrics, inception_weights=weights, lpips_weights=lpips_weights)
+        for path, mod in shadowed.items():
             print(f"{path:40s} -> {mod.__name__}")
+        more_lpips(shadowed)
         if hip_optim:
             for path, obj in install_optim().items():
                 print(f"{path:40s} -> {obj.__module__}.{obj.__qualname__}")
         return 0
     script = os.path.abspath(argv[0])
     ref = os.path.dirname(script)
-    install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid, metrics=hip_metrics, inception_weights=weights,
-                   lpips_weights=lpips_weights)      # the script's --path_type selects
+    more_lpips(install_shadow(ref, dinodisc=hip_dinodisc, optim=hip_optim, all_paths=True, fid=hip_fid, metrics=hip_metrics, inception_weights=weights,
+                              lpips_weights=lpips_weights))      # the script's --path_type selects
     if ref not in sys.path:
         sys.path.insert(0, ref)                     # what `python script.py` would have put first
     sys.argv = [script] + list(argv[1:])

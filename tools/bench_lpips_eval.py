@@ -1,7 +1,8 @@
 #!/usr/bin/env python
-"""Times dmvae_amd.models.lpips_alex.LPIPSAlex on one MI355X against the same module's stock f32 composition, on the same device, in the same process.
+"""Times the evaluation LPIPS' networks (dmvae_amd.models.lpips_alex.LPIPSAlex, dmvae_amd.models.lpips_eval.LPIPSVGG / LPIPSSqueeze) on one MI355X against
+the same module's stock f32 composition, on the same device, in the same process.
 
-    python tools/bench_lpips_eval.py [--pairs 32,128] [--size 256] [--iters 5] [--rounds 3] [--out FILE]
+    python tools/bench_lpips_eval.py [--net alex|vgg|squeeze] [--pairs 32,128] [--size 256] [--iters 5] [--rounds 3] [--chunk N] [--out FILE]
 
   hip     `forward` on the kernels of csrc/inception.hip (exact f32 on v_mfma_f32_16x16x4_f32) and csrc/lpips_eval.hip (input pass, f64 head), f32
           [P, 3, S, S] pairs in, range check off (it is one host synchronisation and not part of either route).
@@ -10,8 +11,9 @@
 
 Parameters are seeded random values (the published weights are not on this machine); times do not depend on them.  Rounds are interleaved: every round
 times both routes, one after the other.  A time is the mean over `--iters` calls between two device events after a warm-up call of the same shape; the
-table gives the median and the spread over the rounds.  The trunk's rate is the five convolutions' 2 Ho Wo Cout Cin k k flops for both images of a pair,
-over the whole call's time: a whole-network rate, not a kernel's share of peak.
+table gives the median and the spread over the rounds.  The trunk's rate is the convolutions' 2 Ho Wo Cout Cin k k flops for both images of a pair (taken
+from the module's own Conv2d layers by a shape-recording pass of the stock route), over the whole call's time: a whole-network rate, not a kernel's
+share of peak.
   The head is then timed alone, level by level, on the taps of the same images: `ops.lpips_head` calls back to back between two device events (each call is
 the reduction launch, the per-pair finalize launch and the workspace allocation).  Its algorithmic bytes are the features it must read once,
 2 P h w c x 4 B (lin and the P results are noise), and the rate printed is those bytes over the call time -- to be read against the 6.3 TB/s a streaming
@@ -39,16 +41,22 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters                         # ms per call
 
 
-def trunk_shapes(size):
-    """-> [(h, w, c, conv flops per image)] per tap, by the layers' own shape arithmetic."""
-    from dmvae_amd.models.lpips_alex import TRUNK
-    out, h, w = [], size, size
-    for _, _, cin, cout, k, stride, pad, pool in TRUNK:
-        if pool:
-            h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
-        h, w = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
-        out.append((h, w, cout, 2 * h * w * cout * cin * k * k))
-    return out
+def trunk_shapes(net, size):
+    """-> ([(h, w, c)] per tap, conv flops per image): one CPU pass of the stock trunk on a zero image, every F.conv2d call recorded."""
+    import torch.nn.functional as F
+    flops, real = [0], F.conv2d
+
+    def counting(x, w, *args, **kw):
+        y = real(x, w, *args, **kw)
+        flops[0] += 2 * y.shape[2] * y.shape[3] * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3]
+        return y
+    F.conv2d = counting
+    try:
+        with torch.no_grad():
+            taps = [(t.shape[2], t.shape[3], t.shape[1]) for t in net._stock_taps(torch.zeros(1, 3, size, size))]
+    finally:
+        F.conv2d = real
+    return taps, flops[0]
 
 
 def random_parameters(net, seed=0):
@@ -64,6 +72,8 @@ def random_parameters(net, seed=0):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--net", default="alex", choices=("alex", "vgg", "squeeze"))
+    ap.add_argument("--chunk", type=int, default=0, help="image pairs per pass of the network (0: 128 for alex and squeeze, 32 for vgg)")
     ap.add_argument("--pairs", default="32,128")
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--iters", type=int, default=5)
@@ -75,13 +85,16 @@ def main():
         sys.exit("bench_lpips_eval: needs a GPU (no CPU timing)")
     from dmvae_amd import ops
     from dmvae_amd.models.lpips_alex import LPIPSAlex
+    from dmvae_amd.models.lpips_eval import LPIPSSqueeze, LPIPSVGG
     dev = "cuda:0"
-    net = LPIPSAlex(chunk=128)
+    cls = {"alex": LPIPSAlex, "vgg": LPIPSVGG, "squeeze": LPIPSSqueeze}[a.net]
+    net = cls(chunk=a.chunk or (32 if a.net == "vgg" else 128))
     random_parameters(net)
+    shapes, per_image = trunk_shapes(net, a.size)
     net = net.to(dev)
-    shapes = trunk_shapes(a.size)
-    flops = 2 * sum(s[3] for s in shapes)                               # both images of a pair
-    lines = [f"LPIPSAlex at {a.size} x {a.size}: {flops / 1e9:.3f} GFLOP per pair in the 2 x 5 convolutions; taps (h, w, c): {[s[:3] for s in shapes]}",
+    flops = 2 * per_image                                               # both images of a pair
+    lines = [f"{cls.__name__} at {a.size} x {a.size}, chunk {net.chunk}: {flops / 1e9:.3f} GFLOP per pair in the 2 x {len(net.convs())} convolutions; "
+             f"taps (h, w, c): {shapes}",
              f"device: {torch.cuda.get_device_name(0)}; iters {a.iters}, rounds {a.rounds}; times are medians over the rounds (min .. max)", ""]
     for p in (int(s) for s in a.pairs.split(",")):
         g = torch.Generator().manual_seed(p)
@@ -99,11 +112,12 @@ def main():
             med = statistics.median(ts)
             lines.append(f"  {k:6s} {med:9.3f} ms ({min(ts):.3f} .. {max(ts):.3f})   {p / med * 1e3:9.1f} pairs/s   {flops * p / med / 1e9:7.2f} TFLOP/s f32 (whole call)")
         lines.append(f"  hip / stock time: {statistics.median(times['hip']) / statistics.median(times['stock']):.2f}")
-        taps = net.taps(x1, x2, chunk=p)
+        taps = net.taps(x1[:net.chunk], x2[:net.chunk])                       # one chunk's taps: what one head call of the network sees
+        hp = taps[0].shape[0] // 2
         lins = net._operands(torch.device(dev))["lin"]
-        out = torch.zeros(p, dtype=torch.float64, device=dev)
+        out = torch.zeros(hp, dtype=torch.float64, device=dev)
         total_head = 0.0
-        lines.append(f"  the head alone, level by level ({a.head_iters} calls back to back; bytes = 2 P h w c x 4):")
+        lines.append(f"  the head alone, level by level ({a.head_iters} calls back to back; bytes = 2 P h w c x 4, P = {hp}, one chunk):")
         for level, (f, lin) in enumerate(zip(taps, lins)):
             ts = [timed(lambda: ops.lpips_head(f, lin, net.eps, out=out, accumulate=level > 0), a.head_iters) for _ in range(a.rounds)]
             med, nbytes = statistics.median(ts), f.numel() * 4
@@ -111,7 +125,7 @@ def main():
             where = "fits the Infinity Cache: re-read from there" if nbytes < 200 * 2 ** 20 else "larger than the Infinity Cache: from HBM"
             lines.append(f"    level {level} {tuple(f.shape)}: {med * 1e3:8.1f} us ({min(ts) * 1e3:.1f} .. {max(ts) * 1e3:.1f})  {nbytes / 2 ** 20:7.1f} MiB  "
                          f"{nbytes / med / 1e9:7.3f} TB/s  ({where})")
-        lines.append(f"    five levels: {total_head:.3f} ms = {100 * total_head / statistics.median(times['hip']):.1f} % of the hip call")
+        lines.append(f"    {len(taps)} levels: {total_head:.3f} ms = {100 * total_head * -(-p // net.chunk) / statistics.median(times['hip']):.1f} % of the hip call ({-(-p // net.chunk)} chunk(s))")
         lines.append("")
     text = "\n".join(lines)
     print(text)
